@@ -10,11 +10,14 @@ gs_sort for the frame's view vector followed by a full render, splat data alread
 the viewport is split into tile-aligned column strips (splat buffer replicated, sort + project replicated on every
 GPU), each rank renders its strip into a device tensor and the strips are gathered to rank 0 over RCCL.
 
-Rank 0 prints ONE JSON line.  `value` = frames/s of the whole job; extra keys give Msplat-frags/s (reference-
-equivalent fragments, counted untimed by the GS_RENDER_COUNT_FRAGS variant), the per-stage GPU times from HIP
-events on the library's stream, the roofline of the dominant kernel and the CPU baseline.
+Rank 0 prints ONE JSON line.  `value` = frames/s of the whole job, `ms_per_step` = milliseconds of one timed step.
+With --full, extra keys give Msplat-frags/s (reference-equivalent fragments, counted untimed by the
+GS_RENDER_COUNT_FRAGS variant), the per-stage GPU times from HIP events on the library's stream, the roofline of
+the dominant kernel, the other configurations and the CPU baseline.  --dump-outputs DIR writes the last timed
+step's frame(s) as float32 .npy files.
 """
 import argparse
+import ctypes
 import importlib
 import gc
 import json
@@ -52,7 +55,17 @@ def main():
                     help="a BASELINE.json configuration -- or a regime of the headline scene (R_outside: the camera outside the cloud, R_unsat: opacity / 10) -- "
                          "by name (aframe-gaussian-splatting_amd/bench_configs.py); default C2, or whatever --splats / --size / --cutout / --xr describe")
     ap.add_argument("--no-configs", action="store_true", help="skip the other BASELINE configurations (`configs` in the line; single GPU, default run only)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline: fragment counts, per-stage times, steady state, whole-sort A/B, the gathered frame's "
+                         "self-check, copy peak, secondary measurements, rooflines, the other configurations and regimes, the CPU baseline "
+                         "(each still subject to the --no-* switches).  Without it a run sets up, warms up, times --steps steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed (its RGBA frame(s), as float32) to DIR/<name>.npy")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs and args.single_process:
+        ap.error("--dump-outputs is written by the per-process form only (not with --single-process)")
     BC = importlib.import_module(PKG + ".bench_configs")
     if args.config:                                          # the table's shape, spelled out for everything below that reads the flags
         c = BC.ALL[args.config]
@@ -179,7 +192,8 @@ def main():
             ctx.render_device(piece_params(k, v, x0, x1, 0), tg["strip"].data_ptr())     # synchronous
         tg["frame"] = mg.gather_strips(tg["strip"], W, H, dist, tg["all"])
 
-    def frame(i, flags=0):
+    def frame(i, flags=0, out_dev=None):
+        """one step; out_dev: a device buffer the (non-gathered) frame is drawn into instead of the lane's own framebuffer"""
         k = i % ORBIT_FRAMES
         if torch_gather:
             frame_torch_gather(k)
@@ -197,7 +211,7 @@ def main():
             else:
                 ctx.sort(cams[k]["view"], cams[k]["cutout"], want_indices=False)
             views[k][0].flags = flags
-            ctx.render_device(views[k][0], None)
+            ctx.render_device(views[k][0], out_dev)
 
     def count_frame(k, flags):
         """fragments of this rank's pieces of pose k (counting renders are synchronous, per context)"""
@@ -292,21 +306,22 @@ def main():
     # reference-equivalent fragments per orbit frame (untimed; no early termination), and the fragments the blend really
     # evaluates with early termination on (sampled poses)
     frames_used = sorted(set((args.warmup + i) % ORBIT_FRAMES for i in range(args.steps)))
-    frags = {k: count_frame(k, capi.RENDER_COUNT_FRAGS) for k in frames_used}
     sample = frames_used[:: max(1, len(frames_used) // 8)][:8]
-    evaluated = [count_frame(k, capi.RENDER_COUNT_FRAGS | capi.RENDER_COUNT_EVALUATED) for k in sample]
-    if world > 1:
-        t = torch.tensor([frags[k] for k in frames_used] + evaluated, dtype=torch.int64, device="cuda")
-        dist.all_reduce(t)
-        vals = t.tolist()
-        frags = dict(zip(frames_used, vals[:len(frames_used)])); evaluated = vals[len(frames_used):]
-    evaluated_per_frame = float(np.mean(evaluated))
-    evaluated_share = evaluated_per_frame / max(1.0, float(np.mean([frags[k] for k in sample])))
+    if args.full:
+        frags = {k: count_frame(k, capi.RENDER_COUNT_FRAGS) for k in frames_used}
+        evaluated = [count_frame(k, capi.RENDER_COUNT_FRAGS | capi.RENDER_COUNT_EVALUATED) for k in sample]
+        if world > 1:
+            t = torch.tensor([frags[k] for k in frames_used] + evaluated, dtype=torch.int64, device="cuda")
+            dist.all_reduce(t)
+            vals = t.tolist()
+            frags = dict(zip(frames_used, vals[:len(frames_used)])); evaluated = vals[len(frames_used):]
+        evaluated_per_frame = float(np.mean(evaluated))
+        evaluated_share = evaluated_per_frame / max(1.0, float(np.mean([frags[k] for k in sample])))
 
     # list entries the blend really stages before its tiles saturate (untimed measurement aid, sampled over 8 poses of the
     # region, rank 0's first piece): the byte count behind `roofline.achieved_touched`
     staged_per_frame = None
-    if rank == 0 and mine:
+    if args.full and rank == 0 and mine:
         v0, xa, xb = mine[0]
         ctx.set_option(capi.OPT_RECORD_STAGED, 1)
         ctx.set_option(capi.OPT_NEAR_PERMILLE, 1000)
@@ -326,6 +341,13 @@ def main():
     # (short runs cycle through their poses until the share has settled; long ones see every pose twice: the share drifts down towards
     # its floor between two visits of a pose; then every pipeline lane allocated and warm, whatever W is; then the W warm-up steps)
     preroll = BC.preroll(frame, sync, frames_used, args.warmup, capi.RENDER_ASYNC, lanes=max(LANES, depth))
+    # --dump-outputs: the last timed step of a frame that stays on this GPU is drawn into a buffer of the caller's, as a consumer of
+    # gs_render_device would pass one (gathered frames are read back from the library's gathered frame instead)
+    k_final = (args.warmup + args.steps - 1) % ORBIT_FRAMES
+    dump_dev = None
+    if args.dump_outputs and not gathered and not torch_gather:
+        q = views[k_final][0]
+        dump_dev = DeviceBuffer(capi, ctx.device, (q.fb_height, q.x1 - q.x0, 4))
     # ---- timed region: exactly K steps, barrier + synchronize on both sides.  A retry request from the closing sync
     # (an asynchronous frame outgrew a buffer or needed the skipped second binning round) invalidates the region: the
     # library has adapted, the region is measured again from scratch.
@@ -338,8 +360,9 @@ def main():
         # into a 1.4 ms region is a third of it -- one run in twelve of the 20-step form came out at 10 900 instead of 14 400 frames/s)
         gc.collect(); gc.disable()
         t_start = time.perf_counter()
-        for i in range(args.steps):
+        for i in range(args.steps - 1):
             frame(args.warmup + i, capi.RENDER_ASYNC)
+        frame(args.warmup + args.steps - 1, capi.RENDER_ASYNC, dump_dev and dump_dev.ptr)
         t_enq = time.perf_counter()
         again = sync()
         elapsed = time.perf_counter() - t_start
@@ -359,74 +382,86 @@ def main():
             frame(k)
     s = ctx.stats()
     ctx.set_option(capi.OPT_PROFILE, 0)
+    if args.dump_outputs and rank == 0:                      # before anything else is drawn: what the last timed step computed
+        if dump_dev:
+            outputs = {"frame": dump_dev.read()}
+        elif torch_gather:
+            outputs = {"frame": tg["frame"].cpu().numpy()}
+        else:
+            outputs = {("frame" if len(widths) == 1 else "frame_view%d" % v): ctx.read_gathered(v, W, H) for v in range(len(widths))}
+        dump_outputs(args.dump_outputs, outputs)
+    if dump_dev:
+        dump_dev.free()
     blends_per_step = len(mine) if gathered else 1
     # (frames gs_sync() drew again by itself -- GS_OPT_AUTO_RETRY -- are inside the region's time and counted on top)
     assert s["acc_frames"] == (args.steps + s.get("retried_frames", 0) - retried_before) * blends_per_step or gathered, (
         s["acc_frames"], args.steps, s.get("retried_frames", 0), retried_before, blends_per_step)
     blend_frames = max(1, s["prof_frames"])                  # renders of the timed region whose blend was bracketed by HIP events
-    # per-stage breakdown: a second, UNTIMED pass over the same frames with events around every stage (7 per frame
-    # instead of 2; they cost ~4 % of the frame rate, so the timed region carries only the blend's)
-    ctx.set_option(capi.OPT_PROFILE, 1)
-    sync()
-    for i in range(args.steps):
-        frame(args.warmup + i, capi.RENDER_ASYNC)
-    sync()
-    s2 = ctx.stats()
-    ctx.set_option(capi.OPT_PROFILE, 0)
-    # what the region's fill and drain cost: the same loop over a region long enough to hide them (untimed for `value`)
-    steady_fps = None
-    if args.steps < 240:
+    steady_fps = whole_sort_fps = same_protocol_fps = stage = None
+    if args.full:
+        # per-stage breakdown: a second, UNTIMED pass over the same frames with events around every stage (7 per frame
+        # instead of 2; they cost ~4 % of the frame rate, so the timed region carries only the blend's)
+        ctx.set_option(capi.OPT_PROFILE, 1)
         sync()
-        ts = time.perf_counter()
-        for i in range(480):                                 # (the region's own poses, over and over: the share is settled for exactly those)
-            frame(args.warmup + (i % args.steps), capi.RENDER_ASYNC)
-        if not sync():
-            steady_fps = 480 / (time.perf_counter() - ts)
-        if world > 1:
-            t = torch.tensor([steady_fps or 0.0], dtype=torch.float64, device="cuda")
-            dist.all_reduce(t, op=dist.ReduceOp.MIN)
-            steady_fps = float(t.item()) or None
-    # the same region with whole sorts (GS_OPT_SORT_NEAR = 0: the reference's sort, index.js:507-570, for every frame), same process, same
-    # poses, untimed for `value`: what the tail / near-only sorts of the timed frames are worth
-    whole_sort_fps = same_protocol_fps = None
-    if opts.get("OPT_SORT_NEAR", 1) != 0 and not torch_gather:
-        def best_of_3():
-            for j in range(BC.ASYNC_WARM * LANES):
-                frame(args.warmup + (j % args.steps), capi.RENDER_ASYNC)
-            if sync():
-                return None
-            best = None
-            for _ in range(3):
-                gc.collect(); gc.disable()
-                tw = time.perf_counter()
-                for i in range(args.steps):
-                    frame(args.warmup + i, capi.RENDER_ASYNC)
-                ag = sync()
-                dt = time.perf_counter() - tw
-                gc.enable()
-                if not ag and (best is None or dt < best):
-                    best = dt
-            return args.steps / best if best else None
-        try:
-            ctx.set_option(capi.OPT_SORT_NEAR, 0)
-            whole_sort_fps = best_of_3()
-        finally:
-            ctx.set_option(capi.OPT_SORT_NEAR, opts.get("OPT_SORT_NEAR", 1))
+        for i in range(args.steps):
+            frame(args.warmup + i, capi.RENDER_ASYNC)
+        sync()
+        s2 = ctx.stats()
+        ctx.set_option(capi.OPT_PROFILE, 0)
+        # what the region's fill and drain cost: the same loop over a region long enough to hide them (untimed for `value`)
+        steady_fps = None
+        if args.steps < 240:
             sync()
-        # ... and the library's default again, by the same protocol (best of three regions right after each other: `value` is ONE region,
-        # and one region's spread is of the size of the difference)
-        for k in frames_used:
-            frame(k)
-        same_protocol_fps = best_of_3()
-        if world > 1:
-            t = torch.tensor([whole_sort_fps or 0.0, same_protocol_fps or 0.0], dtype=torch.float64, device="cuda")
-            dist.all_reduce(t, op=dist.ReduceOp.MIN)
-            whole_sort_fps, same_protocol_fps = (float(v) or None for v in t.tolist())
-    k2 = max(1, s2["prof_frames"]) / float(max(1, blends_per_step))     # profiled steps
-    # (with two frames per launch the HIP events bracket a PAIR's kernels: a frame's share is half of the interval)
-    stage = {"ms_sort": s2["sum_ms_sort"] * args.steps / k2 / frame_batch, "ms_project": s2["sum_ms_project"] * args.steps / k2 / frame_batch,
-             "ms_bin": s2["sum_ms_bin"] * args.steps / k2 / frame_batch,
-             "ms_blend": s["sum_ms_blend"] * args.steps * blends_per_step / blend_frames / frame_batch}
+            ts = time.perf_counter()
+            for i in range(480):                                 # (the region's own poses, over and over: the share is settled for exactly those)
+                frame(args.warmup + (i % args.steps), capi.RENDER_ASYNC)
+            if not sync():
+                steady_fps = 480 / (time.perf_counter() - ts)
+            if world > 1:
+                t = torch.tensor([steady_fps or 0.0], dtype=torch.float64, device="cuda")
+                dist.all_reduce(t, op=dist.ReduceOp.MIN)
+                steady_fps = float(t.item()) or None
+        # the same region with whole sorts (GS_OPT_SORT_NEAR = 0: the reference's sort, index.js:507-570, for every frame), same process, same
+        # poses, untimed for `value`: what the tail / near-only sorts of the timed frames are worth
+        whole_sort_fps = same_protocol_fps = None
+        if opts.get("OPT_SORT_NEAR", 1) != 0 and not torch_gather:
+            def best_of_3():
+                for j in range(BC.ASYNC_WARM * LANES):
+                    frame(args.warmup + (j % args.steps), capi.RENDER_ASYNC)
+                if sync():
+                    return None
+                best = None
+                for _ in range(3):
+                    gc.collect(); gc.disable()
+                    tw = time.perf_counter()
+                    for i in range(args.steps):
+                        frame(args.warmup + i, capi.RENDER_ASYNC)
+                    ag = sync()
+                    dt = time.perf_counter() - tw
+                    gc.enable()
+                    if not ag and (best is None or dt < best):
+                        best = dt
+                return args.steps / best if best else None
+            try:
+                ctx.set_option(capi.OPT_SORT_NEAR, 0)
+                whole_sort_fps = best_of_3()
+            finally:
+                ctx.set_option(capi.OPT_SORT_NEAR, opts.get("OPT_SORT_NEAR", 1))
+                sync()
+            # ... and the library's default again, by the same protocol (best of three regions right after each other: `value` is ONE region,
+            # and one region's spread is of the size of the difference)
+            for k in frames_used:
+                frame(k)
+            same_protocol_fps = best_of_3()
+            if world > 1:
+                t = torch.tensor([whole_sort_fps or 0.0, same_protocol_fps or 0.0], dtype=torch.float64, device="cuda")
+                dist.all_reduce(t, op=dist.ReduceOp.MIN)
+                whole_sort_fps, same_protocol_fps = (float(v) or None for v in t.tolist())
+        k2 = max(1, s2["prof_frames"]) / float(max(1, blends_per_step))     # profiled steps
+        # (with two frames per launch the HIP events bracket a PAIR's kernels: a frame's share is half of the interval)
+        stage = {"ms_sort": s2["sum_ms_sort"] * args.steps / k2 / frame_batch, "ms_project": s2["sum_ms_project"] * args.steps / k2 / frame_batch,
+                 "ms_bin": s2["sum_ms_bin"] * args.steps / k2 / frame_batch,
+                 "ms_blend": s["sum_ms_blend"] * args.steps * blends_per_step / blend_frames / frame_batch}
     pairs, visible, sorted_n = s["acc_pairs"], s["acc_visible"], s["acc_sorted"] / float(max(1, blends_per_step))
     if world > 1:
         t = torch.tensor([elapsed], dtype=torch.float64, device="cuda")
@@ -436,35 +471,36 @@ def main():
     # self-check of the gathered path: the image(s) assembled on rank 0 for the LAST pose must equal, bit for bit, what rank 0
     # renders alone for the same pose (the splat buffer is replicated, pieces are tile-aligned)
     frame_check = None
-    if gathered:
+    if gathered and args.full:
         k_last = (args.warmup + args.steps - 1) % ORBIT_FRAMES
         frame_check = assembled_frame_ok(k_last)             # collective: every rank
-    copy_peak = measured_copy_peak(ctx, capi) if rank == 0 else None
-    total_frags = sum(frags[(args.warmup + i) % ORBIT_FRAMES] for i in range(args.steps))
+    copy_peak = measured_copy_peak(ctx, capi) if rank == 0 and args.full else None
+    total_frags = sum(frags[(args.warmup + i) % ORBIT_FRAMES] for i in range(args.steps)) if args.full else None
     extras = None
-    if rank == 0 and world == 1 and not args.no_extras and not args.xr:
+    if args.full and rank == 0 and world == 1 and not args.no_extras and not args.xr:
         extras = secondary_measurements(ctx, capi, synth, rows, cams, views, n_splats, args, frame_batch, pmc_load(world, n_splats, args)[0])
     if rank == 0:
         K = args.steps
         fps = K / elapsed
-        # dominant kernel = the per-tile blend.  Algorithmic bytes per launch, launch = one piece's blend:
-        #   B_blend = I*(4 + 32) (pair list entry + projected record, read once per tile) + 4*fb (RGBA8 write)
-        launches = K * blends_per_step
-        blend_bytes = (pairs / launches) * 36.0 + 4.0 * own_px / max(1, len(mine))
-        blend_s = stage["ms_blend"] / launches * 1e-3
-        achieved = blend_bytes / blend_s / 1e9 if blend_s > 0 else 0.0
-        touched_bytes = (staged_per_frame or 0.0) / max(1, len(mine)) * 36.0 + 4.0 * own_px / max(1, len(mine))
-        achieved_touched = touched_bytes / blend_s / 1e9 if blend_s > 0 else 0.0
-        # whole-frame algorithmic bytes (SURVEY.md 8d formula), this rank's share
-        V, Vp, I = sorted_n / K, visible / K, pairs / K
-        frame_bytes = (16 * n_splats + 4 * V) + (Vp * 36 + V * 4 + Vp * 32) + (I * 20) + (I * 36 + 4 * own_px)
-        pmc_cfg, traffic_src = pmc_load(world, n_splats, args)
-        traffic = frame_traffic = None
-        if pmc_cfg:
-            row, fpl = pmc_blend_row(pmc_cfg)
-            if row:
-                traffic = round(row["hbm_bytes"] * frame_batch / fpl)      # per launch of THIS run (frame_batch frames)
-            frame_traffic = pmc_cfg.get("frame_hbm_bytes")
+        if args.full:
+            # dominant kernel = the per-tile blend.  Algorithmic bytes per launch, launch = one piece's blend:
+            #   B_blend = I*(4 + 32) (pair list entry + projected record, read once per tile) + 4*fb (RGBA8 write)
+            launches = K * blends_per_step
+            blend_bytes = (pairs / launches) * 36.0 + 4.0 * own_px / max(1, len(mine))
+            blend_s = stage["ms_blend"] / launches * 1e-3
+            achieved = blend_bytes / blend_s / 1e9 if blend_s > 0 else 0.0
+            touched_bytes = (staged_per_frame or 0.0) / max(1, len(mine)) * 36.0 + 4.0 * own_px / max(1, len(mine))
+            achieved_touched = touched_bytes / blend_s / 1e9 if blend_s > 0 else 0.0
+            # whole-frame algorithmic bytes (SURVEY.md 8d formula), this rank's share
+            V, Vp, I = sorted_n / K, visible / K, pairs / K
+            frame_bytes = (16 * n_splats + 4 * V) + (Vp * 36 + V * 4 + Vp * 32) + (I * 20) + (I * 36 + 4 * own_px)
+            pmc_cfg, traffic_src = pmc_load(world, n_splats, args)
+            traffic = frame_traffic = None
+            if pmc_cfg:
+                row, fpl = pmc_blend_row(pmc_cfg)
+                if row:
+                    traffic = round(row["hbm_bytes"] * frame_batch / fpl)      # per launch of THIS run (frame_batch frames)
+                frame_traffic = pmc_cfg.get("frame_hbm_bytes")
         if args.xr:
             metric = "XR stereo frames/sec, 2 x %dx%d (2064x2208 x xrPixelRatio 0.5), one shared head-camera sort" % (W, H)
             workload = "train.splat-shaped synthetic, N=%d splats, XR stereo 2 x %dx%d, 120-frame orbit (index.html:13 pose, eyes +-32 mm)" % (n_splats, W, H)
@@ -509,73 +545,76 @@ def main():
             # what was timed, at the top level (VERDICT r5 "next" #3): the sort's form, the share of the order a frame binned and blended,
             # and the same region with whole sorts
             "sort_mode": work["sort_mode"], "near_permille": work["near_permille"],
-            "whole_sort_fps": round(whole_sort_fps, 1) if whole_sort_fps else None,
-            "sort_mode_ab": {"whole_sorts_fps": round(whole_sort_fps, 1) if whole_sort_fps else None,
-                             "default_sorts_fps": round(same_protocol_fps, 1) if same_protocol_fps else None,
-                             "note": "the timed region again after `value` was taken, best of three regions each, same process and poses: with "
-                                     "GS_OPT_SORT_NEAR = 0 (every frame the reference's whole sort) and with the library's default (sort_mode)"},
-            "cold_orbit_fps_first_lap": None,                 # filled in from secondary_measurements (single GPU)
             "occlusion_binning": {"near_permille": s["near_permille"], "unsat_tiles_last_frame": s["unsat_tiles"],
                                   "timed_region_retries": retries},
-            "msplat_frags_per_s": round(total_frags / 1e6 / elapsed, 1),
-            "frags_per_frame": round(total_frags / K),
-            "frags_evaluated_per_frame": round(evaluated_per_frame),
-            "msplat_frags_evaluated_per_s": round(evaluated_per_frame * fps / 1e6, 1),
-            "frags_evaluated_share": round(evaluated_share, 5),
-            "per_frame": {"V_sorted": round(V), "Vp_visible": round(Vp), "I_pairs": round(I),
-                          "ms_sort": round(stage["ms_sort"] / K, 4), "ms_project": round(stage["ms_project"] / K, 4),
-                          "ms_bin": round(stage["ms_bin"] / K, 4), "ms_blend": round(stage["ms_blend"] / K, 4)},
-            "frame_hbm": {"algorithmic_bytes": round(frame_bytes), "achieved_GBps": round(frame_bytes * fps / 1e9, 1),
-                          "frac_of_peak": round(frame_bytes * fps / 1e9 / HBM_PEAK_GBS, 5),
-                          "traffic": frame_traffic, "traffic_over_algorithmic": round(frame_traffic / frame_bytes, 3) if frame_traffic else None,
-                          "traffic_GBps": round(frame_traffic * fps / 1e9, 1) if frame_traffic else None,
-                          "note": "algorithmic_bytes = SURVEY.md 8(d): (16N + 4V) + (36Vp + 4V + 32Vp) + 20 I + (36 I + 4 fb) per frame, its "
-                                  "20 I priced for (tile, splat) records through a sort; `traffic` = counter bytes (2*FETCH_SIZE + WRITE_SIZE) of "
-                                  "every paired launch of the profiled pipelined loop (k_twin / k_sort_depth_pair: two frames each) per frame (" + traffic_src + ")"},
-            "roofline": {"kernel": "k_blend", "bound": "hbm", "achieved": round(achieved, 2), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": round(achieved / HBM_PEAK_GBS, 5), "traffic": traffic, "traffic_source": traffic_src,
-                         "measured_copy_GBps": copy_peak,
-                         "note": "the contract's roof for this path is HBM (no contraction anywhere: no MFMA), and `achieved` is the "
-                                 "algorithmic 36*I + 4*fb bytes over the kernel's launch time; the kernel itself is limited by VALU "
-                                 "issue, not by memory: see roofline_valu",
-                         "bytes_per_launch": round(blend_bytes * frame_batch), "avg_launch_ms": round(blend_s * frame_batch * 1e3, 4),
-                         "frames_per_launch": frame_batch,
-                         "launches_timed": int(blend_frames),
-                         "achieved_touched": round(achieved_touched, 2), "touched_bytes_per_launch": round(touched_bytes * frame_batch),
-                         "touched_bytes_per_frame": round(touched_bytes)},
-            "roofline_valu": None,                           # filled in by secondary_measurements (single GPU)
         }
-        if extras:
-            out.update(extras)
-            out["cold_orbit_fps_first_lap"] = (extras.get("cold_orbit") or {}).get("fps_first_lap")
-        # one roofline entry per stage of the headline frame ("per kernel and per frame"), counter bytes beside them
-        try:
-            out["rooflines"] = stage_rooflines(out["per_frame"], n_splats, V, Vp, I, own_px, pmc_cfg)
-        except Exception as e:                                        # noqa: BLE001 -- an extra never costs the line
-            out.setdefault("extras_failed", {})["rooflines"] = repr(e)[:200]
-        # the other BASELINE.json configurations, each in a context of its own, as the table draws them (C4 and C5 on this ONE GPU)
-        if world == 1 and cfg_name == "C2" and not args.no_configs and not args.no_extras:
-            out["configs"] = {}
-            cs, cw = min(K, 120), args.warmup
-            for other in ("C1", "C3", "C4", "C5"):
-                try:
-                    out["configs"][other] = measure_config(other, capi, synth, BC, cs, cw, ctx.device)
-                except Exception as e:                                    # noqa: BLE001
-                    out["configs"][other] = {"error": (type(e).__name__ + ": " + str(e))[:300]}
-            # ... and the regimes of the headline scene the headline pose does not show, measured the same way (bench_configs.REGIMES;
-            # drawn and checked as benched by tests/test_as_benched.py), with the blend's lane utilisation
-            out["regimes"] = {}
-            for other in sorted(BC.REGIMES):
-                try:
-                    out["regimes"][other] = measure_config(other, capi, synth, BC, cs, cw, ctx.device, utilisation=True)
-                except Exception as e:                                    # noqa: BLE001
-                    out["regimes"][other] = {"error": (type(e).__name__ + ": " + str(e))[:300]}
+        if args.full:
+            out.update({
+                "whole_sort_fps": round(whole_sort_fps, 1) if whole_sort_fps else None,
+                "sort_mode_ab": {"whole_sorts_fps": round(whole_sort_fps, 1) if whole_sort_fps else None,
+                                 "default_sorts_fps": round(same_protocol_fps, 1) if same_protocol_fps else None,
+                                 "note": "the timed region again after `value` was taken, best of three regions each, same process and poses: with "
+                                         "GS_OPT_SORT_NEAR = 0 (every frame the reference's whole sort) and with the library's default (sort_mode)"},
+                "cold_orbit_fps_first_lap": None,                 # filled in from secondary_measurements (single GPU)
+                "msplat_frags_per_s": round(total_frags / 1e6 / elapsed, 1),
+                "frags_per_frame": round(total_frags / K),
+                "frags_evaluated_per_frame": round(evaluated_per_frame),
+                "msplat_frags_evaluated_per_s": round(evaluated_per_frame * fps / 1e6, 1),
+                "frags_evaluated_share": round(evaluated_share, 5),
+                "per_frame": {"V_sorted": round(V), "Vp_visible": round(Vp), "I_pairs": round(I),
+                              "ms_sort": round(stage["ms_sort"] / K, 4), "ms_project": round(stage["ms_project"] / K, 4),
+                              "ms_bin": round(stage["ms_bin"] / K, 4), "ms_blend": round(stage["ms_blend"] / K, 4)},
+                "frame_hbm": {"algorithmic_bytes": round(frame_bytes), "achieved_GBps": round(frame_bytes * fps / 1e9, 1),
+                              "frac_of_peak": round(frame_bytes * fps / 1e9 / HBM_PEAK_GBS, 5),
+                              "traffic": frame_traffic, "traffic_over_algorithmic": round(frame_traffic / frame_bytes, 3) if frame_traffic else None,
+                              "traffic_GBps": round(frame_traffic * fps / 1e9, 1) if frame_traffic else None,
+                              "note": "algorithmic_bytes = SURVEY.md 8(d): (16N + 4V) + (36Vp + 4V + 32Vp) + 20 I + (36 I + 4 fb) per frame, its "
+                                      "20 I priced for (tile, splat) records through a sort; `traffic` = counter bytes (2*FETCH_SIZE + WRITE_SIZE) of "
+                                      "every paired launch of the profiled pipelined loop (k_twin / k_sort_depth_pair: two frames each) per frame (" + traffic_src + ")"},
+                "roofline": {"kernel": "k_blend", "bound": "hbm", "achieved": round(achieved, 2), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                             "frac": round(achieved / HBM_PEAK_GBS, 5), "traffic": traffic, "traffic_source": traffic_src,
+                             "measured_copy_GBps": copy_peak,
+                             "note": "the contract's roof for this path is HBM (no contraction anywhere: no MFMA), and `achieved` is the "
+                                     "algorithmic 36*I + 4*fb bytes over the kernel's launch time; the kernel itself is limited by VALU "
+                                     "issue, not by memory: see roofline_valu",
+                             "bytes_per_launch": round(blend_bytes * frame_batch), "avg_launch_ms": round(blend_s * frame_batch * 1e3, 4),
+                             "frames_per_launch": frame_batch,
+                             "launches_timed": int(blend_frames),
+                             "achieved_touched": round(achieved_touched, 2), "touched_bytes_per_launch": round(touched_bytes * frame_batch),
+                             "touched_bytes_per_frame": round(touched_bytes)},
+                "roofline_valu": None,                           # filled in by secondary_measurements (single GPU)
+            })
+            if extras:
+                out.update(extras)
+                out["cold_orbit_fps_first_lap"] = (extras.get("cold_orbit") or {}).get("fps_first_lap")
+            # one roofline entry per stage of the headline frame ("per kernel and per frame"), counter bytes beside them
             try:
-                out["lane_utilisation"] = lane_utilisation(ctx, capi, cams, views, W, H, sample)
-            except Exception as e:                                        # noqa: BLE001
-                out.setdefault("extras_failed", {})["lane_utilisation"] = repr(e)[:200]
-        if world == 1 and not args.no_cpu_baseline and not args.xr:
-            out["cpu_baseline"] = cpu_baseline(rows, cams[args.warmup % ORBIT_FRAMES], synth)
+                out["rooflines"] = stage_rooflines(out["per_frame"], n_splats, V, Vp, I, own_px, pmc_cfg)
+            except Exception as e:                                        # noqa: BLE001 -- an extra never costs the line
+                out.setdefault("extras_failed", {})["rooflines"] = repr(e)[:200]
+            # the other BASELINE.json configurations, each in a context of its own, as the table draws them (C4 and C5 on this ONE GPU)
+            if world == 1 and cfg_name == "C2" and not args.no_configs and not args.no_extras:
+                out["configs"] = {}
+                cs, cw = min(K, 120), args.warmup
+                for other in ("C1", "C3", "C4", "C5"):
+                    try:
+                        out["configs"][other] = measure_config(other, capi, synth, BC, cs, cw, ctx.device)
+                    except Exception as e:                                    # noqa: BLE001
+                        out["configs"][other] = {"error": (type(e).__name__ + ": " + str(e))[:300]}
+                # ... and the regimes of the headline scene the headline pose does not show, measured the same way (bench_configs.REGIMES;
+                # drawn and checked as benched by tests/test_as_benched.py), with the blend's lane utilisation
+                out["regimes"] = {}
+                for other in sorted(BC.REGIMES):
+                    try:
+                        out["regimes"][other] = measure_config(other, capi, synth, BC, cs, cw, ctx.device, utilisation=True)
+                    except Exception as e:                                    # noqa: BLE001
+                        out["regimes"][other] = {"error": (type(e).__name__ + ": " + str(e))[:300]}
+                try:
+                    out["lane_utilisation"] = lane_utilisation(ctx, capi, cams, views, W, H, sample)
+                except Exception as e:                                        # noqa: BLE001
+                    out.setdefault("extras_failed", {})["lane_utilisation"] = repr(e)[:200]
+            if world == 1 and not args.no_cpu_baseline and not args.xr:
+                out["cpu_baseline"] = cpu_baseline(rows, cams[args.warmup % ORBIT_FRAMES], synth)
         if (args.size or args.cutout or args.splats) and not args.xr:
             out["metric"] = out["metric"].replace("@1920x1080", "@%dx%d" % (W, H)).replace("1M-splat", "%d-splat" % n_splats)
         os.write(real_stdout, (json.dumps(out) + "\n").encode())
@@ -583,6 +622,49 @@ def main():
     if world > 1:
         dist.barrier()
         dist.destroy_process_group()
+
+
+DUMP_BUDGET_BYTES = 64_000_000
+
+
+class DeviceBuffer:
+    """--dump-outputs: a device allocation of the benchmark's own, the caller's buffer the last timed step is drawn into (tight RGBA8 rows)"""
+
+    def __init__(self, capi, device, shape):
+        self.hip, self.shape = capi.hip_runtime(), tuple(int(v) for v in shape)
+        p = ctypes.c_void_p()
+        rc = self.hip.hipSetDevice(ctypes.c_int(device)) or self.hip.hipMalloc(ctypes.byref(p), ctypes.c_size_t(int(np.prod(self.shape))))
+        if rc or not p.value:
+            raise RuntimeError("hipMalloc of the --dump-outputs frame failed (%d)" % rc)
+        self.ptr = p.value
+
+    def read(self):
+        """the buffer as a uint8 array (after the frames drawn into it are complete: gs_sync)"""
+        out = np.empty(self.shape, np.uint8)
+        rc = self.hip.hipMemcpy(out.ctypes.data_as(ctypes.c_void_p), ctypes.c_void_p(self.ptr), ctypes.c_size_t(out.nbytes), ctypes.c_int(2))
+        if rc:
+            raise RuntimeError("hipMemcpy of the --dump-outputs frame failed (%d)" % rc)
+        return out
+
+    def free(self):
+        if self.ptr:
+            self.hip.hipFree(ctypes.c_void_p(self.ptr))
+            self.ptr = None
+
+
+def dump_outputs(dirname, arrays):
+    """--dump-outputs: every array as DIR/<name>.npy in float32.  An array above its share of DUMP_BUDGET_BYTES is written as a fixed,
+    seeded sample of its rows (first axis), the row indices beside it as DIR/<name>_rows.npy (float64)."""
+    os.makedirs(dirname, exist_ok=True)
+    share = DUMP_BUDGET_BYTES // max(1, len(arrays))
+    for name, a in sorted(arrays.items()):
+        a = np.asarray(a, np.float32)
+        if a.nbytes + 4096 > share:
+            row_bytes = a.nbytes // a.shape[0]
+            keep = np.sort(np.random.default_rng(1234).choice(a.shape[0], size=max(1, (share - 8192) // (row_bytes + 8)), replace=False))
+            np.save(os.path.join(dirname, name + "_rows.npy"), keep.astype(np.float64))
+            a = a[keep]
+        np.save(os.path.join(dirname, name + ".npy"), a)
 
 
 def single_process_main(args):

@@ -28,7 +28,7 @@ def run(world, port, *args, env=None):
 
 @pytest.mark.parametrize("world", [2, 3])
 def test_column_strips_over_ranks(world):
-    d, err = run(world, 29620 + world, "--steps", "6", "--warmup", "2")
+    d, err = run(world, 29620 + world, "--full", "--steps", "6", "--warmup", "2")
     assert d["n_gpus"] == world and d["steps"] == 6 and d["warmup"] == 2 and d["value"] > 0 and d["scaling"] == "strong"
     assert d["config"]["parallelism"].startswith("column strips x%d" % world) and "RCCL" in d["config"]["parallelism"]
     assert d["config"]["gathered_frame_equals_single_gpu_render"] is True
@@ -58,7 +58,7 @@ def test_sort_share_switched_on_for_long_scenes_only():
 def test_fallback_when_the_librarys_communicator_cannot_be_set_up():
     # gs_comm_init fails on ONE rank.  The run still yields a line (VERDICT r4 "next" #8: the first real multi-GPU run must, whatever breaks):
     # the last rung of the ladder -- strips gathered by torch.distributed -- labelled as the FALLBACK it is, with what was tried before it
-    d, _ = run(2, 29634, "--steps", "4", "--warmup", "2", env={"BENCH_STANDIN_COMM_FAIL": "1"})
+    d, _ = run(2, 29634, "--full", "--steps", "4", "--warmup", "2", env={"BENCH_STANDIN_COMM_FAIL": "1"})
     assert "FALLBACK" in d["config"]["parallelism"] and d["config"]["gathered_frame_equals_single_gpu_render"] is True and d["value"] > 0
     path = d["config"]["multi_gpu_path"]
     assert path[0][0].startswith("library gather") and "could not be set up" in path[0][1] and "torch.distributed" in path[-1][0] and path[-1][1] == "ok"
@@ -76,7 +76,7 @@ def test_fallback_when_the_librarys_communicator_cannot_be_set_up():
 def test_feature_ladder_steps_down_when_a_probe_fails():
     # paired gathered frames assemble a WRONG image on this "node" (stand-in): the probe notices before anything is measured, the pairs
     # are switched off, the next rung's probe passes, and the line says which rung it was measured on
-    d, _ = run(2, 29637, "--steps", "4", "--warmup", "2", env={"BENCH_STANDIN_PAIRS_BAD": "1"})
+    d, _ = run(2, 29637, "--full", "--steps", "4", "--warmup", "2", env={"BENCH_STANDIN_PAIRS_BAD": "1"})
     path = d["config"]["multi_gpu_path"]
     assert path[0][0].startswith("gathered frames paired") and "differs" in path[0][1]
     assert path[-1] == ["gathered frames, one per launch", "ok"]

@@ -72,7 +72,8 @@ def test_oracle_under_asan_and_ubsan():
     asan = subprocess.run(["gcc", "-print-file-name=libasan.so"], capture_output=True, text=True).stdout.strip()
     if not os.path.isabs(asan) or not os.path.exists(asan):
         pytest.skip("libasan.so not found")
-    env = dict(os.environ, GS_ORACLE_LIB=so, GS_ROOT=ROOT, LD_PRELOAD=asan,
+    # (the runtime goes first in the preload list; whatever the environment already preloads stays behind it)
+    env = dict(os.environ, GS_ORACLE_LIB=so, GS_ROOT=ROOT, LD_PRELOAD=":".join(p for p in (asan, os.environ.get("LD_PRELOAD")) if p),
                ASAN_OPTIONS="detect_leaks=0:abort_on_error=0:halt_on_error=1", UBSAN_OPTIONS="print_stacktrace=1:halt_on_error=1")
     r = subprocess.run([sys.executable, "-c", CHILD], capture_output=True, text=True, env=env, timeout=900)
     assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-4000:])

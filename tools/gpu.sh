@@ -25,13 +25,10 @@ job_test() { timeout ${T:-900} python -m pytest tests -m gpu -q -x -s -k "$1" 2>
 job_bench20() {
     local n=${1:-3}
     for i in $(seq 1 "$n"); do
-        timeout 600 python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-extras 2>gpurun_out/bench20_$TAG.$i.err > gpurun_out/bench20_$TAG.$i.json
-        python - "$i" <<'EOF'
-import json, sys, os
-t = os.environ.get("TAG", "r6")
-d = json.load(open("gpurun_out/bench20_%s.%s.json" % (t, sys.argv[1])))
-print("steps20", d["value"], "steady", d["config"].get("steady_state_fps"), "region_ms", d["config"].get("region_ms"), "sort_mode", d["config"].get("sort_mode"))
-EOF
+        timeout 600 python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-extras 2>/dev/null | python -c '
+import json, sys
+d = json.loads(sys.stdin.read())
+print("steps20", d["value"], "steady", d["config"].get("steady_state_fps"), "region_ms", d["config"].get("region_ms"), "sort_mode", d["config"].get("sort_mode"))'
     done
 }
 job_bench() { timeout ${T:-1500} python bench.py "$@" 2>gpurun_out/bench_$TAG.err > gpurun_out/bench_$TAG.json; tail -c 600 gpurun_out/bench_$TAG.json; }
@@ -69,7 +66,7 @@ job_cumask() {   # CU-masked lane streams: needs the library built with tools/ex
     # the C2 driver form with the two best of them, and the per-queue timeline of one
     for v in "" "GS_LANE_CUS=11,11,10" "GS_BLEND_CUS=24"; do
         echo "== bench.py --steps 20 --warmup 5 :: ${v:-no mask}" | tee -a gpurun_out/cumask_$tag.txt
-        for i in 1 2 3; do env $v timeout 200 python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-extras 2>/dev/null | python -c "import json,sys; d=json.loads(sys.stdin.read()); print('steps20', d['value'], 'steady', d['config'].get('steady_state_fps'))" | tee -a gpurun_out/cumask_$tag.txt; done
+        for i in 1 2 3; do env $v timeout 200 python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-extras 2>/dev/null | python -c "import json,sys; d=json.loads(sys.stdin.read()); print('steps20', d['value'], 'steady', d['config'].get('steady_state_fps'))"; done
     done
 }
 job_variants() {   # every csrc/libgs_variant_*.so (tools/build_render_variant.sh) next to the product: stage_bench with the given args
