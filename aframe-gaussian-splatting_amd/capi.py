@@ -24,6 +24,7 @@ OPT_AUTO_RETRY = 13
 OPT_SORT_SHARE = 15
 OPT_BINNING = 16
 OPT_SUBTILE = 17
+OPT_ROW_WALK = 18
 TRANSPORT_RCCL, TRANSPORT_INPROC = 0, 1
 COMM_ID_BYTES = 128
 BUF_CENTER_SCALE, BUF_COV_COLOR, BUF_SORT_ROWS, BUF_SORTED, BUF_PROJECTED, BUF_TILE_COUNT, BUF_TILE_STATS, BUF_UNSAT_MASK = 0, 1, 2, 3, 4, 5, 6, 7
@@ -59,7 +60,7 @@ class Stats(C.Structure):
                 ("sum_ms_blend", C.c_float), ("acc_frames", C.c_uint64), ("acc_sorted", C.c_uint64), ("acc_visible", C.c_uint64),
                 ("acc_pairs", C.c_uint64), ("unsat_tiles", C.c_uint32), ("near_permille", C.c_uint32),
                 ("sort_records", C.c_uint32), ("retried_frames", C.c_uint32), ("spec_sorts", C.c_uint32), ("spec_misses", C.c_uint32), ("need_splats", C.c_uint32),
-                ("sort_mode", C.c_uint32), ("subtile", C.c_uint32)]
+                ("sort_mode", C.c_uint32), ("subtile", C.c_uint32), ("row_walk", C.c_uint32)]
 
     def as_dict(self):
         return {n: getattr(self, n) for n, _ in self._fields_}

@@ -974,7 +974,7 @@ GS_API int gs_create(int device, gs_ctx **out)
     if (!ctx) { snprintf(g_create_err, sizeof g_create_err, "out of host memory"); return GS_E_OOM; }
     memset(ctx, 0, sizeof *ctx);
     ctx->device = device; ctx->renderable = true; ctx->t_eps = 1.0f / 1024.0f; ctx->near_frac = 0.25f;
-    ctx->lanes[0] = ctx; ctx->pipe_depth = 3; ctx->enqueue_threads = true; ctx->frame_batch = 1; ctx->exec = ctx; ctx->sort_near_opt = 1; ctx->auto_retry = true; ctx->subtile_opt = 1;
+    ctx->lanes[0] = ctx; ctx->pipe_depth = 3; ctx->enqueue_threads = true; ctx->frame_batch = 1; ctx->exec = ctx; ctx->sort_near_opt = 1; ctx->auto_retry = true; ctx->subtile_opt = 1; ctx->row_walk_opt = 1;
     { const char *e = getenv("GS_SPEC_STASH"); ctx->near_spec_opt = !(e && e[0] == '0'); }   // (A/B: near-only sorts without the speculative stash)
 #define CREATE_HIP(call) do { hipError_t _e = (call); if (_e != hipSuccess) {                                              \
         snprintf(g_create_err, sizeof g_create_err, "%s failed: %s", #call, hipGetErrorString(_e)); gs_destroy(ctx);      \
@@ -1342,6 +1342,14 @@ int gs_sort_by_call(gs_ctx *ctx, const float view[4], const float *cutout16, voi
     return gs_sort_call_issue(ctx, call_p);
 }
 
+// GS_OPT_ROW_WALK = 1 walks the rows in frames that follow a collected frame whose visible splats touched at least GS_ROW_WALK_RATIO tiles
+// each on average and whose tile rows held at most GS_ROW_WALK_RUNS runs each (docs/LAB_NOTES.md, round 7: the measurements)
+#ifndef GS_ROW_WALK_RATIO
+#define GS_ROW_WALK_RATIO 32.0
+#endif
+#ifndef GS_ROW_WALK_RUNS
+#define GS_ROW_WALK_RUNS 8192.0
+#endif
 int gs_fill_uniforms(gs_ctx *ctx /* owner: options, adaptive share, scene */, const gs_render_params *p, GsFrameUniforms &u)
 {
     if (!p) FAIL(GS_E_BADARG, "render params NULL");
@@ -1378,6 +1386,18 @@ int gs_fill_uniforms(gs_ctx *ctx /* owner: options, adaptive share, scene */, co
     // sub-tile lists in the blend (GS_OPT_SUBTILE): where the last collected frame's visible splats touched few tiles each
     static const double subtile_ratio = getenv("GS_SUBTILE_RATIO") ? atof(getenv("GS_SUBTILE_RATIO")) : 16.0;
     u.subtile = ctx->subtile_opt == 2 ? 1u : (ctx->subtile_opt == 1 && ctx->last_visible && (double)ctx->last_pairs < subtile_ratio * (double)ctx->last_visible ? 1u : 0u);
+    // row walk in the blend (GS_OPT_ROW_WALK): where the last collected frame's visible splats were large (a tile's nearest runs mostly
+    // cover it: the walk finds its entries in few steps) and its tile rows held few runs; never with sub-tile lists (small splats)
+    // (GS_ROW_WALK_RATIO / GS_ROW_WALK_RUNS in the environment override the two bounds)
+    static const double walk_ratio = getenv("GS_ROW_WALK_RATIO") ? atof(getenv("GS_ROW_WALK_RATIO")) : GS_ROW_WALK_RATIO;
+    static const double walk_runs = getenv("GS_ROW_WALK_RUNS") ? atof(getenv("GS_ROW_WALK_RUNS")) : GS_ROW_WALK_RUNS;
+    const uint32_t runs = __atomic_load_n(&ctx->run_hint, __ATOMIC_RELAXED);
+    u.row_walk = ctx->row_walk_opt == 2 ? 1u : (ctx->row_walk_opt == 1 && !u.subtile && ctx->last_visible && runs &&
+                                                (double)ctx->last_pairs >= walk_ratio * (double)ctx->last_visible &&
+                                                (double)runs <= walk_runs * (double)u.tiles_y ? 1u : 0u);
+    // (measurement renders, sub-tile lists and the split blend keep the tile lists)
+    if ((u.flags & GS_RENDER_COUNT_FRAGS) || u.record_staged || u.subtile || u.split_min) u.row_walk = 0;
+    u.walk_ref = 0;
     return GS_OK;
 }
 
@@ -1502,6 +1522,14 @@ int gs_lane_call(gs_ctx *ctx, bool async, std::function<int(gs_ctx *)> call, boo
     return rc != GS_OK ? rc : rc2;
 }
 
+// whether round 0 of frame `u` on lane L walks its tile rows: chosen, and the frame is binned by span lists (run_round: at most 256
+// tile columns and rows, a row-count table within its limit, not GS_OPT_BINNING = 1)
+static bool row_walk_taken(const gs_ctx *L, const GsFrameUniforms &u)
+{
+    const gs_ctx *P = gs_root(const_cast<gs_ctx *>(L));
+    return u.row_walk && P->bin_mode != 1 && u.tiles_x <= 256 && u.tiles_y <= 256 && gs_row_tables_entries(P->n, (uint32_t)u.tiles_y) != 0;
+}
+
 static int render_common(gs_ctx *ctx, const gs_render_params *p, void *device_rgba, uint8_t *host_rgba, size_t stride)
 {
     GsFrameUniforms u;
@@ -1524,6 +1552,7 @@ int gs_render_uniforms(gs_ctx *ctx, const GsFrameUniforms &u_in, void *device_rg
     if (!u.status) { u.status = &L->ctl->status_ring[L->status_seq % GS_STATUS_RING]; L->status_seq++; }
     L->status_cur = u.status;
     L->stats.subtile = u.subtile;
+    L->stats.row_walk = row_walk_taken(L, u) ? 1u : 0u;
     u.need_seed = L->need_seed_pending; L->need_seed_pending = 0;  // (a seed for the lane's need words travels with its next frame)
     bool async = (u.flags & GS_RENDER_ASYNC) && !(u.flags & GS_RENDER_COUNT_FRAGS);
     // A context that has not MEASURED its share yet (fresh, cleared, the share un-pinned) draws its first two-round frame synchronously
@@ -1895,6 +1924,10 @@ GS_API int gs_set_option(gs_ctx *ctx, int option, int64_t value)
     case GS_OPT_SUBTILE:
         if (value < 0 || value > 2) FAIL(GS_E_BADARG, "sub-tile lists: 0 (off), 1 (where splats are small) or 2 (always)");
         ctx->subtile_opt = (int)value;
+        return GS_OK;
+    case GS_OPT_ROW_WALK:
+        if (value < 0 || value > 2) FAIL(GS_E_BADARG, "row walk: 0 (off), 1 (where splats are large) or 2 (always)");
+        ctx->row_walk_opt = (int)value;
         return GS_OK;
     case GS_OPT_SORT_NEAR:
         if (value < 0 || value > 2) FAIL(GS_E_BADARG, "near-only sorts: 0 (off), 1 (scenes of 4 M splats and more) or 2 (always)");

@@ -141,6 +141,9 @@ struct GsFrameUniforms {           // per-render constants, passed by value to k
                                    // A tile's list entries are then the sorted positions themselves, else (tile, position) records
     uint32_t subtile;              // GS_OPT_SUBTILE: k_blend splits a staged batch into the lists of the tile's sixteen 4x4-pixel blocks where that
                                    // shortens the walk (gs_render.hip: same pixels either way)
+    uint32_t row_walk;             // GS_OPT_ROW_WALK: round 0 of a span-list frame builds no tile lists; blend<0> collects each tile's entries from
+                                   // its tile row's runs (gs_render.hip: the same entries in the same order)
+    uint32_t walk_ref;             // (set by the launch path) run_ref = run_geom + walk_ref: where the runs' sorted positions follow their geometry
 };
 
 struct GsLaneWorker;
@@ -239,6 +242,7 @@ struct gs_ctx {
     int *seg_diff;                          // ... and per k_lists item (tile row, segment of its runs) the segment's difference array over the tile columns
     int bin_mode;                           // owner: GS_OPT_BINNING
     int subtile_opt;                        // owner: GS_OPT_SUBTILE (0 off, 1 where the last collected frames' splats were small, 2 always)
+    int row_walk_opt;                       // owner: GS_OPT_ROW_WALK (0 off, 1 where the last collected frames' splats were large, 2 always)
     uint32_t last_pairs, last_visible;      // owner: I and Vp of the last collected frame (what GS_OPT_SUBTILE = 1 decides on)
     uint2 *tile_range; size_t tile_cap;     // per tile [start,end) into the sorted pair list
     uint8_t *fb; size_t fb_cap;             // RGBA8 strip

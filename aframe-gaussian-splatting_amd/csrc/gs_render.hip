@@ -590,13 +590,18 @@ __global__ __launch_bounds__(GS_BLOCK) void k_tile_ranges(const uint2 *__restric
 //   k_emit_runs          per chunk: the runs again, each written to ITS ROW's segment of the run arrays at
 //                        start(row) + runs before the chunk + rank inside the chunk.  The rank -- how many earlier positions of
 //                        the chunk touch the same row -- comes from a 256-bit occupancy word per tile row that the chunk's
-//                        threads OR their bit into: order-free to build, a popcount to read
+//                        threads OR their bit into: order-free to build, a popcount to read.  Block 0 also keeps the round's
+//                        bookkeeping in the control block (what k_pairs_check does for the pair records) and leaves every tile
+//                        row's (first run, runs) behind row_tot (what the row walk below reads)
 //   k_seg_count          item = (tile row, segment of its runs): the segment's difference array over the tile columns (+1 at a run's
 //                        first column, -1 behind its last), one row of ints per item
 //   k_lists              same items: per-column counts of the runs BEFORE the segment and of ALL the row's runs from the rows of
 //                        k_seg_count (added up, one prefix sum) -> the tiles' ranges and each column's write cursor; then the
-//                        walk.  Also the round's bookkeeping in the control block (what k_pairs_check does for the pair
-//                        records): block 0.
+//                        walk.
+// Row walk (GS_OPT_ROW_WALK, round 0 of plain frames): neither k_seg_count nor k_lists runs.  A tile's list is exactly the runs of
+// its row that cover its column, in run order, and blend<0> -- which reads a list from its end (nearest first) and stops where
+// the tile saturates -- collects those entries itself from the end of its row's runs (k_blend_body): most of a list is never
+// read (early termination: a quarter of the headline frame's entries are evaluated), so most of it need not be written.
 // ROUND 1 counts, ranks and appends only tiles whose bit is set in the unsaturated-tile mask (a run stays one record; its
 // columns are filtered by the walk).  Tile lists hold the sorted positions themselves (GsFrameUniforms::rc_stride != 0 says so).
 #ifndef GS_LIST_SEG
@@ -695,6 +700,46 @@ __global__ __launch_bounds__(GS_BLOCK) void k_row_scan(uint32_t *__restrict__ ro
     k_row_scan_body<ROUND>(row_cnt, row_tot, ctl, near_count, rc_stride, tiles_y, mask, mask_words);
 }
 
+// The round's books in the control block (what k_pairs_check does for the pair records), kept by block 0 of k_emit_runs once the
+// row totals are final: I = the round's tiles (64 bits), runs = its tile-row runs.  (Until round 7 block 0 of k_lists kept them;
+// frames whose blend walks the row runs launch no k_lists.)
+template <int ROUND>
+__device__ __forceinline__ void round_books(GsControl *ctl, unsigned long long I, uint32_t runs, uint32_t j_lo, uint32_t j_hi, uint32_t near_count,
+                                            const uint32_t *__restrict__ part_vis, uint32_t nparts, int last_round, uint32_t pair_cap)
+{
+    __shared__ uint32_t s_vis;
+    const uint32_t tid = threadIdx.x;
+    const int lane = threadIdx.x & 63;
+    if (tid == 0) s_vis = 0;
+    __syncthreads();
+    uint32_t v = 0;
+    if (j_hi > j_lo) for (uint32_t i = tid; i < nparts; i += GS_BLOCK) v += part_vis[i];
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
+    if (lane == 0 && v) atomicAdd(&s_vis, v);
+    __syncthreads();
+    if (tid == 0) {
+        const uint32_t total = I > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)I;
+        ctl->vis_total = 0; ctl->n_emit_extra = 0;
+        ctl->n_runs = (ROUND == 0 ? 0u : ctl->n_runs) + runs;   // runs of the frame (a hint for the next frames: k_seg_count or not, the row walk or not)
+        if (ROUND == 0) { ctl->n_visible = 0; ctl->n_pairs_frame = 0; ctl->want_frame = 0; }
+        else { ctl->unsat_round0 = ctl->unsat_count; if (ctl->unsat_count) ctl->unsat_events += 1; }
+        ctl->j_lo = j_lo; ctl->j_hi = j_hi;                      // blend<1> returns at once when nothing was left for round 1
+        ctl->scan_total = total;
+        ctl->want_frame = (ctl->want_frame + total < total) ? 0xFFFFFFFFu : ctl->want_frame + total;   // (saturating)
+        if (ctl->want_frame > ctl->max_total) ctl->max_total = ctl->want_frame;
+        if (total > pair_cap) { ctl->pair_overflow = 1; ctl->overflow_sticky = 1; ctl->n_pairs = 0; }
+        else if (ROUND == 0) { ctl->pair_overflow = 0; ctl->n_pairs = total; }
+        else ctl->n_pairs = ctl->pair_overflow ? 0u : total;
+        ctl->n_visible += s_vis; ctl->n_pairs_frame += ctl->n_pairs;
+        if (ROUND == 0 && near_count != 0xFFFFFFFFu) ctl->unsat_count = 0;   // counted by blend<0>, read by round 1
+        if (last_round) {
+            ctl->acc_frames += 1; ctl->acc_sorted += ctl->n_kept; ctl->acc_visible += ctl->n_visible; ctl->acc_pairs += ctl->n_pairs_frame;
+        }
+    }
+    __syncthreads();
+}
+
 // The runs of one chunk of 256 sorted positions, each to its tile row's segment (see above).  The traversal is k_project's:
 // splats of one or two tile rows by their own thread, of up to 16 rows by 16 lanes, beyond by a wavefront -- twice, once to build
 // the occupancy words and once to write.
@@ -703,7 +748,8 @@ __device__ __forceinline__ void k_emit_runs_body(const gsm::Projected *__restric
                                                  const uint32_t *__restrict__ tile_count, const uint32_t *__restrict__ row_cnt,
                                                  const uint2 *__restrict__ row_tot, const GsFrameUniforms &u,
                                                  uint32_t *__restrict__ run_geom, uint32_t *__restrict__ run_ref,
-                                                 const uint32_t *__restrict__ mask, const GsControl *ctl, uint32_t pair_cap)
+                                                 const uint32_t *__restrict__ mask, GsControl *ctl, uint32_t pair_cap, uint2 *__restrict__ row_runs,
+                                                 const uint32_t *__restrict__ part_vis, uint32_t nparts, int last_round)
 {
     __shared__ float s_rec[GS_BLOCK][6];
     __shared__ uint32_t s_rows[GS_BLOCK], s_t[GS_BLOCK];            // queued splats: first | last << 16 tile row, thread (= position in the chunk)
@@ -714,13 +760,18 @@ __device__ __forceinline__ void k_emit_runs_body(const gsm::Projected *__restric
     const uint32_t tid = threadIdx.x;
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
     const uint32_t tiles_y = (uint32_t)u.tiles_y;
-    {
-        const unsigned long long I = row_prefixes<false>(row_tot, tiles_y, s_rowrun, s_rowpair, nullptr, s_p);   // first run of every tile row
-        // a round that does not fit the buffers (or follows one of this frame that did not) bins nothing: k_lists flags the frame
-        if (I > pair_cap || (ROUND == 1 && ctl->pair_overflow)) return;
-    }
+    const unsigned long long I = row_prefixes<false>(row_tot, tiles_y, s_rowrun, s_rowpair, nullptr, s_p);   // first run of every tile row
     uint32_t j_lo, j_hi;
     round_range<ROUND>(ctl, u.near_count, j_lo, j_hi);
+    // a round that does not fit the buffers (or follows one of this frame that did not) bins nothing: the books flag the frame
+    // (read before block 0 writes them; what they set to 1 here is a round with I > pair_cap, which returns either way)
+    const bool overflow = I > pair_cap || (ROUND == 1 && ctl->pair_overflow);
+    if (blockIdx.x == 0) {
+        round_books<ROUND>(ctl, I, s_rowrun[GS_BLOCK], j_lo, j_hi, u.near_count, part_vis, nparts, last_round, pair_cap);
+        // (first run, runs) of every tile row: where blend<0> of a row-walk frame finds a tile's entries (none when nothing was binned)
+        if (ROUND == 0 && tid < tiles_y) row_runs[tid] = make_uint2(s_rowrun[tid], overflow ? 0u : s_rowrun[tid + 1] - s_rowrun[tid]);
+    }
+    if (overflow) return;
     const uint32_t nchunks = (j_hi - j_lo + GS_BLOCK - 1) / GS_BLOCK;
     for (uint32_t c = blockIdx.x; c < nchunks; c += gridDim.x) {
         s_m[tid][0] = 0ull; s_m[tid][1] = 0ull; s_m[tid][2] = 0ull; s_m[tid][3] = 0ull;
@@ -796,9 +847,10 @@ __global__ __launch_bounds__(GS_BLOCK) void k_emit_runs(const gsm::Projected *__
                                                         const uint32_t *__restrict__ tile_count, const uint32_t *__restrict__ row_cnt,
                                                         const uint2 *__restrict__ row_tot, GsFrameUniforms u,
                                                         uint32_t *__restrict__ run_geom, uint32_t *__restrict__ run_ref,
-                                                        const uint32_t *__restrict__ mask, const GsControl *ctl, uint32_t pair_cap)
+                                                        const uint32_t *__restrict__ mask, GsControl *ctl, uint32_t pair_cap, uint2 *__restrict__ row_runs,
+                                                        const uint32_t *__restrict__ part_vis, uint32_t nparts, int last_round)
 {
-    k_emit_runs_body<ROUND>(proj, rect, tile_count, row_cnt, row_tot, u, run_geom, run_ref, mask, ctl, pair_cap);
+    k_emit_runs_body<ROUND>(proj, rect, tile_count, row_cnt, row_tot, u, run_geom, run_ref, mask, ctl, pair_cap, row_runs, part_vis, nparts, last_round);
 }
 
 // Per item of k_lists -- (tile row, segment of the row's runs) -- the difference array of the segment's runs over the tile columns
@@ -871,15 +923,14 @@ __device__ __forceinline__ unsigned long long wave_incl_scan_u64(unsigned long l
 template <int ROUND, bool SEGC>
 __device__ __forceinline__ void k_lists_body(const uint32_t *__restrict__ run_geom, const uint32_t *__restrict__ run_ref,
                                              const uint2 *__restrict__ row_tot, const int *__restrict__ seg_diff, uint32_t *__restrict__ lists, uint2 *__restrict__ tile_range,
-                                             const GsFrameUniforms &u, const uint32_t *__restrict__ mask, GsControl *ctl, uint32_t pair_cap,
-                                             const uint32_t *__restrict__ part_vis, uint32_t nparts, int last_round)
+                                             const GsFrameUniforms &u, const uint32_t *__restrict__ mask, const GsControl *ctl, uint32_t pair_cap)
 {
     __shared__ uint32_t s_rrun[GS_BLOCK + 1], s_rpair[GS_BLOCK + 1], s_item[GS_BLOCK + 1];   // prefix sums over the tile rows: runs, tiles, items
     __shared__ unsigned long long s_d[GS_BLOCK + 1];                // difference array over the tile columns: all runs of the row | runs before the segment << 32
     __shared__ __attribute__((aligned(16))) unsigned long long s_m[GS_BLOCK][4];                 // per tile column: the runs of the batch that cover it
     __shared__ uint32_t s_r[GS_BLOCK];                              // the batch's sorted positions
     __shared__ uint32_t s_off[GS_BLOCK], s_on[GS_BLOCK];            // per tile column: write cursor at the segment's start, column taken (ROUND 1: unsaturated)
-    __shared__ uint32_t s_w[4], s_vis;
+    __shared__ uint32_t s_w[4];
     __shared__ unsigned long long s_p[4];
     const uint32_t tid = threadIdx.x;
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
@@ -888,38 +939,6 @@ __device__ __forceinline__ void k_lists_body(const uint32_t *__restrict__ run_ge
     const unsigned long long I = row_prefixes<true>(row_tot, tiles_y, s_rrun, s_rpair, s_item, s_p);
     const uint32_t NI = s_item[GS_BLOCK];
     const bool overflow = I > pair_cap || (ROUND == 1 && ctl->pair_overflow);
-    uint32_t j_lo, j_hi;
-    round_range<ROUND>(ctl, u.near_count, j_lo, j_hi);
-    if (blockIdx.x == 0) {
-        // the round's bookkeeping (k_pairs_check's, for the pair records)
-        if (tid == 0) s_vis = 0;
-        __syncthreads();
-        uint32_t v = 0;
-        if (j_hi > j_lo) for (uint32_t i = tid; i < nparts; i += GS_BLOCK) v += part_vis[i];
-#pragma unroll
-        for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
-        if (lane == 0 && v) atomicAdd(&s_vis, v);
-        __syncthreads();
-        if (tid == 0) {
-            const uint32_t total = I > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)I;
-            ctl->vis_total = 0; ctl->n_emit_extra = 0;
-            ctl->n_runs = (ROUND == 0 ? 0u : ctl->n_runs) + s_rrun[GS_BLOCK];   // runs of the frame (a hint for the next frames: k_seg_count or not)
-            if (ROUND == 0) { ctl->n_visible = 0; ctl->n_pairs_frame = 0; ctl->want_frame = 0; }
-            else { ctl->unsat_round0 = ctl->unsat_count; if (ctl->unsat_count) ctl->unsat_events += 1; }
-            ctl->j_lo = j_lo; ctl->j_hi = j_hi;                      // blend<1> returns at once when nothing was left for round 1
-            ctl->scan_total = total;
-            ctl->want_frame = (ctl->want_frame + total < total) ? 0xFFFFFFFFu : ctl->want_frame + total;   // (saturating)
-            if (ctl->want_frame > ctl->max_total) ctl->max_total = ctl->want_frame;
-            if (total > pair_cap) { ctl->pair_overflow = 1; ctl->overflow_sticky = 1; ctl->n_pairs = 0; }
-            else if (ROUND == 0) { ctl->pair_overflow = 0; ctl->n_pairs = total; }
-            else ctl->n_pairs = ctl->pair_overflow ? 0u : total;
-            ctl->n_visible += s_vis; ctl->n_pairs_frame += ctl->n_pairs;
-            if (ROUND == 0 && u.near_count != 0xFFFFFFFFu) ctl->unsat_count = 0;   // counted by blend<0>, read by round 1
-            if (last_round) {
-                ctl->acc_frames += 1; ctl->acc_sorted += ctl->n_kept; ctl->acc_visible += ctl->n_visible; ctl->acc_pairs += ctl->n_pairs_frame;
-            }
-        }
-    }
     __syncthreads();
     for (uint32_t item = blockIdx.x; item < NI; item += gridDim.x) {
         uint32_t row = 0;                                            // the largest row with s_item[row] <= item
@@ -1039,10 +1058,9 @@ __device__ __forceinline__ void k_lists_body(const uint32_t *__restrict__ run_ge
 template <int ROUND, bool SEGC>
 __global__ __launch_bounds__(GS_BLOCK) void k_lists(const uint32_t *__restrict__ run_geom, const uint32_t *__restrict__ run_ref,
                                                     const uint2 *__restrict__ row_tot, const int *__restrict__ seg_diff, uint32_t *__restrict__ lists, uint2 *__restrict__ tile_range,
-                                                    GsFrameUniforms u, const uint32_t *__restrict__ mask, GsControl *ctl, uint32_t pair_cap,
-                                                    const uint32_t *__restrict__ part_vis, uint32_t nparts, int last_round)
+                                                    GsFrameUniforms u, const uint32_t *__restrict__ mask, const GsControl *ctl, uint32_t pair_cap)
 {
-    k_lists_body<ROUND, SEGC>(run_geom, run_ref, row_tot, seg_diff, lists, tile_range, u, mask, ctl, pair_cap, part_vis, nparts, last_round);
+    k_lists_body<ROUND, SEGC>(run_geom, run_ref, row_tot, seg_diff, lists, tile_range, u, mask, ctl, pair_cap);
 }
 
 // Fragment shader + blend for one 16x16 tile, ONE wavefront per tile, four horizontally adjacent pixels per lane
@@ -1142,7 +1160,13 @@ __device__ __forceinline__ uint32_t subtile_mask(const float4 ra, const float bx
 // SCENE: the opaque scene's depth buffer (fragment kept iff its window depth <= the buffer: depthTest LEQUAL,
 // depthWrite off, index.js:179-180) and/or colour image (the destination the splats are blended over).
 // SUB: with the sub-tile lists (GS_OPT_SUBTILE; a kernel of its own: the lists cost 20 vector registers, i.e. a wave per SIMD)
-template <bool COUNT, int ROUND, bool SCENE, bool SUB>
+// WALK: the row walk (GS_OPT_ROW_WALK; round 0 of plain frames): no tile lists were built.  `tile_range` is then the table of every
+// tile row's (first run, runs) and `pairs` the run geometry (first tile column | length << 16), the runs' sorted positions u.walk_ref
+// words behind it.  The wave fills each batch itself from the end of its row's runs, 64 runs per step: a ballot of the runs that cover
+// its column, compacted by mbcnt into the batch's slots; a step with more hits than free slots takes the nearest ones and the next
+// step resumes right behind the last run taken.  Batches are thus the list's batches -- same entries, same slots, same order -- and
+// the images, exits and need records are the list path's, bit for bit; the walk stops where the list walk would (every lane left).
+template <bool COUNT, int ROUND, bool SCENE, bool SUB, bool WALK = false>
 __device__ __forceinline__ void k_blend_body(const uint2 *__restrict__ tile_range, const void *__restrict__ pairs,
                                              const gsm::Projected *__restrict__ proj, const GsFrameUniforms &u,
                                              uint8_t *__restrict__ out, float4 *__restrict__ state, uint32_t *__restrict__ mask,
@@ -1154,6 +1178,8 @@ __device__ __forceinline__ void k_blend_body(const uint2 *__restrict__ tile_rang
     __shared__ float4 s_ent[3 * (GS_BLEND_BATCH + 1)];
     __shared__ float s_z[GS_BLEND_BATCH + 2];                    // their window depths (SCENE only)
     __shared__ __attribute__((aligned(16))) uint8_t s_list[SUB ? GS_SUBTILE_GROUPS * GS_SUBTILE_STRIDE : 16];   // GS_OPT_SUBTILE: per 4x4-pixel block, the batch's entries (slots) that can reach it
+    __shared__ uint32_t s_j[WALK ? GS_BLEND_BATCH : 1];          // WALK: the batch's sorted positions, by slot
+    static_assert(!WALK || (!COUNT && ROUND == 0 && !SUB), "the row walk serves round 0 of plain frames");
     const int lane = threadIdx.x;
     // (a round whose records did not fit bins nothing and this kernel draws the background: the completion word says so)
     if (blockIdx.x == 0 && lane == 0 && u.status && ctl->pair_overflow) atomicOr(u.status, 2u);
@@ -1209,14 +1235,46 @@ __device__ __forceinline__ void k_blend_body(const uint2 *__restrict__ tile_rang
     asm volatile("" : "+v"(kbig), "+v"(kone));                     // compiler builds each pair again in front of every use, 2 moves per entry)
     bool live = GS_LANE_LIVE();
     uint32_t nfr = 0, staged = 0, evaluated = 0;
-    const uint2 range = tile_range[tile];
-    if (u.split_min && range.y - range.x >= u.split_min) continue;  // a long list: k_blend_px takes the tile (GS_OPT_BLEND_SPLIT)
+    const uint2 range = WALK ? tile_range[ty] : tile_range[tile];  // the list [x, y) / WALK: the row's runs [x, x + y)
+    if (!WALK && u.split_min && range.y - range.x >= u.split_min) continue;  // a long list: k_blend_px takes the tile (GS_OPT_BLEND_SPLIT)
+    const uint32_t *__restrict__ run_geom = reinterpret_cast<const uint32_t *>(pairs), *__restrict__ run_ref = run_geom + u.walk_ref;
+    uint32_t cur = range.x + range.y;                               // WALK: the row's runs not examined yet are [range.x, cur)
     uint32_t j_mine = 0xFFFFFFFFu, nb_last = 0, e_l = 0;            // the sorted position this lane staged last / the size of the last batch / the last entry
                                                                     // of that batch this lane evaluated (GsControl::need_near)
     const uint32_t need_known = ctl->need_near[tile % GS_NEED_WORDS];   // (read now, compared at the end: a stale value only costs an atomic)
 
-    for (uint32_t end = range.y; end > range.x;) {
-        const uint32_t nb = min((uint32_t)GS_BLEND_BATCH, end - range.x);
+    for (uint32_t end = range.y; WALK ? cur > range.x : end > range.x;) {
+        uint32_t nb;
+        if (WALK) {
+            // the batch's entries: the nearest GS_BLEND_BATCH runs below the cursor that cover column tx (wave-uniform: nb, cur)
+            nb = 0;
+            do {
+                const uint32_t avail = cur - range.x;
+                bool hit = false;
+                uint32_t jr = 0;
+                if ((uint32_t)lane < avail) {
+                    const uint32_t i = cur - 1u - (uint32_t)lane, g = run_geom[i];
+                    jr = run_ref[i];
+                    hit = tx - (g & 0xFFFFu) < (g >> 16);
+                }
+                const unsigned long long bal = __ballot(hit);
+                const uint32_t pos = nb + __builtin_amdgcn_mbcnt_hi((uint32_t)(bal >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)bal, 0u));
+                if (hit && pos < GS_BLEND_BATCH) s_j[pos] = jr;
+                const uint32_t nh = (uint32_t)__popcll(bal);
+                if (nb + nh > GS_BLEND_BATCH) {
+                    // more hits than free slots: the batch ends with the run of the lane that took the last slot, and the next batch
+                    // starts right behind it
+                    const unsigned long long last = __ballot(hit && pos == GS_BLEND_BATCH - 1u);
+                    cur -= (uint32_t)__ffsll((long long)last);
+                    nb = GS_BLEND_BATCH;
+                } else {
+                    nb += nh;
+                    cur -= min(avail, 64u);
+                }
+            } while (nb < GS_BLEND_BATCH && cur > range.x);
+            if (nb == 0) break;                                     // (no run of the rest of the row covers the column)
+            __syncthreads();
+        } else nb = min((uint32_t)GS_BLEND_BATCH, end - range.x);
         staged += nb;
         nb_last = nb; e_l = 0;
         uint32_t m16 = 0;                                          // GS_OPT_SUBTILE: the 4x4-pixel blocks of the tile this lane's entry can reach
@@ -1224,7 +1282,7 @@ __device__ __forceinline__ void k_blend_body(const uint2 *__restrict__ tile_rang
         for (int h = 0; h < GS_BLEND_BATCH / 64; h++) {            // nearest first: reverse the back-to-front list
             const uint32_t slot = h * 64 + lane;
             if (slot < nb) {
-                const uint32_t j = span ? reinterpret_cast<const uint32_t *>(pairs)[end - 1 - slot] : reinterpret_cast<const uint2 *>(pairs)[end - 1 - slot].y;
+                const uint32_t j = WALK ? s_j[slot] : span ? reinterpret_cast<const uint32_t *>(pairs)[end - 1 - slot] : reinterpret_cast<const uint2 *>(pairs)[end - 1 - slot].y;
                 const float4 *src = reinterpret_cast<const float4 *>(proj + j);
                 const float4 ra = src[0], rb = src[1];
                 if (GS_BLEND_BATCH == 64) j_mine = j;
@@ -1478,19 +1536,19 @@ __device__ __forceinline__ void k_blend_body(const uint2 *__restrict__ tile_rang
         staged = evaluated;
     }
 #undef GS_LANE_LIVE
-    if (u.record_staged && lane == 0) const_cast<uint2 *>(tile_range)[tile] = make_uint2(staged, range.y - range.x);   // GS_OPT_RECORD_STAGED
+    if (!WALK && u.record_staged && lane == 0) const_cast<uint2 *>(tile_range)[tile] = make_uint2(staged, range.y - range.x);   // GS_OPT_RECORD_STAGED
     __syncthreads();                                               // s_ent is reused by the next tile of this wave
     }
 }
 
-template <bool COUNT, int ROUND, bool SCENE, bool SUB = false>
+template <bool COUNT, int ROUND, bool SCENE, bool SUB = false, bool WALK = false>
 __global__ __launch_bounds__(64) void k_blend(const uint2 *__restrict__ tile_range, const void *__restrict__ pairs,
                                               const gsm::Projected *__restrict__ proj, GsFrameUniforms u,
                                               uint8_t *__restrict__ out, float4 *__restrict__ state, uint32_t *__restrict__ mask,
                                               const float *__restrict__ zwin, const float *__restrict__ scene_depth,
                                               const uint32_t *__restrict__ scene_rgba, GsControl *ctl)
 {
-    k_blend_body<COUNT, ROUND, SCENE, SUB>(tile_range, pairs, proj, u, out, state, mask, zwin, scene_depth, scene_rgba, ctl);
+    k_blend_body<COUNT, ROUND, SCENE, SUB, WALK>(tile_range, pairs, proj, u, out, state, mask, zwin, scene_depth, scene_rgba, ctl);
 }
 
 // GS_OPT_BLEND_SPLIT: the tiles with LONG lists, four wavefronts per tile, ONE pixel per lane (wave w: tile rows 4w .. 4w+3).
@@ -1713,6 +1771,16 @@ int launch_blend(gs_ctx *ctx, const GsFrameUniforms &u, GsFrameUniforms v, uint8
     const uint32_t gb = ROUND == 1 ? (ntiles < 1024 ? ntiles : 1024) : ntiles;
     const bool scene = u.has_depth || u.has_scene_rgba;
     if ((u.flags & GS_RENDER_COUNT_FRAGS) || u.record_staged) v.split_min = 0;     // measurement renders: every tile by k_blend
+    if (ROUND == 0 && v.row_walk) {
+        // no tile lists (run_round_spans): the tiles' entries from their rows' runs; fpairs = the run geometry
+        const uint2 *rows = ctx->row_tot + GS_BLOCK;
+        if (scene) hipLaunchKernelGGL((k_blend<false, 0, true, false, true>), dim3(gb), dim3(64), 0, st, rows, fpairs, bproj, v, out, ctx->state,
+                                      ctx->unsat_mask, bzwin, ctx->scene_depth, ctx->scene_rgba, ctx->ctl);
+        else hipLaunchKernelGGL((k_blend<false, 0, false, false, true>), dim3(gb), dim3(64), 0, st, rows, fpairs, bproj, v, out, ctx->state,
+                                ctx->unsat_mask, bzwin, ctx->scene_depth, ctx->scene_rgba, ctx->ctl);
+        GS_HIP(hipGetLastError());
+        return GS_OK;
+    }
     if (v.split_min) {
         // the tiles with long lists first (the long pole): workgroups stride over all tiles' ranges and take the long ones
         const uint32_t gp = ntiles < 2048 ? ntiles : 2048;
@@ -1765,13 +1833,22 @@ int gs_ensure_row_tables(gs_ctx *ctx, size_t entries)
         ctx->row_cnt_cap = cap;
     }
     // (each table under its own check: a failed second allocation must not leave the first one vouching for both)
-    if (!ctx->row_tot) { GS_HIP(hipMalloc((void **)&ctx->row_tot, GS_BLOCK * sizeof(uint2))); ctx->row_tot_cap = GS_BLOCK; }
+    // (row_tot: (runs, tiles) per tile row, then (first run, runs) per tile row for the row walk)
+    if (!ctx->row_tot) { GS_HIP(hipMalloc((void **)&ctx->row_tot, 2 * GS_BLOCK * sizeof(uint2))); ctx->row_tot_cap = 2 * GS_BLOCK; }
     // (k_seg_count: a row of 256 ints per k_lists item; at most GS_LIST_SEGS items per tile row, at most 256 tile rows: 4.25 MB)
     if (!ctx->seg_diff) GS_HIP(hipMalloc((void **)&ctx->seg_diff, (size_t)GS_BLOCK * (GS_LIST_SEGS + 1u) * GS_BLOCK * sizeof(int)));
     return GS_OK;
 }
 
-// one round with span lists: project (+ row counts) -> row scan -> runs -> lists -> blend
+// Whether round ROUND of a span-list frame takes the row walk (GS_OPT_ROW_WALK): round 0 of a plain frame -- no fragment count, no
+// staged-entry record, no sub-tile lists, no split blend -- that the host chose it for
+template <int ROUND>
+bool row_walk_round(const GsFrameUniforms &u)
+{
+    return ROUND == 0 && u.row_walk && !(u.flags & GS_RENDER_COUNT_FRAGS) && !u.record_staged && !u.subtile && !u.split_min;
+}
+
+// one round with span lists: project (+ row counts) -> row scan -> runs -> lists -> blend (row walk: no lists)
 template <int ROUND>
 int run_round_spans(gs_ctx *ctx, const GsFrameUniforms &u, uint8_t *out, bool last_round, uint32_t g, uint32_t stride)
 {
@@ -1780,6 +1857,8 @@ int run_round_spans(gs_ctx *ctx, const GsFrameUniforms &u, uint8_t *out, bool la
     if (rcc != GS_OK) return rcc;
     GsFrameUniforms v = u;
     v.rc_stride = stride;
+    v.row_walk = row_walk_round<ROUND>(u) ? 1u : 0u;
+    v.walk_ref = (uint32_t)ctx->pair_cap;
     // the pair buffers hold the runs (geometry and sorted position of each: there are never more runs than tiles) and the lists
     uint32_t *run_geom = reinterpret_cast<uint32_t *>(ctx->pair_a), *run_ref = run_geom + ctx->pair_cap, *lists = reinterpret_cast<uint32_t *>(ctx->pair_b);
     const uint32_t pc = (uint32_t)ctx->pair_cap;
@@ -1790,7 +1869,12 @@ int run_round_spans(gs_ctx *ctx, const GsFrameUniforms &u, uint8_t *out, bool la
     hipLaunchKernelGGL(k_row_scan<ROUND>, dim3((uint32_t)u.tiles_y), dim3(GS_BLOCK), 0, st, ctx->row_cnt, ctx->row_tot, (const GsControl *)ctx->ctl, u.near_count,
                        stride, (uint32_t)u.tiles_y, ctx->unsat_mask, u.mask_words);
     hipLaunchKernelGGL(k_emit_runs<ROUND>, dim3(g), dim3(GS_BLOCK), 0, st, ctx->proj, ctx->rect, ctx->tile_count, ctx->row_cnt, ctx->row_tot, v,
-                       run_geom, run_ref, ctx->unsat_mask, (const GsControl *)ctx->ctl, pc);
+                       run_geom, run_ref, ctx->unsat_mask, ctx->ctl, pc, ctx->row_tot + GS_BLOCK, ctx->part_vis, g, last_round ? 1 : 0);
+    if (v.row_walk) {
+        GS_HIP(hipGetLastError());
+        if (ROUND == 0) GS_PROF_RECORD(ctx, 4);
+        return launch_blend<ROUND>(ctx, u, v, out, run_geom, ctx->proj, ctx->zwin);
+    }
     uint32_t gl = (uint32_t)u.tiles_y * GS_LIST_SEGS; if (gl > (ROUND == 1 ? 512u : 2048u)) gl = ROUND == 1 ? 512u : 2048u;
     // frames of many runs per tile row (many small splats: a cut-out scene, the cloud seen from outside, tiles that do not saturate)
     // count their segments in a launch of their own; frames of few (the headline pose: 3 000 per row) let every k_lists item count its
@@ -1800,10 +1884,10 @@ int run_round_spans(gs_ctx *ctx, const GsFrameUniforms &u, uint8_t *out, bool la
         hipLaunchKernelGGL(k_seg_count<ROUND>, dim3(gl), dim3(GS_BLOCK), 0, st, (const uint32_t *)run_geom, (const uint2 *)ctx->row_tot, ctx->seg_diff, v,
                            (const GsControl *)ctx->ctl, pc);
         hipLaunchKernelGGL((k_lists<ROUND, true>), dim3(gl), dim3(GS_BLOCK), 0, st, run_geom, run_ref, ctx->row_tot, (const int *)ctx->seg_diff, lists, ctx->tile_range, v,
-                           ctx->unsat_mask, ctx->ctl, pc, ctx->part_vis, g, last_round ? 1 : 0);
+                           ctx->unsat_mask, (const GsControl *)ctx->ctl, pc);
     } else
         hipLaunchKernelGGL((k_lists<ROUND, false>), dim3(gl), dim3(GS_BLOCK), 0, st, run_geom, run_ref, ctx->row_tot, (const int *)ctx->seg_diff, lists, ctx->tile_range, v,
-                           ctx->unsat_mask, ctx->ctl, pc, ctx->part_vis, g, last_round ? 1 : 0);
+                           ctx->unsat_mask, (const GsControl *)ctx->ctl, pc);
     GS_HIP(hipGetLastError());
     if (ROUND == 0) GS_PROF_RECORD(ctx, 4);
     return launch_blend<ROUND>(ctx, u, v, out, lists, ctx->proj, ctx->zwin);
@@ -1833,6 +1917,7 @@ int run_round(gs_ctx *ctx, const GsFrameUniforms &u, uint8_t *out, bool last_rou
     const int tb = bits_for(ntiles);
     GsFrameUniforms v = u;
     v.rc_stride = 0;
+    v.row_walk = 0;
     hipLaunchKernelGGL((k_project<ROUND, false>), dim3(g), dim3(GS_BLOCK), 0, st, ctx->sorted, ctx->splat, u, ctx->proj, ctx->rect,
                        ctx->tile_count, ctx->spine, ctx->part_vis, ctx->unsat_mask, ctx->zwin, ctx->ctl);
     GS_HIP(hipGetLastError());
@@ -1872,7 +1957,7 @@ template <int ROUND, bool SEGC> GS_BODY(F_lists, k_lists_body<ROUND, SEGC>);
 template <int ROUND> GS_BODY(F_pairs_check, k_pairs_check_body<ROUND>);
 template <int ROUND> GS_BODY(F_emit, k_emit_body<ROUND>);
 GS_BODY(F_tile_ranges, k_tile_ranges_body);
-template <int ROUND, bool SCENE, bool SUB> GS_BODY(F_blend, k_blend_body<false, ROUND, SCENE, SUB>);
+template <int ROUND, bool SCENE, bool SUB, bool WALK> GS_BODY(F_blend, k_blend_body<false, ROUND, SCENE, SUB, WALK>);
 template <int ROUND, bool SCENE> GS_BODY(F_blend_px, k_blend_px_body<ROUND, SCENE>);
 
 // the blend of one round for two frames (launch_blend's paired form)
@@ -1892,12 +1977,14 @@ int launch_blend2(gs_ctx *const S[2], const GsFrameUniforms &u, const GsFrameUni
                      bzwin[1], (const float *)S[1]->scene_depth, (const uint32_t *)S[1]->scene_rgba, S[1]->ctl))
     if (u.split_min) { if (scene) GS_BLENDPX2(true); else GS_BLENDPX2(false); }   // the tiles with long lists first
 #undef GS_BLENDPX2
-#define GS_BLEND2_(SC, SB) gs_twin<F_blend<ROUND, SC, SB>, 64>(gb, st,                                                                                          \
-        gs_pack_make((const uint2 *)S[0]->tile_range, fpairs[0], bproj[0], V[0], out[0], S[0]->state, S[0]->unsat_mask,         \
+#define GS_BLEND2_(SC, SB, WK) gs_twin<F_blend<ROUND, SC, SB, WK>, 64>(gb, st,                                                                                  \
+        gs_pack_make(WK ? (const uint2 *)S[0]->row_tot + GS_BLOCK : (const uint2 *)S[0]->tile_range, fpairs[0], bproj[0], V[0], out[0], S[0]->state, S[0]->unsat_mask, \
                      bzwin[0], (const float *)S[0]->scene_depth, (const uint32_t *)S[0]->scene_rgba, S[0]->ctl),                        \
-        gs_pack_make((const uint2 *)S[1]->tile_range, fpairs[1], bproj[1], V[1], out[1], S[1]->state, S[1]->unsat_mask,         \
+        gs_pack_make(WK ? (const uint2 *)S[1]->row_tot + GS_BLOCK : (const uint2 *)S[1]->tile_range, fpairs[1], bproj[1], V[1], out[1], S[1]->state, S[1]->unsat_mask, \
                      bzwin[1], (const float *)S[1]->scene_depth, (const uint32_t *)S[1]->scene_rgba, S[1]->ctl))
-#define GS_BLEND2(SC) do { if (V[0].subtile) GS_BLEND2_(SC, true); else GS_BLEND2_(SC, false); } while (0)
+    // (row walk: no tile lists -- the rows' run tables and fpairs = the run geometry; run_round_spans2)
+#define GS_BLEND2(SC) do { if (ROUND == 0 && V[0].row_walk) GS_BLEND2_(SC, false, (ROUND == 0)); else if (V[0].subtile) GS_BLEND2_(SC, true, false); \
+                           else GS_BLEND2_(SC, false, false); } while (0)
     if (scene) GS_BLEND2(true); else GS_BLEND2(false);
 #undef GS_BLEND2
 #undef GS_BLEND2_
@@ -1915,7 +2002,7 @@ int run_round_spans2(gs_ctx *const S[2], const GsFrameUniforms U[2], uint8_t *co
     hipStream_t st = ctx->stream;
     for (int k = 0; k < 2; k++) { const int rcc = gs_ensure_row_tables(S[k], (size_t)stride * (size_t)u.tiles_y); if (rcc != GS_OK) return rcc; }
     GsFrameUniforms V[2] = { U[0], U[1] };
-    for (int k = 0; k < 2; k++) V[k].rc_stride = stride;
+    for (int k = 0; k < 2; k++) { V[k].rc_stride = stride; V[k].row_walk = row_walk_round<ROUND>(U[0]) ? 1u : 0u; V[k].walk_ref = (uint32_t)S[k]->pair_cap; }
     uint32_t *geom[2], *ref[2], *lists[2];
     for (int k = 0; k < 2; k++) { geom[k] = reinterpret_cast<uint32_t *>(S[k]->pair_a); ref[k] = geom[k] + S[k]->pair_cap; lists[k] = reinterpret_cast<uint32_t *>(S[k]->pair_b); }
     gs_twin<F_project<ROUND, true>, GS_BLOCK>(g, st,
@@ -1930,9 +2017,19 @@ int run_round_spans2(gs_ctx *const S[2], const GsFrameUniforms U[2], uint8_t *co
         gs_pack_make(S[1]->row_cnt, S[1]->row_tot, (const GsControl *)S[1]->ctl, U[1].near_count, stride, (uint32_t)u.tiles_y, S[1]->unsat_mask, u.mask_words));
     gs_twin<F_emit_runs<ROUND>, GS_BLOCK>(g, st,
         gs_pack_make((const gsm::Projected *)S[0]->proj, (const uint2 *)S[0]->rect, (const uint32_t *)S[0]->tile_count, (const uint32_t *)S[0]->row_cnt,
-                     (const uint2 *)S[0]->row_tot, V[0], geom[0], ref[0], (const uint32_t *)S[0]->unsat_mask, (const GsControl *)S[0]->ctl, (uint32_t)S[0]->pair_cap),
+                     (const uint2 *)S[0]->row_tot, V[0], geom[0], ref[0], (const uint32_t *)S[0]->unsat_mask, S[0]->ctl, (uint32_t)S[0]->pair_cap,
+                     S[0]->row_tot + GS_BLOCK, (const uint32_t *)S[0]->part_vis, g, last_round ? 1 : 0),
         gs_pack_make((const gsm::Projected *)S[1]->proj, (const uint2 *)S[1]->rect, (const uint32_t *)S[1]->tile_count, (const uint32_t *)S[1]->row_cnt,
-                     (const uint2 *)S[1]->row_tot, V[1], geom[1], ref[1], (const uint32_t *)S[1]->unsat_mask, (const GsControl *)S[1]->ctl, (uint32_t)S[1]->pair_cap));
+                     (const uint2 *)S[1]->row_tot, V[1], geom[1], ref[1], (const uint32_t *)S[1]->unsat_mask, S[1]->ctl, (uint32_t)S[1]->pair_cap,
+                     S[1]->row_tot + GS_BLOCK, (const uint32_t *)S[1]->part_vis, g, last_round ? 1 : 0));
+    if (V[0].row_walk) {
+        GS_HIP(hipGetLastError());
+        if (ROUND == 0) GS_PROF_RECORD(ctx, 4);
+        const void *fgeom[2] = { geom[0], geom[1] };
+        const gsm::Projected *bproj[2] = { S[0]->proj, S[1]->proj };
+        const float *bzwin[2] = { S[0]->zwin, S[1]->zwin };
+        return launch_blend2<ROUND>(S, u, V, out, fgeom, bproj, bzwin);
+    }
     uint32_t gl = (uint32_t)u.tiles_y * GS_LIST_SEGS; if (gl > (ROUND == 1 ? 512u : 2048u)) gl = ROUND == 1 ? 512u : 2048u;
     const bool segc = ROUND == 0 && __atomic_load_n(&gs_root(ctx)->run_hint, __ATOMIC_RELAXED) > GS_SEGC_RUNS_PER_ROW * (uint32_t)u.tiles_y;
     if (segc)
@@ -1941,9 +2038,9 @@ int run_round_spans2(gs_ctx *const S[2], const GsFrameUniforms U[2], uint8_t *co
             gs_pack_make((const uint32_t *)geom[1], (const uint2 *)S[1]->row_tot, S[1]->seg_diff, V[1], (const GsControl *)S[1]->ctl, (uint32_t)S[1]->pair_cap));
 #define GS_LISTS2(SC) gs_twin<F_lists<ROUND, SC>, GS_BLOCK>(gl, st,                                                                                              \
         gs_pack_make((const uint32_t *)geom[0], (const uint32_t *)ref[0], (const uint2 *)S[0]->row_tot, (const int *)S[0]->seg_diff, lists[0], S[0]->tile_range, V[0], \
-                     (const uint32_t *)S[0]->unsat_mask, S[0]->ctl, (uint32_t)S[0]->pair_cap, (const uint32_t *)S[0]->part_vis, g, last_round ? 1 : 0),                \
+                     (const uint32_t *)S[0]->unsat_mask, (const GsControl *)S[0]->ctl, (uint32_t)S[0]->pair_cap),                                                    \
         gs_pack_make((const uint32_t *)geom[1], (const uint32_t *)ref[1], (const uint2 *)S[1]->row_tot, (const int *)S[1]->seg_diff, lists[1], S[1]->tile_range, V[1], \
-                     (const uint32_t *)S[1]->unsat_mask, S[1]->ctl, (uint32_t)S[1]->pair_cap, (const uint32_t *)S[1]->part_vis, g, last_round ? 1 : 0))
+                     (const uint32_t *)S[1]->unsat_mask, (const GsControl *)S[1]->ctl, (uint32_t)S[1]->pair_cap))
     if (segc) GS_LISTS2(true); else GS_LISTS2(false);
 #undef GS_LISTS2
     GS_HIP(hipGetLastError());
@@ -1974,6 +2071,7 @@ int run_round2(gs_ctx *const S[2], const GsFrameUniforms U[2], uint8_t *const ou
     const int tb = bits_for(ntiles);
     GsFrameUniforms V[2] = { U[0], U[1] };
     V[0].rc_stride = V[1].rc_stride = 0;
+    V[0].row_walk = V[1].row_walk = 0;
     gs_twin<F_project<ROUND, false>, GS_BLOCK>(g, st,
         gs_pack_make((const uint32_t *)S[0]->sorted, (const uint4 *)S[0]->splat, U[0], S[0]->proj, S[0]->rect, S[0]->tile_count, S[0]->spine, S[0]->part_vis,
                      (const uint32_t *)S[0]->unsat_mask, S[0]->zwin, S[0]->ctl),
@@ -2035,7 +2133,7 @@ bool gs_frames_batchable(const GsFrameUniforms &a, const GsFrameUniforms &b)
 {
     return a.near_count == b.near_count && a.skip_round1 == b.skip_round1 && a.W == b.W && a.H == b.H && a.x0 == b.x0 && a.x1 == b.x1 &&
            a.flags == b.flags && !(a.flags & (GS_RENDER_COUNT_FRAGS | GS_RENDER_COUNT_EVALUATED)) && !a.record_staged && !b.record_staged &&
-           a.split_min == b.split_min && a.subtile == b.subtile && a.has_depth == b.has_depth && a.has_scene_rgba == b.has_scene_rgba && a.t_eps == b.t_eps;
+           a.split_min == b.split_min && a.subtile == b.subtile && a.row_walk == b.row_walk && a.has_depth == b.has_depth && a.has_scene_rgba == b.has_scene_rgba && a.t_eps == b.t_eps;
 }
 
 int gs_run_render2(gs_ctx *const S[2], const GsFrameUniforms U[2], uint8_t *const device_out[2])

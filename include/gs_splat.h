@@ -400,6 +400,7 @@ typedef struct gs_stats {
                              forms (GS_OPT_SORT_NEAR): 1 = threshold from a depth histogram, 2 = candidates from the depth pass' own stash,
                              3 = tail sort (the segments the frame does not read neither scattered nor sorted)                       */
     uint32_t subtile;     /* 1 if the last frame's blend walked sub-tile lists (GS_OPT_SUBTILE)                                        */
+    uint32_t row_walk;    /* 1 if the last frame's first binning round built no tile lists: its blend walked the tile rows' runs (GS_OPT_ROW_WALK) */
 } gs_stats;
 
 #define GS_OPT_PROFILE 1        /* 1: bracket every stage with HIP events on the frame's stream (7 per frame); 2: only
@@ -438,6 +439,15 @@ typedef struct gs_stats {
                                    frames that follow collected frames whose visible splats touched fewer than 16 tiles each on average
                                    (GS_SUBTILE_RATIO in the environment overrides the 16); 2: always (a batch of large splats is still walked
                                    whole: the decision is per batch).                                                              */
+#define GS_OPT_ROW_WALK 18       /* how the first binning round hands a tile its entries (same pixels, bit for bit, whatever the value).  With span
+                                   lists (GS_OPT_BINNING 0) a tile's list is the runs of its tile row that cover its column, in order; the blend
+                                   reads a list from its nearest end and stops where the tile saturates, so where splats are large most of the
+                                   lists are written and never read.  With the row walk no lists are built (one launch less per frame): the
+                                   blend collects each tile's entries from its row's runs, 64 runs per step, as far as it blends.  0: never
+                                   (the lists); 1 (default): in frames that follow collected frames whose visible splats touched at least 32
+                                   tiles each on average and whose tile rows held at most 8192 runs each; 2: always.  Renders that count
+                                   fragments or record staged entries, sub-tile lists (GS_OPT_SUBTILE), the split blend (GS_OPT_BLEND_SPLIT)
+                                   and the second binning round keep the lists.                                                     */
 #define GS_OPT_ENQUEUE_THREADS 7 /* default 1: gs_sort() (without an output array) and gs_render_device(GS_RENDER_ASYNC) hand the
                                    frame to a worker thread of its pipeline lane, which does the ~18 kernel launches, so the
                                    launches of the frames in flight run in parallel; failures surface at gs_sync().  0: the
