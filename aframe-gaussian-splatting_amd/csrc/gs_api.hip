@@ -1553,6 +1553,7 @@ int gs_render_uniforms(gs_ctx *ctx, const GsFrameUniforms &u_in, void *device_rg
     L->status_cur = u.status;
     L->stats.subtile = u.subtile;
     L->stats.row_walk = row_walk_taken(L, u) ? 1u : 0u;
+    L->stats.binning = gs_round0_binning(L, u);
     u.need_seed = L->need_seed_pending; L->need_seed_pending = 0;  // (a seed for the lane's need words travels with its next frame)
     bool async = (u.flags & GS_RENDER_ASYNC) && !(u.flags & GS_RENDER_COUNT_FRAGS);
     // A context that has not MEASURED its share yet (fresh, cleared, the share un-pinned) draws its first two-round frame synchronously

@@ -414,6 +414,7 @@ int gs_run_round1(gs_ctx *ctx, const GsFrameUniforms &u, uint8_t *device_out);
 // `tiles_y` tile rows over `n` sorted positions asks for (so that a context can size them before its first queued frames)
 int gs_row_tables_ensure(gs_ctx *ctx, size_t entries);
 size_t gs_row_tables_entries(size_t n, uint32_t tiles_y);
+uint32_t gs_round0_binning(const gs_ctx *L, const GsFrameUniforms &u);   // gs_stats::binning of a frame (gs_render.hip)
 // two frames per launch (GS_OPT_FRAME_BATCH): whether two frames qualify, and the batched form of gs_run_render for those that do
 bool gs_frames_batchable(const GsFrameUniforms &a, const GsFrameUniforms &b);
 int gs_run_render2(gs_ctx *const S[2], const GsFrameUniforms U[2], uint8_t *const device_out[2]);

@@ -2126,6 +2126,15 @@ int run_round2(gs_ctx *const S[2], const GsFrameUniforms U[2], uint8_t *const ou
 int gs_row_tables_ensure(gs_ctx *ctx, size_t entries) { return gs_ensure_row_tables(ctx, entries); }
 size_t gs_row_tables_entries(size_t n, uint32_t tiles_y) { return gs_row_table_entries(n, tiles_y); }
 
+// gs_stats::binning of frame u on lane L: 1 where its first round takes the pair records (run_round: the same stride over the same
+// positions), 0 for span lists -- set per frame, also for a frame that runs no round (nothing resident): what a round would take
+uint32_t gs_round0_binning(const gs_ctx *L, const GsFrameUniforms &u)
+{
+    const uint32_t Vmax = (uint32_t)L->n;
+    const uint32_t jrange = u.near_count != 0xFFFFFFFFu && u.near_count < Vmax ? u.near_count : Vmax;
+    return span_list_stride(L, u, jrange) ? 0u : 1u;
+}
+
 // Two frames that take the same path, one launch per kernel (GS_OPT_FRAME_BATCH; grid (x, 2), blockIdx.y = the frame).  S[0], S[1]:
 // sibling lanes on ONE stream, each with its own scratch, control block and output.  Frames that count fragments or record
 // the staged depths take the per-frame path -- gs_frames_batchable() says whether two frames qualify.

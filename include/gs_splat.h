@@ -401,6 +401,9 @@ typedef struct gs_stats {
                              3 = tail sort (the segments the frame does not read neither scattered nor sorted)                       */
     uint32_t subtile;     /* 1 if the last frame's blend walked sub-tile lists (GS_OPT_SUBTILE)                                        */
     uint32_t row_walk;    /* 1 if the last frame's first binning round built no tile lists: its blend walked the tile rows' runs (GS_OPT_ROW_WALK) */
+    uint32_t binning;     /* how the last frame's first binning round binned (GS_OPT_BINNING): 0 = span lists, 1 = (tile, splat) pair records
+                             (asked for, or a strip of more than 256 tile columns or rows, or a row-count table beyond its limit); a frame
+                             that runs no round (nothing resident) reports what its round would have taken                             */
 } gs_stats;
 
 #define GS_OPT_PROFILE 1        /* 1: bracket every stage with HIP events on the frame's stream (7 per frame); 2: only

@@ -43,6 +43,40 @@ def pix_check(tag, got, want, tol=PIXEL_TOL_LSB):
     return rep
 
 
+# The blend paths, each forced by options (nothing left to the per-frame automatic choices) and proven by the statistics of the frame
+# that ran it: a test that names a path fails if the library silently drew that frame another way.
+PATH_OPTIONS = {
+    "lists": {capi.OPT_BINNING: 0, capi.OPT_ROW_WALK: 0, capi.OPT_SUBTILE: 0},
+    "walk": {capi.OPT_BINNING: 0, capi.OPT_ROW_WALK: 2, capi.OPT_SUBTILE: 0},
+    "subtile": {capi.OPT_BINNING: 0, capi.OPT_ROW_WALK: 0, capi.OPT_SUBTILE: 2},
+    "pairs": {capi.OPT_BINNING: 1, capi.OPT_ROW_WALK: 0, capi.OPT_SUBTILE: 0},
+    "split": {capi.OPT_BINNING: 0, capi.OPT_ROW_WALK: 0, capi.OPT_SUBTILE: 0, capi.OPT_BLEND_SPLIT: 1},
+}
+PATH_PROOF = {
+    "lists": {"row_walk": 0, "subtile": 0, "binning": 0},
+    "walk": {"row_walk": 1, "subtile": 0, "binning": 0},
+    "subtile": {"row_walk": 0, "subtile": 1},
+    "pairs": {"row_walk": 0, "binning": 1},
+    "split": {"row_walk": 0, "subtile": 0},
+}
+
+
+def force_path(c, path, near_permille=1000):
+    """Set the options of a named blend path on context c; near_permille: GS_OPT_NEAR_PERMILLE (1000: one binning round, 0: the
+    adaptive share of the default options)."""
+    c.set_option(capi.OPT_NEAR_PERMILLE, near_permille)
+    for k, v in PATH_OPTIONS[path].items():
+        c.set_option(k, v)
+
+
+def assert_path(c, path, tag=""):
+    """The last frame of context c ran the named path (gs_stats: row_walk, subtile, binning)."""
+    st = c.stats()
+    got = {k: st[k] for k in PATH_PROOF[path]}
+    assert got == PATH_PROOF[path], (tag, path, got)
+    return st
+
+
 @pytest.fixture(scope="module")
 def ctx():
     c = capi.Context(0)
@@ -1155,7 +1189,9 @@ def test_pack_fuzz_random_bytes_match_oracle(ctx, seed):
 @pytest.mark.parametrize("seed", range(4))
 def test_render_fuzz_random_scenes_match_oracle(ctx, seed):
     """Random small scenes rendered from random orbit poses at odd resolutions: identical fragment counts, pixels within
-    the tolerance, for full frames and a 4-aligned strip."""
+    the tolerance, for full frames and a 4-aligned strip -- first with the default options (the adaptive share: two binning rounds;
+    the automatic path choices), then once per forced blend path (lists, row walk, sub-tile lists, pair records) on a fresh context,
+    the share still adaptive, each frame's path proven by its statistics."""
     g = np.random.Generator(np.random.PCG64(3000 + seed))
     n = int(g.choice([1, 50, 3000, 20000]))
     rows = synth.make_splat_rows(n, seed=3100 + seed)
@@ -1174,6 +1210,20 @@ def test_render_fuzz_random_scenes_match_oracle(ctx, seed):
     x0 = 4 * int(g.integers(0, w // 8 + 1)); x1 = int(g.integers(x0 + 1, w + 1))
     part = ctx.render(_params(cam, x0=x0, x1=x1))
     assert np.array_equal(part, got[:, x0:x1])
+    for path in ("lists", "walk", "subtile", "pairs"):
+        with capi.Context(0) as c:
+            force_path(c, path, near_permille=0)                            # (0: the adaptive share, as by default)
+            c.push_splat(rows)
+            assert np.array_equal(c.sort(cam["view"]), idx)
+            img = c.render(_params(cam))
+            assert_path(c, path, seed)
+            assert np.array_equal(img, got), path                          # every path draws the default frame, bit for bit
+            c.render(_params(cam, flags=capi.RENDER_COUNT_FRAGS))
+            assert c.stats()["n_frags"] == frags, path
+            assert c.stats()["row_walk"] == 0, path                         # (counting renders keep the lists)
+            part = c.render(_params(cam, x0=x0, x1=x1))
+            assert_path(c, path, (seed, x0, x1))
+            assert np.array_equal(part, got[:, x0:x1]), path
 
 
 def test_stream_coupling_calls_order_frames_with_caller_streams(scene_small):
