@@ -25,9 +25,11 @@ OPT_SORT_SHARE = 15
 OPT_BINNING = 16
 OPT_SUBTILE = 17
 OPT_ROW_WALK = 18
+OPT_SH_DEGREE = 19
 TRANSPORT_RCCL, TRANSPORT_INPROC = 0, 1
 COMM_ID_BYTES = 128
 BUF_CENTER_SCALE, BUF_COV_COLOR, BUF_SORT_ROWS, BUF_SORTED, BUF_PROJECTED, BUF_TILE_COUNT, BUF_TILE_STATS, BUF_UNSAT_MASK = 0, 1, 2, 3, 4, 5, 6, 7
+BUF_SH = 8
 
 EXPORTS = [
     "gs_create", "gs_destroy", "gs_last_error", "gs_version", "gs_device_count", "gs_clear", "gs_push_splat", "gs_push_matrices", "gs_load_ply",
@@ -40,6 +42,7 @@ EXPORTS = [
     "gs_create_multi", "gs_multi_destroy", "gs_multi_last_error", "gs_multi_devices", "gs_multi_ctx", "gs_multi_clear",
     "gs_multi_push_splat", "gs_multi_load_ply", "gs_multi_count", "gs_multi_set_option", "gs_multi_sort", "gs_multi_render",
     "gs_multi_render_device", "gs_multi_read", "gs_multi_sync",
+    "gs_ply_sh", "gs_ply_sh_host", "gs_push_sh", "gs_sh_count", "gs_sh_eval", "gs_sh_eval_unrounded", "gs_camera_in_object", "gs_multi_push_sh",
 ]
 
 
@@ -61,7 +64,7 @@ class Stats(C.Structure):
                 ("acc_pairs", C.c_uint64), ("unsat_tiles", C.c_uint32), ("near_permille", C.c_uint32),
                 ("sort_records", C.c_uint32), ("retried_frames", C.c_uint32), ("spec_sorts", C.c_uint32), ("spec_misses", C.c_uint32), ("need_splats", C.c_uint32),
                 ("sort_mode", C.c_uint32), ("subtile", C.c_uint32), ("row_walk", C.c_uint32),
-                ("binning", C.c_uint32)]
+                ("binning", C.c_uint32), ("sh_degree", C.c_uint32)]
 
     def as_dict(self):
         return {n: getattr(self, n) for n, _ in self._fields_}
@@ -164,6 +167,15 @@ def load(build_if_missing=True):
     L.gs_scaled_size.argtypes = [i32, i32, C.c_double, C.POINTER(i32), C.POINTER(i32)]; L.gs_scaled_size.restype = None
     L.gs_set_option.argtypes = [vp, i32, C.c_int64]
     L.gs_get_stats.argtypes = [vp, C.POINTER(Stats)]
+    if hasattr(L, "gs_push_sh"):                               # (an older build loaded through GS_SPLAT_LIB for an A/B run has none)
+        L.gs_ply_sh.argtypes = [vp, vp, sz, i32, vp, C.POINTER(sz), C.POINTER(i32)]
+        L.gs_ply_sh_host.argtypes = [vp, sz, i32, vp, C.POINTER(sz), C.POINTER(i32), C.c_char_p, sz]
+        L.gs_push_sh.argtypes = [vp, vp, sz, i32]
+        L.gs_multi_push_sh.argtypes = [vp, vp, sz, i32]
+        L.gs_sh_count.argtypes = [vp, C.POINTER(sz), C.POINTER(i32)]
+        L.gs_sh_eval.argtypes = [vp, i32, vp, vp, vp]
+        L.gs_sh_eval_unrounded.argtypes = [vp, i32, vp, vp, vp]
+        L.gs_camera_in_object.argtypes = [vp, vp]
     L.gs_download.argtypes = [vp, i32, vp, sz]
     L.gs_comm_unique_id.argtypes = [vp, vp]
     L.gs_comm_init.argtypes = [vp, vp, i32, i32]
@@ -279,6 +291,61 @@ def ply_to_splat(ply_bytes):
     return out
 
 
+def _sh_rows(sh_rows, degree):
+    k = 3 * (int(degree) + 1) ** 2
+    rows = np.ascontiguousarray(sh_rows, np.float32).reshape(-1)
+    if rows.size % k:
+        raise ValueError("SH rows of degree %d are %d floats each" % (degree, k))
+    return rows, rows.size // k
+
+
+def ply_sh(ply_bytes, degree=3, ctx=None):
+    """The SH rows of a PLY in the converter's row order -> (float32[n, 3 (D+1)^2], D); D = min(degree, what the file carries),
+    (empty, -1) for a file without usable coefficients.  ctx: a Context (gs_ply_sh) or None (gs_ply_sh_host)."""
+    buf = np.frombuffer(bytes(ply_bytes), np.uint8)
+    n = C.c_size_t(0); d = C.c_int(-1); err = C.create_string_buffer(256)
+
+    def call(out):
+        if ctx is not None:
+            ctx._ck(load().gs_ply_sh(ctx._h, _p(buf), buf.size, int(degree), out, C.byref(n), C.byref(d)))
+            return
+        rc = load().gs_ply_sh_host(_p(buf), buf.size, int(degree), out, C.byref(n), C.byref(d), err, 256)
+        if rc != GS_OK:
+            raise GsError(rc, err.value.decode())
+
+    call(None)
+    if d.value < 0:
+        return np.zeros((0, 0), np.float32), -1
+    out = np.zeros((n.value, 3 * (d.value + 1) ** 2), np.float32)
+    if n.value:
+        call(_p(out))
+    return out, d.value
+
+
+def sh_eval(sh_row, degree, cam, pos, unrounded=False):
+    """gs_sh_eval: one SH row (3 (degree+1)^2 f32, channel-major), camera (f64 x3) and position (f32 x3) in object space -> uint8[3]
+    (unrounded=True: the three f64 values before the byte rounding, in units of one colour byte)."""
+    row, n = _sh_rows(sh_row, degree)
+    if n != 1:
+        raise ValueError("one row expected")
+    cam = np.ascontiguousarray(cam, np.float64).reshape(3); pos = np.ascontiguousarray(pos, np.float32).reshape(3)
+    out = np.zeros(3, np.float64 if unrounded else np.uint8)
+    rc = (load().gs_sh_eval_unrounded if unrounded else load().gs_sh_eval)(_p(row), int(degree), _p(cam), _p(pos), _p(out))
+    if rc != GS_OK:
+        raise GsError(rc, "gs_sh_eval: bad argument")
+    return out
+
+
+def camera_in_object(model_view):
+    """gs_camera_in_object: the camera position in object space (f64 x3) a frame with this model_view evaluates SH colours for."""
+    mv = np.ascontiguousarray(np.asarray(model_view, np.float32).reshape(16))
+    out = np.zeros(3, np.float64)
+    rc = load().gs_camera_in_object(_p(mv), _p(out))
+    if rc != GS_OK:
+        raise GsError(rc, "gs_camera_in_object: singular model_view")
+    return out
+
+
 def make_params(mv, proj, width, height, x0=0, x1=None, focal_=0.0, background=(0.0, 0.0, 0.0, 1.0), flags=0):
     p = RenderParams()
     p.model_view[:] = [float(v) for v in np.asarray(mv, np.float32)]
@@ -349,6 +416,24 @@ class Context:
     def load_ply(self, ply_bytes):
         buf = np.frombuffer(bytes(ply_bytes), np.uint8)
         self._ck(self._L.gs_load_ply(self._h, _p(buf), buf.size))
+
+    # view-dependent colour (GS_OPT_SH_DEGREE)
+    def push_sh(self, sh_rows, degree):
+        rows, n = _sh_rows(sh_rows, degree)
+        self._ck(self._L.gs_push_sh(self._h, _p(rows), n, int(degree)))
+
+    def ply_sh(self, ply_bytes, degree=3):
+        return ply_sh(ply_bytes, degree, ctx=self)
+
+    def sh_count(self):
+        n = C.c_size_t(0); d = C.c_int(0)
+        self._ck(self._L.gs_sh_count(self._h, C.byref(n), C.byref(d)))
+        return n.value, d.value
+
+    def download_sh(self):
+        """The SH store: float32[rows, 3 (D+1)^2] (0 rows while nothing is stored)."""
+        n, d = self.sh_count()
+        return self.download(BUF_SH, n, np.float32, 3 * (d + 1) ** 2 if n else 0)
 
     def count(self):
         return self._L.gs_count(self._h)
@@ -579,6 +664,10 @@ class Multi:
     def load_ply(self, ply_bytes):
         buf = np.frombuffer(bytes(ply_bytes), np.uint8)
         self._ck(self._L.gs_multi_load_ply(self._h, _p(buf), buf.size))
+
+    def push_sh(self, sh_rows, degree):
+        rows, n = _sh_rows(sh_rows, degree)
+        self._ck(self._L.gs_multi_push_sh(self._h, _p(rows), n, int(degree)))
 
     def count(self):
         return self._L.gs_multi_count(self._h)

@@ -13,6 +13,7 @@
 #include <vector>
 #include "gs_internal.h"
 #include "gs_ply.h"
+#include "gs_sh.h"
 #include "gs_host_tables.h"
 
 #ifndef GS_NEAR_FLOOR_MULT
@@ -1000,7 +1001,7 @@ GS_API int gs_destroy(gs_ctx *ctx)
     for (int i = GS_MAX_LANES - 1; i >= 1; i--)                  // twins before the lanes whose streams they borrow
         if (ctx->lanes[i]) { free_frame_resources(ctx->lanes[i]); delete ctx->lanes[i]; ctx->lanes[i] = nullptr; }
     free_frame_resources(ctx);
-    dev_free(ctx->splat); dev_free(ctx->sort_rows); dev_free(ctx->bound_r); dev_free(ctx->pow10tab);
+    dev_free(ctx->splat); dev_free(ctx->sort_rows); dev_free(ctx->bound_r); dev_free(ctx->pow10tab); dev_free(ctx->sh);
     dev_free(ctx->scene_depth); dev_free(ctx->scene_rgba);
     if (ctx->ev_sort) (void)hipEventDestroy(ctx->ev_sort);
     delete ctx;
@@ -1012,7 +1013,7 @@ GS_API int gs_clear(gs_ctx *ctx)
     CHECK_CTX(ctx);
     GS_HIP(hipSetDevice(ctx->device));
     TRY(drain_all(ctx));
-    ctx->n = 0; ctx->renderable = true; ctx->pair_hint = 0; ctx->run_hint = 0; ctx->last_pairs = 0; ctx->last_visible = 0;
+    ctx->n = 0; ctx->sh_n = 0; ctx->sh_deg = 0; ctx->renderable = true; ctx->pair_hint = 0; ctx->run_hint = 0; ctx->last_pairs = 0; ctx->last_visible = 0;
     ctx->near_frac = 0.25f; ctx->near_floor = 0.0f; ctx->clean_frames = 0; ctx->skip_hold = 0; ctx->single_round_frames = 0; ctx->last_kept = 0; ctx->share_measured = false; ctx->need_margin = 0.0f; ctx->cold_sorts = 0; ctx->cold_frames = 0; ctx->share_kind = 0; memset(ctx->need_hist, 0, sizeof ctx->need_hist);
     ctx->near_stash_off = false; ctx->near_spec = false; ctx->near_spec_hold = 0; ctx->near_spec_backoff = 0; ctx->near_spec_miss_credit = 0;
     for (int i = 0; i < GS_MAX_LANES; i++) {
@@ -1078,6 +1079,79 @@ GS_API int gs_push_matrices(gs_ctx *ctx, const float *matrices, size_t nrows)
     return GS_OK;
 }
 
+// ---- view-dependent colour: the SH store (gs_sh.h).  Rows parallel to the splats, owner only; a frame gets the pointer, the row
+// count and the camera through its uniforms (gs_fill_uniforms), so the lanes hold nothing.
+static int sh_ensure_capacity(gs_ctx *ctx, size_t want, int degree)
+{
+    if (want <= ctx->sh_cap) return GS_OK;
+    size_t cap = ctx->sh_cap ? ctx->sh_cap : (size_t)1 << 16;
+    while (cap < want) cap *= 2;
+    const size_t row = 3 * (size_t)gsm::sh_channel_stride(degree);
+    float *nw = nullptr;
+    TRY(dev_alloc(ctx, &nw, cap * row));
+    if (ctx->sh_n) {
+        const hipError_t e = hipMemcpy(nw, ctx->sh, ctx->sh_n * row * sizeof(float), hipMemcpyDeviceToDevice);
+        if (e != hipSuccess) { dev_free(nw); FAIL(GS_E_HIP, "copying the SH rows failed: %s", hipGetErrorString(e)); }
+    }
+    dev_free(ctx->sh);
+    ctx->sh = nw; ctx->sh_cap = cap;
+    return GS_OK;
+}
+
+GS_API int gs_push_sh(gs_ctx *ctx, const float *sh_rows, size_t nrows, int degree)
+{
+    CHECK_CTX(ctx);
+    if (degree < 1 || degree > GS_SH_MAX_DEGREE) FAIL(GS_E_BADARG, "gs_push_sh: degree must be 1..3");
+    if (ctx->sh_n && degree != ctx->sh_deg) FAIL(GS_E_BADARG, "gs_push_sh: rows of degree %d behind stored rows of degree %d", degree, ctx->sh_deg);
+    if (nrows == 0) return GS_OK;
+    if (!sh_rows) FAIL(GS_E_BADARG, "gs_push_sh: sh_rows is NULL");
+    if (ctx->sh_n + nrows > 0x7FFFFFF0ull) FAIL(GS_E_BADARG, "more than 2^31 SH rows");
+    GS_HIP(hipSetDevice(ctx->device));
+    TRY(drain_all(ctx));                                        // frames in flight read the store
+    if (!ctx->sh_n && ctx->sh_deg != degree) { dev_free(ctx->sh); ctx->sh_cap = 0; }   // (an emptied store of another row size)
+    TRY(sh_ensure_capacity(ctx, ctx->sh_n + nrows, degree));
+    // tight rows in, channels padded to whole 16-byte words in the store
+    const int K = gsm::sh_coefs(degree), KS = gsm::sh_channel_stride(degree);
+    const float *src = sh_rows;
+    std::vector<float> padded;
+    if (KS != K) {
+        try { padded.assign(nrows * 3 * (size_t)KS, 0.0f); } catch (...) { FAIL(GS_E_OOM, "out of host memory for %zu SH rows", nrows); }
+        for (size_t i = 0; i < nrows; i++)
+            for (int c = 0; c < 3; c++) memcpy(&padded[(i * 3 + c) * KS], sh_rows + (i * 3 + c) * K, (size_t)K * sizeof(float));
+        src = padded.data();
+    }
+    GS_HIP(hipMemcpy(ctx->sh + ctx->sh_n * 3 * (size_t)KS, src, nrows * 3 * (size_t)KS * sizeof(float), hipMemcpyHostToDevice));
+    ctx->sh_n += nrows; ctx->sh_deg = degree;
+    return GS_OK;
+}
+
+GS_API int gs_sh_count(const gs_ctx *ctx, size_t *out_nrows, int *out_degree)
+{
+    if (!ctx) return GS_E_BADARG;
+    if (out_nrows) *out_nrows = ctx->sh_n;
+    if (out_degree) *out_degree = ctx->sh_n ? ctx->sh_deg : 0;
+    return GS_OK;
+}
+
+GS_API int gs_ply_sh(gs_ctx *ctx, const void *bytes, size_t nbytes, int degree, float *out_sh, size_t *out_nrows, int *out_degree)
+{
+    CHECK_CTX(ctx);
+    return gs_ply_sh_host(bytes, nbytes, degree, out_sh, out_nrows, out_degree, ctx->err, sizeof ctx->err);
+}
+
+// gs_load_ply with GS_OPT_SH_DEGREE at 1..3: the file's SH rows behind the store, while the store is parallel to the splats
+static int load_ply_sh(gs_ctx *ctx, const void *bytes, size_t nbytes, size_t n_before, size_t n_loaded)
+{
+    if (ctx->sh_opt < 1 || ctx->sh_n != n_before) return GS_OK;
+    size_t n = 0; int D = -1;
+    TRY(gs_ply_sh_host(bytes, nbytes, ctx->sh_opt, nullptr, &n, &D, ctx->err, sizeof ctx->err));
+    if (D < 1 || n != n_loaded || (ctx->sh_n && D != ctx->sh_deg)) return GS_OK;
+    std::vector<float> rows;
+    try { rows.resize(n * 3 * (size_t)gsm::sh_coefs(D)); } catch (...) { FAIL(GS_E_OOM, "out of host memory for %zu SH rows", n); }
+    TRY(gs_ply_sh_host(bytes, nbytes, ctx->sh_opt, rows.data(), &n, &D, ctx->err, sizeof ctx->err));
+    return gs_push_sh(ctx, rows.data(), n, D);
+}
+
 // .ply -> .splat rows on the GPU (gs_ply.hip); rows_dev receives a device buffer of *nrows x 32 B that the caller frees.
 // A NaN importance (engine-defined order in the reference) is handed to the host converter so that there is ONE
 // definition of that case.
@@ -1116,9 +1190,11 @@ GS_API int gs_load_ply(gs_ctx *ctx, const void *bytes, size_t nbytes)
     uint4 *rows = nullptr; size_t n = 0;
     TRY(ply_rows_to_device(ctx, bytes, nbytes, &rows, &n));
     if (!n) return GS_OK;
+    const size_t n_before = ctx->n;
     int rc = ensure_capacity(ctx, ctx->n + n);
     if (rc == GS_OK) rc = append_device_rows(ctx, rows, n);         // the rows never leave HBM
     dev_free(rows);
+    if (rc == GS_OK) rc = load_ply_sh(ctx, bytes, nbytes, n_before, n);
     return rc;
 }
 
@@ -1398,6 +1474,16 @@ int gs_fill_uniforms(gs_ctx *ctx /* owner: options, adaptive share, scene */, co
     // (measurement renders, sub-tile lists and the split blend keep the tile lists)
     if ((u.flags & GS_RENDER_COUNT_FRAGS) || u.record_staged || u.subtile || u.split_min) u.row_walk = 0;
     u.walk_ref = 0;
+    // view-dependent colour (GS_OPT_SH_DEGREE): the degree the frame evaluates and the camera it evaluates for
+    u.sh_degree = 0; u.sh_n = 0; u.sh_row_q = 0; u.sh_rows = nullptr; u.sh_cam[0] = u.sh_cam[1] = u.sh_cam[2] = 0.0;
+    if (ctx->sh_opt > 0 && ctx->sh_n) {
+        u.sh_degree = (uint32_t)(ctx->sh_opt < ctx->sh_deg ? ctx->sh_opt : ctx->sh_deg);
+        u.sh_n = (uint32_t)ctx->sh_n; u.sh_row_q = 3u * (uint32_t)gsm::sh_channel_stride(ctx->sh_deg) / 4u;
+        u.sh_rows = reinterpret_cast<const uint4 *>(ctx->sh);
+        const bool regular = gsm::camera_in_object(u.mv, u.sh_cam);
+        u.sh_cam[2] = -u.sh_cam[2];                                  // model_view acts on (x, y, -z): back to the rows' space (gs_sh.h)
+        if (!regular) FAIL(GS_E_BADARG, "model_view is singular: no camera position to evaluate the spherical harmonics for");
+    }
     return GS_OK;
 }
 
@@ -1554,6 +1640,7 @@ int gs_render_uniforms(gs_ctx *ctx, const GsFrameUniforms &u_in, void *device_rg
     L->stats.subtile = u.subtile;
     L->stats.row_walk = row_walk_taken(L, u) ? 1u : 0u;
     L->stats.binning = gs_round0_binning(L, u);
+    L->stats.sh_degree = u.sh_degree;
     u.need_seed = L->need_seed_pending; L->need_seed_pending = 0;  // (a seed for the lane's need words travels with its next frame)
     bool async = (u.flags & GS_RENDER_ASYNC) && !(u.flags & GS_RENDER_COUNT_FRAGS);
     // A context that has not MEASURED its share yet (fresh, cleared, the share un-pinned) draws its first two-round frame synchronously
@@ -1930,6 +2017,10 @@ GS_API int gs_set_option(gs_ctx *ctx, int option, int64_t value)
         if (value < 0 || value > 2) FAIL(GS_E_BADARG, "row walk: 0 (off), 1 (where splats are large) or 2 (always)");
         ctx->row_walk_opt = (int)value;
         return GS_OK;
+    case GS_OPT_SH_DEGREE:
+        if (value < 0 || value > GS_SH_MAX_DEGREE) FAIL(GS_E_BADARG, "spherical-harmonics degree: 0 (off) to 3");
+        ctx->sh_opt = (int)value;
+        return GS_OK;
     case GS_OPT_SORT_NEAR:
         if (value < 0 || value > 2) FAIL(GS_E_BADARG, "near-only sorts: 0 (off), 1 (scenes of 4 M splats and more) or 2 (always)");
         GS_HIP(hipSetDevice(ctx->device));
@@ -1980,6 +2071,12 @@ GS_API int gs_download(gs_ctx *ctx, int which, void *out, size_t nbytes)
         if (nbytes > ctx->n * 16 || nbytes % 16) FAIL(GS_E_BADARG, "buffer %d holds %zu bytes, %zu requested", which, ctx->n * 16, nbytes);
         if (nbytes) GS_HIP(hipMemcpy2D(out, 16, (const char *)ctx->splat + (which == GS_BUF_COV_COLOR ? 16 : 0), 32, 16, nbytes / 16,
                                         hipMemcpyDeviceToHost));
+        return GS_OK;
+    }
+    if (which == GS_BUF_SH) {                                    // tight rows out of the padded store
+        const size_t K = (size_t)gsm::sh_coefs(ctx->sh_deg), KS = (size_t)gsm::sh_channel_stride(ctx->sh_deg);
+        if (nbytes > ctx->sh_n * 3 * K * 4 || nbytes % (K * 4)) FAIL(GS_E_BADARG, "buffer %d holds %zu bytes, %zu requested", which, ctx->sh_n * 3 * K * 4, nbytes);
+        if (nbytes) GS_HIP(hipMemcpy2D(out, K * 4, ctx->sh, KS * 4, K * 4, nbytes / (K * 4), hipMemcpyDeviceToHost));
         return GS_OK;
     }
     switch (which) {

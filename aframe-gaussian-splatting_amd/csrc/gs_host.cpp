@@ -1,7 +1,9 @@
 // gs_host.cpp -- host-side pieces of the boundary that are not on the per-frame GPU path:
 //   * the uniform producers (tick / getModelViewMatrix / getProjectionMatrix, index.js:438-487): a dozen 4x4
 //     f64 operations per frame, in three.js' operation order so the f32 uniforms match the reference's;
-//   * processPlyBuffer (index.js:600-745): the one-time .ply -> .splat row conversion.
+//   * processPlyBuffer (index.js:600-745): the one-time .ply -> .splat row conversion;
+//   * view-dependent colour (gs_sh.h): the SH rows of a .ply in the converter's order, one colour on the host, and the
+//     camera position the projection kernel evaluates them for.
 #include <math.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -11,6 +13,7 @@
 #include <vector>
 #include "../../include/gs_splat.h"
 #include "gs_ply.h"
+#include "gs_sh.h"
 
 namespace {
 
@@ -254,10 +257,90 @@ static int ply_to_splat(const void *bytes, size_t nbytes, void *out_rows, size_t
     return GS_OK;
 }
 
+// The spherical-harmonics rows of a PLY (gs_sh.h), in the order ply_to_splat emits the splat rows.  The degree a file
+// carries follows from how many f_rest_* it declares (0 -> 0, 9 -> 1, 24 -> 2, 45 -> 3); any other count, a gap in the
+// numbering or a missing f_dc_* means "no SH": degree -1, no rows, no error.
+static int ply_sh(const void *bytes, size_t nbytes, int degree, float *out_sh, size_t *out_nrows, int *out_degree, char *err, size_t errlen)
+{
+    if (!bytes || !out_nrows || !out_degree) return fail(err, errlen, GS_E_BADARG, "gs_ply_sh: NULL argument");
+    if (degree < 0 || degree > GS_SH_MAX_DEGREE) return fail(err, errlen, GS_E_BADARG, "gs_ply_sh: degree must be 0..3");
+    *out_nrows = 0; *out_degree = -1;
+    const uint8_t *buf = (const uint8_t *)bytes;
+    gsm::PlyLayout L;
+    size_t n = 0, data_start = 0;
+    int rc = gs_ply_plan(bytes, nbytes, &L, &n, &data_start, err, errlen);
+    if (rc != GS_OK) return rc;
+    Header h;
+    rc = parse_header(buf, nbytes, h, err, errlen);
+    if (rc != GS_OK) return rc;
+    size_t n_rest = 0;
+    for (const Prop &p : h.props) if (p.name.compare(0, 7, "f_rest_") == 0) n_rest++;
+    int file_degree = n_rest == 0 ? 0 : n_rest == 9 ? 1 : n_rest == 24 ? 2 : n_rest == 45 ? 3 : -1;
+    const Prop *src[3][16];
+    for (int c = 0; c < 3 && file_degree >= 0; c++) {
+        char nm[32];
+        snprintf(nm, sizeof nm, "f_dc_%d", c);
+        if (!(src[c][0] = h.find(nm))) file_degree = -1;
+        const int per = (int)n_rest / 3;                              // f_rest_* per channel in the file
+        for (int k = 1; k <= per && file_degree >= 0; k++) {
+            snprintf(nm, sizeof nm, "f_rest_%d", c * per + (k - 1));
+            if (!(src[c][k] = h.find(nm))) file_degree = -1;
+        }
+    }
+    if (file_degree < 0) return GS_OK;
+    const int D = degree < file_degree ? degree : file_degree, K = gsm::sh_coefs(D);
+    *out_degree = D; *out_nrows = n;
+    if (!out_sh || !n) return GS_OK;
+    const uint8_t *data = buf + data_start;
+    // the converter's order (index.js:653-668): descending importance, ties stable
+    std::vector<float> importance(n, 0.0f);
+    std::vector<uint32_t> order(n);
+    for (size_t i = 0; i < n; i++) order[i] = (uint32_t)i;
+    if (L.has_scale)
+        for (size_t i = 0; i < n; i++) importance[i] = gsm::ply_importance(data + i * L.row_bytes, L);
+    std::stable_sort(order.begin(), order.end(),
+                     [&](uint32_t b, uint32_t a) { return (double)importance[a] - (double)importance[b] < 0; });
+    for (size_t j = 0; j < n; j++) {
+        const uint8_t *row = data + (size_t)order[j] * L.row_bytes;
+        float *o = out_sh + j * 3 * (size_t)K;
+        for (int c = 0; c < 3; c++)
+            for (int k = 0; k < K; k++) o[c * K + k] = (float)gsm::ply_read(row + src[c][k]->offset, src[c][k]->type);
+    }
+    return GS_OK;
+}
+
 GS_API int gs_ply_to_splat(const void *bytes, size_t nbytes, void *out_rows, size_t *out_nrows, char *err, size_t errlen)
 {
     try { return ply_to_splat(bytes, nbytes, out_rows, out_nrows, err, errlen); }
     catch (...) { return fail(err, errlen, GS_E_OOM, "out of host memory while converting the .ply"); }
+}
+
+GS_API int gs_ply_sh_host(const void *bytes, size_t nbytes, int degree, float *out_sh, size_t *out_nrows, int *out_degree, char *err, size_t errlen)
+{
+    try { return ply_sh(bytes, nbytes, degree, out_sh, out_nrows, out_degree, err, errlen); }
+    catch (...) { return fail(err, errlen, GS_E_OOM, "out of host memory while reading the .ply coefficients"); }
+}
+
+GS_API int gs_sh_eval(const float *sh_row, int degree, const double cam[3], const float pos[3], uint8_t rgb[3])
+{
+    if (!sh_row || !cam || !pos || !rgb || degree < 0 || degree > GS_SH_MAX_DEGREE) return GS_E_BADARG;
+    const gsm::ShRowPtr coef = { sh_row, gsm::sh_coefs(degree) };
+    gsm::sh_color(coef, degree, cam, pos, rgb);
+    return GS_OK;
+}
+
+GS_API int gs_sh_eval_unrounded(const float *sh_row, int degree, const double cam[3], const float pos[3], double out[3])
+{
+    if (!sh_row || !cam || !pos || !out || degree < 0 || degree > GS_SH_MAX_DEGREE) return GS_E_BADARG;
+    const gsm::ShRowPtr coef = { sh_row, gsm::sh_coefs(degree) };
+    gsm::sh_unrounded(coef, degree, cam, pos, out);
+    return GS_OK;
+}
+
+GS_API int gs_camera_in_object(const float model_view[16], double out[3])
+{
+    if (!model_view || !out) return GS_E_BADARG;
+    return gsm::camera_in_object(model_view, out) ? GS_OK : GS_E_BADARG;
 }
 
 }  // extern "C"

@@ -144,6 +144,12 @@ struct GsFrameUniforms {           // per-render constants, passed by value to k
     uint32_t row_walk;             // GS_OPT_ROW_WALK: round 0 of a span-list frame builds no tile lists; blend<0> collects each tile's entries from
                                    // its tile row's runs (gs_render.hip: the same entries in the same order)
     uint32_t walk_ref;             // (set by the launch path) run_ref = run_geom + walk_ref: where the runs' sorted positions follow their geometry
+    // view-dependent colour (GS_OPT_SH_DEGREE; behind everything else: the fields above keep their places).  Read by k_project<.., SH> only
+    uint32_t sh_degree;            // the degree this frame evaluates: min(option, degree of the stored rows); 0 = the packed byte colours (no SH kernel)
+    uint32_t sh_n;                 // splats [0, sh_n) have a row in the SH store
+    uint32_t sh_row_q;             // 16-byte words per stored row (3 channels of sh_channel_stride(stored degree) f32)
+    const uint4 *sh_rows;          // the store
+    double sh_cam[3];              // the camera in the rows' object space (gsm::camera_in_object of mv with z negated, on the host)
 };
 
 struct GsLaneWorker;
@@ -186,6 +192,10 @@ struct gs_ctx {
     float *bound_r;                // N x upper bound of the splat's largest standard deviation in object space: sqrt(3 max|Sigma_ij|)
                                    // (Gershgorin), +inf where unknown -- what gs_sort_for's strip test needs, 4 B per splat
     double *pow10tab;              // parseInt table (gs_host_tables.h)
+    // view-dependent colour (owner only; gs_fill_uniforms hands a frame what it needs): SH rows parallel to the splats, channel-major,
+    // every channel padded to whole 16-byte words (gs_sh.h: sh_channel_stride)
+    float *sh; size_t sh_n, sh_cap; int sh_deg;   // rows stored / rows allocated / their degree (0 while empty)
+    int sh_opt;                    // GS_OPT_SH_DEGREE
 
     // sort scratch (sized by cap)
     float *depth;                  // stored f32 depth or +inf for culled

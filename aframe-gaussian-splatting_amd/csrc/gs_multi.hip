@@ -210,6 +210,12 @@ GS_API int gs_multi_load_ply(gs_multi *m, const void *bytes, size_t nbytes)
     return run_all(m, [bytes, nbytes](gs_ctx *c, int) { return gs_load_ply(c, bytes, nbytes); });
 }
 
+GS_API int gs_multi_push_sh(gs_multi *m, const float *sh_rows, size_t nrows, int degree)
+{
+    if (!m) return GS_E_BADARG;
+    return run_all(m, [sh_rows, nrows, degree](gs_ctx *c, int) { return gs_push_sh(c, sh_rows, nrows, degree); });
+}
+
 GS_API size_t gs_multi_count(const gs_multi *m) { return (m && !m->f.empty()) ? gs_count(m->f[0]->ctx) : 0; }
 
 GS_API int gs_multi_set_option(gs_multi *m, int option, int64_t value)

@@ -24,6 +24,7 @@
 // The fixed-function rasteriser + ROP of the reference have no structural counterpart; parity is defined at
 // the pixel level against oracle/gs_oracle.c (docs/LAB_NOTES.md "Pixel parity argument").
 #include "gs_internal.h"
+#include "gs_sh.h"
 
 namespace {
 
@@ -105,7 +106,38 @@ __device__ __forceinline__ void round_range(const GsControl *ctl, uint32_t near_
 // RUNS (span-list binning, below): the chunk also leaves, per tile row, how many of its splats touch the row (runs) and how many
 // tiles they touch there, packed `runs | tiles << 9` (at most 256 runs of at most 256 tiles), in row_cnt[row][chunk]; `spine` is
 // not written.
-template <int ROUND, bool RUNS>
+// SH (view-dependent colour, GS_OPT_SH_DEGREE): a splat that is about to write its projected record replaces the RGB bytes of its
+// colour word by the spherical harmonics of its SH row, evaluated for the frame's camera (gs_sh.h: f64, the host's arithmetic).
+// Only such splats pay -- the few per cent of the order a frame projects and keeps; binning and blend see the record only.
+// The row is read as 16-byte words, as many per channel as the frame's degree needs (1, 3, 4 of the stored 1, 3, 4), into registers
+// that are indexed by constants once sh_unrounded's loops are unrolled: nothing goes to scratch.
+struct ShRowRegs {
+    float v[3][16];
+    __device__ __forceinline__ float operator()(int c, int k) const { return v[c][k]; }
+};
+__device__ __forceinline__ uint32_t sh_colour_word(const GsFrameUniforms &u, uint32_t idx, const float cs[4], uint32_t rgba)
+{
+    if (idx >= u.sh_n) return rgba;                                 // beyond the last SH row: the packed byte colour
+    const uint32_t chan_q = u.sh_row_q / 3u, need_q = u.sh_degree == 1u ? 1u : (u.sh_degree == 2u ? 3u : 4u);
+    const uint4 *__restrict__ row = u.sh_rows + (size_t)idx * u.sh_row_q;
+    ShRowRegs r;
+#pragma unroll
+    for (int c = 0; c < 3; c++)
+#pragma unroll
+        for (int q = 0; q < 4; q++) {
+            uint4 w = make_uint4(0u, 0u, 0u, 0u);
+            if ((uint32_t)q < need_q) w = row[(uint32_t)c * chan_q + (uint32_t)q];
+            r.v[c][4 * q] = __uint_as_float(w.x); r.v[c][4 * q + 1] = __uint_as_float(w.y);
+            r.v[c][4 * q + 2] = __uint_as_float(w.z); r.v[c][4 * q + 3] = __uint_as_float(w.w);
+        }
+    const double cam[3] = { u.sh_cam[0], u.sh_cam[1], u.sh_cam[2] };
+    const float pos[3] = { cs[0], cs[1], -cs[2] };                  // the row's position: the centre texel holds (x, y, -z) (index.js:350-354)
+    uint8_t b[3];
+    gsm::sh_color(r, (int)u.sh_degree, cam, pos, b);
+    return (rgba & 0xFF000000u) | (uint32_t)b[0] | ((uint32_t)b[1] << 8) | ((uint32_t)b[2] << 16);
+}
+
+template <int ROUND, bool RUNS, bool SH = false>
 __device__ __forceinline__ void k_project_body(const uint32_t *__restrict__ sorted, const uint4 *__restrict__ splat,
                                                const GsFrameUniforms &u, gsm::Projected *__restrict__ proj, uint2 *__restrict__ rect,
                                                uint32_t *__restrict__ tile_count, uint32_t *__restrict__ spine,
@@ -155,7 +187,7 @@ __device__ __forceinline__ void k_project_body(const uint32_t *__restrict__ sort
                     if (!RUNS || ty1 - ty0 >= 2) rect[j] = make_uint2(tx0 | (ty0 << 16), tx1 | (ty1 << 16));   // (RUNS, one or two tile rows: the runs themselves, below)
                     float4 *dst = reinterpret_cast<float4 *>(proj + j);
                     dst[0] = make_float4(p.cx, p.cy, p.ax, p.ay);
-                    dst[1] = make_float4(p.bx, p.by, __uint_as_float(p.rgba), p.alpha);
+                    dst[1] = make_float4(p.bx, p.by, __uint_as_float(SH ? sh_colour_word(u, idx, cs, p.rgba) : p.rgba), p.alpha);
                     if (u.has_depth) zwin[j] = x.zndc * 0.5f + 0.5f;           // gl_FragCoord.z of every fragment of the quad
                     if (ty1 - ty0 >= 2) {
                         // three or more tile rows: counted cooperatively, one lane per row -- by 16-lane groups up to 16 rows
@@ -246,6 +278,17 @@ __global__ __launch_bounds__(GS_BLOCK) void k_project(const uint32_t *__restrict
                                                       float *__restrict__ zwin, GsControl *ctl)
 {
     k_project_body<ROUND, RUNS>(sorted, splat, u, proj, rect, tile_count, spine, part_vis, mask, zwin, ctl);
+}
+
+// ... with view-dependent colour (a kernel of its own name: the instantiations above stay what they were)
+template <int ROUND, bool RUNS>
+__global__ __launch_bounds__(GS_BLOCK) void k_project_sh(const uint32_t *__restrict__ sorted, const uint4 *__restrict__ splat,
+                                                         GsFrameUniforms u, gsm::Projected *__restrict__ proj, uint2 *__restrict__ rect,
+                                                         uint32_t *__restrict__ tile_count, uint32_t *__restrict__ spine,
+                                                         uint32_t *__restrict__ part_vis, const uint32_t *__restrict__ mask,
+                                                         float *__restrict__ zwin, GsControl *ctl)
+{
+    k_project_body<ROUND, RUNS, true>(sorted, splat, u, proj, rect, tile_count, spine, part_vis, mask, zwin, ctl);
 }
 
 // One workgroup: exclusive scan of the per-chunk totals (spine) -> chunk base offsets, I = grand total (refused and
@@ -1862,6 +1905,10 @@ int run_round_spans(gs_ctx *ctx, const GsFrameUniforms &u, uint8_t *out, bool la
     // the pair buffers hold the runs (geometry and sorted position of each: there are never more runs than tiles) and the lists
     uint32_t *run_geom = reinterpret_cast<uint32_t *>(ctx->pair_a), *run_ref = run_geom + ctx->pair_cap, *lists = reinterpret_cast<uint32_t *>(ctx->pair_b);
     const uint32_t pc = (uint32_t)ctx->pair_cap;
+    if (v.sh_degree)                                            // view-dependent colour: the SH instantiation (GS_OPT_SH_DEGREE)
+        hipLaunchKernelGGL((k_project_sh<ROUND, true>), dim3(g), dim3(GS_BLOCK), 0, st, ctx->sorted, ctx->splat, v, ctx->proj, ctx->rect,
+                           ctx->tile_count, ctx->row_cnt, ctx->part_vis, ctx->unsat_mask, ctx->zwin, ctx->ctl);
+    else
     hipLaunchKernelGGL((k_project<ROUND, true>), dim3(g), dim3(GS_BLOCK), 0, st, ctx->sorted, ctx->splat, v, ctx->proj, ctx->rect,
                        ctx->tile_count, ctx->row_cnt, ctx->part_vis, ctx->unsat_mask, ctx->zwin, ctx->ctl);
     GS_HIP(hipGetLastError());
@@ -1918,6 +1965,10 @@ int run_round(gs_ctx *ctx, const GsFrameUniforms &u, uint8_t *out, bool last_rou
     GsFrameUniforms v = u;
     v.rc_stride = 0;
     v.row_walk = 0;
+    if (u.sh_degree)
+        hipLaunchKernelGGL((k_project_sh<ROUND, false>), dim3(g), dim3(GS_BLOCK), 0, st, ctx->sorted, ctx->splat, u, ctx->proj, ctx->rect,
+                           ctx->tile_count, ctx->spine, ctx->part_vis, ctx->unsat_mask, ctx->zwin, ctx->ctl);
+    else
     hipLaunchKernelGGL((k_project<ROUND, false>), dim3(g), dim3(GS_BLOCK), 0, st, ctx->sorted, ctx->splat, u, ctx->proj, ctx->rect,
                        ctx->tile_count, ctx->spine, ctx->part_vis, ctx->unsat_mask, ctx->zwin, ctx->ctl);
     GS_HIP(hipGetLastError());
@@ -1950,6 +2001,7 @@ int run_round(gs_ctx *ctx, const GsFrameUniforms &u, uint8_t *out, bool last_rou
 }
 
 template <int ROUND, bool RUNS> GS_BODY(F_project, k_project_body<ROUND, RUNS>);
+template <int ROUND, bool RUNS> GS_BODY(F_project_sh, k_project_body<ROUND, RUNS, true>);
 template <int ROUND> GS_BODY(F_row_scan, k_row_scan_body<ROUND>);
 template <int ROUND> GS_BODY(F_emit_runs, k_emit_runs_body<ROUND>);
 template <int ROUND> GS_BODY(F_seg_count, k_seg_count_body<ROUND>);
@@ -2005,11 +2057,12 @@ int run_round_spans2(gs_ctx *const S[2], const GsFrameUniforms U[2], uint8_t *co
     for (int k = 0; k < 2; k++) { V[k].rc_stride = stride; V[k].row_walk = row_walk_round<ROUND>(U[0]) ? 1u : 0u; V[k].walk_ref = (uint32_t)S[k]->pair_cap; }
     uint32_t *geom[2], *ref[2], *lists[2];
     for (int k = 0; k < 2; k++) { geom[k] = reinterpret_cast<uint32_t *>(S[k]->pair_a); ref[k] = geom[k] + S[k]->pair_cap; lists[k] = reinterpret_cast<uint32_t *>(S[k]->pair_b); }
-    gs_twin<F_project<ROUND, true>, GS_BLOCK>(g, st,
-        gs_pack_make((const uint32_t *)S[0]->sorted, (const uint4 *)S[0]->splat, V[0], S[0]->proj, S[0]->rect, S[0]->tile_count, S[0]->row_cnt, S[0]->part_vis,
-                     (const uint32_t *)S[0]->unsat_mask, S[0]->zwin, S[0]->ctl),
-        gs_pack_make((const uint32_t *)S[1]->sorted, (const uint4 *)S[1]->splat, V[1], S[1]->proj, S[1]->rect, S[1]->tile_count, S[1]->row_cnt, S[1]->part_vis,
-                     (const uint32_t *)S[1]->unsat_mask, S[1]->zwin, S[1]->ctl));
+    const auto pp0 = gs_pack_make((const uint32_t *)S[0]->sorted, (const uint4 *)S[0]->splat, V[0], S[0]->proj, S[0]->rect, S[0]->tile_count, S[0]->row_cnt, S[0]->part_vis,
+                                  (const uint32_t *)S[0]->unsat_mask, S[0]->zwin, S[0]->ctl);
+    const auto pp1 = gs_pack_make((const uint32_t *)S[1]->sorted, (const uint4 *)S[1]->splat, V[1], S[1]->proj, S[1]->rect, S[1]->tile_count, S[1]->row_cnt, S[1]->part_vis,
+                                  (const uint32_t *)S[1]->unsat_mask, S[1]->zwin, S[1]->ctl);
+    if (u.sh_degree) gs_twin<F_project_sh<ROUND, true>, GS_BLOCK>(g, st, pp0, pp1);   // (paired frames share their degree: gs_frames_batchable)
+    else gs_twin<F_project<ROUND, true>, GS_BLOCK>(g, st, pp0, pp1);
     GS_HIP(hipGetLastError());
     if (ROUND == 0) GS_PROF_RECORD(ctx, 3);
     gs_twin<F_row_scan<ROUND>, GS_BLOCK>((uint32_t)u.tiles_y, st,
@@ -2072,11 +2125,12 @@ int run_round2(gs_ctx *const S[2], const GsFrameUniforms U[2], uint8_t *const ou
     GsFrameUniforms V[2] = { U[0], U[1] };
     V[0].rc_stride = V[1].rc_stride = 0;
     V[0].row_walk = V[1].row_walk = 0;
-    gs_twin<F_project<ROUND, false>, GS_BLOCK>(g, st,
-        gs_pack_make((const uint32_t *)S[0]->sorted, (const uint4 *)S[0]->splat, U[0], S[0]->proj, S[0]->rect, S[0]->tile_count, S[0]->spine, S[0]->part_vis,
-                     (const uint32_t *)S[0]->unsat_mask, S[0]->zwin, S[0]->ctl),
-        gs_pack_make((const uint32_t *)S[1]->sorted, (const uint4 *)S[1]->splat, U[1], S[1]->proj, S[1]->rect, S[1]->tile_count, S[1]->spine, S[1]->part_vis,
-                     (const uint32_t *)S[1]->unsat_mask, S[1]->zwin, S[1]->ctl));
+    const auto pp0 = gs_pack_make((const uint32_t *)S[0]->sorted, (const uint4 *)S[0]->splat, U[0], S[0]->proj, S[0]->rect, S[0]->tile_count, S[0]->spine, S[0]->part_vis,
+                                  (const uint32_t *)S[0]->unsat_mask, S[0]->zwin, S[0]->ctl);
+    const auto pp1 = gs_pack_make((const uint32_t *)S[1]->sorted, (const uint4 *)S[1]->splat, U[1], S[1]->proj, S[1]->rect, S[1]->tile_count, S[1]->spine, S[1]->part_vis,
+                                  (const uint32_t *)S[1]->unsat_mask, S[1]->zwin, S[1]->ctl);
+    if (u.sh_degree) gs_twin<F_project_sh<ROUND, false>, GS_BLOCK>(g, st, pp0, pp1);   // (paired frames share their degree: gs_frames_batchable)
+    else gs_twin<F_project<ROUND, false>, GS_BLOCK>(g, st, pp0, pp1);
     GS_HIP(hipGetLastError());
     if (ROUND == 0) GS_PROF_RECORD(ctx, 3);
     gs_twin<F_pairs_check<ROUND>, GS_BLOCK>(1, st,
@@ -2142,7 +2196,8 @@ bool gs_frames_batchable(const GsFrameUniforms &a, const GsFrameUniforms &b)
 {
     return a.near_count == b.near_count && a.skip_round1 == b.skip_round1 && a.W == b.W && a.H == b.H && a.x0 == b.x0 && a.x1 == b.x1 &&
            a.flags == b.flags && !(a.flags & (GS_RENDER_COUNT_FRAGS | GS_RENDER_COUNT_EVALUATED)) && !a.record_staged && !b.record_staged &&
-           a.split_min == b.split_min && a.subtile == b.subtile && a.row_walk == b.row_walk && a.has_depth == b.has_depth && a.has_scene_rgba == b.has_scene_rgba && a.t_eps == b.t_eps;
+           a.split_min == b.split_min && a.subtile == b.subtile && a.row_walk == b.row_walk && a.has_depth == b.has_depth && a.has_scene_rgba == b.has_scene_rgba && a.t_eps == b.t_eps &&
+           a.sh_degree == b.sh_degree;
 }
 
 int gs_run_render2(gs_ctx *const S[2], const GsFrameUniforms U[2], uint8_t *const device_out[2])

@@ -17,7 +17,11 @@ const schema = {                                   // index.js:2-7
   cutoutEntity: { type: 'selector' },
   pixelRatio: { type: 'number', default: 1 },
   xrPixelRatio: { type: 'number', default: 0.5 },
+  // beyond the reference: the highest spherical-harmonics band of a .ply to keep and evaluate per frame (view-dependent colour,
+  // GS_OPT_SH_DEGREE); 0 = the reference's baked f_dc colour.  `.splat` files carry no coefficients and ignore it.
+  shDegree: { type: 'number', default: 0 },
 };
+const OPT_SH_DEGREE = 19;
 const ROW_LENGTH = 3 * 4 + 3 * 4 + 4 + 4;          // index.js:227
 
 function elementsOf(m) { return m && m.elements ? m.elements : m; }
@@ -25,9 +29,11 @@ function elementsOf(m) { return m && m.elements ? m.elements : m; }
 class GaussianSplatting {
   constructor(data, options) {
     this.data = Object.assign({ src: schema.src.default, cutoutEntity: null, pixelRatio: schema.pixelRatio.default,
-      xrPixelRatio: schema.xrPixelRatio.default }, data || {});
+      xrPixelRatio: schema.xrPixelRatio.default, shDegree: schema.shDegree.default }, data || {});
     this.device = (options && options.device) || 0;
     this.handle = native.create(this.device);       // replaces `new Worker(...)` + GL resource creation
+    this.shDegree = Math.max(0, Math.min(3, Math.floor(Number(this.data.shDegree) || 0)));
+    if (this.shDegree > 0) native.setOption(this.handle, OPT_SH_DEGREE, this.shDegree);
     this.loadedVertexCount = 0;
     this.rowLength = ROW_LENGTH;
     this.sortReady = true;
@@ -65,8 +71,13 @@ class GaussianSplatting {
     try {
       if (isPly) {
         const all = Buffer.alloc(total); fs.readSync(fd, all, 0, total, 0);
-        const rows = this.processPlyBuffer(all.buffer.slice(all.byteOffset, all.byteOffset + total));
+        const input = all.buffer.slice(all.byteOffset, all.byteOffset + total);
+        const rows = this.processPlyBuffer(input);
         this.pushDataBuffer(rows, Math.floor(rows.byteLength / this.rowLength));
+        if (this.shDegree > 0) {                     // the coefficients processPlyBuffer drops, in its row order
+          const sh = native.plySh(this.handle, input, this.shDegree);
+          if (sh.degree > 0) native.pushSh(this.handle, sh.rows, sh.degree);
+        }
       } else {
         const step = chunkBytes || (1 << 22);
         let pending = Buffer.alloc(0), pos = 0;

@@ -261,6 +261,53 @@ static napi_value fn_ply_to_splat_gpu(napi_env env, napi_callback_info info)
     return ab;
 }
 
+/* plySh(h, inputBuffer, degree) -> { degree, rows: Float32Array }: the SH rows of the PLY in the order of plyToSplatGpu's rows
+ * (gs_ply_sh); degree -1 and no rows for a file without usable coefficients */
+static napi_value fn_ply_sh(napi_env env, napi_callback_info info)
+{
+    napi_value argv[3];
+    if (!get_args(env, info, 3, argv, NULL)) return NULL;
+    gs_ctx *ctx = get_ctx(env, argv[0]); if (!ctx) return NULL;
+    void *data; size_t len;
+    if (!get_bytes(env, argv[1], &data, &len)) { napi_throw_type_error(env, NULL, "expected an ArrayBuffer or TypedArray"); return NULL; }
+    int32_t degree = 3;
+    if (!is_nullish(env, argv[2])) NAPI_OK(napi_get_value_int32(env, argv[2], &degree));
+    size_t n = 0; int d = -1;
+    int rc = gs_ply_sh(ctx, data, len, degree, NULL, &n, &d);
+    if (rc != GS_OK) return throw_gs(env, ctx, rc);
+    const size_t floats = d < 0 ? 0 : n * 3 * (size_t)((d + 1) * (d + 1));
+    napi_value ab, arr, obj, dv; void *out;
+    NAPI_OK(napi_create_arraybuffer(env, floats * 4, &out, &ab));
+    if (floats) { rc = gs_ply_sh(ctx, data, len, degree, (float *)out, &n, &d); if (rc != GS_OK) return throw_gs(env, ctx, rc); }
+    NAPI_OK(napi_create_typedarray(env, napi_float32_array, floats, ab, 0, &arr));
+    NAPI_OK(napi_create_object(env, &obj));
+    NAPI_OK(napi_create_int32(env, d, &dv));
+    NAPI_OK(napi_set_named_property(env, obj, "degree", dv));
+    NAPI_OK(napi_set_named_property(env, obj, "rows", arr));
+    return obj;
+}
+
+/* pushSh(h, rows, degree) -> rows in the SH store: gs_push_sh, parallel to pushSplat */
+static napi_value fn_push_sh(napi_env env, napi_callback_info info)
+{
+    napi_value argv[3];
+    if (!get_args(env, info, 3, argv, NULL)) return NULL;
+    gs_ctx *ctx = get_ctx(env, argv[0]); if (!ctx) return NULL;
+    void *data; size_t len;
+    if (!get_bytes(env, argv[1], &data, &len)) { napi_throw_type_error(env, NULL, "expected an ArrayBuffer or TypedArray"); return NULL; }
+    int32_t degree = 0;
+    NAPI_OK(napi_get_value_int32(env, argv[2], &degree));
+    if (degree < 1 || degree > 3) { napi_throw_range_error(env, NULL, "pushSh: degree must be 1..3"); return NULL; }
+    const size_t row = 12 * (size_t)((degree + 1) * (degree + 1));
+    int rc = gs_push_sh(ctx, (const float *)data, len / row, degree);
+    if (rc != GS_OK) return throw_gs(env, ctx, rc);
+    size_t n = 0;
+    (void)gs_sh_count(ctx, &n, NULL);
+    napi_value r;
+    NAPI_OK(napi_create_double(env, (double)n, &r));
+    return r;
+}
+
 static napi_value fn_count(napi_env env, napi_callback_info info)
 {
     napi_value argv[1], r;
@@ -718,6 +765,7 @@ static napi_value fn_stats(napi_env env, napi_callback_info info)
     PUT("msBin", s.ms_bin); PUT("msBlend", s.ms_blend); PUT("msRender", s.ms_render);
     PUT("accFrames", s.acc_frames); PUT("unsatTiles", s.unsat_tiles); PUT("nearPermille", s.near_permille); PUT("sortRecords", s.sort_records);
     PUT("retriedFrames", s.retried_frames); PUT("specSorts", s.spec_sorts); PUT("specMisses", s.spec_misses); PUT("needSplats", s.need_splats); PUT("sortMode", s.sort_mode); PUT("subtile", s.subtile);
+    PUT("shDegree", s.sh_degree);
 #undef PUT
     return o;
 }
@@ -1016,7 +1064,7 @@ static napi_value init(napi_env env, napi_value exports)
 {
     static const struct { const char *name; napi_callback fn; } fns[] = {
         { "create", fn_create }, { "destroy", fn_destroy }, { "clear", fn_clear }, { "pushSplat", fn_push_splat },
-        { "pushMatrices", fn_push_matrices }, { "loadPly", fn_load_ply }, { "plyToSplat", fn_ply_to_splat }, { "plyToSplatGpu", fn_ply_to_splat_gpu },
+        { "pushMatrices", fn_push_matrices }, { "loadPly", fn_load_ply }, { "plyToSplat", fn_ply_to_splat }, { "plyToSplatGpu", fn_ply_to_splat_gpu }, { "plySh", fn_ply_sh }, { "pushSh", fn_push_sh },
         { "count", fn_count },
         { "sort", fn_sort }, { "sortAsync", fn_sort_async }, { "sortBegin", fn_sort_begin }, { "sortPoll", fn_sort_poll }, { "render", fn_render }, { "renderInto", fn_render_into },
         { "renderAsync", fn_render_async }, { "allocFrame", fn_alloc_frame }, { "sync", fn_sync },

@@ -67,11 +67,14 @@ def make_splat_rows_fast(n, seed=SEED_BASE + 5, block=1 << 21):
     return rows.reshape(-1)
 
 
-def rows_to_inria_ply(rows_u8):
+def rows_to_inria_ply(rows_u8, f_rest=None):
     """Inverse of processPlyBuffer for synthetic data: .splat rows -> INRIA-layout binary PLY bytes
-    (62 float props, 248 B/row) so the `.ply` loader path (index.js:600-745) can be exercised."""
+    (62 float props, 248 B/row) so the `.ply` loader path (index.js:600-745) can be exercised.
+    f_rest: optional (n, R) array for the f_rest_0..R-1 properties (R = 45: degree 3, red's 15 first; default: 45 zeros)."""
     rows = np.asarray(rows_u8, np.uint8).reshape(-1, 32)
     n = rows.shape[0]
+    if f_rest is not None:
+        return _rows_to_ply_with_rest(rows, np.asarray(f_rest, np.float32).reshape(n, -1))
     pos = rows[:, 0:12].copy().view("<f4").reshape(n, 3)
     sc = rows[:, 12:24].copy().view("<f4").reshape(n, 3).astype(np.float64)
     rgba = rows[:, 24:28].astype(np.float64)
@@ -87,6 +90,19 @@ def rows_to_inria_ply(rows_u8):
     body[:, 58:62] = q
     hdr = "ply\nformat binary_little_endian 1.0\nelement vertex %d\n" % n + "".join("property float %s\n" % p for p in props) + "end_header\n"
     return hdr.encode("ascii") + body.tobytes()
+
+
+def _rows_to_ply_with_rest(rows, f_rest):
+    """rows_to_inria_ply with the given f_rest columns: the same bytes as without for 45 columns of zeros."""
+    n, r = f_rest.shape
+    base = np.frombuffer(rows_to_inria_ply(rows), np.uint8)
+    start = bytes(base[:4096]).index(b"end_header\n") + 11
+    body0 = base[start:].view("<f4").reshape(n, 62)
+    body = np.concatenate([body0[:, :9], f_rest.astype("<f4"), body0[:, 54:]], axis=1)
+    props = ["x", "y", "z", "nx", "ny", "nz", "f_dc_0", "f_dc_1", "f_dc_2"] + ["f_rest_%d" % i for i in range(r)] + \
+            ["opacity", "scale_0", "scale_1", "scale_2", "rot_0", "rot_1", "rot_2", "rot_3"]
+    hdr = "ply\nformat binary_little_endian 1.0\nelement vertex %d\n" % n + "".join("property float %s\n" % p for p in props) + "end_header\n"
+    return hdr.encode("ascii") + np.ascontiguousarray(body).tobytes()
 
 
 # ---------------------------------------------------------------- cameras (three.js conventions, column-major)

@@ -92,6 +92,41 @@ GS_API int gs_ply_to_splat_gpu(gs_ctx *ctx, const void *bytes, size_t nbytes, vo
 GS_API int gs_ply_to_splat(const void *bytes, size_t nbytes, void *out_rows, size_t *out_nrows, char *err,
                            size_t errlen);
 
+/* ---- view-dependent colour (no reference counterpart: processPlyBuffer keeps f_dc_* only, index.js:725-729) ----------------
+ * An INRIA .ply carries 45 f_rest_* coefficients per splat next to f_dc_*: real spherical harmonics of degree 1..3 (Kerbl et al.
+ * 2023), the view-dependent part of the colour.  With GS_OPT_SH_DEGREE above 0 the context keeps them -- one SH ROW per splat:
+ * 3 * (D+1)^2 f32, channel-major sh[c][k], k = 0 is f_dc_c -- and the projection kernel replaces the RGB bytes of every splat it
+ * projects by `clamped_u8((0.5 + SH_C0*sh[c][0] + sum_k basis_k(d)*sh[c][k]) * 255)`, d = the unit vector from the camera to the
+ * splat in object space (f64, fixed operation order: csrc/gs_sh.h).  Degree 0, and any splat whose higher coefficients are all
+ * zero, give exactly the byte processPlyBuffer bakes.  Alpha stays the packed byte.  Off by default. */
+
+/* The SH rows of a PLY in the order of the rows gs_ply_to_splat_gpu / gs_ply_to_splat return for it (descending importance, ties
+ * stable, index.js:668), for callers that convert and then push (gaussian_splatting.js:66-69).  degree 0..3: the highest band
+ * wanted; *out_degree = min(degree, what the file carries: 0, 9, 24 or 45 f_rest_* -> 0..3), rows of 3 * (*out_degree+1)^2 f32.
+ * A file with another count, a gap in the numbering or no f_dc_*: *out_degree = -1, *out_nrows = 0, GS_OK.  out_sh == NULL: size
+ * query.  Properties of any declared type are read as processPlyBuffer reads them and rounded to f32.  Runs on the host. */
+GS_API int gs_ply_sh(gs_ctx *ctx, const void *bytes, size_t nbytes, int degree, float *out_sh, size_t *out_nrows, int *out_degree);
+/* ... the same without a context (as gs_ply_to_splat is to gs_ply_to_splat_gpu); err (optional) receives the message. */
+GS_API int gs_ply_sh_host(const void *bytes, size_t nbytes, int degree, float *out_sh, size_t *out_nrows, int *out_degree, char *err,
+                          size_t errlen);
+/* Append `nrows` SH rows of `degree` (1..3), parallel to gs_push_splat: row i of the SH store belongs to splat i.  Splats beyond
+ * the last SH row draw with their packed byte colour (progressive loading, .splat data).  A degree other than that of the rows
+ * already stored: GS_E_BADARG.  gs_clear empties the store.  gs_load_ply with GS_OPT_SH_DEGREE at 1..3 does this by itself when
+ * the store is still parallel to the splats (as many SH rows as splats before the call, of the same degree). */
+GS_API int gs_push_sh(gs_ctx *ctx, const float *sh_rows, size_t nrows, int degree);
+/* Rows in the SH store and their degree (0 rows: *out_degree = 0); gs_download(GS_BUF_SH) returns them. */
+GS_API int gs_sh_count(const gs_ctx *ctx, size_t *out_nrows, int *out_degree);
+/* One colour on the host, by the very arithmetic of the kernel: sh_row of `degree` (0..3), camera and splat position in the
+ * rows' object space (positions as a .ply / .splat row stores them: the space the coefficients were trained in) -> rgb bytes.  gs_sh_eval_unrounded: the three values before clamped_u8, in units of one colour byte. */
+GS_API int gs_sh_eval(const float *sh_row, int degree, const double cam[3], const float pos[3], uint8_t rgb[3]);
+GS_API int gs_sh_eval_unrounded(const float *sh_row, int degree, const double cam[3], const float pos[3], double out[3]);
+/* The camera position in object space a frame with this model_view evaluates its colours for: the inverse of the affine 4x4
+ * applied to the origin, in f64 by cofactors of the upper 3x3 in a fixed order -- the very bits the kernel is handed.
+ * GS_E_BADARG for a singular matrix (a render refuses it likewise, but only while SH is active).  model_view acts on the packed
+ * centre (x, y, -z) (index.js:350-354), so this is the camera in that mirrored space; a frame negates out[2] -- exactly -- to get
+ * the camera in the rows' space, which is what the kernel and gs_sh_eval take. */
+GS_API int gs_camera_in_object(const float model_view[16], double out[3]);
+
 /* Number of splats resident (reference: loadedVertexCount / matrices.length/16). */
 GS_API size_t gs_count(const gs_ctx *ctx);
 
@@ -277,6 +312,7 @@ GS_API gs_ctx *gs_multi_ctx(gs_multi *m, int i);
 GS_API int gs_multi_clear(gs_multi *m);                                              /* gs_clear on every device          */
 GS_API int gs_multi_push_splat(gs_multi *m, const void *rows, size_t nrows);         /* gs_push_splat, uploads in parallel */
 GS_API int gs_multi_load_ply(gs_multi *m, const void *bytes, size_t nbytes);
+GS_API int gs_multi_push_sh(gs_multi *m, const float *sh_rows, size_t nrows, int degree);   /* gs_push_sh on every device     */
 GS_API size_t gs_multi_count(const gs_multi *m);
 GS_API int gs_multi_set_option(gs_multi *m, int option, int64_t value);              /* gs_set_option on every device     */
 /* tick + worker sort for the frame `views` describe (one view, or the two XR eyes with the head camera's view row, index.js:441):
@@ -404,6 +440,7 @@ typedef struct gs_stats {
     uint32_t binning;     /* how the last frame's first binning round binned (GS_OPT_BINNING): 0 = span lists, 1 = (tile, splat) pair records
                              (asked for, or a strip of more than 256 tile columns or rows, or a row-count table beyond its limit); a frame
                              that runs no round (nothing resident) reports what its round would have taken                             */
+    uint32_t sh_degree;   /* the spherical-harmonics degree the last frame's projection evaluated (GS_OPT_SH_DEGREE): 0 = packed byte colours   */
 } gs_stats;
 
 #define GS_OPT_PROFILE 1        /* 1: bracket every stage with HIP events on the frame's stream (7 per frame); 2: only
@@ -451,6 +488,13 @@ typedef struct gs_stats {
                                    tiles each on average and whose tile rows held at most 8192 runs each; 2: always.  Renders that count
                                    fragments or record staged entries, sub-tile lists (GS_OPT_SUBTILE), the split blend (GS_OPT_BLEND_SPLIT)
                                    and the second binning round keep the lists.                                                     */
+#define GS_OPT_SH_DEGREE 19      /* view-dependent colour.  0 (default): the reference's behaviour -- gs_load_ply keeps f_dc_* only, baked into the
+                                   colour byte (index.js:725-729); nothing is retained, nothing evaluated, and the kernels are the ones that run
+                                   without this option.  1..3: the highest spherical-harmonics band gs_load_ply keeps and a frame evaluates; the
+                                   effective degree of a frame is min(value, degree of the stored rows) and may change between frames.  Such a
+                                   frame's projection evaluates the colour of every splat it projects for the frame's camera (each eye and each
+                                   strip its own) where it writes the projected record; binning and blend see that record only.  A singular
+                                   model_view is GS_E_BADARG for such a frame.                                                       */
 #define GS_OPT_ENQUEUE_THREADS 7 /* default 1: gs_sort() (without an output array) and gs_render_device(GS_RENDER_ASYNC) hand the
                                    frame to a worker thread of its pipeline lane, which does the ~18 kernel launches, so the
                                    launches of the frames in flight run in parallel; failures surface at gs_sync().  0: the
@@ -468,6 +512,7 @@ GS_API int gs_get_stats(gs_ctx *ctx, gs_stats *out);
 #define GS_BUF_TILE_STATS 6   /* tiles x 2 u32  (entries staged, list length) after a GS_OPT_RECORD_STAGED render  */
 #define GS_BUF_UNSAT_MASK 7   /* tiles_y x ceil(tiles_x / 32) u32: one bit per tile the first binning round of the last render left
                                  unsaturated (measurement aid)                                                         */
+#define GS_BUF_SH 8           /* rows x 3 (D+1)^2 f32  the SH store, tight rows as pushed (gs_sh_count: rows and D)                   */
 GS_API int gs_download(gs_ctx *ctx, int which, void *out, size_t nbytes);
 
 #ifdef __cplusplus
