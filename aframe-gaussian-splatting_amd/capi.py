@@ -43,7 +43,9 @@ EXPORTS = [
     "gs_multi_push_splat", "gs_multi_load_ply", "gs_multi_count", "gs_multi_set_option", "gs_multi_sort", "gs_multi_render",
     "gs_multi_render_device", "gs_multi_read", "gs_multi_sync",
     "gs_ply_sh", "gs_ply_sh_host", "gs_push_sh", "gs_sh_count", "gs_sh_eval", "gs_sh_eval_unrounded", "gs_camera_in_object", "gs_multi_push_sh",
+    "gs_render_surface", "gs_render_surface_device", "gs_pick",
 ]
+SURFACE_NONE = 0xFFFFFFFF          # gs_surface.id / gs_hit.id where the transmittance never falls below one half
 
 
 class Piece(C.Structure):
@@ -64,10 +66,21 @@ class Stats(C.Structure):
                 ("acc_pairs", C.c_uint64), ("unsat_tiles", C.c_uint32), ("near_permille", C.c_uint32),
                 ("sort_records", C.c_uint32), ("retried_frames", C.c_uint32), ("spec_sorts", C.c_uint32), ("spec_misses", C.c_uint32), ("need_splats", C.c_uint32),
                 ("sort_mode", C.c_uint32), ("subtile", C.c_uint32), ("row_walk", C.c_uint32),
-                ("binning", C.c_uint32), ("sh_degree", C.c_uint32)]
+                ("binning", C.c_uint32), ("sh_degree", C.c_uint32), ("surface", C.c_uint32)]
 
     def as_dict(self):
         return {n: getattr(self, n) for n, _ in self._fields_}
+
+
+class Surface(C.Structure):
+    _fields_ = [("id", C.c_void_p), ("depth", C.c_void_p), ("alpha", C.c_void_p)]
+
+
+class Hit(C.Structure):
+    _fields_ = [("id", C.c_uint32), ("depth", C.c_float), ("alpha", C.c_float), ("pos", C.c_float * 3)]
+
+
+HIT_DTYPE = np.dtype([("id", np.uint32), ("depth", np.float32), ("alpha", np.float32), ("pos", np.float32, 3)])
 
 
 class GsError(RuntimeError):
@@ -176,6 +189,10 @@ def load(build_if_missing=True):
         L.gs_sh_eval.argtypes = [vp, i32, vp, vp, vp]
         L.gs_sh_eval_unrounded.argtypes = [vp, i32, vp, vp, vp]
         L.gs_camera_in_object.argtypes = [vp, vp]
+    if hasattr(L, "gs_pick"):
+        L.gs_render_surface.argtypes = [vp, C.POINTER(RenderParams), vp, sz, C.POINTER(Surface)]
+        L.gs_render_surface_device.argtypes = [vp, C.POINTER(RenderParams), vp, C.POINTER(Surface)]
+        L.gs_pick.argtypes = [vp, C.POINTER(RenderParams), vp, sz, vp]
     L.gs_download.argtypes = [vp, i32, vp, sz]
     L.gs_comm_unique_id.argtypes = [vp, vp]
     L.gs_comm_init.argtypes = [vp, vp, i32, i32]
@@ -501,6 +518,33 @@ class Context:
 
     def render_device(self, params, device_ptr=None):
         self._ck(self._L.gs_render_device(self._h, C.byref(params), C.c_void_p(device_ptr) if device_ptr else None))
+
+    # surface output: what lies under a pixel
+    def render_surface(self, params, rgba=True, planes=("id", "depth", "alpha")):
+        """gs_render_surface -> (rgba | None, id, depth, alpha): the frame and, per pixel, the splat at which the transmittance falls
+        below one half (SURFACE_NONE: never), its window depth (1.0: none) and the accumulated alpha.  A plane not named in `planes`
+        is not asked for (None)."""
+        h, sw = max(params.fb_height, 0), max(params.x1 - params.x0, 0)
+        out = np.zeros((h, sw, 4), np.uint8) if rgba else None
+        pid = np.zeros((h, sw), np.uint32) if "id" in planes else None
+        dep = np.zeros((h, sw), np.float32) if "depth" in planes else None
+        alp = np.zeros((h, sw), np.float32) if "alpha" in planes else None
+        s = Surface(*[a.ctypes.data if a is not None and a.size else None for a in (pid, dep, alp)])
+        self._ck(self._L.gs_render_surface(self._h, C.byref(params), _p(out) if rgba and out.size else None, 0, C.byref(s)))
+        return out, pid, dep, alp
+
+    def render_surface_device(self, params, device_rgba=None, id_ptr=None, depth_ptr=None, alpha_ptr=None):
+        s = Surface(id_ptr or None, depth_ptr or None, alpha_ptr or None)
+        self._ck(self._L.gs_render_surface_device(self._h, C.byref(params), C.c_void_p(device_rgba) if device_rgba else None, C.byref(s)))
+
+    def pick(self, params, points):
+        """gs_pick: points = (n, 2) int (column, row; row 0 = top) -> structured array (id, depth, alpha, pos[3]) of what the full
+        frame's planes hold there; pos = the hit splat's position as its .splat row stores it (NaN where id == SURFACE_NONE)."""
+        pts = np.ascontiguousarray(np.asarray(points, np.int32).reshape(-1, 2))
+        out = np.zeros(max(len(pts), 1), HIT_DTYPE)
+        assert HIT_DTYPE.itemsize == C.sizeof(Hit)
+        self._ck(self._L.gs_pick(self._h, C.byref(params), _p(pts) if len(pts) else None, len(pts), _p(out)))
+        return out[:len(pts)]
 
     def render_stereo(self, left, right):
         arr = (RenderParams * 2)(left, right)

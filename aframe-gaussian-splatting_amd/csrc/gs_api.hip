@@ -817,7 +817,7 @@ static void free_frame_resources(gs_ctx *c)
     dev_free(c->proj); dev_free(c->rect); dev_free(c->tile_count); dev_free(c->zwin);
     dev_free(c->pair_a); dev_free(c->pair_b); dev_free(c->emit_extra); dev_free(c->row_cnt); dev_free(c->row_tot); dev_free(c->seg_diff);
     gs_comm_free_lane(c);
-    dev_free(c->tile_range); dev_free(c->fb); dev_free(c->ctl); dev_free(c->state); dev_free(c->unsat_mask);
+    dev_free(c->tile_range); dev_free(c->fb); dev_free(c->ctl); dev_free(c->state); dev_free(c->unsat_mask); dev_free(c->surf_buf);
     dev_free(c->part_min); dev_free(c->part_max); dev_free(c->part_cnt); dev_free(c->part_valid); dev_free(c->part_vis); dev_free(c->dhist[0]); dev_free(c->dhist[1]);
     if (c->ctl_host) { (void)hipHostFree(c->ctl_host); c->ctl_host = nullptr; }
     if (c->ring) { for (int i = 0; i < GS_PROF_RING * GS_PROF_EVENTS; i++) if (c->ring[i]) (void)hipEventDestroy(c->ring[i]); free(c->ring); c->ring = nullptr; }
@@ -1484,6 +1484,7 @@ int gs_fill_uniforms(gs_ctx *ctx /* owner: options, adaptive share, scene */, co
         u.sh_cam[2] = -u.sh_cam[2];                                  // model_view acts on (x, y, -z): back to the rows' space (gs_sh.h)
         if (!regular) FAIL(GS_E_BADARG, "model_view is singular: no camera position to evaluate the spherical harmonics for");
     }
+    u.surf_id = nullptr; u.surf_depth = nullptr; u.surf_alpha = nullptr; u.surface = 0;   // (gs_render_surface sets them)
     return GS_OK;
 }
 
@@ -1641,6 +1642,7 @@ int gs_render_uniforms(gs_ctx *ctx, const GsFrameUniforms &u_in, void *device_rg
     L->stats.row_walk = row_walk_taken(L, u) ? 1u : 0u;
     L->stats.binning = gs_round0_binning(L, u);
     L->stats.sh_degree = u.sh_degree;
+    L->stats.surface = u.surface ? 1u : 0u;
     u.need_seed = L->need_seed_pending; L->need_seed_pending = 0;  // (a seed for the lane's need words travels with its next frame)
     bool async = (u.flags & GS_RENDER_ASYNC) && !(u.flags & GS_RENDER_COUNT_FRAGS);
     // A context that has not MEASURED its share yet (fresh, cleared, the share un-pinned) draws its first two-round frame synchronously
@@ -1708,6 +1710,109 @@ GS_API int gs_render_stereo(gs_ctx *ctx, const gs_render_params eyes[2], uint8_t
     if (!eyes || !rgba_out || !rgba_out[0] || !rgba_out[1]) FAIL(GS_E_BADARG, "gs_render_stereo: NULL argument");
     TRY(render_common(ctx, &eyes[0], nullptr, rgba_out[0], stride));
     return render_common(ctx, &eyes[1], nullptr, rgba_out[1], stride);
+}
+
+// ---- surface output: per pixel the splat at which the transmittance falls below one half, its window depth, the accumulated alpha
+// A surface frame is a synchronous frame on the tile lists (as a counting render is): the row walk, sub-tile lists and the split blend
+// are switched off in ITS uniforms, the context's options stay what they are; paired launches serve queued frames only.
+static int surface_common(gs_ctx *ctx, const gs_render_params *p, void *device_rgba, uint8_t *host_rgba, size_t stride, const gs_surface *dev)
+{
+    if (p && (p->flags & GS_RENDER_COUNT_FRAGS)) FAIL(GS_E_BADARG, "a surface frame cannot count fragments (GS_RENDER_COUNT_FRAGS)");
+    GsFrameUniforms u;
+    TRY(gs_fill_uniforms(ctx, p, u));
+    u.flags &= ~(uint32_t)GS_RENDER_ASYNC;
+    u.subtile = 0; u.row_walk = 0; u.split_min = 0;
+    u.surface = 1; u.surf_id = dev->id; u.surf_depth = dev->depth; u.surf_alpha = dev->alpha;
+    return gs_render_uniforms(ctx, u, device_rgba, host_rgba, stride);
+}
+
+// the context's own planes for a strip of sw x h pixels (owner; surface frames are synchronous: nothing in flight reads them)
+static int surface_scratch(gs_ctx *ctx, size_t sw, size_t h, gs_surface *dev)
+{
+    const size_t plane = (sw * h * 4 + 255) & ~(size_t)255;
+    if (3 * plane > ctx->surf_cap) {
+        GS_HIP(hipSetDevice(ctx->device));
+        dev_free(ctx->surf_buf); ctx->surf_cap = 0;
+        TRY(dev_alloc(ctx, &ctx->surf_buf, 3 * plane));
+        ctx->surf_cap = 3 * plane;
+    }
+    dev->id = reinterpret_cast<uint32_t *>(ctx->surf_buf);
+    dev->depth = reinterpret_cast<float *>(ctx->surf_buf + plane);
+    dev->alpha = reinterpret_cast<float *>(ctx->surf_buf + 2 * plane);
+    return GS_OK;
+}
+
+GS_API int gs_render_surface_device(gs_ctx *ctx, const gs_render_params *p, void *device_rgba, const gs_surface *device_out)
+{
+    CHECK_CTX(ctx);
+    if (!device_out) FAIL(GS_E_BADARG, "gs_render_surface_device: device_out is NULL");
+    return surface_common(ctx, p, device_rgba, nullptr, 0, device_out);
+}
+
+GS_API int gs_render_surface(gs_ctx *ctx, const gs_render_params *p, uint8_t *rgba_out, size_t stride, const gs_surface *host_out)
+{
+    CHECK_CTX(ctx);
+    if (!host_out) FAIL(GS_E_BADARG, "gs_render_surface: host_out is NULL");
+    if (p && (p->flags & GS_RENDER_COUNT_FRAGS)) FAIL(GS_E_BADARG, "a surface frame cannot count fragments (GS_RENDER_COUNT_FRAGS)");
+    GsFrameUniforms chk;
+    TRY(gs_fill_uniforms(ctx, p, chk));                          // (the strip's size is known to be sane from here on)
+    const size_t sw = (size_t)(p->x1 - p->x0), h = (size_t)p->fb_height;
+    gs_surface dev;
+    TRY(surface_scratch(ctx, sw, h, &dev));
+    TRY(surface_common(ctx, p, nullptr, rgba_out, stride, &dev));
+    // (the frame is complete: a synchronous frame returns behind its kernels)
+    if (host_out->id) GS_HIP(hipMemcpy(host_out->id, dev.id, sw * h * 4, hipMemcpyDeviceToHost));
+    if (host_out->depth) GS_HIP(hipMemcpy(host_out->depth, dev.depth, sw * h * 4, hipMemcpyDeviceToHost));
+    if (host_out->alpha) GS_HIP(hipMemcpy(host_out->alpha, dev.alpha, sw * h * 4, hipMemcpyDeviceToHost));
+    return GS_OK;
+}
+
+// One 16-pixel-aligned column strip per distinct tile column among the points: such a strip reproduces the full frame's columns bit
+// for bit (include/gs_splat.h: strips whose x0 is a multiple of 4), and costs a sixteenth of a tile row's blend per tile row.
+GS_API int gs_pick(gs_ctx *ctx, const gs_render_params *p, const int32_t *xy, size_t npoints, gs_hit *out)
+{
+    CHECK_CTX(ctx);
+    if (!p) FAIL(GS_E_BADARG, "render params NULL");
+    if (!out || (npoints && !xy)) FAIL(GS_E_BADARG, "gs_pick: NULL argument");
+    if (p->flags & GS_RENDER_COUNT_FRAGS) FAIL(GS_E_BADARG, "a surface frame cannot count fragments (GS_RENDER_COUNT_FRAGS)");
+    if (!ctx->renderable && ctx->n) FAIL(GS_E_STATE, "context was fed worker matrices only (gs_push_matrices): it can sort but not render");
+    gs_render_params q = *p;
+    q.x0 = 0; q.x1 = p->fb_width;
+    GsFrameUniforms chk;
+    TRY(gs_fill_uniforms(ctx, &q, chk));
+    for (size_t i = 0; i < npoints; i++)
+        if (xy[2 * i] < 0 || xy[2 * i] >= p->fb_width || xy[2 * i + 1] < 0 || xy[2 * i + 1] >= p->fb_height)
+            FAIL(GS_E_BADARG, "gs_pick: point %zu (%d, %d) lies outside the %dx%d frame", i, xy[2 * i], xy[2 * i + 1], p->fb_width, p->fb_height);
+    const size_t h = (size_t)p->fb_height;
+    std::vector<bool> done(npoints, false);
+    std::vector<uint32_t> host;                                  // the strip's three planes as the scratch holds them: one copy
+    for (size_t i = 0; i < npoints; i++) {
+        if (done[i]) continue;
+        q.x0 = xy[2 * i] / GS_TILE * GS_TILE;
+        q.x1 = q.x0 + GS_TILE < p->fb_width ? q.x0 + GS_TILE : p->fb_width;
+        const size_t sw = (size_t)(q.x1 - q.x0);
+        gs_surface dev;
+        TRY(surface_scratch(ctx, sw, h, &dev));
+        TRY(surface_common(ctx, &q, nullptr, nullptr, 0, &dev));
+        const size_t plane = (size_t)(reinterpret_cast<uint8_t *>(dev.depth) - reinterpret_cast<uint8_t *>(dev.id)) / 4;   // words between two planes
+        host.resize(2 * plane + sw * h);
+        GS_HIP(hipMemcpy(host.data(), dev.id, host.size() * 4, hipMemcpyDeviceToHost));
+        for (size_t k = i; k < npoints; k++) {
+            if (done[k] || xy[2 * k] < q.x0 || xy[2 * k] >= q.x1) continue;
+            const size_t o = (size_t)xy[2 * k + 1] * sw + (size_t)(xy[2 * k] - q.x0);
+            gs_hit &hit = out[k];
+            hit.id = host[o];
+            memcpy(&hit.depth, &host[plane + o], 4); memcpy(&hit.alpha, &host[2 * plane + o], 4);
+            hit.pos[0] = hit.pos[1] = hit.pos[2] = nanf("");
+            if (hit.id != 0xFFFFFFFFu && hit.id < ctx->n) {
+                float c[3];                                         // the packed centre (x, y, -z): index.js:350-354
+                GS_HIP(hipMemcpy(c, ctx->splat + 2 * (size_t)hit.id, sizeof c, hipMemcpyDeviceToHost));
+                hit.pos[0] = c[0]; hit.pos[1] = c[1]; hit.pos[2] = -c[2];
+            }
+            done[k] = true;
+        }
+    }
+    return GS_OK;
 }
 
 GS_API int gs_set_scene(gs_ctx *ctx, const float *depth, const uint8_t *rgba, int fb_width, int fb_height)

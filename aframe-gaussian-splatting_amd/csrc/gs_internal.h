@@ -150,6 +150,11 @@ struct GsFrameUniforms {           // per-render constants, passed by value to k
     uint32_t sh_row_q;             // 16-byte words per stored row (3 channels of sh_channel_stride(stored degree) f32)
     const uint4 *sh_rows;          // the store
     double sh_cam[3];              // the camera in the rows' object space (gsm::camera_in_object of mv with z negated, on the host)
+    // surface output (gs_render_surface; behind everything else again).  `surface` is read by k_project (zwin is written), the planes by k_blend_surf only
+    uint32_t *surf_id;             // (x1 - x0) x H planes, tight, laid out like the strip's colour; any may be null (not written)
+    float *surf_depth;
+    float *surf_alpha;
+    uint32_t surface;              // != 0: a surface frame -- tile lists, k_blend_surf
 };
 
 struct GsLaneWorker;
@@ -241,7 +246,7 @@ struct gs_ctx {
     uint2 *rect;                   // V x (tx0 | ty0<<16, tx1 | ty1<<16), strip-local tile coords
     uint32_t *tile_count;          // V
     uint2 *emit_extra;             // pair_cap / GS_EMIT_PAIRS + 2 (chunk, slice) items of the chunks with more than GS_EMIT_PAIRS pairs
-    float *zwin;                   // V window depth of each sorted splat (written only while a scene depth buffer is set)
+    float *zwin;                   // V window depth of each sorted splat (written while a scene depth buffer is set, and by surface frames)
     float *scene_depth; uint32_t *scene_rgba; int scene_w, scene_h;   // gs_set_scene
     uint2 *pair_a, *pair_b; size_t pair_cap;   // (tile id, sorted position) records, ping-pong
     uint32_t blend_split_min;               // owner: GS_OPT_BLEND_SPLIT
@@ -256,6 +261,7 @@ struct gs_ctx {
     uint32_t last_pairs, last_visible;      // owner: I and Vp of the last collected frame (what GS_OPT_SUBTILE = 1 decides on)
     uint2 *tile_range; size_t tile_cap;     // per tile [start,end) into the sorted pair list
     uint8_t *fb; size_t fb_cap;             // RGBA8 strip
+    uint8_t *surf_buf; size_t surf_cap;     // owner: the three planes of gs_render_surface / gs_pick (id, depth, alpha; 256-byte aligned each)
     // multi-GPU frames (gs_comm.hip)
     struct GsComm *comm;                    // owner: the communicator this context joined (gs_comm_init)
     uint8_t *gstage; size_t gstage_cap;     // lane: the pieces of a gathered frame, tight rows each (its own; on the root everybody's)

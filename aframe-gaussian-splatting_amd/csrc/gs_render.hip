@@ -188,7 +188,7 @@ __device__ __forceinline__ void k_project_body(const uint32_t *__restrict__ sort
                     float4 *dst = reinterpret_cast<float4 *>(proj + j);
                     dst[0] = make_float4(p.cx, p.cy, p.ax, p.ay);
                     dst[1] = make_float4(p.bx, p.by, __uint_as_float(SH ? sh_colour_word(u, idx, cs, p.rgba) : p.rgba), p.alpha);
-                    if (u.has_depth) zwin[j] = x.zndc * 0.5f + 0.5f;           // gl_FragCoord.z of every fragment of the quad
+                    if (u.has_depth | u.surface) zwin[j] = x.zndc * 0.5f + 0.5f;   // gl_FragCoord.z of every fragment of the quad (a surface frame's depth plane)
                     if (ty1 - ty0 >= 2) {
                         // three or more tile rows: counted cooperatively, one lane per row -- by 16-lane groups up to 16 rows
                         // (queued from the front), by a whole wavefront beyond (queued from the back of the same arrays)
@@ -1209,20 +1209,29 @@ __device__ __forceinline__ uint32_t subtile_mask(const float4 ra, const float bx
 // its column, compacted by mbcnt into the batch's slots; a step with more hits than free slots takes the nearest ones and the next
 // step resumes right behind the last run taken.  Batches are thus the list's batches -- same entries, same slots, same order -- and
 // the images, exits and need records are the list path's, bit for bit; the walk stops where the list walk would (every lane left).
-template <bool COUNT, int ROUND, bool SCENE, bool SUB, bool WALK = false>
+// SURF: a surface frame (gs_render_surface): next to the colour the tile writes, per pixel, the list entry at which the transmittance
+// falls below one half -- the first entry with T_before >= 0.5 > T_after, the median of the blending weights -- as the splat's index
+// (`sorted` at the entry's position), its window depth (zwin) and the pixel's accumulated alpha 1 - T.  T never rises, so a pixel
+// whose T is below one half when a batch (or round 1) begins has its surface already: nothing is carried between the rounds beyond
+// the state they share anyway.  Per entry the four T are compared with 0.5 and the entry's slot is latched (the smallest slot: the
+// first crossing); the slot's sorted position and depth are kept at staging (s_j) and read back when the batch ends.  Lists only
+// (span lists or pair records), the compare/select step; pixels outside the strip start at T = 0: never a crossing, never written.
+template <bool COUNT, int ROUND, bool SCENE, bool SUB, bool WALK = false, bool SURF = false>
 __device__ __forceinline__ void k_blend_body(const uint2 *__restrict__ tile_range, const void *__restrict__ pairs,
                                              const gsm::Projected *__restrict__ proj, const GsFrameUniforms &u,
                                              uint8_t *__restrict__ out, float4 *__restrict__ state, uint32_t *__restrict__ mask,
                                              const float *__restrict__ zwin, const float *__restrict__ scene_depth,
-                                             const uint32_t *__restrict__ scene_rgba, GsControl *ctl)
+                                             const uint32_t *__restrict__ scene_rgba, GsControl *ctl,
+                                             const uint32_t *__restrict__ sorted = nullptr)
 {
     // one batch of list entries (+1 inert slot), 48 bytes each: the projected record's geometry (cx, cy, ax, ay | bx, by, -, -)
     // and its colour converted once per record (rgb8 * alpha / 255, alpha) -- one LDS base address serves all three reads
     __shared__ float4 s_ent[3 * (GS_BLEND_BATCH + 1)];
     __shared__ float s_z[GS_BLEND_BATCH + 2];                    // their window depths (SCENE only)
     __shared__ __attribute__((aligned(16))) uint8_t s_list[SUB ? GS_SUBTILE_GROUPS * GS_SUBTILE_STRIDE : 16];   // GS_OPT_SUBTILE: per 4x4-pixel block, the batch's entries (slots) that can reach it
-    __shared__ uint32_t s_j[WALK ? GS_BLEND_BATCH : 1];          // WALK: the batch's sorted positions, by slot
+    __shared__ uint32_t s_j[SURF ? 2 * GS_BLEND_BATCH : WALK ? GS_BLEND_BATCH : 1];   // WALK: the batch's sorted positions, by slot; SURF: those, and the window depths behind them
     static_assert(!WALK || (!COUNT && ROUND == 0 && !SUB), "the row walk serves round 0 of plain frames");
+    static_assert(!SURF || (!COUNT && !SUB && !WALK), "a surface frame takes the tile lists");
     const int lane = threadIdx.x;
     // (a round whose records did not fit bins nothing and this kernel draws the background: the completion word says so)
     if (blockIdx.x == 0 && lane == 0 && u.status && ctl->pair_overflow) atomicOr(u.status, 2u);
@@ -1278,6 +1287,10 @@ __device__ __forceinline__ void k_blend_body(const uint2 *__restrict__ tile_rang
     asm volatile("" : "+v"(kbig), "+v"(kone));                     // compiler builds each pair again in front of every use, 2 moves per entry)
     bool live = GS_LANE_LIVE();
     uint32_t nfr = 0, staged = 0, evaluated = 0;
+    // SURF: the sorted position and window depth of each pixel's surface (none yet), and the slot latched in the batch under way
+    uint32_t sfj0 = 0xFFFFFFFFu, sfj1 = 0xFFFFFFFFu, sfj2 = 0xFFFFFFFFu, sfj3 = 0xFFFFFFFFu;
+    float sfz0 = 1.0f, sfz1 = 1.0f, sfz2 = 1.0f, sfz3 = 1.0f;
+    uint32_t sfc0 = 0xFFFFFFFFu, sfc1 = 0xFFFFFFFFu, sfc2 = 0xFFFFFFFFu, sfc3 = 0xFFFFFFFFu;
     const uint2 range = WALK ? tile_range[ty] : tile_range[tile];  // the list [x, y) / WALK: the row's runs [x, x + y)
     if (!WALK && u.split_min && range.y - range.x >= u.split_min) continue;  // a long list: k_blend_px takes the tile (GS_OPT_BLEND_SPLIT)
     const uint32_t *__restrict__ run_geom = reinterpret_cast<const uint32_t *>(pairs), *__restrict__ run_ref = run_geom + u.walk_ref;
@@ -1321,6 +1334,8 @@ __device__ __forceinline__ void k_blend_body(const uint2 *__restrict__ tile_rang
         staged += nb;
         nb_last = nb; e_l = 0;
         uint32_t m16 = 0;                                          // GS_OPT_SUBTILE: the 4x4-pixel blocks of the tile this lane's entry can reach
+        // SURF: the pixels that have no surface yet when the batch begins (T exactly 0.5 has not crossed)
+        const bool sfo0 = SURF && TA.x >= 0.5f, sfo1 = SURF && TA.y >= 0.5f, sfo2 = SURF && TB.x >= 0.5f, sfo3 = SURF && TB.y >= 0.5f;
 #pragma unroll
         for (int h = 0; h < GS_BLEND_BATCH / 64; h++) {            // nearest first: reverse the back-to-front list
             const uint32_t slot = h * 64 + lane;
@@ -1341,6 +1356,7 @@ __device__ __forceinline__ void k_blend_body(const uint2 *__restrict__ tile_rang
                 // compiler copies the word to a register of its own first, one VALU instruction per list entry)
                 s_ent[3 * slot + 2] = make_float4(-rb.w, (float)(rgba & 0xFF) * a255, (float)((rgba >> 8) & 0xFF) * a255, (float)((rgba >> 16) & 0xFF) * a255);
                 if (SCENE) s_z[slot] = u.has_depth ? zwin[j] : 0.0f;
+                if (SURF) { s_j[slot] = j; s_j[GS_BLEND_BATCH + slot] = __float_as_uint(zwin[j]); }
             }
         }
         if (lane == 0 && (nb & 1)) {
@@ -1384,7 +1400,7 @@ __device__ __forceinline__ void k_blend_body(const uint2 *__restrict__ tile_rang
                 const f2 pxA_##K = fma2_lo12(dxA_##K, axbx_##K, dyab_##K), pxB_##K = fma2_lo12(dxB_##K, axbx_##K, dyab_##K); \
                 const f2 pyA_##K = fma2_hi12(dxA_##K, axbx_##K, dyab_##K), pyB_##K = fma2_hi12(dxB_##K, axbx_##K, dyab_##K); \
                 const f2 qA = fma2(pxA_##K, pxA_##K, pyA_##K * pyA_##K), qB = fma2(pxB_##K, pxB_##K, pyB_##K * pyB_##K);
-#define GS_BLEND_APPLY(qA, qB, EB, zz)                                                                                 \
+#define GS_BLEND_APPLY(qA, qB, EB, zz, ss)                                                                             \
                 {                                                                                                      \
                     bool p0 = qA.x <= qmA.x, p1 = qA.y <= qmA.y, p2 = qB.x <= qmB.x, p3 = qB.y <= qmB.y;               \
                     if (SCENE) { p0 = p0 && zz <= zb0; p1 = p1 && zz <= zb1; p2 = p2 && zz <= zb2; p3 = p3 && zz <= zb3; } \
@@ -1410,6 +1426,11 @@ __device__ __forceinline__ void k_blend_body(const uint2 *__restrict__ tile_rang
                         const f2 chv_ = { ch_.x, ch_.y };                                                              \
                         cbA = fma2_hi0(chv_, eA, cbA); cbB = fma2_hi0(chv_, eB, cbB);                                  \
                         if (COUNT) nfr += (uint32_t)p0 + (uint32_t)p1 + (uint32_t)p2 + (uint32_t)p3;                   \
+                        if (SURF) {                                  /* the first slot behind which T < 0.5 */         \
+                            const uint32_t s_ = (ss);                                                                  \
+                            sfc0 = TA.x < 0.5f ? min(sfc0, s_) : sfc0; sfc1 = TA.y < 0.5f ? min(sfc1, s_) : sfc1;      \
+                            sfc2 = TB.x < 0.5f ? min(sfc2, s_) : sfc2; sfc3 = TB.y < 0.5f ? min(sfc3, s_) : sfc3;      \
+                        }                                                                                              \
                         live = GS_LANE_LIVE();                                                                         \
                     }                                                                                                  \
                 }
@@ -1452,8 +1473,8 @@ __device__ __forceinline__ void k_blend_body(const uint2 *__restrict__ tile_rang
                     GS_BLEND_APPLY_W(qA1, qB1, eb1)
                 } else {
                 const float z0 = SCENE ? s_z[i0] : 0.0f, z1 = SCENE ? s_z[i1] : 0.0f;
-                GS_BLEND_APPLY(qA0, qB0, eb0, z0)
-                GS_BLEND_APPLY(qA1, qB1, eb1, z1)
+                GS_BLEND_APPLY(qA0, qB0, eb0, z0, i0)
+                GS_BLEND_APPLY(qA1, qB1, eb1, z1, i1)
                 }
                 if (!live) { i_last = min(i1 < GS_SUBTILE_INERT ? i1 : (i0 < GS_SUBTILE_INERT ? i0 : 0u), nb - 1u); break; }
             }
@@ -1475,13 +1496,13 @@ __device__ __forceinline__ void k_blend_body(const uint2 *__restrict__ tile_rang
                 GS_BLEND_Q(1, eb + 48, qA1, qB1)                      // slot nb holds an inert record when nb is odd
                 const uint32_t s = SCENE ? vo / 48u : 0u;               // (the entry's index: only the scene's depth test needs it)
                 const float z0 = SCENE ? s_z[s] : 0.0f;
-                if (GS_BLEND_FACTOR && !COUNT && !SCENE) {
+                if (GS_BLEND_FACTOR && !COUNT && !SCENE && !SURF) {
                     GS_BLEND_APPLY_W(qA0, qB0, eb)
                     GS_BLEND_APPLY_W(qA1, qB1, eb + 48)
                 } else {
-                GS_BLEND_APPLY(qA0, qB0, eb, z0)
+                GS_BLEND_APPLY(qA0, qB0, eb, z0, vo / 48u)
                 const float z1 = SCENE ? s_z[s + 1] : 0.0f;
-                GS_BLEND_APPLY(qA1, qB1, eb + 48, z1)
+                GS_BLEND_APPLY(qA1, qB1, eb + 48, z1, vo / 48u + 1u)
                 }
                 if (!live) break;
             }
@@ -1491,6 +1512,14 @@ __device__ __forceinline__ void k_blend_body(const uint2 *__restrict__ tile_rang
 #undef GS_BLEND_APPLY_W
 #undef GS_BLEND_APPLY
 #undef GS_BLEND_Q
+        if (SURF) {
+            // the slots latched in this batch -> the entries' sorted positions and depths (before the next batch restages them)
+            if (sfo0 && sfc0 != 0xFFFFFFFFu) { sfj0 = s_j[sfc0]; sfz0 = __uint_as_float(s_j[GS_BLEND_BATCH + sfc0]); }
+            if (sfo1 && sfc1 != 0xFFFFFFFFu) { sfj1 = s_j[sfc1]; sfz1 = __uint_as_float(s_j[GS_BLEND_BATCH + sfc1]); }
+            if (sfo2 && sfc2 != 0xFFFFFFFFu) { sfj2 = s_j[sfc2]; sfz2 = __uint_as_float(s_j[GS_BLEND_BATCH + sfc2]); }
+            if (sfo3 && sfc3 != 0xFFFFFFFFu) { sfj3 = s_j[sfc3]; sfz3 = __uint_as_float(s_j[GS_BLEND_BATCH + sfc3]); }
+            sfc0 = sfc1 = sfc2 = sfc3 = 0xFFFFFFFFu;
+        }
         end -= nb;
         __syncthreads();                                           // s_ent is rewritten by the next batch
         if (__all(!live)) break;
@@ -1567,6 +1596,46 @@ __device__ __forceinline__ void k_blend_body(const uint2 *__restrict__ tile_rang
 #pragma unroll
             for (int k = 0; k < 4; k++) if (xb + k < u.x1) dst[k] = px[k];
         }
+        if (SURF) {
+            // the three planes, laid out like the strip's colour: round 0 writes every pixel (a surface or "none"), round 1 the
+            // surfaces it found itself and every alpha
+            const size_t so = (size_t)orow * sw + (xb - u.x0);
+            const bool quad = xb + 3 < u.x1 && (sw & 3) == 0;
+            const uint32_t jk[4] = { sfj0, sfj1, sfj2, sfj3 };
+            const float zk[4] = { sfz0, sfz1, sfz2, sfz3 };
+            if (u.surf_id) {
+                // the splat's index as the sort numbers it: what k_project read at this position
+                const uint32_t near_sorted = ctl->near_sorted, n_rec = ctl->n_sorted, j_base = near_sorted ? ctl->n_valid - n_rec : 0u;
+                uint32_t ik[4];
+#pragma unroll
+                for (int k = 0; k < 4; k++) {
+                    ik[k] = 0xFFFFFFFFu;
+                    if (jk[k] != 0xFFFFFFFFu) ik[k] = !near_sorted ? sorted[jk[k]] : (jk[k] - j_base < n_rec ? sorted[jk[k] - j_base] : 0u);
+                }
+                uint32_t *d = u.surf_id + so;
+                if (ROUND == 0 && quad && !((uintptr_t)u.surf_id & 15u)) *reinterpret_cast<uint4 *>(d) = make_uint4(ik[0], ik[1], ik[2], ik[3]);
+                else {
+#pragma unroll
+                    for (int k = 0; k < 4; k++) if (xb + k < u.x1 && (ROUND == 0 || jk[k] != 0xFFFFFFFFu)) d[k] = ik[k];
+                }
+            }
+            if (u.surf_depth) {
+                float *d = u.surf_depth + so;
+                if (ROUND == 0 && quad && !((uintptr_t)u.surf_depth & 15u)) *reinterpret_cast<float4 *>(d) = make_float4(zk[0], zk[1], zk[2], zk[3]);
+                else {
+#pragma unroll
+                    for (int k = 0; k < 4; k++) if (xb + k < u.x1 && (ROUND == 0 || jk[k] != 0xFFFFFFFFu)) d[k] = zk[k];
+                }
+            }
+            if (u.surf_alpha) {
+                float *d = u.surf_alpha + so;
+                if (quad && !((uintptr_t)u.surf_alpha & 15u)) *reinterpret_cast<float4 *>(d) = make_float4(1.0f - Tk[0], 1.0f - Tk[1], 1.0f - Tk[2], 1.0f - Tk[3]);
+                else {
+#pragma unroll
+                    for (int k = 0; k < 4; k++) if (xb + k < u.x1) d[k] = 1.0f - Tk[k];
+                }
+            }
+        }
     }
     if (COUNT) {
 #pragma unroll
@@ -1592,6 +1661,17 @@ __global__ __launch_bounds__(64) void k_blend(const uint2 *__restrict__ tile_ran
                                               const uint32_t *__restrict__ scene_rgba, GsControl *ctl)
 {
     k_blend_body<COUNT, ROUND, SCENE, SUB, WALK>(tile_range, pairs, proj, u, out, state, mask, zwin, scene_depth, scene_rgba, ctl);
+}
+
+// ... of a surface frame (a kernel of its own name: the instantiations above stay what they were)
+template <int ROUND, bool SCENE>
+__global__ __launch_bounds__(64) void k_blend_surf(const uint2 *__restrict__ tile_range, const void *__restrict__ pairs,
+                                                   const gsm::Projected *__restrict__ proj, GsFrameUniforms u,
+                                                   uint8_t *__restrict__ out, float4 *__restrict__ state, uint32_t *__restrict__ mask,
+                                                   const float *__restrict__ zwin, const float *__restrict__ scene_depth,
+                                                   const uint32_t *__restrict__ scene_rgba, GsControl *ctl, const uint32_t *__restrict__ sorted)
+{
+    k_blend_body<false, ROUND, SCENE, false, false, true>(tile_range, pairs, proj, u, out, state, mask, zwin, scene_depth, scene_rgba, ctl, sorted);
 }
 
 // GS_OPT_BLEND_SPLIT: the tiles with LONG lists, four wavefronts per tile, ONE pixel per lane (wave w: tile rows 4w .. 4w+3).
@@ -1814,6 +1894,15 @@ int launch_blend(gs_ctx *ctx, const GsFrameUniforms &u, GsFrameUniforms v, uint8
     const uint32_t gb = ROUND == 1 ? (ntiles < 1024 ? ntiles : 1024) : ntiles;
     const bool scene = u.has_depth || u.has_scene_rgba;
     if ((u.flags & GS_RENDER_COUNT_FRAGS) || u.record_staged) v.split_min = 0;     // measurement renders: every tile by k_blend
+    if (v.surface) {
+        // a surface frame: tile lists, one wavefront per tile (gs_render_surface switches the other paths off for the frame)
+        if (scene) hipLaunchKernelGGL((k_blend_surf<ROUND, true>), dim3(gb), dim3(64), 0, st, ctx->tile_range, fpairs, bproj, v, out, ctx->state,
+                                      ctx->unsat_mask, bzwin, ctx->scene_depth, ctx->scene_rgba, ctx->ctl, (const uint32_t *)ctx->sorted);
+        else hipLaunchKernelGGL((k_blend_surf<ROUND, false>), dim3(gb), dim3(64), 0, st, ctx->tile_range, fpairs, bproj, v, out, ctx->state,
+                                ctx->unsat_mask, bzwin, ctx->scene_depth, ctx->scene_rgba, ctx->ctl, (const uint32_t *)ctx->sorted);
+        GS_HIP(hipGetLastError());
+        return GS_OK;
+    }
     if (ROUND == 0 && v.row_walk) {
         // no tile lists (run_round_spans): the tiles' entries from their rows' runs; fpairs = the run geometry
         const uint2 *rows = ctx->row_tot + GS_BLOCK;
@@ -2197,7 +2286,7 @@ bool gs_frames_batchable(const GsFrameUniforms &a, const GsFrameUniforms &b)
     return a.near_count == b.near_count && a.skip_round1 == b.skip_round1 && a.W == b.W && a.H == b.H && a.x0 == b.x0 && a.x1 == b.x1 &&
            a.flags == b.flags && !(a.flags & (GS_RENDER_COUNT_FRAGS | GS_RENDER_COUNT_EVALUATED)) && !a.record_staged && !b.record_staged &&
            a.split_min == b.split_min && a.subtile == b.subtile && a.row_walk == b.row_walk && a.has_depth == b.has_depth && a.has_scene_rgba == b.has_scene_rgba && a.t_eps == b.t_eps &&
-           a.sh_degree == b.sh_degree;
+           a.sh_degree == b.sh_degree && !a.surface && !b.surface;
 }
 
 int gs_run_render2(gs_ctx *const S[2], const GsFrameUniforms U[2], uint8_t *const device_out[2])
@@ -2249,7 +2338,14 @@ int gs_run_render(gs_ctx *ctx, const GsFrameUniforms &u, uint8_t *device_out)
         GS_HIP(hipMemsetAsync(ctx->tile_range, 0, sizeof(uint2) * ntiles, st));
         GsFrameUniforms ub = u; ub.near_count = 0xFFFFFFFFu;
         GS_PROF_RECORD(ctx, 3); GS_PROF_RECORD(ctx, 4);
-        if (ub.has_scene_rgba)
+        if (ub.surface) {
+            if (ub.has_scene_rgba)
+                hipLaunchKernelGGL((k_blend_surf<0, true>), dim3(ntiles), dim3(64), 0, st, ctx->tile_range, ctx->pair_a, ctx->proj, ub, out,
+                                   ctx->state, ctx->unsat_mask, ctx->zwin, ctx->scene_depth, ctx->scene_rgba, ctx->ctl, (const uint32_t *)ctx->sorted);
+            else
+                hipLaunchKernelGGL((k_blend_surf<0, false>), dim3(ntiles), dim3(64), 0, st, ctx->tile_range, ctx->pair_a, ctx->proj, ub, out,
+                                   ctx->state, ctx->unsat_mask, ctx->zwin, ctx->scene_depth, ctx->scene_rgba, ctx->ctl, (const uint32_t *)ctx->sorted);
+        } else if (ub.has_scene_rgba)
             hipLaunchKernelGGL((k_blend<false, 0, true>), dim3(ntiles), dim3(64), 0, st, ctx->tile_range, ctx->pair_a, ctx->proj, ub, out,
                                ctx->state, ctx->unsat_mask, ctx->zwin, ctx->scene_depth, ctx->scene_rgba, ctx->ctl);
         else

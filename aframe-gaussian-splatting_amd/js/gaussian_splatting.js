@@ -195,7 +195,34 @@ class GaussianSplatting {
     return native.renderAsync(this.handle, p, this._frame(p));
   }
 
+  // Surface output (beyond the reference, whose material has depthWrite: false, index.js:177-181): the frame and, per pixel, the
+  // splat at which the transmittance falls below one half (`id`, 0xFFFFFFFF: none), its window depth (0 = near, 1 = far; 1: none)
+  // and the accumulated alpha -- {rgba, id: Uint32Array, depth: Float32Array, alpha: Float32Array}, row 0 = top.  Synchronous;
+  // draws from the last completed order like render().
+  renderSurface(camera, viewport, options) {
+    return native.renderSurface(this.handle, this._renderParams(camera, viewport, options));
+  }
+
+  // What a cursor, laser-controls or raycaster hit needs: the splat under pixel (x, y) of the CURRENT frame's drawing buffer (the
+  // camera, viewport and options of the last render / frame / renderSurface call; column, row, row 0 = top), or null where nothing
+  // is opaque enough (the transmittance never falls below one half).  -> {index, depth, alpha, position, worldPosition}:
+  // `position` is the splat's centre as its .splat row stores it; `worldPosition` is that point taken to world space by the
+  // entity's matrixWorld.  The rows' space is the reference's mirrored one -- getModelViewMatrix conjugates with diag(1, -1, 1)
+  // and the packed centre is (x, y, -z) (index.js:350-354, 467-487) -- so the three.js object-space point matrixWorld acts on is
+  // (x, -y, -z): what a raycaster's intersection.point holds.
+  pick(x, y) {
+    const v = this._lastView;
+    if (!v) throw new Error('pick: no frame has been drawn yet');
+    const hit = native.pick(this.handle, this._renderParams(v.camera, v.viewport, v.options), new Int32Array([x, y]))[0];
+    if (hit.index < 0) return null;
+    const m = elementsOf(this.object.matrixWorld), px = hit.position[0], py = -hit.position[1], pz = -hit.position[2];
+    hit.worldPosition = [m[0] * px + m[4] * py + m[8] * pz + m[12], m[1] * px + m[5] * py + m[9] * pz + m[13],
+      m[2] * px + m[6] * py + m[10] * pz + m[14]];
+    return hit;
+  }
+
   _renderParams(camera, viewport, options) {
+    this._lastView = { camera, viewport, options };
     const proj = this.getProjectionMatrix(camera).elements;
     const p = Object.assign({
       modelView: this.getModelViewMatrix(camera).elements, projection: proj,

@@ -433,6 +433,78 @@ static napi_value fn_render(napi_env env, napi_callback_info info)
     return ta;
 }
 
+/* renderSurface(h, params) -> {rgba: Uint8Array, id: Uint32Array, depth: Float32Array, alpha: Float32Array}: the frame and, per pixel,
+ * the splat at which the transmittance falls below one half (0xFFFFFFFF: never), its window depth (1: none) and the accumulated
+ * alpha (gs_render_surface); all (x1-x0) x height, row 0 = top */
+static napi_value fn_render_surface(napi_env env, napi_callback_info info)
+{
+    napi_value argv[2];
+    if (!get_args(env, info, 2, argv, NULL)) return NULL;
+    gs_ctx *ctx = get_ctx(env, argv[0]); if (!ctx) return NULL;
+    gs_render_params p;
+    if (!fill_params(env, argv[1], &p)) { napi_throw_type_error(env, NULL, "renderSurface: bad parameter object"); return NULL; }
+    if (p.x1 <= p.x0 || p.fb_height <= 0) { napi_throw_range_error(env, NULL, "renderSurface: empty strip"); return NULL; }
+    const size_t px = (size_t)(p.x1 - p.x0) * (size_t)p.fb_height;
+    napi_value ab[4], ta[4], o; void *out[4];
+    for (int k = 0; k < 4; k++) NAPI_OK(napi_create_arraybuffer(env, px * 4, &out[k], &ab[k]));
+    gs_surface s = { (uint32_t *)out[1], (float *)out[2], (float *)out[3] };
+    int rc = gs_render_surface(ctx, &p, (uint8_t *)out[0], 0, &s);
+    if (rc != GS_OK) return throw_gs(env, ctx, rc);
+    NAPI_OK(napi_create_typedarray(env, napi_uint8_array, px * 4, ab[0], 0, &ta[0]));
+    NAPI_OK(napi_create_typedarray(env, napi_uint32_array, px, ab[1], 0, &ta[1]));
+    NAPI_OK(napi_create_typedarray(env, napi_float32_array, px, ab[2], 0, &ta[2]));
+    NAPI_OK(napi_create_typedarray(env, napi_float32_array, px, ab[3], 0, &ta[3]));
+    NAPI_OK(napi_create_object(env, &o));
+    static const char *names[4] = { "rgba", "id", "depth", "alpha" };
+    for (int k = 0; k < 4; k++) NAPI_OK(napi_set_named_property(env, o, names[k], ta[k]));
+    return o;
+}
+
+/* pick(h, params, Int32Array [x0, y0, x1, y1, ...]) -> [{index, depth, alpha, position}]: what the full frame's planes hold at those
+ * pixels (column, row; row 0 = top) and the hit splat's position as its .splat row stores it (gs_pick); index -1 and position null
+ * where there is no surface */
+static napi_value fn_pick(napi_env env, napi_callback_info info)
+{
+    napi_value argv[3];
+    if (!get_args(env, info, 3, argv, NULL)) return NULL;
+    gs_ctx *ctx = get_ctx(env, argv[0]); if (!ctx) return NULL;
+    gs_render_params p;
+    if (!fill_params(env, argv[1], &p)) { napi_throw_type_error(env, NULL, "pick: bad parameter object"); return NULL; }
+    bool is_ta = false;
+    napi_typedarray_type tt; size_t len = 0; void *data = NULL;
+    if (napi_is_typedarray(env, argv[2], &is_ta) != napi_ok || !is_ta ||
+        napi_get_typedarray_info(env, argv[2], &tt, &len, &data, NULL, NULL) != napi_ok || tt != napi_int32_array || (len & 1)) {
+        napi_throw_type_error(env, NULL, "pick: points must be an Int32Array of (column, row) pairs");
+        return NULL;
+    }
+    const size_t n = len / 2;
+    gs_hit *hits = (gs_hit *)malloc((n ? n : 1) * sizeof(gs_hit));
+    if (!hits) { napi_throw_error(env, NULL, "pick: out of memory"); return NULL; }
+    int rc = gs_pick(ctx, &p, (const int32_t *)data, n, hits);
+    if (rc != GS_OK) { free(hits); return throw_gs(env, ctx, rc); }
+    napi_value arr = NULL;
+    napi_status st = napi_create_array_with_length(env, n, &arr);
+    for (size_t i = 0; st == napi_ok && i < n; i++) {
+        napi_value o, v;
+        const int none = hits[i].id == 0xFFFFFFFFu;
+        if ((st = napi_create_object(env, &o)) != napi_ok) break;
+        if ((st = napi_create_double(env, none ? -1.0 : (double)hits[i].id, &v)) != napi_ok || (st = napi_set_named_property(env, o, "index", v)) != napi_ok) break;
+        if ((st = napi_create_double(env, (double)hits[i].depth, &v)) != napi_ok || (st = napi_set_named_property(env, o, "depth", v)) != napi_ok) break;
+        if ((st = napi_create_double(env, (double)hits[i].alpha, &v)) != napi_ok || (st = napi_set_named_property(env, o, "alpha", v)) != napi_ok) break;
+        if (none) st = napi_get_null(env, &v);
+        else {
+            const double pos[3] = { hits[i].pos[0], hits[i].pos[1], hits[i].pos[2] };
+            v = make_f64_array(env, pos, 3);
+            if (!v) st = napi_generic_failure;
+        }
+        if (st != napi_ok || (st = napi_set_named_property(env, o, "position", v)) != napi_ok) break;
+        st = napi_set_element(env, arr, (uint32_t)i, o);
+    }
+    free(hits);
+    if (st != napi_ok) { napi_throw_error(env, NULL, "pick: could not build the result"); return NULL; }
+    return arr;
+}
+
 /* page-locked framebuffers handed to JavaScript as external ArrayBuffers: gs_render copies into them at PCIe speed and the
  * same memory is reused frame after frame (no per-call allocation, no extra copy) */
 static void frame_finalize(napi_env env, void *data, void *hint) { (void)env; (void)hint; gs_host_free(data); }
@@ -765,7 +837,7 @@ static napi_value fn_stats(napi_env env, napi_callback_info info)
     PUT("msBin", s.ms_bin); PUT("msBlend", s.ms_blend); PUT("msRender", s.ms_render);
     PUT("accFrames", s.acc_frames); PUT("unsatTiles", s.unsat_tiles); PUT("nearPermille", s.near_permille); PUT("sortRecords", s.sort_records);
     PUT("retriedFrames", s.retried_frames); PUT("specSorts", s.spec_sorts); PUT("specMisses", s.spec_misses); PUT("needSplats", s.need_splats); PUT("sortMode", s.sort_mode); PUT("subtile", s.subtile);
-    PUT("shDegree", s.sh_degree);
+    PUT("shDegree", s.sh_degree); PUT("surface", s.surface);
 #undef PUT
     return o;
 }
@@ -1066,7 +1138,7 @@ static napi_value init(napi_env env, napi_value exports)
         { "create", fn_create }, { "destroy", fn_destroy }, { "clear", fn_clear }, { "pushSplat", fn_push_splat },
         { "pushMatrices", fn_push_matrices }, { "loadPly", fn_load_ply }, { "plyToSplat", fn_ply_to_splat }, { "plyToSplatGpu", fn_ply_to_splat_gpu }, { "plySh", fn_ply_sh }, { "pushSh", fn_push_sh },
         { "count", fn_count },
-        { "sort", fn_sort }, { "sortAsync", fn_sort_async }, { "sortBegin", fn_sort_begin }, { "sortPoll", fn_sort_poll }, { "render", fn_render }, { "renderInto", fn_render_into },
+        { "sort", fn_sort }, { "sortAsync", fn_sort_async }, { "sortBegin", fn_sort_begin }, { "sortPoll", fn_sort_poll }, { "render", fn_render }, { "renderInto", fn_render_into }, { "renderSurface", fn_render_surface }, { "pick", fn_pick },
         { "renderAsync", fn_render_async }, { "allocFrame", fn_alloc_frame }, { "sync", fn_sync },
         { "partition", fn_partition }, { "commUniqueId", fn_comm_unique_id }, { "commInit", fn_comm_init },
         { "sortGathered", fn_sort_gathered }, { "renderGathered", fn_render_gathered }, { "readGathered", fn_read_gathered }, { "setScene", fn_set_scene }, { "stats", fn_stats }, { "setOption", fn_set_option },

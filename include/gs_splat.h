@@ -201,6 +201,33 @@ GS_API int gs_sort_for(gs_ctx *ctx, const float view[4], const float *cutout16, 
 /* XR: two eyes share one sort order from the head camera (index.js:441) -- two params, two images. */
 GS_API int gs_render_stereo(gs_ctx *ctx, const gs_render_params eyes[2], uint8_t *rgba_out[2], size_t stride);
 
+/* ---- surface output (no reference counterpart: the material has depthWrite: false, index.js:177-181, so nothing tells a host what
+ * lies under a pixel) ------------------------------------------------------------------------------------------------------
+ * A pixel's fragments are its list entries that pass the discard test (q <= 4, index.js:172) and, while a scene depth is set, the
+ * LEQUAL test, nearest first -- exactly what the blend takes -- with the blend's own transmittance T_k = fma(-alpha, e T_{k-1}, T_{k-1}).
+ * The SURFACE of the pixel is the first fragment k with T_{k-1} >= 0.5 and T_k < 0.5: the median of the blending weights (strict: a T
+ * of exactly 0.5 has not crossed).  Three planes, each (x1-x0) x fb_height, tight, row 0 = top (GS_RENDER_FLIP_Y applies to all three):
+ *   id     u32  the surface splat's index as gs_sort numbers it (the value of the sorted order at that position); 0xFFFFFFFF: T never crosses
+ *   depth  f32  that splat's window depth zndc*0.5+0.5 (0 = near plane, 1 = far plane: the convention gs_set_scene takes); 1.0f: no surface
+ *   alpha  f32  1 - T where the pixel stopped: the value the colour's alpha byte is rounded from
+ * The colour of such a frame is bit-identical to gs_render's on the tile lists with the same GS_OPT_NEAR_PERMILLE.  A surface frame
+ * draws from the last completed order like gs_render; it is always synchronous (GS_RENDER_ASYNC is cleared) and always takes tile
+ * lists -- the row walk, sub-tile lists, the split blend and paired launches are off for that frame only, the options stay as set;
+ * both binning rounds work.  GS_RENDER_COUNT_FRAGS: GS_E_BADARG.  GS_RENDER_NO_EARLY_OUT is allowed.
+ * (The strict rule at T == 0.5 exactly is specified, not tested: byte alphas give no scene whose f32 transmittance lands on it.)
+ * Out of scope: gathered and gs_multi frames, gs_render_stereo (call once per eye), asynchronous surface frames. */
+typedef struct gs_surface { uint32_t *id; float *depth; float *alpha; } gs_surface;   /* any may be NULL: that plane is not written */
+/* host planes; rgba_out may be NULL (no colour wanted) */
+GS_API int gs_render_surface(gs_ctx *ctx, const gs_render_params *p, uint8_t *rgba_out, size_t stride, const gs_surface *host_out);
+/* device planes (tight; 16-byte aligned planes are stored four pixels at a time); device_rgba may be NULL */
+GS_API int gs_render_surface_device(gs_ctx *ctx, const gs_render_params *p, void *device_rgba, const gs_surface *device_out);
+/* What the full-frame planes of `p` (its x0 / x1 are ignored) hold at npoints pixels xy = (column, row; row 0 = top) -- exactly -- and
+ * the hit splat's centre in the rows' object space, as a .splat row stores it (NaN where id is none).  Draws one 16-pixel column
+ * strip per distinct tile column among the points.  A point outside the frame: GS_E_BADARG; a context fed with gs_push_matrices
+ * only: GS_E_STATE. */
+typedef struct gs_hit { uint32_t id; float depth; float alpha; float pos[3]; } gs_hit;
+GS_API int gs_pick(gs_ctx *ctx, const gs_render_params *p, const int32_t *xy, size_t npoints, gs_hit *out);
+
 /* Scene compositing inputs (reference: the splat mesh is drawn in three.js' transparent pass with depthTest: true,
  * depthWrite: false over the opaque scene, index.js:177-181): an optional window-space depth buffer of that scene
  * (GL convention: 0 = near plane, 1 = far plane; a fragment survives iff its depth zndc*0.5+0.5 <= the buffer, LEQUAL)
@@ -441,6 +468,7 @@ typedef struct gs_stats {
                              (asked for, or a strip of more than 256 tile columns or rows, or a row-count table beyond its limit); a frame
                              that runs no round (nothing resident) reports what its round would have taken                             */
     uint32_t sh_degree;   /* the spherical-harmonics degree the last frame's projection evaluated (GS_OPT_SH_DEGREE): 0 = packed byte colours   */
+    uint32_t surface;     /* 1 if the last frame wrote surface planes (gs_render_surface, gs_pick)                                        */
 } gs_stats;
 
 #define GS_OPT_PROFILE 1        /* 1: bracket every stage with HIP events on the frame's stream (7 per frame); 2: only
