@@ -26,6 +26,7 @@ OPT_BINNING = 16
 OPT_SUBTILE = 17
 OPT_ROW_WALK = 18
 OPT_SH_DEGREE = 19
+OPT_ANTIALIAS = 20
 TRANSPORT_RCCL, TRANSPORT_INPROC = 0, 1
 COMM_ID_BYTES = 128
 BUF_CENTER_SCALE, BUF_COV_COLOR, BUF_SORT_ROWS, BUF_SORTED, BUF_PROJECTED, BUF_TILE_COUNT, BUF_TILE_STATS, BUF_UNSAT_MASK = 0, 1, 2, 3, 4, 5, 6, 7
@@ -44,6 +45,7 @@ EXPORTS = [
     "gs_multi_render_device", "gs_multi_read", "gs_multi_sync",
     "gs_ply_sh", "gs_ply_sh_host", "gs_push_sh", "gs_sh_count", "gs_sh_eval", "gs_sh_eval_unrounded", "gs_camera_in_object", "gs_multi_push_sh",
     "gs_render_surface", "gs_render_surface_device", "gs_pick",
+    "gs_antialias_factor",
 ]
 SURFACE_NONE = 0xFFFFFFFF          # gs_surface.id / gs_hit.id where the transmittance never falls below one half
 
@@ -66,7 +68,7 @@ class Stats(C.Structure):
                 ("acc_pairs", C.c_uint64), ("unsat_tiles", C.c_uint32), ("near_permille", C.c_uint32),
                 ("sort_records", C.c_uint32), ("retried_frames", C.c_uint32), ("spec_sorts", C.c_uint32), ("spec_misses", C.c_uint32), ("need_splats", C.c_uint32),
                 ("sort_mode", C.c_uint32), ("subtile", C.c_uint32), ("row_walk", C.c_uint32),
-                ("binning", C.c_uint32), ("sh_degree", C.c_uint32), ("surface", C.c_uint32)]
+                ("binning", C.c_uint32), ("sh_degree", C.c_uint32), ("surface", C.c_uint32), ("antialias", C.c_uint32)]
 
     def as_dict(self):
         return {n: getattr(self, n) for n, _ in self._fields_}
@@ -193,6 +195,8 @@ def load(build_if_missing=True):
         L.gs_render_surface.argtypes = [vp, C.POINTER(RenderParams), vp, sz, C.POINTER(Surface)]
         L.gs_render_surface_device.argtypes = [vp, C.POINTER(RenderParams), vp, C.POINTER(Surface)]
         L.gs_pick.argtypes = [vp, C.POINTER(RenderParams), vp, sz, vp]
+    if hasattr(L, "gs_antialias_factor"):
+        L.gs_antialias_factor.argtypes = [vp, vp]
     L.gs_download.argtypes = [vp, i32, vp, sz]
     L.gs_comm_unique_id.argtypes = [vp, vp]
     L.gs_comm_init.argtypes = [vp, vp, i32, i32]
@@ -361,6 +365,22 @@ def camera_in_object(model_view):
     if rc != GS_OK:
         raise GsError(rc, "gs_camera_in_object: singular model_view")
     return out
+
+
+def antialias_factor(cov):
+    """gs_antialias_factor: cov = (cov00, cov01, cov11), a projected covariance in px^2 before the 0.3 px^2 dilation, or an array of
+    such rows -> the opacity factor c of GS_OPT_ANTIALIAS as float32 (one value, or one per row)."""
+    c = np.ascontiguousarray(cov, np.float32)
+    if c.shape[-1:] != (3,):
+        raise ValueError("rows of (cov00, cov01, cov11) expected")
+    rows = c.reshape(-1, 3)
+    out = np.zeros(len(rows), np.float32)
+    f, base, obase = load().gs_antialias_factor, rows.ctypes.data, out.ctypes.data
+    for i in range(len(rows)):
+        rc = f(base + 12 * i, obase + 4 * i)
+        if rc != GS_OK:
+            raise GsError(rc, "gs_antialias_factor: bad argument")
+    return out.reshape(c.shape[:-1]) if c.ndim > 1 else out[0]
 
 
 def make_params(mv, proj, width, height, x0=0, x1=None, focal_=0.0, background=(0.0, 0.0, 0.0, 1.0), flags=0):

@@ -1485,6 +1485,7 @@ int gs_fill_uniforms(gs_ctx *ctx /* owner: options, adaptive share, scene */, co
         if (!regular) FAIL(GS_E_BADARG, "model_view is singular: no camera position to evaluate the spherical harmonics for");
     }
     u.surf_id = nullptr; u.surf_depth = nullptr; u.surf_alpha = nullptr; u.surface = 0;   // (gs_render_surface sets them)
+    u.antialias = ctx->aa_opt ? 1u : 0u;                            // compensated opacity (GS_OPT_ANTIALIAS), per frame like the SH degree
     return GS_OK;
 }
 
@@ -1643,6 +1644,7 @@ int gs_render_uniforms(gs_ctx *ctx, const GsFrameUniforms &u_in, void *device_rg
     L->stats.binning = gs_round0_binning(L, u);
     L->stats.sh_degree = u.sh_degree;
     L->stats.surface = u.surface ? 1u : 0u;
+    L->stats.antialias = u.antialias ? 1u : 0u;
     u.need_seed = L->need_seed_pending; L->need_seed_pending = 0;  // (a seed for the lane's need words travels with its next frame)
     bool async = (u.flags & GS_RENDER_ASYNC) && !(u.flags & GS_RENDER_COUNT_FRAGS);
     // A context that has not MEASURED its share yet (fresh, cleared, the share un-pinned) draws its first two-round frame synchronously
@@ -2125,6 +2127,10 @@ GS_API int gs_set_option(gs_ctx *ctx, int option, int64_t value)
     case GS_OPT_SH_DEGREE:
         if (value < 0 || value > GS_SH_MAX_DEGREE) FAIL(GS_E_BADARG, "spherical-harmonics degree: 0 (off) to 3");
         ctx->sh_opt = (int)value;
+        return GS_OK;
+    case GS_OPT_ANTIALIAS:
+        if (value != 0 && value != 1) FAIL(GS_E_BADARG, "anti-aliased splats: 0 (off) or 1 (opacity compensated for the 0.3 px^2 dilation)");
+        ctx->aa_opt = (int)value;
         return GS_OK;
     case GS_OPT_SORT_NEAR:
         if (value < 0 || value > 2) FAIL(GS_E_BADARG, "near-only sorts: 0 (off), 1 (scenes of 4 M splats and more) or 2 (always)");

@@ -212,7 +212,32 @@ struct Projected {      // 32-byte record consumed by the blend kernel
     float alpha;        // rgba>>24 / 255
 };
 
-struct ProjExtra { float v1x, v1y, v2x, v2y, zndc; };
+struct ProjExtra { float v1x, v1y, v2x, v2y, zndc; float aa; };   // aa: antialias_factor of the splat (GS_OPT_ANTIALIAS)
+
+// Opacity compensation for the 0.3 px^2 dilation below (GS_OPT_ANTIALIAS): the EWA low-pass filter's normalisation, which the reference
+// leaves out.  c = sqrt(det(Sigma') / (l1 * l2)): the area of the un-dilated Gaussian over the area of the one the quad is really drawn
+// with -- l2 is the eigenvalue AFTER its clamp at 0.1.  Every operation is f32, in this order, un-fused (a numpy f32 mirror follows it
+// bit for bit); a NaN ratio (non-PSD or degenerate covariances, inf / inf) gives 0: fmaxf(NaN, 0) = 0.
+GS_HD float antialias_factor(float cov00, float cov01, float cov11, float l1, float l2)
+{
+    const float p = cov00 * cov11;
+    const float q = cov01 * cov01;
+    const float det = p - q;
+    const float den = l1 * l2;
+    float r = det / den;
+    r = fminf(fmaxf(r, 0.0f), 1.0f);
+    return sqrtf(r);
+}
+// the eigenvalues project_splat draws cov = {cov00, cov01, cov11} with (its very lines)
+GS_HD void dilated_eigenvalues(float cov00, float cov01, float cov11, float &l1, float &l2)
+{
+    const float d1 = cov00 + 0.3f, od = cov01, d2 = cov11 + 0.3f;
+    const float mid = 0.5f * (d1 + d2);
+    const float hd = (d1 - d2) / 2.0f;
+    const float radius = sqrtf(hd * hd + od * od);
+    l1 = mid + radius;
+    l2 = fmaxf(mid - radius, 0.1f);
+}
 
 // Returns false when the vertex shader would emit nothing for this splat (frustum cull index.js:110-115,
 // far-plane clip, or NaN axes).  mv/P are the f32 uniforms, column-major.
@@ -261,6 +286,7 @@ GS_HD bool project_splat(const float cs[4], const uint32_t cc[4], const float *m
     if (!(len > 0.0f) || !(len <= 3.402823466e+38f) || !(fabsf(l1) <= 3.402823466e+38f)) return false;
     const float dvx = dvx0 / len, dvy = dvy0 / len;
     const float s1 = fminf(sqrtf(2.0f * l1), 1024.0f), s2 = fminf(sqrtf(2.0f * l2), 1024.0f);
+    x.aa = antialias_factor(cov00, cov01, cov11, l1, l2);            // (dead code in every caller that does not read it)
     x.v1x = s1 * dvx; x.v1y = s1 * dvy;
     x.v2x = s2 * dvy; x.v2y = s2 * -dvx;
     const float ndcx = px / pw, ndcy = py / pw;

@@ -14,6 +14,7 @@
 #include "../../include/gs_splat.h"
 #include "gs_ply.h"
 #include "gs_sh.h"
+#include "gs_device_math.h"
 
 namespace {
 
@@ -334,6 +335,15 @@ GS_API int gs_sh_eval_unrounded(const float *sh_row, int degree, const double ca
     if (!sh_row || !cam || !pos || !out || degree < 0 || degree > GS_SH_MAX_DEGREE) return GS_E_BADARG;
     const gsm::ShRowPtr coef = { sh_row, gsm::sh_coefs(degree) };
     gsm::sh_unrounded(coef, degree, cam, pos, out);
+    return GS_OK;
+}
+
+GS_API int gs_antialias_factor(const float cov[3], float *out_c)
+{
+    if (!cov || !out_c) return GS_E_BADARG;
+    float l1, l2;
+    gsm::dilated_eigenvalues(cov[0], cov[1], cov[2], l1, l2);
+    *out_c = gsm::antialias_factor(cov[0], cov[1], cov[2], l1, l2);
     return GS_OK;
 }
 

@@ -155,6 +155,8 @@ struct GsFrameUniforms {           // per-render constants, passed by value to k
     float *surf_depth;
     float *surf_alpha;
     uint32_t surface;              // != 0: a surface frame -- tile lists, k_blend_surf
+    // anti-aliased splats (GS_OPT_ANTIALIAS; behind everything else once more).  Read by the host only: it picks k_project_aa
+    uint32_t antialias;            // != 0: this frame's projection writes alpha * antialias_factor into its records
 };
 
 struct GsLaneWorker;
@@ -201,6 +203,7 @@ struct gs_ctx {
     // every channel padded to whole 16-byte words (gs_sh.h: sh_channel_stride)
     float *sh; size_t sh_n, sh_cap; int sh_deg;   // rows stored / rows allocated / their degree (0 while empty)
     int sh_opt;                    // GS_OPT_SH_DEGREE
+    int aa_opt;                    // GS_OPT_ANTIALIAS (owner; taken per frame by gs_fill_uniforms)
 
     // sort scratch (sized by cap)
     float *depth;                  // stored f32 depth or +inf for culled

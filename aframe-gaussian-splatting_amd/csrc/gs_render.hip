@@ -137,7 +137,9 @@ __device__ __forceinline__ uint32_t sh_colour_word(const GsFrameUniforms &u, uin
     return (rgba & 0xFF000000u) | (uint32_t)b[0] | ((uint32_t)b[1] << 8) | ((uint32_t)b[2] << 16);
 }
 
-template <int ROUND, bool RUNS, bool SH = false>
+// AA (anti-aliased splats, GS_OPT_ANTIALIAS): the record's alpha float is alpha * gsm::antialias_factor -- the one word that differs; the
+// splat is written, counted and binned whatever the factor (0 included), so geometry, coverage and every count stay what they are.
+template <int ROUND, bool RUNS, bool SH = false, bool AA = false>
 __device__ __forceinline__ void k_project_body(const uint32_t *__restrict__ sorted, const uint4 *__restrict__ splat,
                                                const GsFrameUniforms &u, gsm::Projected *__restrict__ proj, uint2 *__restrict__ rect,
                                                uint32_t *__restrict__ tile_count, uint32_t *__restrict__ spine,
@@ -187,7 +189,7 @@ __device__ __forceinline__ void k_project_body(const uint32_t *__restrict__ sort
                     if (!RUNS || ty1 - ty0 >= 2) rect[j] = make_uint2(tx0 | (ty0 << 16), tx1 | (ty1 << 16));   // (RUNS, one or two tile rows: the runs themselves, below)
                     float4 *dst = reinterpret_cast<float4 *>(proj + j);
                     dst[0] = make_float4(p.cx, p.cy, p.ax, p.ay);
-                    dst[1] = make_float4(p.bx, p.by, __uint_as_float(SH ? sh_colour_word(u, idx, cs, p.rgba) : p.rgba), p.alpha);
+                    dst[1] = make_float4(p.bx, p.by, __uint_as_float(SH ? sh_colour_word(u, idx, cs, p.rgba) : p.rgba), AA ? p.alpha * x.aa : p.alpha);
                     if (u.has_depth | u.surface) zwin[j] = x.zndc * 0.5f + 0.5f;   // gl_FragCoord.z of every fragment of the quad (a surface frame's depth plane)
                     if (ty1 - ty0 >= 2) {
                         // three or more tile rows: counted cooperatively, one lane per row -- by 16-lane groups up to 16 rows
@@ -289,6 +291,17 @@ __global__ __launch_bounds__(GS_BLOCK) void k_project_sh(const uint32_t *__restr
                                                          float *__restrict__ zwin, GsControl *ctl)
 {
     k_project_body<ROUND, RUNS, true>(sorted, splat, u, proj, rect, tile_count, spine, part_vis, mask, zwin, ctl);
+}
+
+// ... with compensated opacity (GS_OPT_ANTIALIAS), with or without view-dependent colour (kernels of their own name again)
+template <int ROUND, bool RUNS, bool SH>
+__global__ __launch_bounds__(GS_BLOCK) void k_project_aa(const uint32_t *__restrict__ sorted, const uint4 *__restrict__ splat,
+                                                         GsFrameUniforms u, gsm::Projected *__restrict__ proj, uint2 *__restrict__ rect,
+                                                         uint32_t *__restrict__ tile_count, uint32_t *__restrict__ spine,
+                                                         uint32_t *__restrict__ part_vis, const uint32_t *__restrict__ mask,
+                                                         float *__restrict__ zwin, GsControl *ctl)
+{
+    k_project_body<ROUND, RUNS, SH, true>(sorted, splat, u, proj, rect, tile_count, spine, part_vis, mask, zwin, ctl);
 }
 
 // One workgroup: exclusive scan of the per-chunk totals (spine) -> chunk base offsets, I = grand total (refused and
@@ -1994,7 +2007,14 @@ int run_round_spans(gs_ctx *ctx, const GsFrameUniforms &u, uint8_t *out, bool la
     // the pair buffers hold the runs (geometry and sorted position of each: there are never more runs than tiles) and the lists
     uint32_t *run_geom = reinterpret_cast<uint32_t *>(ctx->pair_a), *run_ref = run_geom + ctx->pair_cap, *lists = reinterpret_cast<uint32_t *>(ctx->pair_b);
     const uint32_t pc = (uint32_t)ctx->pair_cap;
-    if (v.sh_degree)                                            // view-dependent colour: the SH instantiation (GS_OPT_SH_DEGREE)
+    if (v.antialias) {                                          // compensated opacity (GS_OPT_ANTIALIAS), with or without SH
+        if (v.sh_degree)
+            hipLaunchKernelGGL((k_project_aa<ROUND, true, true>), dim3(g), dim3(GS_BLOCK), 0, st, ctx->sorted, ctx->splat, v, ctx->proj, ctx->rect,
+                               ctx->tile_count, ctx->row_cnt, ctx->part_vis, ctx->unsat_mask, ctx->zwin, ctx->ctl);
+        else
+            hipLaunchKernelGGL((k_project_aa<ROUND, true, false>), dim3(g), dim3(GS_BLOCK), 0, st, ctx->sorted, ctx->splat, v, ctx->proj, ctx->rect,
+                               ctx->tile_count, ctx->row_cnt, ctx->part_vis, ctx->unsat_mask, ctx->zwin, ctx->ctl);
+    } else if (v.sh_degree)                                     // view-dependent colour: the SH instantiation (GS_OPT_SH_DEGREE)
         hipLaunchKernelGGL((k_project_sh<ROUND, true>), dim3(g), dim3(GS_BLOCK), 0, st, ctx->sorted, ctx->splat, v, ctx->proj, ctx->rect,
                            ctx->tile_count, ctx->row_cnt, ctx->part_vis, ctx->unsat_mask, ctx->zwin, ctx->ctl);
     else
@@ -2054,7 +2074,14 @@ int run_round(gs_ctx *ctx, const GsFrameUniforms &u, uint8_t *out, bool last_rou
     GsFrameUniforms v = u;
     v.rc_stride = 0;
     v.row_walk = 0;
-    if (u.sh_degree)
+    if (u.antialias) {
+        if (u.sh_degree)
+            hipLaunchKernelGGL((k_project_aa<ROUND, false, true>), dim3(g), dim3(GS_BLOCK), 0, st, ctx->sorted, ctx->splat, u, ctx->proj, ctx->rect,
+                               ctx->tile_count, ctx->spine, ctx->part_vis, ctx->unsat_mask, ctx->zwin, ctx->ctl);
+        else
+            hipLaunchKernelGGL((k_project_aa<ROUND, false, false>), dim3(g), dim3(GS_BLOCK), 0, st, ctx->sorted, ctx->splat, u, ctx->proj, ctx->rect,
+                               ctx->tile_count, ctx->spine, ctx->part_vis, ctx->unsat_mask, ctx->zwin, ctx->ctl);
+    } else if (u.sh_degree)
         hipLaunchKernelGGL((k_project_sh<ROUND, false>), dim3(g), dim3(GS_BLOCK), 0, st, ctx->sorted, ctx->splat, u, ctx->proj, ctx->rect,
                            ctx->tile_count, ctx->spine, ctx->part_vis, ctx->unsat_mask, ctx->zwin, ctx->ctl);
     else
@@ -2091,6 +2118,7 @@ int run_round(gs_ctx *ctx, const GsFrameUniforms &u, uint8_t *out, bool last_rou
 
 template <int ROUND, bool RUNS> GS_BODY(F_project, k_project_body<ROUND, RUNS>);
 template <int ROUND, bool RUNS> GS_BODY(F_project_sh, k_project_body<ROUND, RUNS, true>);
+template <int ROUND, bool RUNS, bool SH> GS_BODY(F_project_aa, k_project_body<ROUND, RUNS, SH, true>);
 template <int ROUND> GS_BODY(F_row_scan, k_row_scan_body<ROUND>);
 template <int ROUND> GS_BODY(F_emit_runs, k_emit_runs_body<ROUND>);
 template <int ROUND> GS_BODY(F_seg_count, k_seg_count_body<ROUND>);
@@ -2150,6 +2178,10 @@ int run_round_spans2(gs_ctx *const S[2], const GsFrameUniforms U[2], uint8_t *co
                                   (const uint32_t *)S[0]->unsat_mask, S[0]->zwin, S[0]->ctl);
     const auto pp1 = gs_pack_make((const uint32_t *)S[1]->sorted, (const uint4 *)S[1]->splat, V[1], S[1]->proj, S[1]->rect, S[1]->tile_count, S[1]->row_cnt, S[1]->part_vis,
                                   (const uint32_t *)S[1]->unsat_mask, S[1]->zwin, S[1]->ctl);
+    if (u.antialias) {                                          // (paired frames share the setting too)
+        if (u.sh_degree) gs_twin<F_project_aa<ROUND, true, true>, GS_BLOCK>(g, st, pp0, pp1);
+        else gs_twin<F_project_aa<ROUND, true, false>, GS_BLOCK>(g, st, pp0, pp1);
+    } else
     if (u.sh_degree) gs_twin<F_project_sh<ROUND, true>, GS_BLOCK>(g, st, pp0, pp1);   // (paired frames share their degree: gs_frames_batchable)
     else gs_twin<F_project<ROUND, true>, GS_BLOCK>(g, st, pp0, pp1);
     GS_HIP(hipGetLastError());
@@ -2218,6 +2250,10 @@ int run_round2(gs_ctx *const S[2], const GsFrameUniforms U[2], uint8_t *const ou
                                   (const uint32_t *)S[0]->unsat_mask, S[0]->zwin, S[0]->ctl);
     const auto pp1 = gs_pack_make((const uint32_t *)S[1]->sorted, (const uint4 *)S[1]->splat, U[1], S[1]->proj, S[1]->rect, S[1]->tile_count, S[1]->spine, S[1]->part_vis,
                                   (const uint32_t *)S[1]->unsat_mask, S[1]->zwin, S[1]->ctl);
+    if (u.antialias) {
+        if (u.sh_degree) gs_twin<F_project_aa<ROUND, false, true>, GS_BLOCK>(g, st, pp0, pp1);
+        else gs_twin<F_project_aa<ROUND, false, false>, GS_BLOCK>(g, st, pp0, pp1);
+    } else
     if (u.sh_degree) gs_twin<F_project_sh<ROUND, false>, GS_BLOCK>(g, st, pp0, pp1);   // (paired frames share their degree: gs_frames_batchable)
     else gs_twin<F_project<ROUND, false>, GS_BLOCK>(g, st, pp0, pp1);
     GS_HIP(hipGetLastError());
@@ -2286,7 +2322,7 @@ bool gs_frames_batchable(const GsFrameUniforms &a, const GsFrameUniforms &b)
     return a.near_count == b.near_count && a.skip_round1 == b.skip_round1 && a.W == b.W && a.H == b.H && a.x0 == b.x0 && a.x1 == b.x1 &&
            a.flags == b.flags && !(a.flags & (GS_RENDER_COUNT_FRAGS | GS_RENDER_COUNT_EVALUATED)) && !a.record_staged && !b.record_staged &&
            a.split_min == b.split_min && a.subtile == b.subtile && a.row_walk == b.row_walk && a.has_depth == b.has_depth && a.has_scene_rgba == b.has_scene_rgba && a.t_eps == b.t_eps &&
-           a.sh_degree == b.sh_degree && !a.surface && !b.surface;
+           a.sh_degree == b.sh_degree && a.antialias == b.antialias && !a.surface && !b.surface;
 }
 
 int gs_run_render2(gs_ctx *const S[2], const GsFrameUniforms U[2], uint8_t *const device_out[2])

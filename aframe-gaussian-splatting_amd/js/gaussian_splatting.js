@@ -20,8 +20,13 @@ const schema = {                                   // index.js:2-7
   // beyond the reference: the highest spherical-harmonics band of a .ply to keep and evaluate per frame (view-dependent colour,
   // GS_OPT_SH_DEGREE); 0 = the reference's baked f_dc colour.  `.splat` files carry no coefficients and ignore it.
   shDegree: { type: 'number', default: 0 },
+  // beyond the reference: compensate every splat's opacity for the 0.3 px^2 dilation of its projected covariance (index.js:139-141;
+  // GS_OPT_ANTIALIAS) -- for scenes trained with an anti-aliased rasteriser, and for low pixelRatio / xrPixelRatio.  May be
+  // changed on a live component: the next frame takes it.
+  antialias: { type: 'boolean', default: false },
 };
 const OPT_SH_DEGREE = 19;
+const OPT_ANTIALIAS = 20;
 const ROW_LENGTH = 3 * 4 + 3 * 4 + 4 + 4;          // index.js:227
 
 function elementsOf(m) { return m && m.elements ? m.elements : m; }
@@ -29,11 +34,13 @@ function elementsOf(m) { return m && m.elements ? m.elements : m; }
 class GaussianSplatting {
   constructor(data, options) {
     this.data = Object.assign({ src: schema.src.default, cutoutEntity: null, pixelRatio: schema.pixelRatio.default,
-      xrPixelRatio: schema.xrPixelRatio.default, shDegree: schema.shDegree.default }, data || {});
+      xrPixelRatio: schema.xrPixelRatio.default, shDegree: schema.shDegree.default, antialias: schema.antialias.default }, data || {});
     this.device = (options && options.device) || 0;
     this.handle = native.create(this.device);       // replaces `new Worker(...)` + GL resource creation
     this.shDegree = Math.max(0, Math.min(3, Math.floor(Number(this.data.shDegree) || 0)));
     if (this.shDegree > 0) native.setOption(this.handle, OPT_SH_DEGREE, this.shDegree);
+    this.antialias = false;
+    this.update(this.data);
     this.loadedVertexCount = 0;
     this.rowLength = ROW_LENGTH;
     this.sortReady = true;
@@ -48,6 +55,17 @@ class GaussianSplatting {
     if (r && this.data.pixelRatio > 0 && r.setPixelRatio) r.setPixelRatio(this.data.pixelRatio);
     if (r && this.data.xrPixelRatio > 0 && r.xr && r.xr.setFramebufferScaleFactor) r.xr.setFramebufferScaleFactor(this.data.xrPixelRatio);
     if (this.data.cutoutEntity) this.cutout = this.data.cutoutEntity.object3D || this.data.cutoutEntity;
+    return this;
+  }
+
+  // update (the component life cycle's): the properties that may change on a live component.  `antialias` reaches the library only
+  // when it changes, and only as GS_OPT_ANTIALIAS; the next frame drawn takes it.
+  update(data) {
+    if (data && data.antialias !== undefined) {
+      const on = data.antialias === true || data.antialias === 'true' || data.antialias === 1;
+      this.data.antialias = on;
+      if (on !== this.antialias) { native.setOption(this.handle, OPT_ANTIALIAS, on ? 1 : 0); this.antialias = on; }
+    }
     return this;
   }
 
@@ -336,6 +354,7 @@ function register(AFRAME) {
         if (vp) this.frameSink(g.render(g.camera, vp), vp);
       }
     },
+    update() { if (this.impl) this.impl.update(this.data); },
     remove() { if (this.impl) this.impl.remove(); this.impl = null; },
   });
 }

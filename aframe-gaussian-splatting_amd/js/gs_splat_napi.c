@@ -837,7 +837,7 @@ static napi_value fn_stats(napi_env env, napi_callback_info info)
     PUT("msBin", s.ms_bin); PUT("msBlend", s.ms_blend); PUT("msRender", s.ms_render);
     PUT("accFrames", s.acc_frames); PUT("unsatTiles", s.unsat_tiles); PUT("nearPermille", s.near_permille); PUT("sortRecords", s.sort_records);
     PUT("retriedFrames", s.retried_frames); PUT("specSorts", s.spec_sorts); PUT("specMisses", s.spec_misses); PUT("needSplats", s.need_splats); PUT("sortMode", s.sort_mode); PUT("subtile", s.subtile);
-    PUT("shDegree", s.sh_degree); PUT("surface", s.surface);
+    PUT("shDegree", s.sh_degree); PUT("surface", s.surface); PUT("antialias", s.antialias);
 #undef PUT
     return o;
 }

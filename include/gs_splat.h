@@ -126,6 +126,10 @@ GS_API int gs_sh_eval_unrounded(const float *sh_row, int degree, const double ca
  * centre (x, y, -z) (index.js:350-354), so this is the camera in that mirrored space; a frame negates out[2] -- exactly -- to get
  * the camera in the rows' space, which is what the kernel and gs_sh_eval take. */
 GS_API int gs_camera_in_object(const float model_view[16], double out[3]);
+/* The opacity factor of GS_OPT_ANTIALIAS on the host, by the very arithmetic of the kernel: cov = {cov00, cov01, cov11}, a splat's
+ * projected 2x2 covariance in px^2 BEFORE the 0.3 px^2 dilation -> *out_c in [0, 1] (the formula is spelt out at the option).
+ * GS_E_BADARG for null pointers. */
+GS_API int gs_antialias_factor(const float cov[3], float *out_c);
 
 /* Number of splats resident (reference: loadedVertexCount / matrices.length/16). */
 GS_API size_t gs_count(const gs_ctx *ctx);
@@ -469,6 +473,7 @@ typedef struct gs_stats {
                              that runs no round (nothing resident) reports what its round would have taken                             */
     uint32_t sh_degree;   /* the spherical-harmonics degree the last frame's projection evaluated (GS_OPT_SH_DEGREE): 0 = packed byte colours   */
     uint32_t surface;     /* 1 if the last frame wrote surface planes (gs_render_surface, gs_pick)                                        */
+    uint32_t antialias;   /* 1 if the last frame's projection compensated its opacities (GS_OPT_ANTIALIAS)                                */
 } gs_stats;
 
 #define GS_OPT_PROFILE 1        /* 1: bracket every stage with HIP events on the frame's stream (7 per frame); 2: only
@@ -523,6 +528,20 @@ typedef struct gs_stats {
                                    frame's projection evaluates the colour of every splat it projects for the frame's camera (each eye and each
                                    strip its own) where it writes the projected record; binning and blend see that record only.  A singular
                                    model_view is GS_E_BADARG for such a frame.                                                       */
+#define GS_OPT_ANTIALIAS 20      /* anti-aliased splats.  The vertex shader adds 0.3 px^2 to both diagonal terms of every projected covariance
+                                   (index.js:139-141): the EWA low-pass filter WITHOUT its normalisation -- the drawn Gaussian gets wider and keeps
+                                   its peak, so a splat whose variance is comparable to 0.3 px^2 gains energy (isotropic: (v + 0.3) / v).
+                                   0 (default): the reference's behaviour; the kernels are the ones that run without this option.  1: every
+                                   frame's projection writes alpha' = alpha * c into its record, all in f32, in this order, un-fused:
+                                     det = cov00 * cov11 - cov01 * cov01      (the un-dilated covariance; two products, then the difference)
+                                     c   = sqrt(min(max(det / (l1 * l2), 0), 1))   (l1, l2: the eigenvalues the quad is drawn with, l2 AFTER its
+                                                                                    clamp at 0.1; a NaN ratio counts as 0)
+                                   (Mip-Splatting / gsplat's `antialiased` mode, with the eigenvalues really drawn in the denominator so that
+                                   the energy of what is drawn is conserved).  Only that float changes: quad geometry, bounds, tile coverage,
+                                   runs, lists, n_visible, n_pairs and fragment counts are those of option 0, and a splat with c = 0 is still
+                                   written, counted and binned.  The colour word keeps the packed alpha byte.  Taken per frame (each eye, each
+                                   strip), may change between frames; combines with GS_OPT_SH_DEGREE; paired frames (GS_OPT_FRAME_BATCH) share
+                                   the setting.  Any other value: GS_E_BADARG.  gs_antialias_factor evaluates c on the host.        */
 #define GS_OPT_ENQUEUE_THREADS 7 /* default 1: gs_sort() (without an output array) and gs_render_device(GS_RENDER_ASYNC) hand the
                                    frame to a worker thread of its pipeline lane, which does the ~18 kernel launches, so the
                                    launches of the frames in flight run in parallel; failures surface at gs_sync().  0: the
