@@ -343,44 +343,58 @@ static inline uint32_t gs_div_up(uint64_t a, uint64_t b) { return (uint32_t)((a 
 // 8, grid-strided); returns false for the padding slots of the last eighths.
 __device__ __forceinline__ bool gs_xcd_chunk(uint32_t v, uint32_t nchunks, uint32_t &chunk) { return gsm::xcd_chunk(v, nchunks, chunk); }
 
-// ---- two frames per launch (GS_OPT_FRAME_BATCH)
+// ---- one launch sequence for one frame and for two (GS_OPT_FRAME_BATCH)
 // A frame of 1 M splats is a chain of 18 short dependent kernels, most of them at the launch floor.  Two frames that take the
 // same path can share every launch: grid (x, 2), blockIdx.y = the frame, each with its OWN argument list -- its own scratch,
-// control block, uniforms, output.  The kernels' bodies are __device__ functions `k_xxx_body(args...)` (the plain kernels are
-// thin wrappers around them); k_twin calls a body with the argument pack blockIdx.y selects.
+// control block, uniforms, output.  The host code that decides what to launch exists ONCE, as templates over the frame count NF
+// (run_sort<NF>, run_round<NF>, ...: `S[k]` is frame k's lane); every launch goes through gs_launch<NF, F, threads>, which is
+// given frame k's argument list as a callable k -> gs_pack_make(...):
+//   NF == 1: the pack is taken apart on the host and the plain kernel is launched with a flat parameter list (a nested GsPack lays
+//            its members out differently: the plain kernels keep their kernel-argument offsets, names and launch bounds);
+//   NF == 2: k_twin<F, ...> calls the body with the pack blockIdx.y selects.
+// The kernels' bodies are __device__ functions `k_xxx_body(args...)`; the plain kernels are thin wrappers around them, and a body
+// functor F (GS_BODY) names both.  NF is a compile-time parameter: a twin kernel exists only for what is really drawn in pairs.
 template <class... A> struct GsPack;
 template <> struct GsPack<> {};
 template <class H, class... T> struct GsPack<H, T...> { H h; GsPack<T...> t; };
 static inline GsPack<> gs_pack_make() { return GsPack<>(); }
 template <class H, class... T> static inline GsPack<H, T...> gs_pack_make(H h, T... t) { GsPack<H, T...> p; p.h = h; p.t = gs_pack_make(t...); return p; }
-// F: a type with `template <class... A> static __device__ void call(const A &...)` that forwards to the body (host code may
-// not name a __device__ function, but it may name such a type): GS_BODY(F_name, k_xxx_body<...>)
-#define GS_BODY(Name, ...) struct Name { template <class... A> static __device__ __forceinline__ void call(const A &... a) { __VA_ARGS__(a...); } }
+// F: a type with `call(args...)`, a __device__ function that forwards to the body, and `launch(grid, block, lds, stream, args...)`,
+// a host function that launches the plain kernel (host code may not name a __device__ function, but it may name such a type):
+// GS_BODY(F_name, (k_xxx<...>), (k_xxx_body<...>)) -- in parentheses, for the commas of their template arguments
+#define GS_BODY(Name, Kernel, Body) struct Name {                                                                                          \
+        template <class... A> static __device__ __forceinline__ void call(const A &... a) { Body(a...); }                                   \
+        template <class... A> static void launch(dim3 g, dim3 b, size_t lds, hipStream_t st, const A &... a) { hipLaunchKernelGGL(Kernel, g, b, lds, st, a...); } }
 template <class F, class... B> __device__ __forceinline__ void gs_pack_call(const GsPack<> &, const B &... b) { F::call(b...); }
 template <class F, class H, class... T, class... B> __device__ __forceinline__ void gs_pack_call(const GsPack<H, T...> &p, const B &... b) { gs_pack_call<F>(p.t, b..., p.h); }
+template <class F, class... B> static inline void gs_pack_launch(const GsPack<> &, dim3 g, dim3 nt, size_t lds, hipStream_t st, const B &... b) { F::launch(g, nt, lds, st, b...); }
+template <class F, class H, class... T, class... B> static inline void gs_pack_launch(const GsPack<H, T...> &p, dim3 g, dim3 nt, size_t lds, hipStream_t st, const B &... b) { gs_pack_launch<F>(p.t, g, nt, lds, st, b..., p.h); }
 // (the two packs as ONE array argument indexed by blockIdx.y: with `if (blockIdx.y) call(p1); else call(p0);` the compiler loads BOTH packs'
 // words into scalar registers ahead of the branch, and a body with large uniforms -- the depth pass' strip test, the projection -- then
 // parks scalars in lanes of a vector register: v_readlane was 23 % of the vector instructions of the paired depth pass)
 template <class P> struct GsTwinArgs { P p[2]; };
 template <class F, int NT, class P> __global__ __launch_bounds__(NT) void k_twin(GsTwinArgs<P> a) { gs_pack_call<F>(a.p[blockIdx.y]); }
-// launch body F for two frames: gs_twin<F, threads>(grid_x, stream, pack0, pack1)
-template <class F, int NT, class P> static inline void gs_twin(uint32_t grid_x, hipStream_t st, const P &p0, const P &p1)
-{
-    GsTwinArgs<P> a; a.p[0] = p0; a.p[1] = p1;
-    hipLaunchKernelGGL((k_twin<F, NT, P>), dim3(grid_x, 2), dim3(NT), 0, st, a);
-}
 // ... with a register budget: MINW = the waves per SIMD the kernel must leave room for (512 / MINW vector registers), for bodies whose
 // unrolled loops the compiler would otherwise give 180-250 registers -- workgroups that then wait for half a SIMD's register file to
 // drain while the other frames' blends hold it
 template <class F, int NT, int MINW, class P> __global__ __launch_bounds__(NT, MINW) void k_twin_w(GsTwinArgs<P> a) { gs_pack_call<F>(a.p[blockIdx.y]); }
-template <class F, int NT, int MINW, class P> static inline void gs_twin_w(uint32_t grid_x, hipStream_t st, const P &p0, const P &p1)
+// launch F for NF frames on a grid of grid_x workgroups of NT threads (per frame): gs_launch<NF, F, NT>(grid_x, stream, lds, [&](int k) { return
+// gs_pack_make(...arguments of frame k...); }).  TWIN_MINW != 0: the PAIRED form is k_twin_w with that budget; the plain kernel keeps its own bounds
+template <int NF, class F, int NT, int TWIN_MINW = 0, class Args> static inline void gs_launch(uint32_t grid_x, hipStream_t st, size_t lds, const Args &args)
 {
-    GsTwinArgs<P> a; a.p[0] = p0; a.p[1] = p1;
-    hipLaunchKernelGGL((k_twin_w<F, NT, MINW, P>), dim3(grid_x, 2), dim3(NT), 0, st, a);
+    static_assert(NF == 1 || NF == 2, "one frame or a pair");
+    if constexpr (NF == 1) gs_pack_launch<F>(args(0), dim3(grid_x), dim3(NT), lds, st);
+    else {
+        typedef decltype(args(0)) P;
+        GsTwinArgs<P> a; a.p[0] = args(0); a.p[1] = args(1);
+        if constexpr (TWIN_MINW != 0) hipLaunchKernelGGL((k_twin_w<F, NT, TWIN_MINW, P>), dim3(grid_x, 2), dim3(NT), lds, st, a);
+        else hipLaunchKernelGGL((k_twin<F, NT, P>), dim3(grid_x, 2), dim3(NT), lds, st, a);
+    }
 }
 
 // ---- gs_prims.hip
-// One stable LSD radix pass over n = *n_ptr items on digit (key >> shift) & (2^bits-1).
+// One stable LSD radix pass over n = *n_ptr items on digit (key >> shift) & (2^bits-1), for NF frames (S[k]: the lane whose histogram
+// rows and totals frame k uses, io[k]: its records), one launch per kernel.
 // record formats: GS_RADIX_KEYS    in: a plain key array whose value is the element index; out: the values alone (final pass)
 //                 GS_RADIX_PACKED  (key,val) uint2 records
 //                 GS_RADIX_KEYONLY 4-byte records that are their own payload (in and out)
@@ -389,7 +403,7 @@ template <class F, int NT, int MINW, class P> static inline void gs_twin_w(uint3
 //                                  with shift = idx_bits, value = the low idx_bits bits) -- half the traffic of (key,val) records
 // max_n:     upper bound of *n_ptr (sizes the scratch); hint_n: the count to expect (0 = max_n) -- it picks the grid and
 //            between one- and two-level offsets, nothing that affects the result.
-// have_hist: the caller's producer kernel already filled ctx->hist[chunk][digit] for this digit (skips the histogram launch).
+// have_hist: the caller's producer kernel already filled S[k]->hist[chunk][digit] for this digit (skips the histogram launch).
 // zero_key:  value-only output stores 0 for items with this key (0xFFFFFFFF = never).
 // idx_bits:  GS_RADIX_KEYIDX output: bits reserved for the element index.
 // count_out: GS_RADIX_KEYS input: where the pass leaves the number of records that took a slot (skipped ones do not).
@@ -399,19 +413,14 @@ template <class F, int NT, int MINW, class P> static inline void gs_twin_w(uint3
 #define GS_RADIX_KEYONLY 2
 #define GS_RADIX_KEYIDX 3
 #define GS_RADIX_SKIP 0xFFFFFFFFu   // GS_RADIX_KEYS input only: a record with this key is neither counted nor scattered (compaction)
-int gs_launch_radix_pass(gs_ctx *ctx, const void *in, int in_fmt, void *out, int out_fmt, const uint32_t *n_ptr,
-                         uint32_t max_n, uint32_t hint_n, int shift, int bits, bool have_hist = false, uint32_t zero_key = 0xFFFFFFFFu,
-                         int idx_bits = 0, uint32_t *count_out = nullptr, const uint32_t *fill_to = nullptr);
-// the same pass over two frames' records, one launch per kernel (S[k]: histogram rows / totals of frame k)
-int gs_launch_radix_pass2(gs_ctx *const S[2], const void *const in[2], int in_fmt, void *const out[2], int out_fmt, const uint32_t *const n_ptr[2],
-                          uint32_t max_n, uint32_t hint_n, int shift, int bits, bool have_hist, uint32_t zero_key, int idx_bits,
-                          uint32_t *const count_out[2], const uint32_t *const fill_to[2]);
-// The last two launches of the MSD depth sort (gs_sort.hip: depth -> bucket + rows -> THIS): keys = ctx->key_a (16-bit bucket or
-// GS_RADIX_SKIP per splat), rows = ctx->hist H[chunk][bucket >> 8], group rows = ctx->msd_grp -> ctx->val_a (the index list, zero tail
-// [V', V) included), ctl->n_sorted = V'.  rec = ctx->kv_b used as 4-byte records between the two.
-// near: a near-only sort (no zero tail: k_project supplies the positions behind the records).
-int gs_launch_msd_sort(gs_ctx *ctx, uint32_t n, uint32_t tail_req);
-int gs_launch_msd_sort2(gs_ctx *const S[2], uint32_t n, const uint32_t tail_req[2]);
+struct GsRadixIO { const void *in; void *out; const uint32_t *n_ptr; uint32_t *count_out; const uint32_t *fill_to; };   // one frame's records
+template <int NF> int gs_radix_pass(gs_ctx *const S[], const GsRadixIO io[], int in_fmt, int out_fmt, uint32_t max_n, uint32_t hint_n, int shift, int bits,
+                                    bool have_hist = false, uint32_t zero_key = 0xFFFFFFFFu, int idx_bits = 0);   // (defined for NF = 1, 2)
+// The last two launches of the MSD depth sort (gs_sort.hip: depth -> bucket + rows -> THIS), per frame k on its lane L = S[k]: keys = L->key_a
+// (16-bit bucket or GS_RADIX_SKIP per splat), rows = L->hist H[chunk][bucket >> 8], group rows = L->msd_grp -> L->val_a (the index list, zero
+// tail [V', V) included), ctl->n_sorted = V'.  rec = L->kv_b used as 4-byte records between the two.
+// tail_req[k] != 0: a near-only sort (no zero tail: k_project supplies the positions behind the records).
+template <int NF> int gs_msd_sort(gs_ctx *const S[], uint32_t n, const uint32_t tail_req[]);   // (defined for NF = 1, 2)
 bool gs_msd_enabled();             // (GS_SORT_MSD=0 in the environment: the two LSD passes everywhere)
 // grid used by the radix kernels for hint_n items (a producer that pre-fills the histogram rows uses the same chunking)
 uint32_t gs_radix_grid(uint32_t hint_n);
@@ -425,7 +434,7 @@ int gs_launch_pack(gs_ctx *ctx, const uint4 *rows_dev, size_t first, size_t nrow
 int gs_run_sort(gs_ctx *ctx, const float view[4], const float *cutout16, const GsSortStrip *strip = nullptr, uint32_t near_req = 0);
 // what the lane's order was made from and how much of it exists (a render that needs more sorts again in full by itself)
 void gs_remember_sort(gs_ctx *L, const float view[4], const float *cutout16, const GsSortStrip *strip, uint32_t near_req);
-int gs_run_sort2(gs_ctx *const S[2], const float *const view[2], const float *const cutout16[2], const GsSortStrip *const strip[2], const uint32_t near_req[2]);   // two frames per launch
+int gs_run_sort2(gs_ctx *const S[2], const float *const view[2], const float *const cutout16[2], const GsSortStrip *const strip[2], const uint32_t near_req[2]);   // the same sequence for two frames per launch
 // ---- gs_render.hip
 int gs_run_render(gs_ctx *ctx, const GsFrameUniforms &u, uint8_t *device_out);
 int gs_run_round1(gs_ctx *ctx, const GsFrameUniforms &u, uint8_t *device_out);

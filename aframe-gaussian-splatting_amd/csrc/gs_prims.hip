@@ -18,6 +18,7 @@
 // The kernels read their problem size from device memory (GsControl), so no stage of the frame needs a host round trip.
 // All of a chunk's items are loaded before any is processed, LDS match words / wavefront ballots give the stable in-wave
 // rank (no MFMA: there is no contraction here).
+#include <type_traits>
 #include "gs_internal.h"
 
 namespace {
@@ -718,8 +719,8 @@ __global__ __launch_bounds__(64 * NW, 4) void k_seg_sort(const uint32_t *__restr
 {
     k_seg_sort_body<NW, IPT>(rec, out, seg_tab, fill_to);
 }
-template <int NW> GS_BODY(F_msd_scatter, k_msd_scatter_body<NW>);
-template <int NW, int IPT> GS_BODY(F_seg_sort, k_seg_sort_body<NW, IPT>);
+template <int NW> GS_BODY(F_msd_scatter, (k_msd_scatter<NW>), (k_msd_scatter_body<NW>));
+template <int NW, int IPT> GS_BODY(F_seg_sort, (k_seg_sort<NW, IPT>), (k_seg_sort_body<NW, IPT>));
 #define GS_SEG_GRID 512u           // k_seg_sort: workgroups (they stride over the work items: 256 segments + the extra blocks of the long ones)
 #ifndef GS_SEG_NW
 #define GS_SEG_NW 4                // k_seg_sort: wavefronts per workgroup ...
@@ -737,44 +738,13 @@ uint32_t grid_for(uint32_t items, uint32_t chunk)
     return (g + 7u) & ~7u;                                       // a multiple of 8: workgroup index mod 8 = XCD (gs_xcd_chunk)
 }
 
-template <int NW>
-int launch_pass(gs_ctx *ctx, const void *in, int in_fmt, void *out, int out_fmt, const uint32_t *n_ptr, uint32_t hint_n, int shift,
-                int bits, bool have_hist, uint32_t zero_key, int idx_bits, uint32_t *count_out, const uint32_t *fill_to)
-{
-    constexpr uint32_t CH = 64 * NW * 8;
-    const uint32_t g = grid_for(hint_n, CH);
-    hipStream_t st = ctx->stream;
-    uint32_t *totals = ctx->radix_aux;
-    const dim3 G(g), B(64 * NW);
-    if (have_hist) { /* the producer of `in` already wrote hist[chunk][digit] */ }
-    else if (in_fmt == GS_RADIX_PACKED) hipLaunchKernelGGL((k_radix_hist<true, NW>), G, B, 0, st, (const uint32_t *)in, n_ptr, shift, bits, ctx->hist);
-    else hipLaunchKernelGGL((k_radix_hist<false, NW>), G, B, 0, st, (const uint32_t *)in, n_ptr, shift, bits, ctx->hist);
-    hipLaunchKernelGGL((k_radix_scan<NW>), dim3(gs_div_up(gs_radix_row_stride(1u << bits), 16u)), dim3(64 * NW), 0, st, ctx->hist, n_ptr, CH, bits, totals);
-#define GS_SCATTER(I, O) do { if (bits <= 7) hipLaunchKernelGGL((k_radix_scatter<I, O, 128, NW>), G, B, 0, st, in, out, n_ptr, shift, bits, zero_key, ctx->hist, totals, idx_bits, count_out, fill_to); \
-                              else if (bits == 8) hipLaunchKernelGGL((k_radix_scatter<I, O, 256, NW>), G, B, 0, st, in, out, n_ptr, shift, bits, zero_key, ctx->hist, totals, idx_bits, count_out, fill_to); \
-                              else hipLaunchKernelGGL((k_radix_scatter<I, O, GS_RADIX_MAX_BINS, NW>), G, B, 0, st, in, out, n_ptr, shift, bits, zero_key, ctx->hist, totals, idx_bits, count_out, fill_to); } while (0)
-    if (in_fmt == GS_RADIX_PACKED && out_fmt == GS_RADIX_PACKED) GS_SCATTER(GS_RADIX_PACKED, GS_RADIX_PACKED);
-    else if (in_fmt == GS_RADIX_PACKED && out_fmt == GS_RADIX_KEYS) GS_SCATTER(GS_RADIX_PACKED, GS_RADIX_KEYS);
-    else if (in_fmt == GS_RADIX_KEYS && out_fmt == GS_RADIX_PACKED) GS_SCATTER(GS_RADIX_KEYS, GS_RADIX_PACKED);
-    else if (in_fmt == GS_RADIX_KEYS && out_fmt == GS_RADIX_KEYS) GS_SCATTER(GS_RADIX_KEYS, GS_RADIX_KEYS);
-    else if (in_fmt == GS_RADIX_KEYS && out_fmt == GS_RADIX_KEYIDX) GS_SCATTER(GS_RADIX_KEYS, GS_RADIX_KEYIDX);
-    else if (in_fmt == GS_RADIX_KEYIDX && out_fmt == GS_RADIX_KEYS) GS_SCATTER(GS_RADIX_KEYIDX, GS_RADIX_KEYS);
-    else if (in_fmt == GS_RADIX_PACKED && out_fmt == GS_RADIX_KEYIDX) GS_SCATTER(GS_RADIX_PACKED, GS_RADIX_KEYIDX);
-    else { snprintf(GS_ERRBUF(ctx), GS_ERRLEN, "radix pass: unsupported record formats %d -> %d", in_fmt, out_fmt); return GS_E_BADARG; }
-#undef GS_SCATTER
-    GS_HIP(hipGetLastError());
-    return GS_OK;
-}
+template <bool PACKED, int NW> GS_BODY(F_hist, (k_radix_hist<PACKED, NW>), (k_radix_hist_body<PACKED, NW>));
+template <int NW> GS_BODY(F_scan, (k_radix_scan<NW>), (k_radix_scan_body<NW>));
+template <int I, int O, int B, int NW> GS_BODY(F_scatter, (k_radix_scatter<I, O, B, NW>), (k_radix_scatter_body<I, O, B, NW>));
 
-template <bool PACKED, int NW> GS_BODY(F_hist, k_radix_hist_body<PACKED, NW>);
-template <int NW> GS_BODY(F_scan, k_radix_scan_body<NW>);
-template <int I, int O, int B, int NW> GS_BODY(F_scatter, k_radix_scatter_body<I, O, B, NW>);
-
-// the same pass for two frames in one launch per kernel (GS_OPT_FRAME_BATCH): S[k] supplies histogram rows and totals of frame k
-template <int NW>
-int launch_pass2(gs_ctx *const S[2], const void *const in[2], int in_fmt, void *const out[2], int out_fmt, const uint32_t *const n_ptr[2],
-                 uint32_t hint_n, int shift, int bits, bool have_hist, uint32_t zero_key, int idx_bits, uint32_t *const count_out[2],
-                 const uint32_t *const fill_to[2])
+// histogram (unless the producer of the records wrote the rows) -> scan -> scatter, each launched once for the NF frames
+template <int NW, int NF>
+int launch_pass(gs_ctx *const S[], const GsRadixIO io[], int in_fmt, int out_fmt, uint32_t hint_n, int shift, int bits, bool have_hist, uint32_t zero_key, int idx_bits)
 {
     constexpr uint32_t CH = 64 * NW * 8;
     constexpr int NT = 64 * NW;
@@ -782,95 +752,79 @@ int launch_pass2(gs_ctx *const S[2], const void *const in[2], int in_fmt, void *
     const uint32_t g = grid_for(hint_n, CH);
     hipStream_t st = ctx->stream;
     if (!have_hist) {
-        if (in_fmt == GS_RADIX_PACKED) { typedef F_hist<true, NW> F;
-            gs_twin<F, NT>(g, st, gs_pack_make((const uint32_t *)in[0], n_ptr[0], shift, bits, S[0]->hist), gs_pack_make((const uint32_t *)in[1], n_ptr[1], shift, bits, S[1]->hist)); }
-        else { typedef F_hist<false, NW> F;
-            gs_twin<F, NT>(g, st, gs_pack_make((const uint32_t *)in[0], n_ptr[0], shift, bits, S[0]->hist), gs_pack_make((const uint32_t *)in[1], n_ptr[1], shift, bits, S[1]->hist)); }
+        const auto args = [&](int k) { return gs_pack_make((const uint32_t *)io[k].in, io[k].n_ptr, shift, bits, S[k]->hist); };
+        if (in_fmt == GS_RADIX_PACKED) gs_launch<NF, F_hist<true, NW>, NT>(g, st, 0, args);
+        else gs_launch<NF, F_hist<false, NW>, NT>(g, st, 0, args);
     }
-    { typedef F_scan<NW> F;
-      gs_twin<F, NT>(gs_div_up(gs_radix_row_stride(1u << bits), 16u), st, gs_pack_make(S[0]->hist, n_ptr[0], CH, bits, S[0]->radix_aux),
-                        gs_pack_make(S[1]->hist, n_ptr[1], CH, bits, S[1]->radix_aux)); }
-#define GS_SCATTER2_B(I, O, B) do { typedef F_scatter<I, O, B, NW> F;                     \
-        gs_twin<F, NT>(g, st, gs_pack_make(in[0], out[0], n_ptr[0], shift, bits, zero_key, (const uint32_t *)S[0]->hist, (const uint32_t *)S[0]->radix_aux,  \
-                                              idx_bits, count_out[0], fill_to[0]),                                                                               \
-                          gs_pack_make(in[1], out[1], n_ptr[1], shift, bits, zero_key, (const uint32_t *)S[1]->hist, (const uint32_t *)S[1]->radix_aux,         \
-                                       idx_bits, count_out[1], fill_to[1])); } while (0)
-#define GS_SCATTER2(I, O) do { if (bits <= 7) GS_SCATTER2_B(I, O, 128); else if (bits == 8) GS_SCATTER2_B(I, O, 256); else GS_SCATTER2_B(I, O, GS_RADIX_MAX_BINS); } while (0)
-    if (in_fmt == GS_RADIX_PACKED && out_fmt == GS_RADIX_PACKED) GS_SCATTER2(GS_RADIX_PACKED, GS_RADIX_PACKED);
-    else if (in_fmt == GS_RADIX_KEYS && out_fmt == GS_RADIX_KEYIDX) GS_SCATTER2(GS_RADIX_KEYS, GS_RADIX_KEYIDX);
-    else if (in_fmt == GS_RADIX_KEYIDX && out_fmt == GS_RADIX_KEYS) GS_SCATTER2(GS_RADIX_KEYIDX, GS_RADIX_KEYS);
-    else if (in_fmt == GS_RADIX_KEYS && out_fmt == GS_RADIX_PACKED) GS_SCATTER2(GS_RADIX_KEYS, GS_RADIX_PACKED);
-    else if (in_fmt == GS_RADIX_PACKED && out_fmt == GS_RADIX_KEYS) GS_SCATTER2(GS_RADIX_PACKED, GS_RADIX_KEYS);
-    else if (in_fmt == GS_RADIX_PACKED && out_fmt == GS_RADIX_KEYIDX) GS_SCATTER2(GS_RADIX_PACKED, GS_RADIX_KEYIDX);
-    else { snprintf(GS_ERRBUF(ctx), GS_ERRLEN, "radix pass: unsupported record formats %d -> %d", in_fmt, out_fmt); return GS_E_BADARG; }
-#undef GS_SCATTER2
-#undef GS_SCATTER2_B
+    gs_launch<NF, F_scan<NW>, NT>(gs_div_up(gs_radix_row_stride(1u << bits), 16u), st, 0,
+                                  [&](int k) { return gs_pack_make(S[k]->hist, io[k].n_ptr, CH, bits, S[k]->radix_aux); });
+    const auto scatter = [&](auto I, auto O) {
+        const auto args = [&](int k) { return gs_pack_make(io[k].in, io[k].out, io[k].n_ptr, shift, bits, zero_key, (const uint32_t *)S[k]->hist,
+                                                           (const uint32_t *)S[k]->radix_aux, idx_bits, io[k].count_out, io[k].fill_to); };
+        if (bits <= 7) gs_launch<NF, F_scatter<decltype(I)::value, decltype(O)::value, 128, NW>, NT>(g, st, 0, args);
+        else if (bits == 8) gs_launch<NF, F_scatter<decltype(I)::value, decltype(O)::value, 256, NW>, NT>(g, st, 0, args);
+        else gs_launch<NF, F_scatter<decltype(I)::value, decltype(O)::value, GS_RADIX_MAX_BINS, NW>, NT>(g, st, 0, args);
+    };
+    typedef std::integral_constant<int, GS_RADIX_KEYS> Keys;
+    typedef std::integral_constant<int, GS_RADIX_PACKED> Packed;
+    typedef std::integral_constant<int, GS_RADIX_KEYIDX> KeyIdx;
+    bool known = true;
+    if (in_fmt == GS_RADIX_PACKED && out_fmt == GS_RADIX_PACKED) scatter(Packed(), Packed());
+    else if (in_fmt == GS_RADIX_PACKED && out_fmt == GS_RADIX_KEYS) scatter(Packed(), Keys());
+    else if (in_fmt == GS_RADIX_PACKED && out_fmt == GS_RADIX_KEYIDX) scatter(Packed(), KeyIdx());
+    else if (in_fmt == GS_RADIX_KEYS && out_fmt == GS_RADIX_PACKED) scatter(Keys(), Packed());
+    else if (in_fmt == GS_RADIX_KEYS && out_fmt == GS_RADIX_KEYIDX) scatter(Keys(), KeyIdx());
+    else if (in_fmt == GS_RADIX_KEYIDX && out_fmt == GS_RADIX_KEYS) scatter(KeyIdx(), Keys());
+    else if (in_fmt == GS_RADIX_KEYS && out_fmt == GS_RADIX_KEYS) {
+        // (keys in, values out in one pass: a single frame's form only -- nothing pairs it, so there is no twin kernel for it)
+        if constexpr (NF == 1) scatter(Keys(), Keys()); else known = false;
+    } else known = false;
+    if (!known) { snprintf(GS_ERRBUF(ctx), GS_ERRLEN, "radix pass: unsupported record formats %d -> %d", in_fmt, out_fmt); return GS_E_BADARG; }
     GS_HIP(hipGetLastError());
     return GS_OK;
 }
 
 }  // namespace
 
-int gs_launch_radix_pass2(gs_ctx *const S[2], const void *const in[2], int in_fmt, void *const out[2], int out_fmt, const uint32_t *const n_ptr[2],
-                          uint32_t max_n, uint32_t hint_n, int shift, int bits, bool have_hist, uint32_t zero_key, int idx_bits,
-                          uint32_t *const count_out[2], const uint32_t *const fill_to[2])
+template <int NF>
+int gs_radix_pass(gs_ctx *const S[], const GsRadixIO io[], int in_fmt, int out_fmt, uint32_t max_n, uint32_t hint_n, int shift, int bits, bool have_hist,
+                  uint32_t zero_key, int idx_bits)
 {
     gs_ctx *ctx = S[0];
-    if (bits < 1 || bits > 9) { snprintf(GS_ERRBUF(ctx), GS_ERRLEN, "radix pass: %d-bit digit (1..9 supported)", bits); return GS_E_BADARG; }
-    if (hint_n > max_n || hint_n == 0) hint_n = max_n;
-    return gs_radix_chunk(hint_n) == GS_CHUNK_L ? launch_pass2<8>(S, in, in_fmt, out, out_fmt, n_ptr, hint_n, shift, bits, have_hist, zero_key, idx_bits, count_out, fill_to)
-                                                : launch_pass2<4>(S, in, in_fmt, out, out_fmt, n_ptr, hint_n, shift, bits, have_hist, zero_key, idx_bits, count_out, fill_to);
-}
-
-int gs_launch_msd_sort(gs_ctx *ctx, uint32_t n, uint32_t tail_req)
-{
-    const bool near = tail_req != 0u;
-    // k_seg_sort reads whole blocks: up to GS_SEG_B words past a segment's end, i.e. up to n + GS_SEG_B - 1 words into `rec` (= kv_b, 2 x scratch_cap words)
-    if ((size_t)ctx->scratch_cap * 2 < (size_t)n + GS_SEG_B) { snprintf(GS_ERRBUF(ctx), GS_ERRLEN, "msd sort: scratch of %zu splats is too small for %u records", ctx->scratch_cap, n); return GS_E_STATE; }
-    const uint32_t chunk = gs_radix_chunk(n), g = grid_for(n, chunk);
-    hipStream_t st = ctx->stream;
-    uint32_t *rec = reinterpret_cast<uint32_t *>(ctx->kv_b);
-    if (chunk == GS_CHUNK_L) hipLaunchKernelGGL((k_msd_scatter<8>), dim3(g), dim3(512), 0, st, (const uint32_t *)ctx->key_a, rec, (const uint32_t *)&ctx->ctl->n_total,
-                                                (const uint32_t *)ctx->hist, (const uint32_t *)ctx->msd_grp, &ctx->ctl->n_sorted, ctx->msd_tab, tail_req, ctx->ctl, n);
-    else hipLaunchKernelGGL((k_msd_scatter<4>), dim3(g), dim3(256), 0, st, (const uint32_t *)ctx->key_a, rec, (const uint32_t *)&ctx->ctl->n_total,
-                            (const uint32_t *)ctx->hist, (const uint32_t *)ctx->msd_grp, &ctx->ctl->n_sorted, ctx->msd_tab, tail_req, ctx->ctl, n);
-    hipLaunchKernelGGL((k_seg_sort<GS_SEG_NW, GS_SEG_IPT>), dim3(GS_SEG_GRID), dim3(64 * GS_SEG_NW), 0, st, (const uint32_t *)rec, ctx->val_a, (const uint32_t *)ctx->msd_tab,
-                       near ? (const uint32_t *)nullptr : (const uint32_t *)&ctx->ctl->n_kept);
-    GS_HIP(hipGetLastError());
-    return GS_OK;
-}
-
-int gs_launch_msd_sort2(gs_ctx *const S[2], uint32_t n, const uint32_t tail_req[2])
-{
-    gs_ctx *ctx = S[0];
-    for (int k = 0; k < 2; k++) if ((size_t)S[k]->scratch_cap * 2 < (size_t)n + GS_SEG_B) { snprintf(GS_ERRBUF(ctx), GS_ERRLEN, "msd sort: scratch of %zu splats is too small for %u records", S[k]->scratch_cap, n); return GS_E_STATE; }
-    const uint32_t chunk = gs_radix_chunk(n), g = grid_for(n, chunk);
-    hipStream_t st = ctx->stream;
-    uint32_t *rec[2] = { reinterpret_cast<uint32_t *>(S[0]->kv_b), reinterpret_cast<uint32_t *>(S[1]->kv_b) };
-#define GS_MSD_SC(NW) gs_twin_w<F_msd_scatter<NW>, 64 * NW, 4>(g, st,                                                                                      \
-        gs_pack_make((const uint32_t *)S[0]->key_a, rec[0], (const uint32_t *)&S[0]->ctl->n_total, (const uint32_t *)S[0]->hist, (const uint32_t *)S[0]->msd_grp, &S[0]->ctl->n_sorted, S[0]->msd_tab, tail_req[0], S[0]->ctl, n), \
-        gs_pack_make((const uint32_t *)S[1]->key_a, rec[1], (const uint32_t *)&S[1]->ctl->n_total, (const uint32_t *)S[1]->hist, (const uint32_t *)S[1]->msd_grp, &S[1]->ctl->n_sorted, S[1]->msd_tab, tail_req[1], S[1]->ctl, n))
-    if (chunk == GS_CHUNK_L) GS_MSD_SC(8); else GS_MSD_SC(4);
-#undef GS_MSD_SC
-    typedef F_seg_sort<GS_SEG_NW, GS_SEG_IPT> FS;
-    gs_twin_w<FS, 64 * GS_SEG_NW, 4>(GS_SEG_GRID, st,
-        gs_pack_make((const uint32_t *)rec[0], S[0]->val_a, (const uint32_t *)S[0]->msd_tab, tail_req[0] ? (const uint32_t *)nullptr : (const uint32_t *)&S[0]->ctl->n_kept),
-        gs_pack_make((const uint32_t *)rec[1], S[1]->val_a, (const uint32_t *)S[1]->msd_tab, tail_req[1] ? (const uint32_t *)nullptr : (const uint32_t *)&S[1]->ctl->n_kept));
-    GS_HIP(hipGetLastError());
-    return GS_OK;
-}
-
-uint32_t gs_radix_chunk(uint32_t hint_n) { return hint_n > GS_RADIX_LARGE_N ? GS_CHUNK_L : GS_CHUNK_S; }
-uint32_t gs_radix_grid(uint32_t hint_n) { return grid_for(hint_n, gs_radix_chunk(hint_n)); }
-
-int gs_launch_radix_pass(gs_ctx *ctx, const void *in, int in_fmt, void *out, int out_fmt, const uint32_t *n_ptr,
-                         uint32_t max_n, uint32_t hint_n, int shift, int bits, bool have_hist, uint32_t zero_key, int idx_bits,
-                         uint32_t *count_out, const uint32_t *fill_to)
-{
     if (bits < 1 || bits > 9) { snprintf(GS_ERRBUF(ctx), GS_ERRLEN, "radix pass: %d-bit digit (1..9 supported)", bits); return GS_E_BADARG; }
     if (hint_n > max_n || hint_n == 0) hint_n = max_n;
     // the geometry is a matter of speed only: both forms are exact for any *n_ptr <= max_n (a producer that pre-filled the
     // histogram rows used gs_radix_chunk(hint_n) as well)
-    return gs_radix_chunk(hint_n) == GS_CHUNK_L ? launch_pass<8>(ctx, in, in_fmt, out, out_fmt, n_ptr, hint_n, shift, bits, have_hist, zero_key, idx_bits, count_out, fill_to)
-                                                : launch_pass<4>(ctx, in, in_fmt, out, out_fmt, n_ptr, hint_n, shift, bits, have_hist, zero_key, idx_bits, count_out, fill_to);
+    return gs_radix_chunk(hint_n) == GS_CHUNK_L ? launch_pass<8, NF>(S, io, in_fmt, out_fmt, hint_n, shift, bits, have_hist, zero_key, idx_bits)
+                                                : launch_pass<4, NF>(S, io, in_fmt, out_fmt, hint_n, shift, bits, have_hist, zero_key, idx_bits);
 }
+template int gs_radix_pass<1>(gs_ctx *const[], const GsRadixIO[], int, int, uint32_t, uint32_t, int, int, bool, uint32_t, int);
+template int gs_radix_pass<2>(gs_ctx *const[], const GsRadixIO[], int, int, uint32_t, uint32_t, int, int, bool, uint32_t, int);
+
+// A single frame's kernels are the plain ones, with no register bound beyond their own __launch_bounds__; the PAIRED kernels are
+// k_twin_w with room for 4 waves per SIMD (the fourth argument of gs_launch: a pair's sort runs under other frames' blends, and
+// workgroups of 180-250 registers would wait for half a SIMD's register file to drain).
+template <int NF>
+int gs_msd_sort(gs_ctx *const S[], uint32_t n, const uint32_t tail_req[])
+{
+    gs_ctx *ctx = S[0];
+    // k_seg_sort reads whole blocks: up to GS_SEG_B words past a segment's end, i.e. up to n + GS_SEG_B - 1 words into `rec` (= kv_b, 2 x scratch_cap words)
+    for (int k = 0; k < NF; k++)
+        if ((size_t)S[k]->scratch_cap * 2 < (size_t)n + GS_SEG_B) { snprintf(GS_ERRBUF(ctx), GS_ERRLEN, "msd sort: scratch of %zu splats is too small for %u records", S[k]->scratch_cap, n); return GS_E_STATE; }
+    const uint32_t chunk = gs_radix_chunk(n), g = grid_for(n, chunk);
+    hipStream_t st = ctx->stream;
+    const auto scatter = [&](int k) { return gs_pack_make((const uint32_t *)S[k]->key_a, reinterpret_cast<uint32_t *>(S[k]->kv_b), (const uint32_t *)&S[k]->ctl->n_total, (const uint32_t *)S[k]->hist,
+                                                          (const uint32_t *)S[k]->msd_grp, &S[k]->ctl->n_sorted, S[k]->msd_tab, tail_req[k], S[k]->ctl, n); };
+    if (chunk == GS_CHUNK_L) gs_launch<NF, F_msd_scatter<8>, 512, 4>(g, st, 0, scatter);
+    else gs_launch<NF, F_msd_scatter<4>, 256, 4>(g, st, 0, scatter);
+    gs_launch<NF, F_seg_sort<GS_SEG_NW, GS_SEG_IPT>, 64 * GS_SEG_NW, 4>(GS_SEG_GRID, st, 0, [&](int k) {
+        return gs_pack_make((const uint32_t *)reinterpret_cast<uint32_t *>(S[k]->kv_b), S[k]->val_a, (const uint32_t *)S[k]->msd_tab,
+                            tail_req[k] ? (const uint32_t *)nullptr : (const uint32_t *)&S[k]->ctl->n_kept); });
+    GS_HIP(hipGetLastError());
+    return GS_OK;
+}
+template int gs_msd_sort<1>(gs_ctx *const[], uint32_t, const uint32_t[]);
+template int gs_msd_sort<2>(gs_ctx *const[], uint32_t, const uint32_t[]);
+
+uint32_t gs_radix_chunk(uint32_t hint_n) { return hint_n > GS_RADIX_LARGE_N ? GS_CHUNK_L : GS_CHUNK_S; }
+uint32_t gs_radix_grid(uint32_t hint_n) { return grid_for(hint_n, gs_radix_chunk(hint_n)); }

@@ -23,6 +23,7 @@
 //
 // The fixed-function rasteriser + ROP of the reference have no structural counterpart; parity is defined at
 // the pixel level against oracle/gs_oracle.c (docs/LAB_NOTES.md "Pixel parity argument").
+#include <type_traits>
 #include "gs_internal.h"
 #include "gs_sh.h"
 
@@ -1898,49 +1899,76 @@ __global__ __launch_bounds__(256) void k_blend_px(const uint2 *__restrict__ tile
 
 int bits_for(uint32_t n) { int b = 1; while (b < 32 && (1u << b) < n) b++; return b; }
 
-// the blend of one round over the tile lists `fpairs` (sorted positions if v.rc_stride != 0, else (tile, position) records)
-template <int ROUND>
-int launch_blend(gs_ctx *ctx, const GsFrameUniforms &u, GsFrameUniforms v, uint8_t *out, const void *fpairs, const gsm::Projected *bproj, const float *bzwin)
+// The kernels of a round as body functors (gs_internal.h: GS_BODY), each with its plain kernel: what gs_launch<NF, F, ...> launches for one frame
+// (the plain kernel) and for a pair (k_twin<F, ...>).  A NEW KERNEL gets its body, its thin __global__ wrapper, one line here and one gs_launch
+// in the sequence below -- once, for both frame counts.
+template <int ROUND, bool RUNS> GS_BODY(F_project, (k_project<ROUND, RUNS>), (k_project_body<ROUND, RUNS>));
+template <int ROUND, bool RUNS> GS_BODY(F_project_sh, (k_project_sh<ROUND, RUNS>), (k_project_body<ROUND, RUNS, true>));
+template <int ROUND, bool RUNS, bool SH> GS_BODY(F_project_aa, (k_project_aa<ROUND, RUNS, SH>), (k_project_body<ROUND, RUNS, SH, true>));
+template <int ROUND> GS_BODY(F_row_scan, (k_row_scan<ROUND>), (k_row_scan_body<ROUND>));
+template <int ROUND> GS_BODY(F_emit_runs, (k_emit_runs<ROUND>), (k_emit_runs_body<ROUND>));
+template <int ROUND> GS_BODY(F_seg_count, (k_seg_count<ROUND>), (k_seg_count_body<ROUND>));
+template <int ROUND, bool SEGC> GS_BODY(F_lists, (k_lists<ROUND, SEGC>), (k_lists_body<ROUND, SEGC>));
+template <int ROUND> GS_BODY(F_pairs_check, (k_pairs_check<ROUND>), (k_pairs_check_body<ROUND>));
+template <int ROUND> GS_BODY(F_emit, (k_emit<ROUND>), (k_emit_body<ROUND>));
+GS_BODY(F_tile_ranges, (k_tile_ranges), (k_tile_ranges_body));
+template <int ROUND, bool SCENE, bool SUB, bool WALK> GS_BODY(F_blend, (k_blend<false, ROUND, SCENE, SUB, WALK>), (k_blend_body<false, ROUND, SCENE, SUB, WALK>));
+template <int ROUND, bool SCENE> GS_BODY(F_blend_px, (k_blend_px<ROUND, SCENE>), (k_blend_px_body<ROUND, SCENE>));
+// single-frame only (gs_frames_batchable keeps such frames out of pairs; launch_blend<.., 2> refuses them): there is no twin kernel of these
+template <int ROUND, bool SCENE, bool SUB> GS_BODY(F_blend_count, (k_blend<true, ROUND, SCENE, SUB>), (k_blend_body<true, ROUND, SCENE, SUB>));
+template <int ROUND, bool SCENE> GS_BODY(F_blend_surf, (k_blend_surf<ROUND, SCENE>), (k_blend_body<false, ROUND, SCENE, false, false, true>));
+
+// a run-time flag as a template argument: gs_flag(scene, [&](auto SC) { ... decltype(SC)::value ... })
+template <class Fn> inline void gs_flag(bool on, const Fn &fn) { if (on) fn(std::true_type()); else fn(std::false_type()); }
+
+// The sequences below draw NF frames that take the same path, every kernel launched once: S[k] is frame k's lane (sibling lanes on ONE
+// stream -- S[0]'s --, each with its own scratch, control block and output), U[k] its uniforms, out[k] its image.  Whatever decides the PATH
+// is read from frame 0 (gs_frames_batchable vouches that frame 1 agrees); whatever is an ARGUMENT is frame k's own.
+
+// the blend of one round over the tile lists `lists[k]` (sorted positions if V[k].rc_stride != 0, else (tile, position) records;
+// row walk: the run geometry)
+template <int ROUND, int NF>
+int launch_blend(gs_ctx *const S[], const GsFrameUniforms V[], uint8_t *const out[], const void *const lists[])
 {
+    gs_ctx *ctx = S[0];
+    const GsFrameUniforms &u = V[0];
     const uint32_t ntiles = (uint32_t)u.tiles_x * (uint32_t)u.tiles_y;
     hipStream_t st = ctx->stream;
     const uint32_t gb = ROUND == 1 ? (ntiles < 1024 ? ntiles : 1024) : ntiles;
     const bool scene = u.has_depth || u.has_scene_rgba;
-    if ((u.flags & GS_RENDER_COUNT_FRAGS) || u.record_staged) v.split_min = 0;     // measurement renders: every tile by k_blend
-    if (v.surface) {
-        // a surface frame: tile lists, one wavefront per tile (gs_render_surface switches the other paths off for the frame)
-        if (scene) hipLaunchKernelGGL((k_blend_surf<ROUND, true>), dim3(gb), dim3(64), 0, st, ctx->tile_range, fpairs, bproj, v, out, ctx->state,
-                                      ctx->unsat_mask, bzwin, ctx->scene_depth, ctx->scene_rgba, ctx->ctl, (const uint32_t *)ctx->sorted);
-        else hipLaunchKernelGGL((k_blend_surf<ROUND, false>), dim3(gb), dim3(64), 0, st, ctx->tile_range, fpairs, bproj, v, out, ctx->state,
-                                ctx->unsat_mask, bzwin, ctx->scene_depth, ctx->scene_rgba, ctx->ctl, (const uint32_t *)ctx->sorted);
+    const bool count = (u.flags & GS_RENDER_COUNT_FRAGS) != 0;
+    if (NF != 1 && (count || u.record_staged || u.surface)) { snprintf(GS_ERRBUF(ctx), GS_ERRLEN, "paired blend: a measurement or surface frame"); return GS_E_STATE; }
+    GsFrameUniforms W[NF];
+    for (int k = 0; k < NF; k++) W[k] = V[k];
+    if (count || u.record_staged) W[0].split_min = 0;             // measurement renders: every tile by k_blend
+    const bool walk = ROUND == 0 && u.row_walk;                     // no tile lists (run_round_spans): the tiles' entries from their rows' run tables
+    const auto args = [&](int k) {
+        return gs_pack_make(walk ? (const uint2 *)S[k]->row_tot + GS_BLOCK : (const uint2 *)S[k]->tile_range, lists[k], (const gsm::Projected *)S[k]->proj, W[k], out[k],
+                            S[k]->state, S[k]->unsat_mask, (const float *)S[k]->zwin, (const float *)S[k]->scene_depth, (const uint32_t *)S[k]->scene_rgba, S[k]->ctl);
+    };
+    if constexpr (NF == 1) {
+        if (u.surface) {
+            // a surface frame: tile lists, one wavefront per tile (gs_render_surface switches the other paths off for the frame)
+            const auto sargs = [&](int) {
+                return gs_pack_make((const uint2 *)ctx->tile_range, lists[0], (const gsm::Projected *)ctx->proj, W[0], out[0], ctx->state, ctx->unsat_mask, (const float *)ctx->zwin,
+                                    (const float *)ctx->scene_depth, (const uint32_t *)ctx->scene_rgba, ctx->ctl, (const uint32_t *)ctx->sorted);
+            };
+            gs_flag(scene, [&](auto SC) { gs_launch<1, F_blend_surf<ROUND, decltype(SC)::value>, 64>(gb, st, 0, sargs); });
+            GS_HIP(hipGetLastError());
+            return GS_OK;
+        }
+    }
+    if (walk) {
+        gs_flag(scene, [&](auto SC) { gs_launch<NF, F_blend<ROUND, decltype(SC)::value, false, ROUND == 0>, 64>(gb, st, 0, args); });
         GS_HIP(hipGetLastError());
         return GS_OK;
     }
-    if (ROUND == 0 && v.row_walk) {
-        // no tile lists (run_round_spans): the tiles' entries from their rows' runs; fpairs = the run geometry
-        const uint2 *rows = ctx->row_tot + GS_BLOCK;
-        if (scene) hipLaunchKernelGGL((k_blend<false, 0, true, false, true>), dim3(gb), dim3(64), 0, st, rows, fpairs, bproj, v, out, ctx->state,
-                                      ctx->unsat_mask, bzwin, ctx->scene_depth, ctx->scene_rgba, ctx->ctl);
-        else hipLaunchKernelGGL((k_blend<false, 0, false, false, true>), dim3(gb), dim3(64), 0, st, rows, fpairs, bproj, v, out, ctx->state,
-                                ctx->unsat_mask, bzwin, ctx->scene_depth, ctx->scene_rgba, ctx->ctl);
-        GS_HIP(hipGetLastError());
-        return GS_OK;
-    }
-    if (v.split_min) {
-        // the tiles with long lists first (the long pole): workgroups stride over all tiles' ranges and take the long ones
-        const uint32_t gp = ntiles < 2048 ? ntiles : 2048;
-        if (scene) hipLaunchKernelGGL((k_blend_px<ROUND, true>), dim3(gp), dim3(256), 0, st, ctx->tile_range, fpairs, bproj, v, out, ctx->state,
-                                      ctx->unsat_mask, bzwin, ctx->scene_depth, ctx->scene_rgba, ctx->ctl);
-        else hipLaunchKernelGGL((k_blend_px<ROUND, false>), dim3(gp), dim3(256), 0, st, ctx->tile_range, fpairs, bproj, v, out, ctx->state,
-                                ctx->unsat_mask, bzwin, ctx->scene_depth, ctx->scene_rgba, ctx->ctl);
-    }
-#define GS_LAUNCH_BLEND_(C, S, B) hipLaunchKernelGGL((k_blend<C, ROUND, S, B>), dim3(gb), dim3(64), 0, st, ctx->tile_range, fpairs, bproj, v, \
-                                                out, ctx->state, ctx->unsat_mask, bzwin, ctx->scene_depth, ctx->scene_rgba, ctx->ctl)
-#define GS_LAUNCH_BLEND(C, S) do { if (v.subtile) GS_LAUNCH_BLEND_(C, S, true); else GS_LAUNCH_BLEND_(C, S, false); } while (0)
-    if (u.flags & GS_RENDER_COUNT_FRAGS) { if (scene) GS_LAUNCH_BLEND(true, true); else GS_LAUNCH_BLEND(true, false); }
-    else { if (scene) GS_LAUNCH_BLEND(false, true); else GS_LAUNCH_BLEND(false, false); }
-#undef GS_LAUNCH_BLEND
-#undef GS_LAUNCH_BLEND_
+    // the tiles with long lists first (the long pole): workgroups stride over all tiles' ranges and take the long ones
+    if (W[0].split_min) gs_flag(scene, [&](auto SC) { gs_launch<NF, F_blend_px<ROUND, decltype(SC)::value>, 256>(ntiles < 2048 ? ntiles : 2048, st, 0, args); });
+    gs_flag(scene, [&](auto SC) { gs_flag(u.subtile != 0, [&](auto SB) {
+        if constexpr (NF == 1) { if (count) { gs_launch<1, F_blend_count<ROUND, decltype(SC)::value, decltype(SB)::value>, 64>(gb, st, 0, args); return; } }
+        gs_launch<NF, F_blend<ROUND, decltype(SC)::value, decltype(SB)::value, false>, 64>(gb, st, 0, args);
+    }); });
     GS_HIP(hipGetLastError());
     return GS_OK;
 }
@@ -1993,67 +2021,84 @@ bool row_walk_round(const GsFrameUniforms &u)
     return ROUND == 0 && u.row_walk && !(u.flags & GS_RENDER_COUNT_FRAGS) && !u.record_staged && !u.subtile && !u.split_min;
 }
 
-// one round with span lists: project (+ row counts) -> row scan -> runs -> lists -> blend (row walk: no lists)
-template <int ROUND>
-int run_round_spans(gs_ctx *ctx, const GsFrameUniforms &u, uint8_t *out, bool last_round, uint32_t g, uint32_t stride)
+// the projection of a round: plain, with view-dependent colour (GS_OPT_SH_DEGREE), with compensated opacity (GS_OPT_ANTIALIAS), or both.
+// RUNS: a span-list round (row counts per 256-splat chunk) / the pair records (tiles touched per chunk: the spine).  F[k]: the frame as
+// the kernel sees it
+template <int ROUND, bool RUNS, int NF>
+void launch_project(gs_ctx *const S[], const GsFrameUniforms F[], uint32_t g)
 {
+    hipStream_t st = S[0]->stream;
+    const auto args = [&](int k) {
+        return gs_pack_make((const uint32_t *)S[k]->sorted, (const uint4 *)S[k]->splat, F[k], S[k]->proj, S[k]->rect, S[k]->tile_count, RUNS ? S[k]->row_cnt : S[k]->spine,
+                            S[k]->part_vis, (const uint32_t *)S[k]->unsat_mask, S[k]->zwin, S[k]->ctl);
+    };
+    if (F[0].antialias) {
+        if (F[0].sh_degree) gs_launch<NF, F_project_aa<ROUND, RUNS, true>, GS_BLOCK>(g, st, 0, args);
+        else gs_launch<NF, F_project_aa<ROUND, RUNS, false>, GS_BLOCK>(g, st, 0, args);
+    } else if (F[0].sh_degree) gs_launch<NF, F_project_sh<ROUND, RUNS>, GS_BLOCK>(g, st, 0, args);
+    else gs_launch<NF, F_project<ROUND, RUNS>, GS_BLOCK>(g, st, 0, args);
+}
+
+// one round with span lists: project (+ row counts) -> row scan -> runs -> lists -> blend (row walk: no lists)
+template <int ROUND, int NF>
+int run_round_spans(gs_ctx *const S[], const GsFrameUniforms U[], uint8_t *const out[], bool last_round, uint32_t g, uint32_t stride)
+{
+    gs_ctx *ctx = S[0];
+    const GsFrameUniforms &u = U[0];
     hipStream_t st = ctx->stream;
-    const int rcc = gs_ensure_row_tables(ctx, (size_t)stride * (size_t)u.tiles_y);
-    if (rcc != GS_OK) return rcc;
-    GsFrameUniforms v = u;
-    v.rc_stride = stride;
-    v.row_walk = row_walk_round<ROUND>(u) ? 1u : 0u;
-    v.walk_ref = (uint32_t)ctx->pair_cap;
-    // the pair buffers hold the runs (geometry and sorted position of each: there are never more runs than tiles) and the lists
-    uint32_t *run_geom = reinterpret_cast<uint32_t *>(ctx->pair_a), *run_ref = run_geom + ctx->pair_cap, *lists = reinterpret_cast<uint32_t *>(ctx->pair_b);
-    const uint32_t pc = (uint32_t)ctx->pair_cap;
-    if (v.antialias) {                                          // compensated opacity (GS_OPT_ANTIALIAS), with or without SH
-        if (v.sh_degree)
-            hipLaunchKernelGGL((k_project_aa<ROUND, true, true>), dim3(g), dim3(GS_BLOCK), 0, st, ctx->sorted, ctx->splat, v, ctx->proj, ctx->rect,
-                               ctx->tile_count, ctx->row_cnt, ctx->part_vis, ctx->unsat_mask, ctx->zwin, ctx->ctl);
-        else
-            hipLaunchKernelGGL((k_project_aa<ROUND, true, false>), dim3(g), dim3(GS_BLOCK), 0, st, ctx->sorted, ctx->splat, v, ctx->proj, ctx->rect,
-                               ctx->tile_count, ctx->row_cnt, ctx->part_vis, ctx->unsat_mask, ctx->zwin, ctx->ctl);
-    } else if (v.sh_degree)                                     // view-dependent colour: the SH instantiation (GS_OPT_SH_DEGREE)
-        hipLaunchKernelGGL((k_project_sh<ROUND, true>), dim3(g), dim3(GS_BLOCK), 0, st, ctx->sorted, ctx->splat, v, ctx->proj, ctx->rect,
-                           ctx->tile_count, ctx->row_cnt, ctx->part_vis, ctx->unsat_mask, ctx->zwin, ctx->ctl);
-    else
-    hipLaunchKernelGGL((k_project<ROUND, true>), dim3(g), dim3(GS_BLOCK), 0, st, ctx->sorted, ctx->splat, v, ctx->proj, ctx->rect,
-                       ctx->tile_count, ctx->row_cnt, ctx->part_vis, ctx->unsat_mask, ctx->zwin, ctx->ctl);
+    for (int k = 0; k < NF; k++) { const int rcc = gs_ensure_row_tables(S[k], (size_t)stride * (size_t)u.tiles_y); if (rcc != GS_OK) return rcc; }
+    // the pair buffers hold the runs (geometry and sorted position of each: there are never more runs than tiles) and the lists.
+    // Every lane's runs are laid out by ITS OWN pair capacity (sibling lanes grow theirs separately)
+    GsFrameUniforms V[NF];
+    uint32_t *geom[NF], *ref[NF], *lists[NF];
+    for (int k = 0; k < NF; k++) {
+        V[k] = U[k];
+        V[k].rc_stride = stride;
+        V[k].row_walk = row_walk_round<ROUND>(u) ? 1u : 0u;
+        V[k].walk_ref = (uint32_t)S[k]->pair_cap;
+        geom[k] = reinterpret_cast<uint32_t *>(S[k]->pair_a); ref[k] = geom[k] + S[k]->pair_cap; lists[k] = reinterpret_cast<uint32_t *>(S[k]->pair_b);
+    }
+    launch_project<ROUND, true, NF>(S, V, g);
     GS_HIP(hipGetLastError());
     if (ROUND == 0) GS_PROF_RECORD(ctx, 3);
-    hipLaunchKernelGGL(k_row_scan<ROUND>, dim3((uint32_t)u.tiles_y), dim3(GS_BLOCK), 0, st, ctx->row_cnt, ctx->row_tot, (const GsControl *)ctx->ctl, u.near_count,
-                       stride, (uint32_t)u.tiles_y, ctx->unsat_mask, u.mask_words);
-    hipLaunchKernelGGL(k_emit_runs<ROUND>, dim3(g), dim3(GS_BLOCK), 0, st, ctx->proj, ctx->rect, ctx->tile_count, ctx->row_cnt, ctx->row_tot, v,
-                       run_geom, run_ref, ctx->unsat_mask, ctx->ctl, pc, ctx->row_tot + GS_BLOCK, ctx->part_vis, g, last_round ? 1 : 0);
-    if (v.row_walk) {
+    gs_launch<NF, F_row_scan<ROUND>, GS_BLOCK>((uint32_t)u.tiles_y, st, 0, [&](int k) {
+        return gs_pack_make(S[k]->row_cnt, S[k]->row_tot, (const GsControl *)S[k]->ctl, U[k].near_count, stride, (uint32_t)u.tiles_y, S[k]->unsat_mask, u.mask_words); });
+    gs_launch<NF, F_emit_runs<ROUND>, GS_BLOCK>(g, st, 0, [&](int k) {
+        return gs_pack_make((const gsm::Projected *)S[k]->proj, (const uint2 *)S[k]->rect, (const uint32_t *)S[k]->tile_count, (const uint32_t *)S[k]->row_cnt,
+                            (const uint2 *)S[k]->row_tot, V[k], geom[k], ref[k], (const uint32_t *)S[k]->unsat_mask, S[k]->ctl, (uint32_t)S[k]->pair_cap,
+                            S[k]->row_tot + GS_BLOCK, (const uint32_t *)S[k]->part_vis, g, last_round ? 1 : 0); });
+    const void *fpairs[NF];
+    if (V[0].row_walk) {
         GS_HIP(hipGetLastError());
         if (ROUND == 0) GS_PROF_RECORD(ctx, 4);
-        return launch_blend<ROUND>(ctx, u, v, out, run_geom, ctx->proj, ctx->zwin);
+        for (int k = 0; k < NF; k++) fpairs[k] = geom[k];
+        return launch_blend<ROUND, NF>(S, V, out, fpairs);
     }
     uint32_t gl = (uint32_t)u.tiles_y * GS_LIST_SEGS; if (gl > (ROUND == 1 ? 512u : 2048u)) gl = ROUND == 1 ? 512u : 2048u;
     // frames of many runs per tile row (many small splats: a cut-out scene, the cloud seen from outside, tiles that do not saturate)
     // count their segments in a launch of their own; frames of few (the headline pose: 3 000 per row) let every k_lists item count its
     // row itself -- one launch less.  Decided from the runs of the last collected frame: a matter of speed only, the lists are the same.
     const bool segc = ROUND == 0 && __atomic_load_n(&gs_root(ctx)->run_hint, __ATOMIC_RELAXED) > GS_SEGC_RUNS_PER_ROW * (uint32_t)u.tiles_y;
-    if (segc) {
-        hipLaunchKernelGGL(k_seg_count<ROUND>, dim3(gl), dim3(GS_BLOCK), 0, st, (const uint32_t *)run_geom, (const uint2 *)ctx->row_tot, ctx->seg_diff, v,
-                           (const GsControl *)ctx->ctl, pc);
-        hipLaunchKernelGGL((k_lists<ROUND, true>), dim3(gl), dim3(GS_BLOCK), 0, st, run_geom, run_ref, ctx->row_tot, (const int *)ctx->seg_diff, lists, ctx->tile_range, v,
-                           ctx->unsat_mask, (const GsControl *)ctx->ctl, pc);
-    } else
-        hipLaunchKernelGGL((k_lists<ROUND, false>), dim3(gl), dim3(GS_BLOCK), 0, st, run_geom, run_ref, ctx->row_tot, (const int *)ctx->seg_diff, lists, ctx->tile_range, v,
-                           ctx->unsat_mask, (const GsControl *)ctx->ctl, pc);
+    if (segc)
+        gs_launch<NF, F_seg_count<ROUND>, GS_BLOCK>(gl, st, 0, [&](int k) {
+            return gs_pack_make((const uint32_t *)geom[k], (const uint2 *)S[k]->row_tot, S[k]->seg_diff, V[k], (const GsControl *)S[k]->ctl, (uint32_t)S[k]->pair_cap); });
+    gs_flag(segc, [&](auto SEGC) {
+        gs_launch<NF, F_lists<ROUND, decltype(SEGC)::value>, GS_BLOCK>(gl, st, 0, [&](int k) {
+            return gs_pack_make((const uint32_t *)geom[k], (const uint32_t *)ref[k], (const uint2 *)S[k]->row_tot, (const int *)S[k]->seg_diff, lists[k], S[k]->tile_range, V[k],
+                                (const uint32_t *)S[k]->unsat_mask, (const GsControl *)S[k]->ctl, (uint32_t)S[k]->pair_cap); }); });
     GS_HIP(hipGetLastError());
     if (ROUND == 0) GS_PROF_RECORD(ctx, 4);
-    return launch_blend<ROUND>(ctx, u, v, out, lists, ctx->proj, ctx->zwin);
+    for (int k = 0; k < NF; k++) fpairs[k] = lists[k];
+    return launch_blend<ROUND, NF>(S, V, out, fpairs);
 }
 
 // one round: project -> offsets -> emit -> stable sort by tile -> ranges -> blend.  Round 1 usually finds nothing to
 // do (every tile saturated), so it is launched on small grids: its kernels grid-stride when there is work.
-template <int ROUND>
-int run_round(gs_ctx *ctx, const GsFrameUniforms &u, uint8_t *out, bool last_round)
+template <int ROUND, int NF>
+int run_round(gs_ctx *const S[], const GsFrameUniforms U[], uint8_t *const out[], bool last_round)
 {
+    gs_ctx *ctx = S[0];
+    const GsFrameUniforms &u = U[0];
     const uint32_t ntiles = (uint32_t)u.tiles_x * (uint32_t)u.tiles_y;
     const uint32_t Vmax = (uint32_t)ctx->n;
     hipStream_t st = ctx->stream;
@@ -2062,242 +2107,49 @@ int run_round(gs_ctx *ctx, const GsFrameUniforms &u, uint8_t *out, bool last_rou
     if (ROUND == 1 && g > small) g = small;
     // round 0 of a two-round frame covers at most near_count splats: no point in launching workgroups for the rest
     if (ROUND == 0 && u.near_count != 0xFFFFFFFFu) { const uint32_t gn = gs_div_up(u.near_count < Vmax ? u.near_count : Vmax, GS_BLOCK); if (gn < g) g = gn ? gn : 1; }
-    const uint32_t pc = (uint32_t)ctx->pair_cap;
+    // what sizes the shared launches of the pair records (the emit grid, the radix passes): the smallest capacity among the lanes --
+    // every kernel is still told its own lane's (k_pairs_check clamps frame k's pairs to S[k]'s)
+    uint32_t pc = (uint32_t)S[0]->pair_cap;
+    for (int k = 1; k < NF; k++) if ((uint32_t)S[k]->pair_cap < pc) pc = (uint32_t)S[k]->pair_cap;
     // what the pair sort should expect (grid, one- or two-level offsets): round 1 usually finds nothing; round 0 about what
     // the last collected frames binned (0 = not known yet: the capacity)
     const uint32_t ph = ROUND == 1 ? (uint32_t)(small * GS_CHUNK_S) : __atomic_load_n(&gs_root(ctx)->pair_hint, __ATOMIC_RELAXED);
     const uint32_t jrange = ROUND == 0 ? (u.near_count != 0xFFFFFFFFu && u.near_count < Vmax ? u.near_count : Vmax) : Vmax;
-    if (const uint32_t stride = span_list_stride(ctx, u, jrange)) return run_round_spans<ROUND>(ctx, u, out, last_round, g, stride);
+    if (const uint32_t stride = span_list_stride(ctx, u, jrange)) return run_round_spans<ROUND, NF>(S, U, out, last_round, g, stride);
     // (tile, position) records through two stable radix passes on the tile id: strips beyond 4096 pixels (more than 256 tile columns or
     // rows), or GS_OPT_BINNING = 1
     const int tb = bits_for(ntiles);
-    GsFrameUniforms v = u;
-    v.rc_stride = 0;
-    v.row_walk = 0;
-    if (u.antialias) {
-        if (u.sh_degree)
-            hipLaunchKernelGGL((k_project_aa<ROUND, false, true>), dim3(g), dim3(GS_BLOCK), 0, st, ctx->sorted, ctx->splat, u, ctx->proj, ctx->rect,
-                               ctx->tile_count, ctx->spine, ctx->part_vis, ctx->unsat_mask, ctx->zwin, ctx->ctl);
-        else
-            hipLaunchKernelGGL((k_project_aa<ROUND, false, false>), dim3(g), dim3(GS_BLOCK), 0, st, ctx->sorted, ctx->splat, u, ctx->proj, ctx->rect,
-                               ctx->tile_count, ctx->spine, ctx->part_vis, ctx->unsat_mask, ctx->zwin, ctx->ctl);
-    } else if (u.sh_degree)
-        hipLaunchKernelGGL((k_project_sh<ROUND, false>), dim3(g), dim3(GS_BLOCK), 0, st, ctx->sorted, ctx->splat, u, ctx->proj, ctx->rect,
-                           ctx->tile_count, ctx->spine, ctx->part_vis, ctx->unsat_mask, ctx->zwin, ctx->ctl);
-    else
-    hipLaunchKernelGGL((k_project<ROUND, false>), dim3(g), dim3(GS_BLOCK), 0, st, ctx->sorted, ctx->splat, u, ctx->proj, ctx->rect,
-                       ctx->tile_count, ctx->spine, ctx->part_vis, ctx->unsat_mask, ctx->zwin, ctx->ctl);
+    GsFrameUniforms V[NF];
+    for (int k = 0; k < NF; k++) { V[k] = U[k]; V[k].rc_stride = 0; V[k].row_walk = 0; }
+    launch_project<ROUND, false, NF>(S, U, g);
     GS_HIP(hipGetLastError());
     if (ROUND == 0) GS_PROF_RECORD(ctx, 3);
-    hipLaunchKernelGGL(k_pairs_check<ROUND>, dim3(1), dim3(GS_BLOCK), 0, st, ctx->ctl, (uint32_t)ctx->pair_cap, ctx->spine, ctx->part_vis, g,
-                       u.near_count, last_round ? 1 : 0, ctx->unsat_mask, (uint32_t)u.tiles_y * u.mask_words, ctx->emit_extra);
+    gs_launch<NF, F_pairs_check<ROUND>, GS_BLOCK>(1, st, 0, [&](int k) {
+        return gs_pack_make(S[k]->ctl, (uint32_t)S[k]->pair_cap, S[k]->spine, (const uint32_t *)S[k]->part_vis, g, U[k].near_count, last_round ? 1 : 0, S[k]->unsat_mask,
+                            (uint32_t)u.tiles_y * u.mask_words, S[k]->emit_extra); });
     // (items = the round's chunks + the extra slices of the heavy ones: about I / GS_EMIT_PAIRS more)
     uint32_t ge = g + (ROUND == 1 ? 0u : gs_div_up(ph ? ph : pc, GS_EMIT_PAIRS)); if (ge > GS_MAX_PART) ge = GS_MAX_PART;
-    hipLaunchKernelGGL(k_emit<ROUND>, dim3(ge), dim3(GS_BLOCK), 0, st, ctx->proj, ctx->rect, ctx->tile_count, ctx->spine,
-                       ctx->emit_extra, v, ctx->pair_a, ctx->unsat_mask, ctx->ctl);
+    gs_launch<NF, F_emit<ROUND>, GS_BLOCK>(ge, st, 0, [&](int k) {
+        return gs_pack_make((const gsm::Projected *)S[k]->proj, (const uint2 *)S[k]->rect, (const uint32_t *)S[k]->tile_count, (const uint32_t *)S[k]->spine,
+                            (const uint2 *)S[k]->emit_extra, V[k], S[k]->pair_a, (const uint32_t *)S[k]->unsat_mask, (const GsControl *)S[k]->ctl); });
     GS_HIP(hipGetLastError());
-    int rc;
-    const uint2 *fpairs;
-    if (tb <= 9) {
-        rc = gs_launch_radix_pass(ctx, ctx->pair_a, GS_RADIX_PACKED, ctx->pair_b, GS_RADIX_PACKED, &ctx->ctl->n_pairs, pc, ph, 0, tb);
+    // one pass on the whole tile id, or two on its halves: pair_a -> pair_b (-> pair_a)
+    GsRadixIO io[NF];
+    const void *fpairs[NF];
+    const int b1 = tb <= 9 ? tb : (tb + 1) / 2, b2 = tb - b1;
+    for (int k = 0; k < NF; k++) { io[k] = GsRadixIO{ S[k]->pair_a, S[k]->pair_b, &S[k]->ctl->n_pairs, nullptr, nullptr }; fpairs[k] = S[k]->pair_b; }
+    int rc = gs_radix_pass<NF>(S, io, GS_RADIX_PACKED, GS_RADIX_PACKED, pc, ph, 0, b1);
+    if (rc != GS_OK) return rc;
+    if (b2) {
+        for (int k = 0; k < NF; k++) { io[k].in = S[k]->pair_b; io[k].out = S[k]->pair_a; fpairs[k] = S[k]->pair_a; }
+        rc = gs_radix_pass<NF>(S, io, GS_RADIX_PACKED, GS_RADIX_PACKED, pc, ph, b1, b2);
         if (rc != GS_OK) return rc;
-        fpairs = ctx->pair_b;
-    } else {
-        const int b1 = (tb + 1) / 2, b2 = tb - b1;
-        rc = gs_launch_radix_pass(ctx, ctx->pair_a, GS_RADIX_PACKED, ctx->pair_b, GS_RADIX_PACKED, &ctx->ctl->n_pairs, pc, ph, 0, b1);
-        if (rc != GS_OK) return rc;
-        rc = gs_launch_radix_pass(ctx, ctx->pair_b, GS_RADIX_PACKED, ctx->pair_a, GS_RADIX_PACKED, &ctx->ctl->n_pairs, pc, ph, b1, b2);
-        if (rc != GS_OK) return rc;
-        fpairs = ctx->pair_a;
     }
-    hipLaunchKernelGGL(k_tile_ranges, dim3(ROUND == 1 ? small : 2048), dim3(GS_BLOCK), 0, st, fpairs, ctx->tile_range, ntiles, ROUND, ctx->ctl);
+    gs_launch<NF, F_tile_ranges, GS_BLOCK>(ROUND == 1 ? small : 2048, st, 0, [&](int k) {
+        return gs_pack_make((const uint2 *)fpairs[k], S[k]->tile_range, ntiles, ROUND, (const GsControl *)S[k]->ctl); });
     GS_HIP(hipGetLastError());
     if (ROUND == 0) GS_PROF_RECORD(ctx, 4);
-    return launch_blend<ROUND>(ctx, u, v, out, fpairs, ctx->proj, ctx->zwin);
-}
-
-template <int ROUND, bool RUNS> GS_BODY(F_project, k_project_body<ROUND, RUNS>);
-template <int ROUND, bool RUNS> GS_BODY(F_project_sh, k_project_body<ROUND, RUNS, true>);
-template <int ROUND, bool RUNS, bool SH> GS_BODY(F_project_aa, k_project_body<ROUND, RUNS, SH, true>);
-template <int ROUND> GS_BODY(F_row_scan, k_row_scan_body<ROUND>);
-template <int ROUND> GS_BODY(F_emit_runs, k_emit_runs_body<ROUND>);
-template <int ROUND> GS_BODY(F_seg_count, k_seg_count_body<ROUND>);
-template <int ROUND, bool SEGC> GS_BODY(F_lists, k_lists_body<ROUND, SEGC>);
-template <int ROUND> GS_BODY(F_pairs_check, k_pairs_check_body<ROUND>);
-template <int ROUND> GS_BODY(F_emit, k_emit_body<ROUND>);
-GS_BODY(F_tile_ranges, k_tile_ranges_body);
-template <int ROUND, bool SCENE, bool SUB, bool WALK> GS_BODY(F_blend, k_blend_body<false, ROUND, SCENE, SUB, WALK>);
-template <int ROUND, bool SCENE> GS_BODY(F_blend_px, k_blend_px_body<ROUND, SCENE>);
-
-// the blend of one round for two frames (launch_blend's paired form)
-template <int ROUND>
-int launch_blend2(gs_ctx *const S[2], const GsFrameUniforms &u, const GsFrameUniforms V[2], uint8_t *const out[2], const void *const fpairs[2],
-                  const gsm::Projected *const bproj[2], const float *const bzwin[2])
-{
-    gs_ctx *ctx = S[0];
-    hipStream_t st = ctx->stream;
-    const uint32_t ntiles = (uint32_t)u.tiles_x * (uint32_t)u.tiles_y;
-    const uint32_t gb = ROUND == 1 ? (ntiles < 1024 ? ntiles : 1024) : ntiles;
-    const bool scene = u.has_depth || u.has_scene_rgba;
-#define GS_BLENDPX2(SC) gs_twin<F_blend_px<ROUND, SC>, 256>(ntiles < 2048 ? ntiles : 2048, st,                                                          \
-        gs_pack_make((const uint2 *)S[0]->tile_range, fpairs[0], bproj[0], V[0], out[0], S[0]->state, S[0]->unsat_mask,         \
-                     bzwin[0], (const float *)S[0]->scene_depth, (const uint32_t *)S[0]->scene_rgba, S[0]->ctl),                        \
-        gs_pack_make((const uint2 *)S[1]->tile_range, fpairs[1], bproj[1], V[1], out[1], S[1]->state, S[1]->unsat_mask,         \
-                     bzwin[1], (const float *)S[1]->scene_depth, (const uint32_t *)S[1]->scene_rgba, S[1]->ctl))
-    if (u.split_min) { if (scene) GS_BLENDPX2(true); else GS_BLENDPX2(false); }   // the tiles with long lists first
-#undef GS_BLENDPX2
-#define GS_BLEND2_(SC, SB, WK) gs_twin<F_blend<ROUND, SC, SB, WK>, 64>(gb, st,                                                                                  \
-        gs_pack_make(WK ? (const uint2 *)S[0]->row_tot + GS_BLOCK : (const uint2 *)S[0]->tile_range, fpairs[0], bproj[0], V[0], out[0], S[0]->state, S[0]->unsat_mask, \
-                     bzwin[0], (const float *)S[0]->scene_depth, (const uint32_t *)S[0]->scene_rgba, S[0]->ctl),                        \
-        gs_pack_make(WK ? (const uint2 *)S[1]->row_tot + GS_BLOCK : (const uint2 *)S[1]->tile_range, fpairs[1], bproj[1], V[1], out[1], S[1]->state, S[1]->unsat_mask, \
-                     bzwin[1], (const float *)S[1]->scene_depth, (const uint32_t *)S[1]->scene_rgba, S[1]->ctl))
-    // (row walk: no tile lists -- the rows' run tables and fpairs = the run geometry; run_round_spans2)
-#define GS_BLEND2(SC) do { if (ROUND == 0 && V[0].row_walk) GS_BLEND2_(SC, false, (ROUND == 0)); else if (V[0].subtile) GS_BLEND2_(SC, true, false); \
-                           else GS_BLEND2_(SC, false, false); } while (0)
-    if (scene) GS_BLEND2(true); else GS_BLEND2(false);
-#undef GS_BLEND2
-#undef GS_BLEND2_
-    GS_HIP(hipGetLastError());
-    return GS_OK;
-}
-
-
-// run_round_spans() for two frames, one launch per kernel
-template <int ROUND>
-int run_round_spans2(gs_ctx *const S[2], const GsFrameUniforms U[2], uint8_t *const out[2], bool last_round, uint32_t g, uint32_t stride)
-{
-    gs_ctx *ctx = S[0];
-    const GsFrameUniforms &u = U[0];
-    hipStream_t st = ctx->stream;
-    for (int k = 0; k < 2; k++) { const int rcc = gs_ensure_row_tables(S[k], (size_t)stride * (size_t)u.tiles_y); if (rcc != GS_OK) return rcc; }
-    GsFrameUniforms V[2] = { U[0], U[1] };
-    for (int k = 0; k < 2; k++) { V[k].rc_stride = stride; V[k].row_walk = row_walk_round<ROUND>(U[0]) ? 1u : 0u; V[k].walk_ref = (uint32_t)S[k]->pair_cap; }
-    uint32_t *geom[2], *ref[2], *lists[2];
-    for (int k = 0; k < 2; k++) { geom[k] = reinterpret_cast<uint32_t *>(S[k]->pair_a); ref[k] = geom[k] + S[k]->pair_cap; lists[k] = reinterpret_cast<uint32_t *>(S[k]->pair_b); }
-    const auto pp0 = gs_pack_make((const uint32_t *)S[0]->sorted, (const uint4 *)S[0]->splat, V[0], S[0]->proj, S[0]->rect, S[0]->tile_count, S[0]->row_cnt, S[0]->part_vis,
-                                  (const uint32_t *)S[0]->unsat_mask, S[0]->zwin, S[0]->ctl);
-    const auto pp1 = gs_pack_make((const uint32_t *)S[1]->sorted, (const uint4 *)S[1]->splat, V[1], S[1]->proj, S[1]->rect, S[1]->tile_count, S[1]->row_cnt, S[1]->part_vis,
-                                  (const uint32_t *)S[1]->unsat_mask, S[1]->zwin, S[1]->ctl);
-    if (u.antialias) {                                          // (paired frames share the setting too)
-        if (u.sh_degree) gs_twin<F_project_aa<ROUND, true, true>, GS_BLOCK>(g, st, pp0, pp1);
-        else gs_twin<F_project_aa<ROUND, true, false>, GS_BLOCK>(g, st, pp0, pp1);
-    } else
-    if (u.sh_degree) gs_twin<F_project_sh<ROUND, true>, GS_BLOCK>(g, st, pp0, pp1);   // (paired frames share their degree: gs_frames_batchable)
-    else gs_twin<F_project<ROUND, true>, GS_BLOCK>(g, st, pp0, pp1);
-    GS_HIP(hipGetLastError());
-    if (ROUND == 0) GS_PROF_RECORD(ctx, 3);
-    gs_twin<F_row_scan<ROUND>, GS_BLOCK>((uint32_t)u.tiles_y, st,
-        gs_pack_make(S[0]->row_cnt, S[0]->row_tot, (const GsControl *)S[0]->ctl, U[0].near_count, stride, (uint32_t)u.tiles_y, S[0]->unsat_mask, u.mask_words),
-        gs_pack_make(S[1]->row_cnt, S[1]->row_tot, (const GsControl *)S[1]->ctl, U[1].near_count, stride, (uint32_t)u.tiles_y, S[1]->unsat_mask, u.mask_words));
-    gs_twin<F_emit_runs<ROUND>, GS_BLOCK>(g, st,
-        gs_pack_make((const gsm::Projected *)S[0]->proj, (const uint2 *)S[0]->rect, (const uint32_t *)S[0]->tile_count, (const uint32_t *)S[0]->row_cnt,
-                     (const uint2 *)S[0]->row_tot, V[0], geom[0], ref[0], (const uint32_t *)S[0]->unsat_mask, S[0]->ctl, (uint32_t)S[0]->pair_cap,
-                     S[0]->row_tot + GS_BLOCK, (const uint32_t *)S[0]->part_vis, g, last_round ? 1 : 0),
-        gs_pack_make((const gsm::Projected *)S[1]->proj, (const uint2 *)S[1]->rect, (const uint32_t *)S[1]->tile_count, (const uint32_t *)S[1]->row_cnt,
-                     (const uint2 *)S[1]->row_tot, V[1], geom[1], ref[1], (const uint32_t *)S[1]->unsat_mask, S[1]->ctl, (uint32_t)S[1]->pair_cap,
-                     S[1]->row_tot + GS_BLOCK, (const uint32_t *)S[1]->part_vis, g, last_round ? 1 : 0));
-    if (V[0].row_walk) {
-        GS_HIP(hipGetLastError());
-        if (ROUND == 0) GS_PROF_RECORD(ctx, 4);
-        const void *fgeom[2] = { geom[0], geom[1] };
-        const gsm::Projected *bproj[2] = { S[0]->proj, S[1]->proj };
-        const float *bzwin[2] = { S[0]->zwin, S[1]->zwin };
-        return launch_blend2<ROUND>(S, u, V, out, fgeom, bproj, bzwin);
-    }
-    uint32_t gl = (uint32_t)u.tiles_y * GS_LIST_SEGS; if (gl > (ROUND == 1 ? 512u : 2048u)) gl = ROUND == 1 ? 512u : 2048u;
-    const bool segc = ROUND == 0 && __atomic_load_n(&gs_root(ctx)->run_hint, __ATOMIC_RELAXED) > GS_SEGC_RUNS_PER_ROW * (uint32_t)u.tiles_y;
-    if (segc)
-        gs_twin<F_seg_count<ROUND>, GS_BLOCK>(gl, st,
-            gs_pack_make((const uint32_t *)geom[0], (const uint2 *)S[0]->row_tot, S[0]->seg_diff, V[0], (const GsControl *)S[0]->ctl, (uint32_t)S[0]->pair_cap),
-            gs_pack_make((const uint32_t *)geom[1], (const uint2 *)S[1]->row_tot, S[1]->seg_diff, V[1], (const GsControl *)S[1]->ctl, (uint32_t)S[1]->pair_cap));
-#define GS_LISTS2(SC) gs_twin<F_lists<ROUND, SC>, GS_BLOCK>(gl, st,                                                                                              \
-        gs_pack_make((const uint32_t *)geom[0], (const uint32_t *)ref[0], (const uint2 *)S[0]->row_tot, (const int *)S[0]->seg_diff, lists[0], S[0]->tile_range, V[0], \
-                     (const uint32_t *)S[0]->unsat_mask, (const GsControl *)S[0]->ctl, (uint32_t)S[0]->pair_cap),                                                    \
-        gs_pack_make((const uint32_t *)geom[1], (const uint32_t *)ref[1], (const uint2 *)S[1]->row_tot, (const int *)S[1]->seg_diff, lists[1], S[1]->tile_range, V[1], \
-                     (const uint32_t *)S[1]->unsat_mask, (const GsControl *)S[1]->ctl, (uint32_t)S[1]->pair_cap))
-    if (segc) GS_LISTS2(true); else GS_LISTS2(false);
-#undef GS_LISTS2
-    GS_HIP(hipGetLastError());
-    if (ROUND == 0) GS_PROF_RECORD(ctx, 4);
-    const void *fpairs[2] = { lists[0], lists[1] };
-    const gsm::Projected *bproj[2] = { S[0]->proj, S[1]->proj };
-    const float *bzwin[2] = { S[0]->zwin, S[1]->zwin };
-    return launch_blend2<ROUND>(S, u, V, out, fpairs, bproj, bzwin);
-}
-
-// run_round() for two frames that take the same path: every kernel once, on a grid (x, 2) (blockIdx.y = the frame)
-template <int ROUND>
-int run_round2(gs_ctx *const S[2], const GsFrameUniforms U[2], uint8_t *const out[2], bool last_round)
-{
-    gs_ctx *ctx = S[0];
-    const GsFrameUniforms &u = U[0];
-    const uint32_t ntiles = (uint32_t)u.tiles_x * (uint32_t)u.tiles_y;
-    const uint32_t Vmax = (uint32_t)ctx->n;
-    hipStream_t st = ctx->stream;
-    uint32_t g = gs_div_up(Vmax, GS_BLOCK); if (g > GS_MAX_PART) g = GS_MAX_PART;
-    const uint32_t small = 512;
-    if (ROUND == 1 && g > small) g = small;
-    if (ROUND == 0 && u.near_count != 0xFFFFFFFFu) { const uint32_t gn = gs_div_up(u.near_count < Vmax ? u.near_count : Vmax, GS_BLOCK); if (gn < g) g = gn ? gn : 1; }
-    const uint32_t pc = (uint32_t)(S[0]->pair_cap < S[1]->pair_cap ? S[0]->pair_cap : S[1]->pair_cap);
-    const uint32_t ph = ROUND == 1 ? (uint32_t)(small * GS_CHUNK_S) : __atomic_load_n(&gs_root(ctx)->pair_hint, __ATOMIC_RELAXED);
-    const uint32_t jrange = ROUND == 0 ? (u.near_count != 0xFFFFFFFFu && u.near_count < Vmax ? u.near_count : Vmax) : Vmax;
-    if (const uint32_t stride = span_list_stride(ctx, u, jrange)) return run_round_spans2<ROUND>(S, U, out, last_round, g, stride);
-    const int tb = bits_for(ntiles);
-    GsFrameUniforms V[2] = { U[0], U[1] };
-    V[0].rc_stride = V[1].rc_stride = 0;
-    V[0].row_walk = V[1].row_walk = 0;
-    const auto pp0 = gs_pack_make((const uint32_t *)S[0]->sorted, (const uint4 *)S[0]->splat, U[0], S[0]->proj, S[0]->rect, S[0]->tile_count, S[0]->spine, S[0]->part_vis,
-                                  (const uint32_t *)S[0]->unsat_mask, S[0]->zwin, S[0]->ctl);
-    const auto pp1 = gs_pack_make((const uint32_t *)S[1]->sorted, (const uint4 *)S[1]->splat, U[1], S[1]->proj, S[1]->rect, S[1]->tile_count, S[1]->spine, S[1]->part_vis,
-                                  (const uint32_t *)S[1]->unsat_mask, S[1]->zwin, S[1]->ctl);
-    if (u.antialias) {
-        if (u.sh_degree) gs_twin<F_project_aa<ROUND, false, true>, GS_BLOCK>(g, st, pp0, pp1);
-        else gs_twin<F_project_aa<ROUND, false, false>, GS_BLOCK>(g, st, pp0, pp1);
-    } else
-    if (u.sh_degree) gs_twin<F_project_sh<ROUND, false>, GS_BLOCK>(g, st, pp0, pp1);   // (paired frames share their degree: gs_frames_batchable)
-    else gs_twin<F_project<ROUND, false>, GS_BLOCK>(g, st, pp0, pp1);
-    GS_HIP(hipGetLastError());
-    if (ROUND == 0) GS_PROF_RECORD(ctx, 3);
-    gs_twin<F_pairs_check<ROUND>, GS_BLOCK>(1, st,
-        gs_pack_make(S[0]->ctl, (uint32_t)S[0]->pair_cap, S[0]->spine, (const uint32_t *)S[0]->part_vis, g, U[0].near_count, last_round ? 1 : 0, S[0]->unsat_mask,
-                     (uint32_t)u.tiles_y * u.mask_words, S[0]->emit_extra),
-        gs_pack_make(S[1]->ctl, (uint32_t)S[1]->pair_cap, S[1]->spine, (const uint32_t *)S[1]->part_vis, g, U[1].near_count, last_round ? 1 : 0, S[1]->unsat_mask,
-                     (uint32_t)u.tiles_y * u.mask_words, S[1]->emit_extra));
-    uint32_t ge = g + (ROUND == 1 ? 0u : gs_div_up(ph ? ph : pc, GS_EMIT_PAIRS)); if (ge > GS_MAX_PART) ge = GS_MAX_PART;
-    gs_twin<F_emit<ROUND>, GS_BLOCK>(ge, st,
-        gs_pack_make((const gsm::Projected *)S[0]->proj, (const uint2 *)S[0]->rect, (const uint32_t *)S[0]->tile_count, (const uint32_t *)S[0]->spine,
-                     (const uint2 *)S[0]->emit_extra, V[0], S[0]->pair_a, (const uint32_t *)S[0]->unsat_mask, (const GsControl *)S[0]->ctl),
-        gs_pack_make((const gsm::Projected *)S[1]->proj, (const uint2 *)S[1]->rect, (const uint32_t *)S[1]->tile_count, (const uint32_t *)S[1]->spine,
-                     (const uint2 *)S[1]->emit_extra, V[1], S[1]->pair_a, (const uint32_t *)S[1]->unsat_mask, (const GsControl *)S[1]->ctl));
-    GS_HIP(hipGetLastError());
-    const int fmt = GS_RADIX_PACKED;
-    const void *in[2]; void *outp[2]; const uint32_t *np[2] = { &S[0]->ctl->n_pairs, &S[1]->ctl->n_pairs };
-    uint32_t *cnt[2] = { nullptr, nullptr }; const uint32_t *fill[2] = { nullptr, nullptr };
-    const void *fpairs[2];
-    int rc;
-    if (tb <= 9) {
-        for (int k = 0; k < 2; k++) { in[k] = S[k]->pair_a; outp[k] = S[k]->pair_b; }
-        rc = gs_launch_radix_pass2(S, in, fmt, outp, fmt, np, pc, ph, 0, tb, false, 0xFFFFFFFFu, 0, cnt, fill);
-        if (rc != GS_OK) return rc;
-        fpairs[0] = S[0]->pair_b; fpairs[1] = S[1]->pair_b;
-    } else {
-        const int b1 = (tb + 1) / 2, b2 = tb - b1;
-        for (int k = 0; k < 2; k++) { in[k] = S[k]->pair_a; outp[k] = S[k]->pair_b; }
-        rc = gs_launch_radix_pass2(S, in, fmt, outp, fmt, np, pc, ph, 0, b1, false, 0xFFFFFFFFu, 0, cnt, fill);
-        if (rc != GS_OK) return rc;
-        for (int k = 0; k < 2; k++) { in[k] = S[k]->pair_b; outp[k] = S[k]->pair_a; }
-        rc = gs_launch_radix_pass2(S, in, fmt, outp, fmt, np, pc, ph, b1, b2, false, 0xFFFFFFFFu, 0, cnt, fill);
-        if (rc != GS_OK) return rc;
-        fpairs[0] = S[0]->pair_a; fpairs[1] = S[1]->pair_a;
-    }
-    gs_twin<F_tile_ranges, GS_BLOCK>(ROUND == 1 ? small : 2048, st,
-                                     gs_pack_make((const uint2 *)fpairs[0], S[0]->tile_range, ntiles, ROUND, (const GsControl *)S[0]->ctl),
-                                     gs_pack_make((const uint2 *)fpairs[1], S[1]->tile_range, ntiles, ROUND, (const GsControl *)S[1]->ctl));
-    GS_HIP(hipGetLastError());
-    if (ROUND == 0) GS_PROF_RECORD(ctx, 4);
-    const gsm::Projected *bproj[2] = { S[0]->proj, S[1]->proj };
-    const float *bzwin[2] = { S[0]->zwin, S[1]->zwin };
-    return launch_blend2<ROUND>(S, u, V, out, fpairs, bproj, bzwin);
+    return launch_blend<ROUND, NF>(S, V, out, fpairs);
 }
 
 }  // namespace
@@ -2314,9 +2166,9 @@ uint32_t gs_round0_binning(const gs_ctx *L, const GsFrameUniforms &u)
     return span_list_stride(L, u, jrange) ? 0u : 1u;
 }
 
-// Two frames that take the same path, one launch per kernel (GS_OPT_FRAME_BATCH; grid (x, 2), blockIdx.y = the frame).  S[0], S[1]:
-// sibling lanes on ONE stream, each with its own scratch, control block and output.  Frames that count fragments or record
-// the staged depths take the per-frame path -- gs_frames_batchable() says whether two frames qualify.
+// Two frames that take the same path, one launch per kernel (GS_OPT_FRAME_BATCH; grid (x, 2), blockIdx.y = the frame): run_round<.., 2>, the
+// sequence a single frame runs as run_round<.., 1>.  Frames that count fragments, record the staged depths or draw a surface have no
+// paired kernels and take the per-frame path -- gs_frames_batchable() says whether two frames qualify.
 bool gs_frames_batchable(const GsFrameUniforms &a, const GsFrameUniforms &b)
 {
     return a.near_count == b.near_count && a.skip_round1 == b.skip_round1 && a.W == b.W && a.H == b.H && a.x0 == b.x0 && a.x1 == b.x1 &&
@@ -2332,11 +2184,11 @@ int gs_run_render2(gs_ctx *const S[2], const GsFrameUniforms U[2], uint8_t *cons
     uint8_t *out[2] = { device_out[0] ? device_out[0] : S[0]->fb, device_out[1] ? device_out[1] : S[1]->fb };
     GS_PROF_RECORD(ctx, 2);
     const bool two_rounds = u.near_count != 0xFFFFFFFFu;
-    int rc = run_round2<0>(S, U, out, !two_rounds || u.skip_round1);
+    int rc = run_round<0, 2>(S, U, out, !two_rounds || u.skip_round1);
     if (rc != GS_OK) return rc;
     GS_PROF_RECORD(ctx, 5);
     if (two_rounds && !u.skip_round1) {
-        rc = run_round2<1>(S, U, out, true);
+        rc = run_round<1, 2>(S, U, out, true);
         if (rc != GS_OK) return rc;
     }
     GS_PROF_RECORD(ctx, 6);
@@ -2347,25 +2199,26 @@ int gs_run_render2(gs_ctx *const S[2], const GsFrameUniforms U[2], uint8_t *cons
 int gs_run_round1(gs_ctx *ctx, const GsFrameUniforms &u, uint8_t *device_out)
 {
     GsFrameUniforms v = u; v.skip_round1 = 0;
-    return run_round<1>(ctx, v, device_out ? device_out : ctx->fb, false);
+    uint8_t *const out = device_out ? device_out : ctx->fb;
+    return run_round<1, 1>(&ctx, &v, &out, false);
 }
 
 int gs_run_render(gs_ctx *ctx, const GsFrameUniforms &u, uint8_t *device_out)
 {
     const uint32_t ntiles = (uint32_t)u.tiles_x * (uint32_t)u.tiles_y;
     const uint32_t Vmax = (uint32_t)ctx->n;
-    uint8_t *out = device_out ? device_out : ctx->fb;
+    uint8_t *const out = device_out ? device_out : ctx->fb;
     hipStream_t st = ctx->stream;
 
     GS_PROF_RECORD(ctx, 2);
     if (u.flags & GS_RENDER_COUNT_FRAGS) GS_HIP(hipMemsetAsync(&ctx->ctl->n_frags, 0, sizeof(unsigned long long), st));
     if (Vmax && ctx->have_sort) {
         const bool two_rounds = u.near_count != 0xFFFFFFFFu;
-        int rc = run_round<0>(ctx, u, out, !two_rounds || u.skip_round1);
+        int rc = run_round<0, 1>(&ctx, &u, &out, !two_rounds || u.skip_round1);
         if (rc != GS_OK) return rc;
         GS_PROF_RECORD(ctx, 5);
         if (two_rounds && !u.skip_round1) {
-            rc = run_round<1>(ctx, u, out, true);
+            rc = run_round<1, 1>(&ctx, &u, &out, true);
             if (rc != GS_OK) return rc;
         }
     } else {

@@ -7,6 +7,7 @@
 // neither counted nor scattered), so pass B runs over the V kept splats.  Kept splats whose bucket falls outside
 // [0,65535] (f32 rounding of the stored depth >> depth range) carry key 65536, sort behind every bucket and store 0 --
 // exactly like the reference's out-of-bounds typed-array writes leave 0 in the tail [V',V) of its result.
+#include <type_traits>
 #include "gs_internal.h"
 
 namespace {
@@ -251,7 +252,7 @@ __global__ __launch_bounds__(GS_BLOCK) void k_sort_depth(const float4 *__restric
 // are cache-resident).  Per frame exactly the arithmetic of k_sort_depth.
 struct SpecArgs { uint2 *stash; uint32_t *cnt; const uint32_t *bin_hint; GsControl *ctl; };
 #ifndef GS_DEPTH_PAIR_MIN_N
-#define GS_DEPTH_PAIR_MIN_N (1u << 22)   // paired sorts of fewer splats run k_sort_depth's body twice (gs_run_sort2)
+#define GS_DEPTH_PAIR_MIN_N (1u << 22)   // paired sorts of fewer splats run k_sort_depth's body twice (run_sort<2>)
 #endif
 template <bool STRIP, bool SPEC>
 __global__ __launch_bounds__(GS_BLOCK) void k_sort_depth_pair(const float4 *__restrict__ rows, const float *__restrict__ bound_r, uint32_t n,
@@ -812,8 +813,6 @@ __device__ __forceinline__ void k_near_gather_groups_body(const uint2 *__restric
         if (g == ngroups - 1 && threadIdx.x == 0) ctl->n_sorted = base + k;   // P': what the two passes sort
     }
 }
-GS_BODY(F_near_filter, k_near_filter_body);
-GS_BODY(F_near_gather_groups, k_near_gather_groups_body);
 __global__ __launch_bounds__(GS_BLOCK) void k_near_filter(const uint2 *__restrict__ stash, const uint32_t *__restrict__ cnt, uint32_t n,
                                                           const unsigned long long *__restrict__ part_min, const unsigned long long *__restrict__ part_max,
                                                           const uint32_t *__restrict__ part_cnt, uint32_t nparts, uint2 *__restrict__ group_out,
@@ -827,9 +826,6 @@ __global__ __launch_bounds__(GS_BLOCK) void k_near_gather_groups(const uint2 *__
 {
     k_near_gather_groups_body(group_out, gcnt, n, out, ctl);
 }
-
-template <int NW> GS_BODY(F_near_stash, k_near_stash_body<NW>);
-GS_BODY(F_near_gather, k_near_gather_body);
 
 template <int NW>
 __global__ __launch_bounds__(64 * NW) void k_near_stash(const float *__restrict__ depth, uint32_t n, const unsigned long long *__restrict__ part_min,
@@ -845,8 +841,13 @@ __global__ __launch_bounds__(GS_BLOCK) void k_near_gather(const uint2 *__restric
     k_near_gather_body(stash, cnt, n, chunk, out, ctl);
 }
 
-template <int NW, bool COMPACT, bool NEAR, bool MSD = false> GS_BODY(F_sort_bucket, k_sort_bucket_body<NW, COMPACT, NEAR, MSD>);
-template <bool STRIP, bool SPEC> GS_BODY(F_sort_depth, k_sort_depth_body<STRIP, SPEC>);
+// the sort's kernels as body functors with their plain kernels (gs_internal.h: GS_BODY; what run_sort<NF> launches through gs_launch)
+GS_BODY(F_near_filter, (k_near_filter), (k_near_filter_body));
+GS_BODY(F_near_gather_groups, (k_near_gather_groups), (k_near_gather_groups_body));
+template <int NW> GS_BODY(F_near_stash, (k_near_stash<NW>), (k_near_stash_body<NW>));
+GS_BODY(F_near_gather, (k_near_gather), (k_near_gather_body));
+template <int NW, bool COMPACT, bool NEAR, bool MSD = false> GS_BODY(F_sort_bucket, (k_sort_bucket<NW, COMPACT, NEAR, MSD>), (k_sort_bucket_body<NW, COMPACT, NEAR, MSD>));
+template <bool STRIP, bool SPEC> GS_BODY(F_sort_depth, (k_sort_depth<STRIP, SPEC>), (k_sort_depth_body<STRIP, SPEC>));
 
 }  // namespace
 
@@ -924,144 +925,175 @@ static uint32_t near_hint(const gs_ctx *L, uint32_t n)
     return h < n ? (uint32_t)h : n;
 }
 
-// Two frames' sorts, one launch per kernel (GS_OPT_FRAME_BATCH): S[0] and S[1] are sibling lanes on ONE stream holding the same
-// resident data; each keeps its own depths, keys, tables, partial slots and control block.  Strip sorts (gs_sort_for) pair with strip sorts.
-int gs_run_sort2(gs_ctx *const S[2], const float *const view[2], const float *const cutout16[2], const GsSortStrip *const strip[2], const uint32_t near_req[2])
+// The sort of NF frames, one launch per kernel: NF = 1, or the two frames of a pair (GS_OPT_FRAME_BATCH) -- S[0] and S[1] are then sibling
+// lanes on ONE stream holding the same resident data; each keeps its own depths, keys, tables, partial slots and control block.  A pair
+// takes ONE path: every predicate below is the conjunction over the frames (strip sorts pair with strip sorts, near-only with near-only).
+// strip / near_req: null = none for any frame.
+template <int NF>
+static int run_sort(gs_ctx *const S[], const float *const view[], const float *const cutout16[], const GsSortStrip *const strip[], const uint32_t near_req[])
 {
     gs_ctx *ctx = S[0];
-    S[0]->sort_gen++; S[1]->sort_gen++;
+    for (int k = 0; k < NF; k++) S[k]->sort_gen++;
     const uint32_t n = (uint32_t)ctx->n;
-    SortUniforms u[2];
-    StripUniforms su[2];
-    for (int k = 0; k < 2; k++) fill_sort_uniforms(S[k], view[k], cutout16[k], strip ? strip[k] : nullptr, u[k], su[k]);
+    SortUniforms u[NF];
+    StripUniforms su[NF];
+    for (int k = 0; k < NF; k++) fill_sort_uniforms(S[k], view[k], cutout16[k], strip ? strip[k] : nullptr, u[k], su[k]);
+    // record format of the two passes: 4 bytes while the index fits in 25 bits (GS_OPT_WIDE_PAIRS forces the general form)
     const bool compact = !ctx->wide_pairs && n <= (1u << 25);
-    const bool near_both = compact && near_req && near_req[0] && near_req[1];   // (a pair takes one path)
-    const bool msd = gs_msd_ok(S[0], n, compact) && gs_msd_ok(S[1], n, compact) &&
-                     !(near_both && gs_near_stash_ok(S[0], n, near_req[0]) && gs_near_stash_ok(S[1], n, near_req[1]));   // (long near-only sorts keep their stashes)
+    bool near_all = compact && near_req, msd_ok = true, stash_ok = true, spec_ok = true, strips = true;
+    for (int k = 0; k < NF; k++) {
+        near_all = near_all && near_req[k];
+        msd_ok = msd_ok && gs_msd_ok(S[k], n, compact);
+        stash_ok = stash_ok && near_req && gs_near_stash_ok(S[k], n, near_req[k]);
+        spec_ok = spec_ok && gs_near_spec_ok(S[k], n);
+        strips = strips && u[k].has_strip;
+    }
+    // Long near-only sorts keep their stashes.  A single frame's lane may also ask for the histogram form by name (no_tail_sort: the shared
+    // sort of gs_comm.hip, whose exchange buffer holds ~2 x near_req records) -- that sort is never paired, so a pair does not look at the flag
+    const bool msd = msd_ok && !(near_all && (stash_ok || (NF == 1 && ctx->no_tail_sort)));
     // a near-only sort on the MSD path is a TAIL sort (k_msd_scatter cuts the order at a segment boundary: no histogram, no threshold
-    // search -- each frame of the pair for itself); `near` below is the histogram form of the longer inputs
-    const uint32_t tail[2] = { msd && compact && near_req ? near_req[0] : 0u, msd && compact && near_req ? near_req[1] : 0u };
-    const bool near = near_both && !msd;
-    DepthHist dh[2];
-    for (int k = 0; k < 2; k++) { gs_remember_sort(S[k], view[k], cutout16[k], strip ? strip[k] : nullptr, near ? near_req[k] : tail[k]); dh[k] = next_depth_hist(S[k], near); }
-    if (msd) for (int k = 0; k < 2; k++) gs_msd_arm(S[k], n, dh[k]);
-    const bool strips = u[0].has_strip && u[1].has_strip;
-    if (!strips) u[0].has_strip = u[1].has_strip = 0;              // (a pair takes one path: both strip sorts, or both plain)
-    const uint32_t g = gs_radix_grid(n);
+    // search -- each frame for itself); `near` below is the histogram form of the longer inputs
+    uint32_t tail[NF];
+    for (int k = 0; k < NF; k++) tail[k] = msd && compact && near_req ? near_req[k] : 0u;
+    const bool near = near_all && !msd;
+    DepthHist dh[NF];
+    for (int k = 0; k < NF; k++) { gs_remember_sort(S[k], view[k], cutout16[k], strip ? strip[k] : nullptr, near ? near_req[k] : tail[k]); dh[k] = next_depth_hist(S[k], near); }
+    if (msd) for (int k = 0; k < NF; k++) gs_msd_arm(S[k], n, dh[k]);
+    if (!strips) for (int k = 0; k < NF; k++) u[k].has_strip = 0;   // (frames that disagree: all plain)
+    const uint32_t g = gs_radix_grid(n);                         // same chunking as the radix kernels (pre-filled histogram rows)
     hipStream_t st = ctx->stream;
     GS_PROF_RECORD(ctx, 0);
     uint32_t gd = gs_div_up(n, (uint32_t)(GS_DEPTH_IPT * GS_BLOCK));
     if (gd < 1) gd = 1;
     if (gd > GS_DEPTH_GRID) gd = GS_DEPTH_GRID;
-    // ONE sweep computes both frames' depths: the rows are read once (the lanes of a context alias the owner's resident arrays)
-    if (S[0]->sort_rows != S[1]->sort_rows) { snprintf(GS_ERRBUF(ctx), GS_ERRLEN, "paired sort: the two lanes hold different splat arrays"); return GS_E_STATE; }
     // near-only sorts of long inputs hand their survivors on through per-chunk stashes instead of two whole-length passes (above);
     // with a threshold hint the depth pass stashes the candidates itself and writes no depths (SPEC)
-    const bool stash = near && gs_near_stash_ok(S[0], n, near_req[0]) && gs_near_stash_ok(S[1], n, near_req[1]);
-    const bool spec = stash && gs_near_spec_ok(S[0], n) && gs_near_spec_ok(S[1], n);
+    const bool stash = near && stash_ok;
+    const bool spec = stash && spec_ok;
     uint32_t *const bin_hint = &gs_root(ctx)->ctl->near_bin_hint;
-    const uint32_t nch = gs_div_up(n, (uint32_t)(GS_DEPTH_IPT * GS_BLOCK));
-    SpecArgs sa[2];
-    for (int k = 0; k < 2; k++) { sa[k].stash = S[k]->kv_b; sa[k].cnt = S[k]->hist; sa[k].bin_hint = bin_hint; sa[k].ctl = S[k]->ctl; }
-#define GS_DEPTHP(ST, SP) hipLaunchKernelGGL((k_sort_depth_pair<ST, SP>), dim3(gd), dim3(GS_BLOCK), near ? 2u * GS_DEPTH_BINS * sizeof(uint32_t) : 0u, st, (const float4 *)S[0]->sort_rows, (const float *)S[0]->bound_r, n,  \
-                                         u[0], u[1], su[0], su[1], S[0]->depth, S[1]->depth, S[0]->part_min, S[0]->part_max, S[0]->part_cnt,                            \
-                                         S[1]->part_min, S[1]->part_max, S[1]->part_cnt, dh[0], dh[1], sa[0], sa[1])
-    // ... where one sweep saves memory traffic: inputs the caches do not hold.  Below GS_DEPTH_PAIR_MIN_N splats the rows stay resident
-    // between the two frames' reads, and the one-sweep kernel pays for holding two frames' uniforms (two view rows, two cut-out matrices,
-    // two strips' 31 words each: more than the scalar registers hold -- the compiler parks them in lanes of a vector register, and 39 % of
-    // that kernel's vector instructions at 1 M splats were v_readlane): there the pair is k_sort_depth's body twice, blockIdx.y = the frame
-    if (!near && !spec && n < GS_DEPTH_PAIR_MIN_N) {
-#define GS_DEPTHT(ST) gs_twin<F_sort_depth<ST, false>, GS_BLOCK>(gd, st,                                                                                          \
-        gs_pack_make((const float4 *)S[0]->sort_rows, (const float *)S[0]->bound_r, n, u[0], su[0], S[0]->depth, S[0]->part_min, S[0]->part_max, S[0]->part_cnt, \
-                     dh[0], (uint2 *)nullptr, (uint32_t *)nullptr, (const uint32_t *)bin_hint, S[0]->ctl),                                                        \
-        gs_pack_make((const float4 *)S[1]->sort_rows, (const float *)S[1]->bound_r, n, u[1], su[1], S[1]->depth, S[1]->part_min, S[1]->part_max, S[1]->part_cnt, \
-                     dh[1], (uint2 *)nullptr, (uint32_t *)nullptr, (const uint32_t *)bin_hint, S[1]->ctl))
-        if (strips) GS_DEPTHT(true); else GS_DEPTHT(false);
-#undef GS_DEPTHT
-    }
-    else if (spec) { if (strips) GS_DEPTHP(true, true); else GS_DEPTHP(false, true); }
-    else { if (strips) GS_DEPTHP(true, false); else GS_DEPTHP(false, false); }
-#undef GS_DEPTHP
-    if (stash) {
-        uint2 *list[2] = { S[0]->kv_b + S[0]->scratch_cap / 2, S[1]->kv_b + S[1]->scratch_cap / 2 };
-        if (spec) {
-            uint2 *grp[2] = { S[0]->kv_b + S[0]->scratch_cap / 4, S[1]->kv_b + S[1]->scratch_cap / 4 };
-            const uint32_t ng = gs_spec_groups(n);
-            gs_twin<F_near_filter, GS_BLOCK>(ng, st,
-                gs_pack_make((const uint2 *)S[0]->kv_b, (const uint32_t *)S[0]->hist, n, (const unsigned long long *)S[0]->part_min, (const unsigned long long *)S[0]->part_max,
-                             (const uint32_t *)S[0]->part_cnt, gd, grp[0], S[0]->hist + nch, S[0]->ctl, (const uint32_t *)dh[0].fill, S[0]->sort_near_req, bin_hint),
-                gs_pack_make((const uint2 *)S[1]->kv_b, (const uint32_t *)S[1]->hist, n, (const unsigned long long *)S[1]->part_min, (const unsigned long long *)S[1]->part_max,
-                             (const uint32_t *)S[1]->part_cnt, gd, grp[1], S[1]->hist + nch, S[1]->ctl, (const uint32_t *)dh[1].fill, S[1]->sort_near_req, bin_hint));
-            gs_twin<F_near_gather_groups, GS_BLOCK>(ng, st,
-                gs_pack_make((const uint2 *)grp[0], (const uint32_t *)(S[0]->hist + nch), n, list[0], S[0]->ctl),
-                gs_pack_make((const uint2 *)grp[1], (const uint32_t *)(S[1]->hist + nch), n, list[1], S[1]->ctl));
+
+    // ---- the depth pass: the ONE step whose forms for one frame and for a pair differ (everything behind it goes through gs_launch<NF>)
+    if constexpr (NF == 1) {
+        // (a) one frame: k_sort_depth, LDS for one depth histogram when the sort is near-only
+        const size_t dlds = near ? GS_DEPTH_BINS * sizeof(uint32_t) : 0u;
+#define GS_DEPTH1(ST, SP) hipLaunchKernelGGL((k_sort_depth<ST, SP>), dim3(gd), dim3(GS_BLOCK), dlds, st, ctx->sort_rows, ctx->bound_r, n, u[0], su[0], ctx->depth, \
+                                             ctx->part_min, ctx->part_max, ctx->part_cnt, dh[0], ctx->kv_b, ctx->hist, (const uint32_t *)bin_hint, ctx->ctl)
+        if (spec) { if (strips) GS_DEPTH1(true, true); else GS_DEPTH1(false, true); }
+        else { if (strips) GS_DEPTH1(true, false); else GS_DEPTH1(false, false); }
+#undef GS_DEPTH1
+    } else {
+        // ONE sweep computes both frames' depths: the rows are read once (the lanes of a context alias the owner's resident arrays)
+        if (S[0]->sort_rows != S[1]->sort_rows) { snprintf(GS_ERRBUF(ctx), GS_ERRLEN, "paired sort: the two lanes hold different splat arrays"); return GS_E_STATE; }
+        // ... where one sweep saves memory traffic: inputs the caches do not hold.  Below GS_DEPTH_PAIR_MIN_N splats the rows stay resident
+        // between the two frames' reads, and the one-sweep kernel pays for holding two frames' uniforms (two view rows, two cut-out matrices,
+        // two strips' 31 words each: more than the scalar registers hold -- the compiler parks them in lanes of a vector register, and 39 % of
+        // that kernel's vector instructions at 1 M splats were v_readlane)
+        if (!near && !spec && n < GS_DEPTH_PAIR_MIN_N) {
+            // (b) a short pair: k_sort_depth's body twice, blockIdx.y = the frame (never near-only here: no histogram in LDS)
+            const auto args = [&](int k) {
+                return gs_pack_make((const float4 *)S[k]->sort_rows, (const float *)S[k]->bound_r, n, u[k], su[k], S[k]->depth, S[k]->part_min, S[k]->part_max, S[k]->part_cnt,
+                                    dh[k], (uint2 *)nullptr, (uint32_t *)nullptr, (const uint32_t *)bin_hint, S[k]->ctl);
+            };
+            if (strips) gs_launch<2, F_sort_depth<true, false>, GS_BLOCK>(gd, st, 0, args); else gs_launch<2, F_sort_depth<false, false>, GS_BLOCK>(gd, st, 0, args);
         } else {
-        gs_twin<F_near_stash<8>, 512>(g, st,
-            gs_pack_make((const float *)S[0]->depth, n, (const unsigned long long *)S[0]->part_min, (const unsigned long long *)S[0]->part_max, (const uint32_t *)S[0]->part_cnt, gd,
-                         S[0]->kv_b, S[0]->hist, S[0]->ctl, (const uint32_t *)dh[0].fill, S[0]->sort_near_req, bin_hint),
-            gs_pack_make((const float *)S[1]->depth, n, (const unsigned long long *)S[1]->part_min, (const unsigned long long *)S[1]->part_max, (const uint32_t *)S[1]->part_cnt, gd,
-                         S[1]->kv_b, S[1]->hist, S[1]->ctl, (const uint32_t *)dh[1].fill, S[1]->sort_near_req, bin_hint));
-        gs_twin<F_near_gather, GS_BLOCK>(gs_near_gather_grid(n), st,
-            gs_pack_make((const uint2 *)S[0]->kv_b, (const uint32_t *)S[0]->hist, n, (uint32_t)GS_CHUNK_L, list[0], S[0]->ctl),
-            gs_pack_make((const uint2 *)S[1]->kv_b, (const uint32_t *)S[1]->hist, n, (uint32_t)GS_CHUNK_L, list[1], S[1]->ctl));
+            // (c) a long or speculative pair: k_sort_depth_pair, LDS for two depth histograms when the sorts are near-only
+            const size_t dlds = near ? 2u * GS_DEPTH_BINS * sizeof(uint32_t) : 0u;
+            SpecArgs sa[2];
+            for (int k = 0; k < 2; k++) { sa[k].stash = S[k]->kv_b; sa[k].cnt = S[k]->hist; sa[k].bin_hint = bin_hint; sa[k].ctl = S[k]->ctl; }
+#define GS_DEPTHP(ST, SP) hipLaunchKernelGGL((k_sort_depth_pair<ST, SP>), dim3(gd), dim3(GS_BLOCK), dlds, st, (const float4 *)S[0]->sort_rows, (const float *)S[0]->bound_r, n,  \
+                                             u[0], u[1], su[0], su[1], S[0]->depth, S[1]->depth, S[0]->part_min, S[0]->part_max, S[0]->part_cnt,             \
+                                             S[1]->part_min, S[1]->part_max, S[1]->part_cnt, dh[0], dh[1], sa[0], sa[1])
+            if (spec) { if (strips) GS_DEPTHP(true, true); else GS_DEPTHP(false, true); }
+            else { if (strips) GS_DEPTHP(true, false); else GS_DEPTHP(false, false); }
+#undef GS_DEPTHP
+        }
+    }
+    // ---- end of the depth pass
+
+    GsRadixIO io[NF];
+    int rc;
+    if (stash) {
+        // survivors through per-chunk stashes (k_near_stash / k_near_gather above), or -- the depth pass stashed the candidates -- k_near_filter
+        uint2 *list[NF];
+        for (int k = 0; k < NF; k++) list[k] = S[k]->kv_b + S[k]->scratch_cap / 2;
+        if (spec) {
+            uint2 *grp[NF];
+            for (int k = 0; k < NF; k++) grp[k] = S[k]->kv_b + S[k]->scratch_cap / 4;
+            const uint32_t nch = gs_div_up(n, (uint32_t)(GS_DEPTH_IPT * GS_BLOCK)), ng = gs_spec_groups(n);
+            gs_launch<NF, F_near_filter, GS_BLOCK>(ng, st, 0, [&](int k) {
+                return gs_pack_make((const uint2 *)S[k]->kv_b, (const uint32_t *)S[k]->hist, n, (const unsigned long long *)S[k]->part_min, (const unsigned long long *)S[k]->part_max,
+                                    (const uint32_t *)S[k]->part_cnt, gd, grp[k], S[k]->hist + nch, S[k]->ctl, (const uint32_t *)dh[k].fill, S[k]->sort_near_req, bin_hint); });
+            gs_launch<NF, F_near_gather_groups, GS_BLOCK>(ng, st, 0, [&](int k) {
+                return gs_pack_make((const uint2 *)grp[k], (const uint32_t *)(S[k]->hist + nch), n, list[k], S[k]->ctl); });
+        } else {
+            gs_launch<NF, F_near_stash<8>, 512>(g, st, 0, [&](int k) {
+                return gs_pack_make((const float *)S[k]->depth, n, (const unsigned long long *)S[k]->part_min, (const unsigned long long *)S[k]->part_max, (const uint32_t *)S[k]->part_cnt, gd,
+                                    S[k]->kv_b, S[k]->hist, S[k]->ctl, (const uint32_t *)dh[k].fill, S[k]->sort_near_req, bin_hint); });
+            gs_launch<NF, F_near_gather, GS_BLOCK>(gs_near_gather_grid(n), st, 0, [&](int k) {
+                return gs_pack_make((const uint2 *)S[k]->kv_b, (const uint32_t *)S[k]->hist, n, (uint32_t)GS_CHUNK_L, list[k], S[k]->ctl); });
         }
         GS_HIP(hipGetLastError());
-        const void *in2[2]; void *out2[2]; const uint32_t *np2[2]; uint32_t *cnt2[2] = { nullptr, nullptr }; const uint32_t *fill2[2] = { nullptr, nullptr };
-        for (int k = 0; k < 2; k++) { in2[k] = list[k]; out2[k] = S[k]->key_a; np2[k] = &S[k]->ctl->n_sorted; }
-        int rc2 = gs_launch_radix_pass2(S, in2, GS_RADIX_PACKED, out2, GS_RADIX_KEYIDX, np2, n, near_hint(S[0], n), 0, 9, false, 0xFFFFFFFFu, 25, cnt2, fill2);
-        if (rc2 != GS_OK) return rc2;
-        for (int k = 0; k < 2; k++) { in2[k] = S[k]->key_a; out2[k] = S[k]->val_a; }
-        rc2 = gs_launch_radix_pass2(S, in2, GS_RADIX_KEYIDX, out2, GS_RADIX_KEYS, np2, n, near_hint(S[0], n), 25, 7, false, 0xFFFFFFFFu, 0, cnt2, fill2);
-        if (rc2 != GS_OK) return rc2;
-        GS_PROF_RECORD(ctx, 1);
-        for (int k = 0; k < 2; k++) { S[k]->sorted = S[k]->val_a; S[k]->have_sort = true; }
-        return GS_OK;
-    }
-    if (msd) {
-#define GS_BUCKETM(NW) gs_twin<F_sort_bucket<NW, true, false, true>, 64 * NW>(g, st,                                                                    \
-        gs_pack_make((const float *)S[0]->depth, n, S[0]->key_a, (const unsigned long long *)S[0]->part_min, (const unsigned long long *)S[0]->part_max,     \
-                     (const uint32_t *)S[0]->part_cnt, gd, S[0]->hist, S[0]->ctl, (const uint32_t *)dh[0].fill, S[0]->sort_near_req, bin_hint, S[0]->msd_grp), \
-        gs_pack_make((const float *)S[1]->depth, n, S[1]->key_a, (const unsigned long long *)S[1]->part_min, (const unsigned long long *)S[1]->part_max,     \
-                     (const uint32_t *)S[1]->part_cnt, gd, S[1]->hist, S[1]->ctl, (const uint32_t *)dh[1].fill, S[1]->sort_near_req, bin_hint, S[1]->msd_grp))
-        if (gs_radix_chunk(n) == GS_CHUNK_L) GS_BUCKETM(8); else GS_BUCKETM(4);
-#undef GS_BUCKETM
-        GS_HIP(hipGetLastError());
-        const int rcm = gs_launch_msd_sort2(S, n, tail);
-        if (rcm != GS_OK) return rcm;
-        GS_PROF_RECORD(ctx, 1);
-        for (int k = 0; k < 2; k++) { S[k]->sorted = S[k]->val_a; S[k]->have_sort = true; }
-        return GS_OK;
-    }
-#define GS_BUCKET2(NW, C, NR) gs_twin<F_sort_bucket<NW, C, NR>, 64 * NW>(g, st,                                                                            \
-        gs_pack_make((const float *)S[0]->depth, n, S[0]->key_a, (const unsigned long long *)S[0]->part_min, (const unsigned long long *)S[0]->part_max,     \
-                     (const uint32_t *)S[0]->part_cnt, gd, S[0]->hist, S[0]->ctl, (const uint32_t *)dh[0].fill, S[0]->sort_near_req, bin_hint, (uint32_t *)nullptr), \
-        gs_pack_make((const float *)S[1]->depth, n, S[1]->key_a, (const unsigned long long *)S[1]->part_min, (const unsigned long long *)S[1]->part_max,     \
-                     (const uint32_t *)S[1]->part_cnt, gd, S[1]->hist, S[1]->ctl, (const uint32_t *)dh[1].fill, S[1]->sort_near_req, bin_hint, (uint32_t *)nullptr))
-    if (gs_radix_chunk(n) == GS_CHUNK_L) { if (near) GS_BUCKET2(8, true, true); else if (compact) GS_BUCKET2(8, true, false); else GS_BUCKET2(8, false, false); }
-    else { if (near) GS_BUCKET2(4, true, true); else if (compact) GS_BUCKET2(4, true, false); else GS_BUCKET2(4, false, false); }
-#undef GS_BUCKET2
-    GS_HIP(hipGetLastError());
-    const void *in[2]; void *out[2]; const uint32_t *np[2]; uint32_t *cnt[2]; const uint32_t *fill[2];
-    int rc;
-    if (compact) {
-        for (int k = 0; k < 2; k++) { in[k] = S[k]->key_a; out[k] = S[k]->kv_b; np[k] = &S[k]->ctl->n_total; cnt[k] = &S[k]->ctl->n_sorted; fill[k] = nullptr; }
-        rc = gs_launch_radix_pass2(S, in, GS_RADIX_KEYS, out, GS_RADIX_KEYIDX, np, n, n, 0, 9, true, 0xFFFFFFFFu, 25, cnt, fill);
+        for (int k = 0; k < NF; k++) io[k] = GsRadixIO{ list[k], S[k]->key_a, &S[k]->ctl->n_sorted, nullptr, nullptr };
+        rc = gs_radix_pass<NF>(S, io, GS_RADIX_PACKED, GS_RADIX_KEYIDX, n, near_hint(ctx, n), 0, 9, false, 0xFFFFFFFFu, 25);
         if (rc != GS_OK) return rc;
-        // (a near-only sort leaves no zero tail: k_project supplies the zeros of the positions behind its records)
-        for (int k = 0; k < 2; k++) { in[k] = S[k]->kv_b; out[k] = S[k]->val_a; np[k] = &S[k]->ctl->n_sorted; cnt[k] = nullptr; fill[k] = near ? nullptr : &S[k]->ctl->n_kept; }
-        rc = gs_launch_radix_pass2(S, in, GS_RADIX_KEYIDX, out, GS_RADIX_KEYS, np, n, near ? near_hint(S[0], n) : n, 25, 7, false, 0xFFFFFFFFu, 0, cnt, fill);
+        for (int k = 0; k < NF; k++) { io[k].in = S[k]->key_a; io[k].out = S[k]->val_a; }
+        rc = gs_radix_pass<NF>(S, io, GS_RADIX_KEYIDX, GS_RADIX_KEYS, n, near_hint(ctx, n), 25, 7);
         if (rc != GS_OK) return rc;
     } else {
-        for (int k = 0; k < 2; k++) { in[k] = S[k]->key_a; out[k] = S[k]->kv_b; np[k] = &S[k]->ctl->n_total; cnt[k] = nullptr; fill[k] = nullptr; }
-        rc = gs_launch_radix_pass2(S, in, GS_RADIX_KEYS, out, GS_RADIX_PACKED, np, n, n, 0, 8, true, 0xFFFFFFFFu, 0, cnt, fill);
-        if (rc != GS_OK) return rc;
-        for (int k = 0; k < 2; k++) { in[k] = S[k]->kv_b; out[k] = S[k]->val_a; np[k] = &S[k]->ctl->n_kept; }
-        rc = gs_launch_radix_pass2(S, in, GS_RADIX_PACKED, out, GS_RADIX_KEYS, np, n, n, 8, 9, false, GS_CULLED_KEY, 0, cnt, fill);
-        if (rc != GS_OK) return rc;
+        // bucket keys (+ the histogram rows of the first digit); MSD: rows of the high bucket byte per chunk and per group of chunks
+        const auto bucket = [&](auto NW, auto C, auto NR, auto M) {
+            gs_launch<NF, F_sort_bucket<decltype(NW)::value, decltype(C)::value, decltype(NR)::value, decltype(M)::value>, 64 * decltype(NW)::value>(g, st, 0, [&](int k) {
+                return gs_pack_make((const float *)S[k]->depth, n, S[k]->key_a, (const unsigned long long *)S[k]->part_min, (const unsigned long long *)S[k]->part_max,
+                                    (const uint32_t *)S[k]->part_cnt, gd, S[k]->hist, S[k]->ctl, (const uint32_t *)dh[k].fill, S[k]->sort_near_req, bin_hint,
+                                    decltype(M)::value ? S[k]->msd_grp : (uint32_t *)nullptr); });
+        };
+        const auto bucket_nw = [&](auto C, auto NR, auto M) {
+            if (gs_radix_chunk(n) == GS_CHUNK_L) bucket(std::integral_constant<int, 8>(), C, NR, M); else bucket(std::integral_constant<int, 4>(), C, NR, M);
+        };
+        const std::true_type yes; const std::false_type no;
+        if (msd) bucket_nw(yes, no, yes);
+        else if (near) bucket_nw(yes, yes, no);
+        else if (compact) bucket_nw(yes, no, no);
+        else bucket_nw(no, no, no);
+        GS_HIP(hipGetLastError());
+        if (msd) {
+            // four launches: depth (above), bucket + rows, one stable scatter by the high bucket byte, one LDS sort per segment
+            rc = gs_msd_sort<NF>(S, n, tail);
+            if (rc != GS_OK) return rc;
+        } else if (compact) {
+            for (int k = 0; k < NF; k++) io[k] = GsRadixIO{ S[k]->key_a, S[k]->kv_b, &S[k]->ctl->n_total, &S[k]->ctl->n_sorted, nullptr };
+            rc = gs_radix_pass<NF>(S, io, GS_RADIX_KEYS, GS_RADIX_KEYIDX, n, n, 0, 9, /*have_hist=*/true, 0xFFFFFFFFu, 25);
+            if (rc != GS_OK) return rc;
+            // V' records are left (culled splats and dropped buckets took no slot); slots [V', V) of the result are zero-filled:
+            // the reference's never-written Uint32Array tail
+            // (a near-only sort leaves no zero tail: k_project supplies the zeros of the positions behind its records)
+            for (int k = 0; k < NF; k++) io[k] = GsRadixIO{ S[k]->kv_b, S[k]->val_a, &S[k]->ctl->n_sorted, nullptr, near ? nullptr : &S[k]->ctl->n_kept };
+            rc = gs_radix_pass<NF>(S, io, GS_RADIX_KEYIDX, GS_RADIX_KEYS, n, near ? near_hint(ctx, n) : n, 25, 7);
+            if (rc != GS_OK) return rc;
+        } else {
+            for (int k = 0; k < NF; k++) io[k] = GsRadixIO{ S[k]->key_a, S[k]->kv_b, &S[k]->ctl->n_total, nullptr, nullptr };
+            rc = gs_radix_pass<NF>(S, io, GS_RADIX_KEYS, GS_RADIX_PACKED, n, n, 0, 8, /*have_hist=*/true);
+            if (rc != GS_OK) return rc;
+            // pass A dropped the culled splats: V records are left.  Splats with a dropped bucket (key 65536) sort behind every
+            // bucket and store 0: the tail [V',V) of the result is 0 like the reference's never-written Uint32Array slots
+            for (int k = 0; k < NF; k++) io[k] = GsRadixIO{ S[k]->kv_b, S[k]->val_a, &S[k]->ctl->n_kept, nullptr, nullptr };
+            rc = gs_radix_pass<NF>(S, io, GS_RADIX_PACKED, GS_RADIX_KEYS, n, n, 8, 9, false, GS_CULLED_KEY);
+            if (rc != GS_OK) return rc;
+        }
     }
     GS_PROF_RECORD(ctx, 1);
-    for (int k = 0; k < 2; k++) { S[k]->sorted = S[k]->val_a; S[k]->have_sort = true; }
+    for (int k = 0; k < NF; k++) { S[k]->sorted = S[k]->val_a; S[k]->have_sort = true; }
     return GS_OK;
+}
+
+int gs_run_sort(gs_ctx *ctx, const float view[4], const float *cutout16, const GsSortStrip *strip, uint32_t near_req)
+{
+    return run_sort<1>(&ctx, &view, &cutout16, &strip, &near_req);
+}
+
+int gs_run_sort2(gs_ctx *const S[2], const float *const view[2], const float *const cutout16[2], const GsSortStrip *const strip[2], const uint32_t near_req[2])
+{
+    return run_sort<2>(S, view, cutout16, strip, near_req);
 }
 
 // the uniforms of one sort: view row and cutout matrix widened to f64; for a strip sort (gs_sort_for) the rows of the frame's
@@ -1105,105 +1137,4 @@ static void fill_sort_uniforms(const gs_ctx *ctx, const float view[4], const flo
         u.has_strip = (su.norm_a == su.norm_a && su.focal > 0.0f && strip->x1 > strip->x0) ? 1 : 0;
     }
 
-}
-
-int gs_run_sort(gs_ctx *ctx, const float view[4], const float *cutout16, const GsSortStrip *strip, uint32_t near_req)
-{
-    ctx->sort_gen++;
-    const uint32_t n = (uint32_t)ctx->n;
-    SortUniforms u;
-    StripUniforms su;
-    fill_sort_uniforms(ctx, view, cutout16, strip, u, su);
-    // record format of the two passes: 4 bytes while the index fits in 25 bits (GS_OPT_WIDE_PAIRS forces the general form)
-    const bool compact = !ctx->wide_pairs && n <= (1u << 25);
-    const bool msd = gs_msd_ok(ctx, n, compact) && !(compact && near_req && (gs_near_stash_ok(ctx, n, near_req) || ctx->no_tail_sort));   // (long near-only sorts keep their stashes)
-    const uint32_t tail = msd && compact ? near_req : 0u;          // (a near-only sort on the MSD path: k_msd_scatter cuts the order at a segment boundary)
-    const bool near = compact && near_req && !msd;               // (... on the longer inputs: depth histogram + threshold)
-    gs_remember_sort(ctx, view, cutout16, strip, near ? near_req : tail);
-    DepthHist dh = next_depth_hist(ctx, near);
-    if (msd) gs_msd_arm(ctx, n, dh);
-
-    const uint32_t g = gs_radix_grid(n);                         // same chunking as the radix kernels (pre-filled histogram rows)
-    GS_PROF_RECORD(ctx, 0);
-    uint32_t gd = gs_div_up(n, (uint32_t)(GS_DEPTH_IPT * GS_BLOCK));
-    if (gd < 1) gd = 1;
-    if (gd > GS_DEPTH_GRID) gd = GS_DEPTH_GRID;
-    const size_t dlds = near ? GS_DEPTH_BINS * sizeof(uint32_t) : 0u;
-    const bool stash = near && gs_near_stash_ok(ctx, n, near_req);
-    const bool spec = stash && gs_near_spec_ok(ctx, n);
-    uint32_t *const bin_hint = &gs_root(ctx)->ctl->near_bin_hint;
-#define GS_DEPTH1(ST, SP) hipLaunchKernelGGL((k_sort_depth<ST, SP>), dim3(gd), dim3(GS_BLOCK), dlds, ctx->stream, ctx->sort_rows, ctx->bound_r, n, u, su, ctx->depth, \
-                                             ctx->part_min, ctx->part_max, ctx->part_cnt, dh, ctx->kv_b, ctx->hist, (const uint32_t *)bin_hint, ctx->ctl)
-    if (spec) { if (u.has_strip) GS_DEPTH1(true, true); else GS_DEPTH1(false, true); }
-    else { if (u.has_strip) GS_DEPTH1(true, false); else GS_DEPTH1(false, false); }
-#undef GS_DEPTH1
-    if (stash) {
-        // (survivors through per-chunk stashes: k_near_stash / k_near_gather above; candidates stashed by the depth pass: k_near_filter)
-        uint2 *list = ctx->kv_b + ctx->scratch_cap / 2;
-        if (spec) {
-            uint2 *grp = ctx->kv_b + ctx->scratch_cap / 4;
-            const uint32_t nch = gs_div_up(n, (uint32_t)(GS_DEPTH_IPT * GS_BLOCK)), ng = gs_spec_groups(n);
-            hipLaunchKernelGGL(k_near_filter, dim3(ng), dim3(GS_BLOCK), 0, ctx->stream, (const uint2 *)ctx->kv_b, (const uint32_t *)ctx->hist, n, (const unsigned long long *)ctx->part_min,
-                               (const unsigned long long *)ctx->part_max, (const uint32_t *)ctx->part_cnt, gd, grp, ctx->hist + nch, ctx->ctl, (const uint32_t *)dh.fill, ctx->sort_near_req, bin_hint);
-            hipLaunchKernelGGL(k_near_gather_groups, dim3(ng), dim3(GS_BLOCK), 0, ctx->stream, (const uint2 *)grp, (const uint32_t *)(ctx->hist + nch), n, list, ctx->ctl);
-        } else {
-        hipLaunchKernelGGL((k_near_stash<8>), dim3(g), dim3(512), 0, ctx->stream, (const float *)ctx->depth, n, (const unsigned long long *)ctx->part_min,
-                           (const unsigned long long *)ctx->part_max, (const uint32_t *)ctx->part_cnt, gd, ctx->kv_b, ctx->hist, ctx->ctl, (const uint32_t *)dh.fill, ctx->sort_near_req, bin_hint);
-        hipLaunchKernelGGL(k_near_gather, dim3(gs_near_gather_grid(n)), dim3(GS_BLOCK), 0, ctx->stream, (const uint2 *)ctx->kv_b, (const uint32_t *)ctx->hist, n,
-                           (uint32_t)GS_CHUNK_L, list, ctx->ctl);
-        }
-        GS_HIP(hipGetLastError());
-        int rcs = gs_launch_radix_pass(ctx, list, GS_RADIX_PACKED, ctx->key_a, GS_RADIX_KEYIDX, &ctx->ctl->n_sorted, n, near_hint(ctx, n), 0, 9, false, 0xFFFFFFFFu, 25);
-        if (rcs != GS_OK) return rcs;
-        rcs = gs_launch_radix_pass(ctx, ctx->key_a, GS_RADIX_KEYIDX, ctx->val_a, GS_RADIX_KEYS, &ctx->ctl->n_sorted, n, near_hint(ctx, n), 25, 7, false, 0xFFFFFFFFu, 0, nullptr, nullptr);
-        if (rcs != GS_OK) return rcs;
-        GS_PROF_RECORD(ctx, 1);
-        ctx->sorted = ctx->val_a;
-        ctx->have_sort = true;
-        return GS_OK;
-    }
-    if (msd) {
-        // four launches: depth (above), bucket + rows of the high bucket byte, one stable scatter by that byte, one LDS sort per segment
-#define GS_LAUNCH_BUCKETM(NW) hipLaunchKernelGGL((k_sort_bucket<NW, true, false, true>), dim3(g), dim3(64 * NW), 0, ctx->stream, (const float *)ctx->depth, n, ctx->key_a,     \
-                                                     (const unsigned long long *)ctx->part_min, (const unsigned long long *)ctx->part_max, (const uint32_t *)ctx->part_cnt, gd, \
-                                                     ctx->hist, ctx->ctl, (const uint32_t *)dh.fill, ctx->sort_near_req, bin_hint, ctx->msd_grp)
-        if (gs_radix_chunk(n) == GS_CHUNK_L) GS_LAUNCH_BUCKETM(8); else GS_LAUNCH_BUCKETM(4);
-#undef GS_LAUNCH_BUCKETM
-        GS_HIP(hipGetLastError());
-        const int rcm = gs_launch_msd_sort(ctx, n, tail);
-        if (rcm != GS_OK) return rcm;
-        GS_PROF_RECORD(ctx, 1);
-        ctx->sorted = ctx->val_a;
-        ctx->have_sort = true;
-        return GS_OK;
-    }
-#define GS_LAUNCH_BUCKET(NW, C, NR) hipLaunchKernelGGL((k_sort_bucket<NW, C, NR>), dim3(g), dim3(64 * NW), 0, ctx->stream, ctx->depth, n, ctx->key_a, \
-                                                       ctx->part_min, ctx->part_max, ctx->part_cnt, gd, ctx->hist, ctx->ctl, (const uint32_t *)dh.fill, ctx->sort_near_req, bin_hint, (uint32_t *)nullptr)
-    if (gs_radix_chunk(n) == GS_CHUNK_L) { if (near) GS_LAUNCH_BUCKET(8, true, true); else if (compact) GS_LAUNCH_BUCKET(8, true, false); else GS_LAUNCH_BUCKET(8, false, false); }
-    else { if (near) GS_LAUNCH_BUCKET(4, true, true); else if (compact) GS_LAUNCH_BUCKET(4, true, false); else GS_LAUNCH_BUCKET(4, false, false); }
-#undef GS_LAUNCH_BUCKET
-    GS_HIP(hipGetLastError());
-    int rc;
-    if (compact) {
-        rc = gs_launch_radix_pass(ctx, ctx->key_a, GS_RADIX_KEYS, ctx->kv_b, GS_RADIX_KEYIDX, &ctx->ctl->n_total, n, n, 0, 9, /*have_hist=*/true,
-                                  0xFFFFFFFFu, 25, &ctx->ctl->n_sorted);
-        if (rc != GS_OK) return rc;
-        // V' records are left (culled splats and dropped buckets took no slot); slots [V', V) of the result are zero-filled:
-        // the reference's never-written Uint32Array tail
-        // (a near-only sort leaves no zero tail: k_project supplies the zeros of the positions behind its records)
-        rc = gs_launch_radix_pass(ctx, ctx->kv_b, GS_RADIX_KEYIDX, ctx->val_a, GS_RADIX_KEYS, &ctx->ctl->n_sorted, n, near ? near_hint(ctx, n) : n, 25, 7, false,
-                                  0xFFFFFFFFu, 0, nullptr, near ? nullptr : &ctx->ctl->n_kept);
-        if (rc != GS_OK) return rc;
-    } else {
-        rc = gs_launch_radix_pass(ctx, ctx->key_a, GS_RADIX_KEYS, ctx->kv_b, GS_RADIX_PACKED, &ctx->ctl->n_total, n, n, 0, 8, /*have_hist=*/true);
-        if (rc != GS_OK) return rc;
-        // pass A dropped the culled splats: V records are left.  Splats with a dropped bucket (key 65536) sort behind every
-        // bucket and store 0: the tail [V',V) of the result is 0 like the reference's never-written Uint32Array slots
-        rc = gs_launch_radix_pass(ctx, ctx->kv_b, GS_RADIX_PACKED, ctx->val_a, GS_RADIX_KEYS, &ctx->ctl->n_kept, n, n, 8, 9, false, GS_CULLED_KEY);
-        if (rc != GS_OK) return rc;
-    }
-    GS_PROF_RECORD(ctx, 1);
-    ctx->sorted = ctx->val_a;
-    ctx->have_sort = true;
-    return GS_OK;
 }

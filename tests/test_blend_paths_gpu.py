@@ -12,7 +12,8 @@ to make a chosen run of tile columns in a chosen tile row.  Before a layout is r
 (GS_OPT_RECORD_STAGED + GS_BUF_TILE_STATS list lengths): "column 4 of tile row 5 holds exactly 65 entries".  The oracle draws only the
 strip under test.
 
-Budget: about 3 s of wall time on one MI355X (1.7 s of test time: ~170 fresh contexts, the oracle drawing only the strips under test)."""
+Budget: about 3 s of wall time on one MI355X (1.5 s of test time as last measured, 0.15 s of it the nine contexts of the paired-frames
+test: ~180 fresh contexts, the oracle drawing only the strips under test)."""
 import math
 
 import numpy as np
@@ -546,29 +547,51 @@ def test_two_rounds_walk_and_lists(cloud):
         pix_check("two_rounds", img, want)
 
 
-def test_paired_frames_equal_synchronous_ones(cloud):
-    """GS_OPT_FRAME_BATCH 2: queued frames drawn two per launch equal the same frames drawn synchronously, walked and listed.  (Pairing
-    is opportunistic -- an enqueue thread that does not see the twin frame in time draws the frame alone -- and no statistic counts
-    it, so this proves the frames right whichever way they were drawn, not that they were paired.)"""
-    rows = cloud[0]
+def _paired_equal_synchronous(rows, path, near_permille=1000, scene=None):
+    """Four poses of the 320x180 cloud drawn synchronously, then queued -- all four before the first sync() -- with GS_OPT_FRAME_BATCH 2."""
     w, h = 320, 180
     cams = [synth.index_html_camera(w, h, 50.0 * k, capi=capi) for k in range(4)]
+    tag = (path, near_permille, scene is not None)
+    with capi.Context(0) as c:
+        force_path(c, path, near_permille)
+        c.push_splat(rows)
+        if scene is not None:
+            c.set_scene(*scene)
+        want = []
+        for cam in cams:
+            c.sort(cam["view"])
+            want.append(c.render(capi.make_params(cam["gs_mv"], cam["gs_proj"], w, h, focal_=cam["focal"])))
+            assert_path(c, path, tag)
+        c.set_option(capi.OPT_FRAME_BATCH, 2)
+        bufs = [capi.host_frame(h, w) for _ in cams]
+        for (b, _), cam in zip(bufs, cams):
+            c.sort(cam["view"], want_indices=False)
+            c.render_into(capi.make_params(cam["gs_mv"], cam["gs_proj"], w, h, focal_=cam["focal"], flags=capi.RENDER_ASYNC), b)
+        c.sync()
+        assert_path(c, path, tag + ("paired",))
+        for k, ((b, o), wnt) in enumerate(zip(bufs, want)):
+            d = int(np.abs(b.astype(int) - wnt.astype(int)).max())
+            print("paired vs synchronous:", tag, "pose", k, "max |dRGBA8| =", d)
+            assert d == 0, (tag, k, d)
+            o.free()
+
+
+def test_paired_frames_equal_synchronous_ones(cloud):
+    """GS_OPT_FRAME_BATCH 2: queued frames drawn two per launch equal the same frames drawn synchronously, bit for bit, on every path --
+    walked, listed, sub-tile lists, pair records (the paired radix passes and k_tile_ranges) and the split blend (the paired k_blend_px)
+    -- each against its own synchronous frames; walked and listed also over two binning rounds (GS_OPT_NEAR_PERMILLE 400: the share
+    test_two_rounds_walk_and_lists shows leaves tiles to round 1) and with scene depth + colour set.  (Pairing
+    is opportunistic -- an enqueue thread that does not see the twin frame in time draws the frame alone -- and no statistic counts
+    it, so this proves the frames right whichever way they were drawn, not that they were paired.  The two-view form is no surer a way
+    in: its enqueue thread gives the second view 200 us and then draws the first alone too, and it takes device outputs only, which
+    render_stereo does not use.)"""
+    rows = cloud[0]
+    for p in ("walk", "lists", "subtile", "pairs", "split"):
+        _paired_equal_synchronous(rows, p)
+    g = np.random.Generator(np.random.PCG64(9))
+    depth = g.uniform(0.995, 1.0, (180, 320)).astype(np.float32)
+    depth[:, : 320 // 3] = 1.0
+    rgba = g.integers(0, 256, (180, 320, 4)).astype(np.uint8)
     for p in ("walk", "lists"):
-        with capi.Context(0) as c:
-            force_path(c, p)
-            c.push_splat(rows)
-            want = []
-            for cam in cams:
-                c.sort(cam["view"])
-                want.append(c.render(capi.make_params(cam["gs_mv"], cam["gs_proj"], w, h, focal_=cam["focal"])))
-                assert_path(c, p)
-            c.set_option(capi.OPT_FRAME_BATCH, 2)
-            bufs = [capi.host_frame(h, w) for _ in cams]
-            for (b, _), cam in zip(bufs, cams):
-                c.sort(cam["view"], want_indices=False)
-                c.render_into(capi.make_params(cam["gs_mv"], cam["gs_proj"], w, h, focal_=cam["focal"], flags=capi.RENDER_ASYNC), b)
-            c.sync()
-            assert_path(c, p, "paired")
-            for (b, o), wnt in zip(bufs, want):
-                assert np.array_equal(b, wnt), p
-                o.free()
+        _paired_equal_synchronous(rows, p, near_permille=400)
+        _paired_equal_synchronous(rows, p, scene=(depth, rgba))
