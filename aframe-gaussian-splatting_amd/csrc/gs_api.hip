@@ -16,9 +16,6 @@
 #include "gs_sh.h"
 #include "gs_host_tables.h"
 
-#ifndef GS_NEAR_FLOOR_MULT
-#define GS_NEAR_FLOOR_MULT 1.3f     // the adaptive share never again shrinks below this x the share that failed (1.2: 5 % faster on one orbit, redraws on another)
-#endif
 static thread_local char g_create_err[512] = "";
 thread_local char *gs_tl_err = nullptr;
 
@@ -254,17 +251,6 @@ static int prof_advance(gs_ctx *ctx)
     return GS_OK;
 }
 
-// after a stream sync: publish the counters of the last completed frame and react to pair-buffer overflow
-// the share of splats binned first was too small for a frame drawn with `frac_used`: never again below 1.3 x that, now 1.5 x that
-static void share_raise(gs_ctx *ctx /* owner */, float frac_used)
-{
-    const float fl = frac_used * GS_NEAR_FLOOR_MULT > 1.0f ? 1.0f : frac_used * GS_NEAR_FLOOR_MULT;
-    if (fl > ctx->near_floor) ctx->near_floor = fl;
-    float nf = frac_used * 1.5f; if (nf < ctx->near_floor) nf = ctx->near_floor; if (nf > 1.0f) nf = 1.0f;
-    if (nf > ctx->near_frac) ctx->near_frac = nf;
-    ctx->clean_frames = 0; ctx->skip_hold = 32;
-}
-
 // the speculative stash of near-only sorts failed: at once out of use for a while if the view does not suit it (kind 2), at the second
 // miss within a few collections if the threshold bin keeps outrunning the hint -- one miss is a camera jump, two in a row are a view
 // whose threshold is not smooth (the 20 M cloud seen from outside: the bin moves by up to three from one 3-degree pose to the next), and
@@ -278,104 +264,37 @@ static void gs_spec_back_off(gs_ctx *ctx /* owner */, bool unsuited)
     __atomic_store_n(&ctx->near_spec_hold, ctx->near_spec_backoff, __ATOMIC_RELAXED);
 }
 
-#ifndef GS_NEED_MARGIN_MIN
-#define GS_NEED_MARGIN_MIN 1.04f    // what the margin on the measured share shrinks to while no frame misses (it starts at GS_NEED_MARGIN)
-#endif
-#ifndef GS_NEED_MARGIN
-#define GS_NEED_MARGIN 1.15         // the share binned first = what the collected frames' tiles needed x this (the walked share ended 1.17-1.3 x above the share that had failed)
-#endif
-// The share of splats binned first, from what the blends of the collected frames MEASURED (GsControl::need_near: per tile, how many of
-// the nearest splats it read before its pixels were saturated).  Rounds 1-4 walked the share: x 0.9 per collection from 25 % until a
-// share failed, x 1.5 then -- a fresh context needed dozens of collections (and one failure) to arrive, and a 20 M-splat scene drew
-// its first hundred frames with 5 M positions in the first round (`cold_orbit`: 63 frames/s).  One collection is enough now.
-static void share_from_need(gs_ctx *ctx /* owner */, uint32_t need, uint32_t frames)
+// The lanes' need words are brought near what the collected frames measured (gs_share_lane_seed says which lanes and with what).
+static void seed_need_words(gs_ctx *ctx /* owner */, uint32_t need, bool idle_only)
 {
-    if (need) ctx->stats.need_splats = need;
-    if (!need || ctx->near_fixed_permille > 0 || !ctx->n) return;
-    // what the share follows: the largest need of the recent past -- sixteen buckets of at least sixteen frames each (a collection of
-    // queued frames is a bucket; synchronous frames, a collection each, share one) -- so that a pose which needs less does not take
-    // away what another pose of the same orbit needs: bench.py's orbit is 120 poses whose needs lie between 80 and 125 permille, and a
-    // caller may queue hundreds of frames, all drawn with ONE share, before it collects.  Up at once, down when the window has moved on.
-    const int HN = (int)(sizeof ctx->need_hist / sizeof ctx->need_hist[0]);
-    if (ctx->need_hist_frames[ctx->need_hist_pos] >= 16u) {
-        ctx->need_hist_pos = (ctx->need_hist_pos + 1) % HN;
-        ctx->need_hist[ctx->need_hist_pos] = 0; ctx->need_hist_frames[ctx->need_hist_pos] = 0;
-    }
-    if (need > ctx->need_hist[ctx->need_hist_pos]) ctx->need_hist[ctx->need_hist_pos] = need;
-    // (frames gs_sync is drawing AGAIN -- adapt_frozen -- measure, but are no new evidence of a camera at rest: they neither age the window
-    // nor shrink the margin that their own miss has just raised)
-    if (!ctx->adapt_frozen) ctx->need_hist_frames[ctx->need_hist_pos] += frames ? frames : 1u;
-    uint32_t m = 0;
-    for (int k = 0; k < HN; k++) if (ctx->need_hist[k] > m) m = ctx->need_hist[k];
-    float target = 1.0f;                                         // 0xFFFFFFFF: a tile that no share saturates (sky): one round over everything
-    if (m != 0xFFFFFFFFu) {
-        // the margin on top follows what the camera does: 1.15 to begin with, a hundredth less with every collection that nothing missed
-        // -- with every eight frames of a collection of queued frames: a caller that collects every 24 frames was at 1.10 after a whole
-        // lap of 120 new poses without a miss, i.e. had binned 6 % more than it came to need for all of it --
-        // (down to 1.04: a still or periodic camera needs none, and 10 % of share are 10 % of the binning and the blend's staging), a tenth
-        // more after a miss
-        if (ctx->need_margin < GS_NEED_MARGIN_MIN) ctx->need_margin = (float)GS_NEED_MARGIN;
-        const float less = ctx->adapt_frozen ? 0.0f : 0.01f * (float)(frames > 8u ? frames / 8u : 1u);
-        ctx->need_margin = ctx->need_margin - less < GS_NEED_MARGIN_MIN ? GS_NEED_MARGIN_MIN : ctx->need_margin - less;
-        target = (float)((double)m * (double)ctx->need_margin / (double)ctx->n);
-        if (target > 0.85f) target = 1.0f;                       // (two rounds over nearly everything cost more than one)
-    }
-    if (target >= 1.0f && ctx->last_kept) {
-        // One round over everything -- but "everything" is the V splats the sort KEEPS, and a cut-out or a strip may keep a few per cent
-        // of the N resident ones (the cut-out demo: 226 K of 6.3 M).  A share of 100 % sizes the round for N positions: grids, and row
-        // tables of N / 256 chunks per tile row that the row scan reads in full -- project 34 us instead of 24, binning 73 instead of 61.
-        // A share that covers V with a quarter to spare draws the same single round (nothing lies beyond it: no tile is flagged) on
-        // tables of that size; should V grow past it between two collections, the tiles that want more flag their frames like any
-        // other share that was too small.
-        const double cover = ((double)ctx->last_kept * 1.25 + 4096.0) / (double)ctx->n;
-        if (cover < 0.85) target = (float)cover;
-    }
-    if (target < ctx->near_floor) target = ctx->near_floor;      // (a walked share's floor, where there is one)
-    // (never fewer than 4096 positions: until round 6 never less than one permille -- 21 K positions of a 20 M scene, eight times what a
-    // frame sorted for its frustum needs there)
-    { const float fl = 4096.0f / (float)ctx->n; if (target < fl) target = fl > 1.0f ? 1.0f : fl; }
-    ctx->near_frac = target;
-    ctx->share_measured = true;
-}
-
-// a MISS under a measured share (round 1 skipped, a tile unsaturated; the frames are drawn again): the frames that missed needed more
-// than `frac_used`, how much more the frames drawn again will measure.  No floor -- the walk's "never again below 1.3 x the share that
-// failed" ratchets (1.3 x 92, then 1.3 x 120 = 156 permille over poses that need 80-115) where the measurement simply follows.
-static void share_missed(gs_ctx *ctx /* owner */, float frac_used)
-{
-    float nf = frac_used * 1.3f; if (nf > 1.0f) nf = 1.0f;
-    if (nf > ctx->near_frac) ctx->near_frac = nf;
-    if (ctx->need_margin < GS_NEED_MARGIN_MIN) ctx->need_margin = (float)GS_NEED_MARGIN;
-    ctx->need_margin = ctx->need_margin + 0.1f > 1.3f ? 1.3f : ctx->need_margin + 0.1f;
-    const uint32_t as_need = (uint32_t)((double)nf * (double)ctx->n / (double)ctx->need_margin);   // (the window remembers it like a measurement)
-    if (as_need > ctx->need_hist[ctx->need_hist_pos]) ctx->need_hist[ctx->need_hist_pos] = as_need;
-    ctx->clean_frames = 0; ctx->skip_hold = 32;
-}
-
-// Every lane's words are brought near what the collected frames measured: a lane whose words are far below it (a lane that has drawn
-// nothing yet -- its block is zero --, or nothing of this view) would have EVERY tile of its next frame issue its atomic: 8160 on one
-// line, ~90 us -- the first frame of five lanes after a run of synchronous frames, i.e. the fill of bench.py's twenty-frame region.
-static int seed_need_words(gs_ctx *ctx /* owner */, uint32_t need, bool idle_only = false)
-{
-    if (!need) return GS_OK;
-    const uint32_t seed = need == 0xFFFFFFFFu ? need : (uint32_t)((uint64_t)need * 9u / 10u);
+    if (!need) return;
     for (int i = 0; i < GS_MAX_LANES; i++) {
         gs_ctx *L = ctx->lanes[i];
         if (!L || !L->ctl) continue;
         // (from a synchronous frame: a lane with queued, uncollected frames keeps its words -- the seed its next projection would store is the
         // host's ESTIMATE, and the larger maxima the frames in flight recorded would be lost before gs_sync reads them: ADVICE r5)
         if (idle_only && L->async_pending) continue;
-        const uint32_t have = L->need_word_est;
-        const bool stale = need == 0xFFFFFFFFu ? have != 0xFFFFFFFFu : (have != 0xFFFFFFFFu && (uint64_t)have * 10u < (uint64_t)need * 8u);
-        if (!stale) continue;
-        L->need_seed_pending = seed ? seed : 1u;
-        L->need_word_est = seed;
+        gs_share_lane_seed(L->share_lane, need);
     }
-    return GS_OK;
 }
 
-static int collect_status(gs_ctx *lane, bool *overflowed, bool *share_failed = nullptr, uint32_t *spec_failed = nullptr, uint32_t *need_out = nullptr,
-                          uint32_t *frames_out = nullptr)
+// every lane's next frame clears its need words (with the owner's gs_share_reset_kind_switch / _unpin)
+static void reseed_lanes(gs_ctx *ctx /* owner */)
+{
+    for (int i = 0; i < GS_MAX_LANES; i++) if (ctx->lanes[i]) gs_share_lane_reseed(ctx->lanes[i]->share_lane);
+}
+
+// The share policy's step for a whole collection (after the lanes' collect_status): gs_share_decide once, then the seeds.
+static void decide_share(gs_ctx *ctx /* owner */, float frac_used, const GsShareTally &tally, bool idle_only)
+{
+    const uint32_t need = gs_share_decide(ctx->share, ctx->n, frac_used, tally);
+    if (need) ctx->stats.need_splats = need;
+    seed_need_words(ctx, need, idle_only);
+}
+
+// after a stream sync: publish the counters of the last completed frame, hand what they say about the share of splats binned first
+// to the policy (gs_share.h) and react to pair-buffer overflow
+static int collect_status(gs_ctx *lane, bool *overflowed, GsShareTally &tally, uint32_t *spec_failed)
 {
     gs_ctx *ctx = gs_root(lane);                                // the adaptive share is one state for all lanes ...
     const GsControl *c = lane->ctl_host;                        // ... fed by each lane's own counters
@@ -383,82 +302,22 @@ static int collect_status(gs_ctx *lane, bool *overflowed, bool *share_failed = n
     lane->stats.acc_frames = c->acc_frames; lane->stats.acc_sorted = c->acc_sorted; lane->stats.acc_visible = c->acc_visible;
     lane->stats.acc_pairs = c->acc_pairs; lane->stats.sort_records = c->n_sorted;
     lane->stats.sort_mode = c->near_sorted;
-    ctx->last_kept = c->n_kept;
     if (c->n_pairs_frame) { ctx->last_pairs = c->n_pairs_frame; ctx->last_visible = c->n_visible; }
     if (c->n_pairs_frame) __atomic_store_n(&ctx->run_hint, c->n_runs, __ATOMIC_RELAXED);
     if (c->n_pairs_frame) {                                     // sizing hint for the next frames' pair sort (any lane's worker may read it)
         const uint64_t h = (uint64_t)c->n_pairs_frame + c->n_pairs_frame / 4 + GS_CHUNK_L;
         __atomic_store_n(&ctx->pair_hint, h > 0xFFFFFFFFull ? 0u : (uint32_t)h, __ATOMIC_RELAXED);
     }
-    // Adapt the share of splats binned in round 0.  An "event" = a frame whose round 0 left tiles unsaturated (round 1
-    // re-binned for them): the share grows x1.5 and will never again shrink below 1.3 x the share that failed; without
-    // events it shrinks 10 % per collected frame until the first event, 2 % afterwards.  After 16 clean frames round 1 is not even launched (11 empty kernels
-    // cost ~50 us): blend<0> raises round1_missed if that was wrong, and the frame is completed / re-rendered.
-    uint32_t need = 0;
-    for (uint32_t k = 0; k < GS_NEED_WORDS; k++) if (c->need_near[k] > need) need = c->need_near[k];
-    if (need) {
-        // The words are not cleared but SEEDED with 0.9 x the maximum: a tile issues its atomic only when it needs more than the word it
-        // read when it started, so after a clear every tile of the first frames would -- 8160 atomics on one cache line serialise at
-        // ~11 ns each: the first six frames after every gs_sync took twice as long.  Seeded, only the tiles within 10 % of the maximum
-        // speak up; a need that falls is followed 10 % per collection (the word is then an upper bound), one that rises at once.
-        // 0xFFFFFFFF (a tile nothing saturates) is kept, and dropped once in sixteen seedings: the scene may have changed.
-        // (... every fourth collection of the lane: the host follows the maximum of the last eight collections anyway, and a queue entry
-        // per lane and gs_sync is 60 us of a twenty-frame region)
-        lane->need_word_est = need;                                // (what the lane's words hold now: their maximum)
-        if ((++lane->need_probe & 3u) == 0u) {
-            const uint32_t seed = need == 0xFFFFFFFFu ? ((lane->need_probe & 63u) ? 0xFFFFFFFFu : 0u) : (uint32_t)((uint64_t)need * 9u / 10u);
-            lane->need_seed_pending = seed ? seed : 1u;            // (written by the lane's next frame itself: GsFrameUniforms::need_seed)
-            lane->need_word_est = seed;
-        }
-    }
-    // (frames drawn from a truncated order measure nothing.  Frames gs_sync draws AGAIN do -- both rounds, every tile's need recorded, the
-    // sky's 0xFFFFFFFF included -- and what they measure is what the frames that missed had needed: the share is right after ONE miss.
-    // Ignored like the rest of their counters, a camera that left the cloud took eight collections x 24 redrawn frames to get to 100 %)
-    if (c->order_incomplete) need = 0;
-    if (need_out && need > *need_out) *need_out = need;
-    if (ctx->adapt_frozen || c->order_incomplete) {
-        // gs_sync is drawing flagged frames again (redraw_flagged_frames) with the uniforms they were queued with: their share has
-        // been dealt with once already -- every one of them would count as a new failure and multiply the share by 1.5.
-        // order_incomplete: the frames were drawn from an order that lacked splats (a stash overflowed, the speculative stash could
-        // not be vouched for): tiles that did not saturate say nothing about the SHARE -- the frames are drawn again from a whole
-        // sort either way.  (Counting them raised the share 23 -> 40 permille outside the cloud at 20 M, past the 1/32 the chunk
-        // stashes need: 3 718 -> 1 898 frames/s for good, after one overflow.)
-        lane->seen_unsat_events = c->unsat_events; lane->seen_acc_frames = c->acc_frames;
-    } else if (ctx->near_fixed_permille <= 0 && lane->stats.n_tiles) {
-        const uint32_t events = c->unsat_events - lane->seen_unsat_events;
-        const uint64_t frames = c->acc_frames >= lane->seen_acc_frames ? c->acc_frames - lane->seen_acc_frames : 1;
-        lane->seen_unsat_events = c->unsat_events; lane->seen_acc_frames = c->acc_frames;
-        if (frames_out) *frames_out += (uint32_t)(frames ? frames : 1);
-        if (lane->last_two_rounds) {
-            // An "event" -- round 0 left tiles unsaturated and round 1 finished them -- is a failure of a WALKED share; with the blend's
-            // measurement it is not: round 1 recorded what those tiles needed, and the share is set from that (share_from_need).  Counted as a
-            // failure it left a floor of 1.3 x a share that the measurement already covers (bench.py's region: need 111 K splats, the walk of
-            // the pre-roll's two-round frames ended at 1.3 x 120 = 156 permille where 1.15 x 106 = 122 do).  A MISS -- round 1 skipped and a
-            // tile unsaturated: the frame is drawn again -- is a failure either way.
-            // (need == 0xFFFFFFFF -- a tile no share saturates: sky -- is a measurement too: share_from_need goes to one round, or to the share that
-            // covers V, at once; counted as a failure it walked there x 1.3 per collection and came back with the margin at 1.3 and a hold: ADVICE r5)
-            if ((events && !need) || c->round1_missed) {
-                // the share proved too small: raised ONCE per collection by the caller (share_failed) -- the frames of all the lanes a
-                // gs_sync collects were drawn with the same share, and six lanes reporting the same failure used to multiply it by
-                // 1.5^6 and to leave the floor at 1.3 x 1.5^5 of the share that had really failed (a cold context ended up at 70 %)
-                if (share_failed) *share_failed = true;
-            } else {
-                ctx->clean_frames += (uint32_t)(frames ? frames : 1);
-                if (!need) {
-                    // no measurement (counting renders, the pixel-split blend: no need word recorded): the walk of rounds 1-4 -- fast descent (x0.9) until a share
-                    // has proved too small once, then a slow drift (x0.98) above the floor
-                    float nf = ctx->near_frac * (ctx->near_floor > 0.0f ? 0.98f : 0.9f);
-                    if (nf < ctx->near_floor) nf = ctx->near_floor; if (nf < 0.001f) nf = 0.001f;
-                    if (nf < ctx->near_frac) ctx->near_frac = nf;
-                }
-                const uint32_t fr = (uint32_t)(frames ? frames : 1);     // the hold is counted in frames, not in collections
-                ctx->skip_hold = ctx->skip_hold > fr ? ctx->skip_hold - fr : 0;
-            }
-            ctx->single_round_frames = 0;
-        } else if (!need && ctx->near_frac >= 1.0f && ++ctx->single_round_frames >= 64) {
-            ctx->near_frac = 0.5f; ctx->near_floor = 0.0f; ctx->single_round_frames = 0; ctx->clean_frames = 0;   // (unmeasured: re-probe occlusion now and then)
-        }
-    }
+    // The share of splats binned in round 0 (gs_share.h).  A frame whose round 0 left tiles unsaturated either had them finished by
+    // round 1 -- an "event": a failure of a share that is walked (no measurement: x 0.9 per collection, x 0.98 above the floor a
+    // failure leaves), nothing but a larger need where the blend measures -- or, round 1 skipped, was flagged (round1_missed) and is
+    // drawn again: a failure either way.  The lane's counters go in here; the collection's caller decides once for all its lanes.
+    GsShareObs obs;
+    obs.need = 0;
+    for (uint32_t k = 0; k < GS_NEED_WORDS; k++) if (c->need_near[k] > obs.need) obs.need = c->need_near[k];
+    obs.unsat_events = c->unsat_events; obs.acc_frames = c->acc_frames; obs.round1_missed = c->round1_missed;
+    obs.order_incomplete = c->order_incomplete; obs.n_kept = c->n_kept; obs.tiles = lane->stats.n_tiles != 0;
+    gs_share_observe(ctx->share, lane->share_lane, obs, tally);
     if (c->near_overflow) {
         // a chunk of a near-only sort had more survivors than its stash holds (the frame was flagged and is drawn again from a
         // whole sort): this context keeps to the whole-length passes from now on
@@ -480,8 +339,8 @@ static int collect_status(gs_ctx *lane, bool *overflowed, bool *share_failed = n
         else gs_spec_back_off(ctx, c->spec_fail == 2u);
         GS_HIP(hipMemsetAsync(&lane->ctl->spec_fail, 0, sizeof(uint32_t), lane->stream));
     }
-    lane->stats.unsat_tiles = lane->last_two_rounds ? c->unsat_round0 : 0;
-    lane->stats.near_permille = (uint32_t)(ctx->near_frac * 1000.0f + 0.5f);
+    lane->stats.unsat_tiles = lane->share_lane.last_two_rounds ? c->unsat_round0 : 0;
+    lane->stats.near_permille = (uint32_t)(ctx->share.near_frac * 1000.0f + 0.5f);
     *overflowed = c->overflow_sticky != 0;
     if (*overflowed) {
         const size_t need = (size_t)c->max_total + c->max_total / 4 + 1;
@@ -529,17 +388,6 @@ static int prof_advance(gs_ctx *ctx);
 // them (gs_sort.hip: an exact rule on the sort key; the positions it fills equal the whole order's).  The request is made when
 // the sort is issued, from the state the render's uniforms will be made from; a render that turns out to need more of the
 // order (another share, a counting render, round 1 after all, gs_download of the order) sorts again in full first.
-// May a frame leave its second binning round out (and its sort be near-only)?  After 16 clean frames -- but not while the share is
-// still on its fast way DOWN from the default (no floor yet): that descent ends with a share that is too small, and with round 1
-// still launched the frame that finds it is completed by round 1 (an "event") instead of being flagged and drawn again with
-// everything queued behind it.  (A scene that never fails ends at the minimum share: skippable from there.)
-static inline bool round1_skippable(const gs_ctx *ctx /* owner */)
-{
-    // (a MEASURED share -- share_from_need -- needs neither the failure that gives the walked share its floor nor sixteen frames of proof)
-    return ctx->near_fixed_permille <= 0 && ctx->clean_frames >= (ctx->share_measured ? 4u : 16u) && !ctx->skip_hold &&
-           (ctx->near_floor > 0.0f || ctx->near_frac <= 0.0011f || ctx->share_measured);
-}
-
 static uint32_t sort_near_request(const gs_ctx *ctx /* owner */)
 {
     if (!ctx->sort_near_opt || !ctx->renderable) return 0;
@@ -551,11 +399,12 @@ static uint32_t sort_near_request(const gs_ctx *ctx /* owner */)
     const bool tail = gs_msd_enabled() && ctx->n <= (size_t)GS_MSD_MAX_N && !ctx->wide_pairs;
     if (ctx->sort_near_opt == 1 && ctx->n < ((size_t)1 << 22) && !tail) return 0;
     if (ctx->wide_pairs || ctx->n > ((size_t)1 << 25)) return 0;
-    if (!round1_skippable(ctx) || ctx->near_frac >= 1.0f) return 0;
-    const double nc = ceil((double)ctx->near_frac * (double)ctx->n);
+    if (!gs_share_round1_skippable(ctx->share)) return 0;                // (skippable: the share is not pinned)
+    const uint32_t nc = gs_share_near_count(ctx->share, ctx->n);
+    if (nc == 0xFFFFFFFFu) return 0;
     // (a cutout or a strip that keeps little more than the frame reads anyway: the histogram and the threshold would buy nothing)
-    if (ctx->sort_near_opt == 1 && ctx->last_kept && nc * 2.0 > (double)ctx->last_kept) return 0;
-    return nc < 1 ? 1u : (uint32_t)nc;
+    if (ctx->sort_near_opt == 1 && ctx->share.last_kept && (double)nc * 2.0 > (double)ctx->share.last_kept) return 0;
+    return nc;
 }
 static inline bool sort_covers(uint32_t near_req, const GsFrameUniforms &u)
 {
@@ -844,7 +693,7 @@ static int set_profile(gs_ctx *ctx, bool on, bool blend_only, uint32_t every = 1
         ctx->stats.prof_frames = 0;
         ctx->stats.sum_ms_sort = ctx->stats.sum_ms_project = ctx->stats.sum_ms_bin = ctx->stats.sum_ms_blend = 0;
         GS_HIP(hipMemsetAsync(&ctx->ctl->acc_frames, 0, offsetof(GsControl, need_near) - offsetof(GsControl, acc_frames), ctx->stream));
-        ctx->seen_acc_frames = 0;
+        ctx->share_lane.seen_acc_frames = 0;
     }
     ctx->profile = on; ctx->profile_blend_only = on && blend_only; ctx->profile_every = on ? every : 1; ctx->profile_tick = 0;
     return GS_OK;
@@ -974,7 +823,7 @@ GS_API int gs_create(int device, gs_ctx **out)
     gs_ctx *ctx = new (std::nothrow) gs_ctx();
     if (!ctx) { snprintf(g_create_err, sizeof g_create_err, "out of host memory"); return GS_E_OOM; }
     memset(ctx, 0, sizeof *ctx);
-    ctx->device = device; ctx->renderable = true; ctx->t_eps = 1.0f / 1024.0f; ctx->near_frac = 0.25f;
+    ctx->device = device; ctx->renderable = true; ctx->t_eps = 1.0f / 1024.0f; gs_share_reset_create(ctx->share);
     ctx->lanes[0] = ctx; ctx->pipe_depth = 3; ctx->enqueue_threads = true; ctx->frame_batch = 1; ctx->exec = ctx; ctx->sort_near_opt = 1; ctx->auto_retry = true; ctx->subtile_opt = 1; ctx->row_walk_opt = 1;
     { const char *e = getenv("GS_SPEC_STASH"); ctx->near_spec_opt = !(e && e[0] == '0'); }   // (A/B: near-only sorts without the speculative stash)
 #define CREATE_HIP(call) do { hipError_t _e = (call); if (_e != hipSuccess) {                                              \
@@ -1014,7 +863,7 @@ GS_API int gs_clear(gs_ctx *ctx)
     GS_HIP(hipSetDevice(ctx->device));
     TRY(drain_all(ctx));
     ctx->n = 0; ctx->sh_n = 0; ctx->sh_deg = 0; ctx->renderable = true; ctx->pair_hint = 0; ctx->run_hint = 0; ctx->last_pairs = 0; ctx->last_visible = 0;
-    ctx->near_frac = 0.25f; ctx->near_floor = 0.0f; ctx->clean_frames = 0; ctx->skip_hold = 0; ctx->single_round_frames = 0; ctx->last_kept = 0; ctx->share_measured = false; ctx->need_margin = 0.0f; ctx->cold_sorts = 0; ctx->cold_frames = 0; ctx->share_kind = 0; memset(ctx->need_hist, 0, sizeof ctx->need_hist);
+    gs_share_reset_clear(ctx->share);
     ctx->near_stash_off = false; ctx->near_spec = false; ctx->near_spec_hold = 0; ctx->near_spec_backoff = 0; ctx->near_spec_miss_credit = 0;
     for (int i = 0; i < GS_MAX_LANES; i++) {
         gs_ctx *L = ctx->lanes[i];
@@ -1270,20 +1119,15 @@ static int sort_common(gs_ctx *ctx, const float view[4], const float *cutout16, 
         // drawn again by gs_sync until the share had crept up).
         const uint32_t kind = strip ? 2u : 1u;                      // (strips of one frame differ less from each other than any of them from the whole order:
                                                                     // a context that draws several strips in turn keeps one measurement, as before)
-        if (ctx->share_kind && ctx->share_kind != kind && ctx->near_fixed_permille <= 0) {
-            ctx->near_frac = 0.25f; ctx->near_floor = 0.0f; ctx->share_measured = false; ctx->need_margin = 0.0f; ctx->cold_sorts = 0; ctx->cold_frames = 0;
-            ctx->clean_frames = 0; ctx->skip_hold = 0;
-            memset(ctx->need_hist, 0, sizeof ctx->need_hist); memset(ctx->need_hist_frames, 0, sizeof ctx->need_hist_frames);
-            for (int i = 0; i < GS_MAX_LANES; i++) if (ctx->lanes[i]) { ctx->lanes[i]->need_seed_pending = 1u; ctx->lanes[i]->need_word_est = 0; }
-        }
-        ctx->share_kind = kind;
+        if (ctx->share.share_kind && ctx->share.share_kind != kind && ctx->share.near_fixed_permille <= 0) { gs_share_reset_kind_switch(ctx->share); reseed_lanes(ctx); }
+        ctx->share.share_kind = kind;
     }
     const uint32_t near_req = (out_idx || out_n) ? 0u : sort_near_request(ctx);     // (the caller wants the order itself: all of it)
     // (a context that has not measured its share yet draws its next frame synchronously -- gs_render_uniforms --: its sort on the caller's
     // thread then, not on an enqueue thread that was created a moment ago and has to be woken first: 0.14 ms of that call's 0.7)
     // (... at most two sorts in a row: a context whose frames never measure -- counting renders -- keeps its threads)
-    const bool cold = !ctx->share_measured && ctx->near_fixed_permille <= 0 && ctx->cold_sorts < 2u;   // (get_lane has drained the lane: nothing of it is waiting on its thread)
-    if (cold) ctx->cold_sorts++; else if (ctx->share_measured) { ctx->cold_sorts = 0; ctx->cold_frames = 0; }
+    const bool cold = !ctx->share.share_measured && ctx->share.near_fixed_permille <= 0 && ctx->share.cold_sorts < 2u;   // (get_lane has drained the lane: nothing of it is waiting on its thread)
+    if (cold) ctx->share.cold_sorts++; else if (ctx->share.share_measured) { ctx->share.cold_sorts = 0; ctx->share.cold_frames = 0; }
     if (ctx->enqueue_threads && gs_rotates(ctx) && !ctx->user_stream && !out_idx && !out_n && !cold) {
         // nothing to hand back: the lane's worker thread does the launching (a failure surfaces at gs_sync())
         GsLaneCmd c;
@@ -1452,13 +1296,11 @@ int gs_fill_uniforms(gs_ctx *ctx /* owner: options, adaptive share, scene */, co
     u.t_eps = ctx->t_eps; u.flags = p->flags; u.record_staged = ctx->record_staged; u.split_min = ctx->blend_split_min;
     u.mask_words = (uint32_t)(u.tiles_x + 31) / 32;
     // round 0 covers the nearest near_frac * N splats; counting / no-early-out renders need every fragment -> one round
-    const float frac = ctx->near_fixed_permille > 0 ? ctx->near_fixed_permille / 1000.0f : ctx->near_frac;
-    if ((p->flags & (GS_RENDER_COUNT_FRAGS | GS_RENDER_NO_EARLY_OUT)) || frac >= 1.0f) u.near_count = 0xFFFFFFFFu;
-    else { const double nc = ceil((double)frac * (double)ctx->n); u.near_count = nc < 1 ? 1u : (uint32_t)nc; }
+    u.near_count = (p->flags & (GS_RENDER_COUNT_FRAGS | GS_RENDER_NO_EARLY_OUT)) ? 0xFFFFFFFFu : gs_share_near_count(ctx->share, ctx->n);
     u.has_depth = ctx->scene_depth != nullptr; u.has_scene_rgba = ctx->scene_rgba != nullptr;
     if ((u.has_depth || u.has_scene_rgba) && (ctx->scene_w != p->fb_width || ctx->scene_h != p->fb_height))
         FAIL(GS_E_BADARG, "scene inputs are %dx%d but the frame is %dx%d", ctx->scene_w, ctx->scene_h, p->fb_width, p->fb_height);
-    u.skip_round1 = (u.near_count != 0xFFFFFFFFu && round1_skippable(ctx)) ? 1u : 0u;
+    u.skip_round1 = (u.near_count != 0xFFFFFFFFu && gs_share_round1_skippable(ctx->share)) ? 1u : 0u;
     // sub-tile lists in the blend (GS_OPT_SUBTILE): where the last collected frame's visible splats touched few tiles each
     static const double subtile_ratio = getenv("GS_SUBTILE_RATIO") ? atof(getenv("GS_SUBTILE_RATIO")) : 16.0;
     u.subtile = ctx->subtile_opt == 2 ? 1u : (ctx->subtile_opt == 1 && ctx->last_visible && (double)ctx->last_pairs < subtile_ratio * (double)ctx->last_visible ? 1u : 0u);
@@ -1500,7 +1342,7 @@ static int ensure_frame_buffers(gs_ctx *ctx, const GsFrameUniforms &u, bool need
     const size_t mask_total = (size_t)u.tiles_y * u.mask_words;
     if (mask_total > ctx->mask_cap) { dev_free(ctx->unsat_mask); TRY(dev_alloc(ctx, &ctx->unsat_mask, mask_total)); ctx->mask_cap = mask_total; }
     if (ntiles * 256 > ctx->state_cap) { dev_free(ctx->state); TRY(dev_alloc(ctx, &ctx->state, ntiles * 256)); ctx->state_cap = ntiles * 256; }
-    ctx->last_two_rounds = u.near_count != 0xFFFFFFFFu && ctx->n && ctx->have_sort;
+    ctx->share_lane.last_two_rounds = u.near_count != 0xFFFFFFFFu && ctx->n && ctx->have_sort;
     ctx->stats.n_tiles = ntiles; ctx->stats.blend_launches = 1;
     return GS_OK;
 }
@@ -1575,12 +1417,11 @@ static int render_sync_on_lane(gs_ctx *ctx, const GsFrameUniforms &u, void *devi
             GS_HIP(hipStreamSynchronize(ctx->stream));
             ctx->ctl_host->round1_missed = 1;                      // seen by the adaptation below
         }
-        bool over = false, failed = false;
-        uint32_t need = 0, nfr = 0;
-        const float frac_used = gs_root(ctx)->near_frac;
-        TRY(collect_status(ctx, &over, &failed, nullptr, &need, &nfr));
-        if (failed) { if (gs_root(ctx)->share_measured) share_missed(gs_root(ctx), frac_used); else share_raise(gs_root(ctx), frac_used); }
-        else { share_from_need(gs_root(ctx), need, nfr); TRY(seed_need_words(gs_root(ctx), need, true)); }
+        bool over = false;
+        GsShareTally tally{};
+        const float frac_used = gs_root(ctx)->share.near_frac;
+        TRY(collect_status(ctx, &over, tally, nullptr));
+        decide_share(gs_root(ctx), frac_used, tally, true);
         if (!over) break;
         if (attempt >= 2) FAIL(GS_E_OOM, "pair list keeps overflowing (%u pairs)", ctx->ctl_host->scan_total);
     }
@@ -1645,7 +1486,7 @@ int gs_render_uniforms(gs_ctx *ctx, const GsFrameUniforms &u_in, void *device_rg
     L->stats.sh_degree = u.sh_degree;
     L->stats.surface = u.surface ? 1u : 0u;
     L->stats.antialias = u.antialias ? 1u : 0u;
-    u.need_seed = L->need_seed_pending; L->need_seed_pending = 0;  // (a seed for the lane's need words travels with its next frame)
+    u.need_seed = L->share_lane.need_seed_pending; L->share_lane.need_seed_pending = 0;  // (a seed for the lane's need words travels with its next frame)
     bool async = (u.flags & GS_RENDER_ASYNC) && !(u.flags & GS_RENDER_COUNT_FRAGS);
     // A context that has not MEASURED its share yet (fresh, cleared, the share un-pinned) draws its first two-round frame synchronously
     // even when asked to queue it: the frames queued behind it then use the share it measured instead of the 25 % every context starts
@@ -1654,9 +1495,9 @@ int gs_render_uniforms(gs_ctx *ctx, const GsFrameUniforms &u_in, void *device_rg
     // (... at most two such frames in a row, like the cold sorts: a context whose blends never record a need -- counting renders, every tile
     // saturated by round 0 of a walked share -- would otherwise draw EVERY queued frame synchronously,
     // with a drain of every other lane each time: ADVICE r5)
-    if (async && !ctx->share_measured && ctx->near_fixed_permille <= 0 && u.near_count != 0xFFFFFFFFu && ctx->n && ctx->cold_frames < 2u) {
+    if (async && !ctx->share.share_measured && ctx->share.near_fixed_permille <= 0 && u.near_count != 0xFFFFFFFFu && ctx->n && ctx->share.cold_frames < 2u) {
         async = false; u.flags &= ~(uint32_t)GS_RENDER_ASYNC;
-        ctx->cold_frames++;
+        ctx->share.cold_frames++;
         // ... and the lanes that exist get their per-frame buffers for this frame's size now (tile ranges, per-pixel state, row tables:
         // a dozen allocations each), while nothing is in flight, instead of one lane per frame over the next five.  (BEFORE the frame's
         // kernels go out, not under them: allocations made while the device works take longer than the wait they would hide -- the
@@ -1851,7 +1692,7 @@ static int redraw_flagged_frames_impl(gs_ctx *ctx, const bool bad_unit[GS_MAX_PR
 static int redraw_flagged_frames(gs_ctx *ctx, const bool bad_unit[GS_MAX_PRIMARY])
 {
     // (the walk copies the log and keeps a set of outputs: out of host memory there, the caller draws the frames again itself)
-    try { return redraw_flagged_frames_impl(ctx, bad_unit); } catch (...) { ctx->adapt_frozen = false; return GS_E_RETRY; }
+    try { return redraw_flagged_frames_impl(ctx, bad_unit); } catch (...) { ctx->share.adapt_frozen = false; return GS_E_RETRY; }
 }
 static int redraw_flagged_frames_impl(gs_ctx *ctx, const bool bad_unit[GS_MAX_PRIMARY])
 {
@@ -1872,8 +1713,8 @@ static int redraw_flagged_frames_impl(gs_ctx *ctx, const bool bad_unit[GS_MAX_PR
         for (const GsFrameRec &r : L->log->recs) if (r.nrender && r.undecidable) return GS_E_RETRY;
     }
     uint32_t redrawn = 0;
-    struct Thaw { gs_ctx *c; ~Thaw() { c->adapt_frozen = false; } } thaw{ ctx };
-    ctx->adapt_frozen = true;
+    struct Thaw { gs_ctx *c; ~Thaw() { c->share.adapt_frozen = false; } } thaw{ ctx };
+    ctx->share.adapt_frozen = true;
     for (int i = 0; i < GS_MAX_LANES; i++) {
         gs_ctx *L = ctx->lanes[i];
         if (!L || !L->log || !bad_unit[i % GS_MAX_PRIMARY]) continue;
@@ -1909,9 +1750,10 @@ GS_API int gs_sync(gs_ctx *ctx)
 {
     CHECK_CTX(ctx);
     GS_HIP(hipSetDevice(ctx->device));
-    bool any_missed = false, any_over = false, share_failed = false;
-    uint32_t spec_failed = 0, need = 0, nfr = 0;
-    const float frac_used = ctx->near_frac;                       // what every frame queued since the last collection was drawn with
+    bool any_missed = false, any_over = false;
+    uint32_t spec_failed = 0;
+    GsShareTally tally{};
+    const float frac_used = ctx->share.near_frac;                       // what every frame queued since the last collection was drawn with
     // whatever way this call ends, the frames logged so far are not drawn again by a LATER gs_sync (their output buffers may be
     // gone by then): a failure below leaves no records behind
     struct LogGuard { gs_ctx *c; ~LogGuard() { for (int i = 0; i < GS_MAX_LANES; i++) if (c->lanes[i]) log_reset(c->lanes[i]); } } log_guard{ ctx };
@@ -1940,22 +1782,21 @@ GS_API int gs_sync(gs_ctx *ctx)
         L->async_pending = false;
         const bool missed = L->ctl_host->round1_missed != 0;
         static const bool dbg_near = getenv("GS_DEBUG_NEAR") != nullptr;       // (what raised the share: printed per collected lane)
-        if (dbg_near && (L->ctl_host->round1_missed || L->ctl_host->unsat_events != L->seen_unsat_events)) {
+        if (dbg_near && (L->ctl_host->round1_missed || L->ctl_host->unsat_events != L->share_lane.seen_unsat_events)) {
             const GsControl *c = L->ctl_host;
             fprintf(stderr, "[gs] sync lane %d: order_incomplete %u spec_fail %u (T %u chunk limit %u) near_overflow %u missed %u unsat_events %u (seen %u) V %u P %u V' %u near_sorted %u req %u frames %u two_rounds %d near_frac %.4f clean %u hold %u\n", i, c->order_incomplete, c->spec_fail, c->spec_dbg >> 16, c->spec_dbg & 0xFFFFu, c->near_overflow, c->round1_missed,
-                    c->unsat_events, L->seen_unsat_events, c->n_kept, c->n_sorted, c->n_valid, c->near_sorted, L->sort_near_req, c->acc_frames, (int)L->last_two_rounds,
-                    ctx->near_frac, ctx->clean_frames, ctx->skip_hold);
+                    c->unsat_events, L->share_lane.seen_unsat_events, c->n_kept, c->n_sorted, c->n_valid, c->near_sorted, L->sort_near_req, c->acc_frames, (int)L->share_lane.last_two_rounds,
+                    ctx->share.near_frac, ctx->share.clean_frames, ctx->share.skip_hold);
         }
         if (missed) LANE_HIP(L, hipMemsetAsync(&L->ctl->round1_missed, 0, sizeof(uint32_t), L->stream));
         if (L->ctl_host->order_incomplete) LANE_HIP(L, hipMemsetAsync(&L->ctl->order_incomplete, 0, sizeof(uint32_t), L->stream));
         bool over = false;
-        TRY(collect_status(L, &over, &share_failed, &spec_failed, &need, &nfr));
+        TRY(collect_status(L, &over, tally, &spec_failed));
         any_missed |= missed; any_over |= over;
         if (missed || over) bad_unit[i % GS_MAX_PRIMARY] = true;
         if (over && L->ctl_host->max_total > want) want = L->ctl_host->max_total;
     }
-    if (share_failed) { if (ctx->share_measured) share_missed(ctx, frac_used); else share_raise(ctx, frac_used); }   // (once, whatever the number of lanes that saw it)
-    else { share_from_need(ctx, need, nfr); TRY(seed_need_words(ctx, need)); }   // ... else what the collected frames' tiles needed (the maximum over the lanes)
+    decide_share(ctx, frac_used, tally, false);                  // (once, whatever the number of lanes that saw a failure)
     if (spec_failed) gs_spec_back_off(ctx, spec_failed == 2u);
     if (any_over)                                                // one retry for all lanes: each gets room for the largest demand seen
         for (int i = 0; i < GS_MAX_LANES; i++)
@@ -2051,12 +1892,11 @@ GS_API int gs_set_option(gs_ctx *ctx, int option, int64_t value)
         return GS_OK;
     case GS_OPT_NEAR_PERMILLE:
         if (value < 0 || value > 1000) FAIL(GS_E_BADARG, "near permille must be 0 (adaptive) .. 1000 (single round)");
-        ctx->near_fixed_permille = (int)value;
+        ctx->share.near_fixed_permille = (int)value;
         if (value == 0) {
             // adapt from scratch: the default share, nothing measured -- on the device too (each lane's next frame clears its need words:
             // a word that still says "a tile no share saturates" from frames long gone would keep the share at 100 % for 64 collections)
-            ctx->near_frac = 0.25f; ctx->share_measured = false; ctx->need_margin = 0.0f; ctx->cold_sorts = 0; ctx->cold_frames = 0; memset(ctx->need_hist, 0, sizeof ctx->need_hist);
-            for (int i = 0; i < GS_MAX_LANES; i++) if (ctx->lanes[i]) { ctx->lanes[i]->need_seed_pending = 1u; ctx->lanes[i]->need_word_est = 0; }
+            gs_share_reset_unpin(ctx->share); reseed_lanes(ctx);
         }
         return GS_OK;
     case GS_OPT_RECORD_STAGED: ctx->record_staged = value == 2 ? 2u : (value != 0 ? 1u : 0u); return GS_OK;
@@ -2162,7 +2002,7 @@ GS_API int gs_get_stats(gs_ctx *ctx, gs_stats *out)
     }
     s.n_splats = ctx->n;
     s.retried_frames = ctx->stats.retried_frames; s.spec_sorts = ctx->stats.spec_sorts; s.spec_misses = ctx->stats.spec_misses; s.need_splats = ctx->stats.need_splats;
-    s.near_permille = (uint32_t)(ctx->near_frac * 1000.0f + 0.5f);
+    s.near_permille = (uint32_t)(ctx->share.near_frac * 1000.0f + 0.5f);
     *out = s;
     return GS_OK;
 }

@@ -6,6 +6,7 @@
 #include <string.h>
 #include "../../include/gs_splat.h"
 #include "gs_device_math.h"
+#include "gs_share.h"
 
 // The kernels are written for gfx950 (CDNA4) and nothing else: wave64 ballots, packed-fp32 with op_sel, v_min_f64 / v_max_f64 and
 // s_waitcnt forms are written out as gfx9 inline assembly.  Another --offload-arch fails HERE, with a sentence, not in the assembler.
@@ -220,11 +221,6 @@ struct gs_ctx {
     bool no_tail_sort;             // lane: this sort's near-only form must hold AT MOST ~2 x near_req records (the shared sort's exchange buffer): the histogram form, not a tail sort
     uint32_t status_seq, status_base; // lane: renders handed to the lane so far (which word of the ring the next one gets) / its value when the first frame of the collection under way was queued
     uint32_t *status_cur;          // lane: the word of the render handed over last (gs_frame_status_device)
-    uint32_t cold_sorts;           // owner: sorts run on the caller's thread because the share had not been measured yet (at most two in a row)
-    uint32_t share_kind;           // owner: what kind of order the share was measured on -- 1: whole orders (gs_sort), 2: strips' orders (gs_sort_for);
-                                   // 0: nothing yet.  A sort of another kind starts the measurement afresh (positions of a strip's order are not positions of the whole)
-    uint32_t cold_frames;          // owner: queued frames drawn synchronously for the same reason (at most two in a row: a context whose frames
-                                   // never measure -- counting renders -- keeps its pipelining)
     float sv_view[4], sv_cutout[16]; bool sv_has_cutout, sv_has_strip; GsSortStrip sv_strip;
     int sort_near_opt;             // owner: GS_OPT_SORT_NEAR
     bool near_stash_off;           // owner: a chunk's stash overflowed once: near-only sorts keep to the two whole-length passes
@@ -235,7 +231,6 @@ struct gs_ctx {
                                    // passed through such a view gets the path back
     uint32_t near_spec_backoff, near_spec_miss_credit;
     int near_spec_opt;             // owner: 0 = never stash speculatively (GS_SPEC_STASH=0 in the environment: A/B)
-    uint32_t last_kept;            // owner: V of the last collected frame (a near-only sort pays only where V is well above the share read)
 
     // radix / scan scratch
     uint32_t *hist;  size_t hist_cap;       // digit-histogram rows H[radix chunks][bins], scanned in place
@@ -272,19 +267,8 @@ struct gs_ctx {
     int gviews, gw[2], gh[2];               // ... and what they hold
     float4 *state; size_t state_cap;        // per tile 64 lanes x 4 float4: (T, r, g, b) of each lane's 4 pixels, round 0 -> 1
     uint32_t *unsat_mask; size_t mask_cap;  // one bit per tile (rows of mask_words words): left unsaturated by round 0
-    float near_frac;                        // round 0 covers the nearest near_frac * N splats (adapted from unsat_round0)
-    int near_fixed_permille;                // > 0: fixed by GS_OPT_NEAR_PERMILLE instead of adapted
-    bool last_two_rounds;                   // the last enqueued frame ran the two-round path (its unsat count is meaningful)
-    float near_floor;                       // never shrink the share below this (1.3 x the share that last proved too small)
-    bool share_measured;                    // owner: near_frac comes from a measurement (GsControl::need_near) -- share_from_need, gs_api.hip
-    uint32_t need_probe;                    // lane: its collections with a measurement (every fourth re-seeds its words)
-    uint32_t need_word_est;                 // lane: what its need_near words hold at least (host-side estimate: seed_need_words)
-    uint32_t need_seed_pending;             // lane: the seed its next frame's projection writes into the words (GsFrameUniforms::need_seed; 0 = none)
-    float need_margin;                      // owner: the factor on top of the measured need (1.15 ... 1.04 while nothing misses, + 0.1 per miss)
-    uint32_t need_hist[16], need_hist_frames[16]; int need_hist_pos;   // owner: the needs of the last collections and the frames each covered (share_from_need)
-    uint32_t clean_frames, skip_hold;       // collected frames since the last unsaturated one / frames to keep round 1 on
-    uint32_t seen_unsat_events; uint64_t seen_acc_frames;
-    uint32_t single_round_frames;           // consecutive collected frames at near_frac == 1 (re-probe occlusion now and then)
+    GsShare share;                          // owner: the round-0 share policy's state (gs_share.h) ...
+    GsShareLane share_lane;                 // ... and every lane's own part of it
     // per-workgroup partial reductions (instead of same-address global atomics, which serialise at ~11 ns each)
     unsigned long long *part_min, *part_max;   // [GS_MAX_PART]
     uint32_t *part_cnt, *part_valid, *part_vis; // [GS_MAX_PART]
@@ -306,7 +290,6 @@ struct gs_ctx {
     GsFrameLog *log;               // lane: the frames handed to it since the last gs_sync (caller's thread only)
     bool auto_retry;               // owner: GS_OPT_AUTO_RETRY
     int sort_share_permille;       // owner: GS_OPT_SORT_SHARE (0 = every rank sorts every frame)
-    bool adapt_frozen;             // owner: gs_sync is drawing flagged frames again: their counters do not feed the adaptive share
     bool log_stale;                // owner: the resident data / scene changed under frames that are still in the logs
     int pend_lane;                 // owner: lane + 1 of the sort begun with gs_sort_begin and not yet collected by gs_sort_poll (0 = none; -1: begun before
                                    // any push: the reference's [0] reply is owed)
