@@ -31,6 +31,9 @@ TRANSPORT_RCCL, TRANSPORT_INPROC = 0, 1
 COMM_ID_BYTES = 128
 BUF_CENTER_SCALE, BUF_COV_COLOR, BUF_SORT_ROWS, BUF_SORTED, BUF_PROJECTED, BUF_TILE_COUNT, BUF_TILE_STATS, BUF_UNSAT_MASK = 0, 1, 2, 3, 4, 5, 6, 7
 BUF_SH = 8
+BUF_STATE = 9
+STATE_HIDDEN, STATE_SELECTED = 1, 2
+SELECT_INVERT = 1
 
 EXPORTS = [
     "gs_create", "gs_destroy", "gs_last_error", "gs_version", "gs_device_count", "gs_clear", "gs_push_splat", "gs_push_matrices", "gs_load_ply",
@@ -46,6 +49,8 @@ EXPORTS = [
     "gs_ply_sh", "gs_ply_sh_host", "gs_push_sh", "gs_sh_count", "gs_sh_eval", "gs_sh_eval_unrounded", "gs_camera_in_object", "gs_multi_push_sh",
     "gs_render_surface", "gs_render_surface_device", "gs_pick",
     "gs_antialias_factor",
+    "gs_set_state", "gs_set_state_ids", "gs_state_count", "gs_select_box", "gs_select_sphere", "gs_select_rect", "gs_compact",
+    "gs_multi_set_state", "gs_multi_set_state_ids", "gs_multi_select_box", "gs_multi_select_sphere", "gs_multi_select_rect", "gs_multi_compact",
 ]
 SURFACE_NONE = 0xFFFFFFFF          # gs_surface.id / gs_hit.id where the transmittance never falls below one half
 
@@ -68,7 +73,7 @@ class Stats(C.Structure):
                 ("acc_pairs", C.c_uint64), ("unsat_tiles", C.c_uint32), ("near_permille", C.c_uint32),
                 ("sort_records", C.c_uint32), ("retried_frames", C.c_uint32), ("spec_sorts", C.c_uint32), ("spec_misses", C.c_uint32), ("need_splats", C.c_uint32),
                 ("sort_mode", C.c_uint32), ("subtile", C.c_uint32), ("row_walk", C.c_uint32),
-                ("binning", C.c_uint32), ("sh_degree", C.c_uint32), ("surface", C.c_uint32), ("antialias", C.c_uint32)]
+                ("binning", C.c_uint32), ("sh_degree", C.c_uint32), ("n_hidden", C.c_uint32), ("surface", C.c_uint32), ("antialias", C.c_uint32)]
 
     def as_dict(self):
         return {n: getattr(self, n) for n, _ in self._fields_}
@@ -197,6 +202,16 @@ def load(build_if_missing=True):
         L.gs_pick.argtypes = [vp, C.POINTER(RenderParams), vp, sz, vp]
     if hasattr(L, "gs_antialias_factor"):
         L.gs_antialias_factor.argtypes = [vp, vp]
+    if hasattr(L, "gs_set_state"):                             # (an older build loaded through GS_SPLAT_LIB for an A/B run has none)
+        u8, szp = C.c_uint8, C.POINTER(sz)
+        for pre in ("gs_", "gs_multi_"):
+            getattr(L, pre + "set_state").argtypes = [vp, sz, vp, sz]
+            getattr(L, pre + "set_state_ids").argtypes = [vp, vp, sz, u8, u8]
+            getattr(L, pre + "select_box").argtypes = [vp, vp, u8, u8, C.c_uint32, szp]
+            getattr(L, pre + "select_sphere").argtypes = [vp, vp, f32, u8, u8, C.c_uint32, szp]
+            getattr(L, pre + "select_rect").argtypes = [vp, C.POINTER(RenderParams), vp, u8, u8, C.c_uint32, szp]
+            getattr(L, pre + "compact").argtypes = [vp, vp, szp]
+        L.gs_state_count.argtypes = [vp, szp, szp]
     L.gs_download.argtypes = [vp, i32, vp, sz]
     L.gs_comm_unique_id.argtypes = [vp, vp]
     L.gs_comm_init.argtypes = [vp, vp, i32, i32]
@@ -475,6 +490,51 @@ class Context:
     def count(self):
         return self._L.gs_count(self._h)
 
+    # editing the resident cloud: per-splat state bytes (STATE_HIDDEN leaves every sort), region selection, deletion
+    def set_state(self, first, states):
+        st = np.ascontiguousarray(states, np.uint8).reshape(-1)
+        self._ck(self._L.gs_set_state(self._h, int(first), _p(st), st.size))
+
+    def set_state_ids(self, ids, set_bits=0, clear_bits=0):
+        ids = np.ascontiguousarray(ids, np.uint32).reshape(-1)
+        self._ck(self._L.gs_set_state_ids(self._h, _p(ids), ids.size, int(set_bits), int(clear_bits)))
+
+    def select_box(self, box16, set_bits=0, clear_bits=0, flags=0):
+        """state = (state & ~clear_bits) | set_bits for the splats inside the cutout box (SELECT_INVERT: outside) -> how many"""
+        box = np.ascontiguousarray(box16, np.float32).reshape(16)
+        hit = C.c_size_t(0)
+        self._ck(self._L.gs_select_box(self._h, _p(box), int(set_bits), int(clear_bits), int(flags), C.byref(hit)))
+        return hit.value
+
+    def select_sphere(self, centre, radius, set_bits=0, clear_bits=0, flags=0):
+        c = np.ascontiguousarray(centre, np.float32).reshape(3)
+        hit = C.c_size_t(0)
+        self._ck(self._L.gs_select_sphere(self._h, _p(c), float(np.float32(radius)), int(set_bits), int(clear_bits), int(flags), C.byref(hit)))
+        return hit.value
+
+    def select_rect(self, params, rect, set_bits=0, clear_bits=0, flags=0):
+        """rect = (x0, y0, x1, y1) in pixels of the frame `params` describes, row 0 = top; among the splats of the last whole order"""
+        r = np.ascontiguousarray(rect, np.int32).reshape(4)
+        hit = C.c_size_t(0)
+        self._ck(self._L.gs_select_rect(self._h, C.byref(params), _p(r), int(set_bits), int(clear_bits), int(flags), C.byref(hit)))
+        return hit.value
+
+    def compact(self):
+        """gs_compact: delete the hidden splats -> uint32[count afterwards], the old index of every splat that stays"""
+        old = np.zeros(max(self.count(), 1), np.uint32)
+        n = C.c_size_t(0)
+        self._ck(self._L.gs_compact(self._h, _p(old), C.byref(n)))
+        return old[:n.value].copy()
+
+    def state_count(self):
+        """(rows in the state store, hidden splats among them)"""
+        rows, hidden = C.c_size_t(0), C.c_size_t(0)
+        self._ck(self._L.gs_state_count(self._h, C.byref(rows), C.byref(hidden)))
+        return rows.value, hidden.value
+
+    def download_state(self):
+        return self.download(BUF_STATE, self.state_count()[0], np.uint8, 1).reshape(-1)
+
     # sort
     def sort(self, view, cutout=None, want_indices=True):
         view = np.ascontiguousarray(view, np.float32)
@@ -735,6 +795,42 @@ class Multi:
 
     def count(self):
         return self._L.gs_multi_count(self._h)
+
+    # editing the resident cloud: per-splat state bytes (STATE_HIDDEN leaves every sort), region selection, deletion
+    def set_state(self, first, states):
+        st = np.ascontiguousarray(states, np.uint8).reshape(-1)
+        self._ck(self._L.gs_multi_set_state(self._h, int(first), _p(st), st.size))
+
+    def set_state_ids(self, ids, set_bits=0, clear_bits=0):
+        ids = np.ascontiguousarray(ids, np.uint32).reshape(-1)
+        self._ck(self._L.gs_multi_set_state_ids(self._h, _p(ids), ids.size, int(set_bits), int(clear_bits)))
+
+    def select_box(self, box16, set_bits=0, clear_bits=0, flags=0):
+        """state = (state & ~clear_bits) | set_bits for the splats inside the cutout box (SELECT_INVERT: outside) -> how many"""
+        box = np.ascontiguousarray(box16, np.float32).reshape(16)
+        hit = C.c_size_t(0)
+        self._ck(self._L.gs_multi_select_box(self._h, _p(box), int(set_bits), int(clear_bits), int(flags), C.byref(hit)))
+        return hit.value
+
+    def select_sphere(self, centre, radius, set_bits=0, clear_bits=0, flags=0):
+        c = np.ascontiguousarray(centre, np.float32).reshape(3)
+        hit = C.c_size_t(0)
+        self._ck(self._L.gs_multi_select_sphere(self._h, _p(c), float(np.float32(radius)), int(set_bits), int(clear_bits), int(flags), C.byref(hit)))
+        return hit.value
+
+    def select_rect(self, params, rect, set_bits=0, clear_bits=0, flags=0):
+        """rect = (x0, y0, x1, y1) in pixels of the frame `params` describes, row 0 = top; among the splats of the last whole order"""
+        r = np.ascontiguousarray(rect, np.int32).reshape(4)
+        hit = C.c_size_t(0)
+        self._ck(self._L.gs_multi_select_rect(self._h, C.byref(params), _p(r), int(set_bits), int(clear_bits), int(flags), C.byref(hit)))
+        return hit.value
+
+    def compact(self):
+        """gs_compact: delete the hidden splats -> uint32[count afterwards], the old index of every splat that stays"""
+        old = np.zeros(max(self.count(), 1), np.uint32)
+        n = C.c_size_t(0)
+        self._ck(self._L.gs_multi_compact(self._h, _p(old), C.byref(n)))
+        return old[:n.value].copy()
 
     def set_option(self, opt, value):
         self._ck(self._L.gs_multi_set_option(self._h, int(opt), int(value)))

@@ -173,6 +173,21 @@ static int ensure_lane_scratch(gs_ctx *ctx, size_t cap)
     return ensure_scan_scratch(ctx);
 }
 
+// the state store's allocation (owner): ctx->cap zero-filled bytes at least, the first edit_n of them kept
+static int edit_ensure_alloc(gs_ctx *ctx)
+{
+    const size_t want = ctx->cap ? ctx->cap : (size_t)1 << 16;
+    if (ctx->edit_state && ctx->edit_cap >= want) return GS_OK;
+    uint8_t *nw = nullptr;
+    TRY(dev_alloc(ctx, &nw, want));
+    hipError_t e = hipMemset(nw, 0, want);
+    if (e == hipSuccess && ctx->edit_state && ctx->edit_n) e = hipMemcpy(nw, ctx->edit_state, ctx->edit_n, hipMemcpyDeviceToDevice);
+    if (e != hipSuccess) { dev_free(nw); FAIL(GS_E_HIP, "growing the state store failed: %s", hipGetErrorString(e)); }
+    dev_free(ctx->edit_state);
+    ctx->edit_state = nw; ctx->edit_cap = want;
+    return GS_OK;
+}
+
 // grow the resident per-splat arrays (owner only) to hold at least `want` splats, preserving the data
 static int ensure_capacity(gs_ctx *ctx, size_t want)
 {
@@ -192,6 +207,7 @@ static int ensure_capacity(gs_ctx *ctx, size_t want)
     dev_free(ctx->splat); dev_free(ctx->sort_rows); dev_free(ctx->bound_r);
     ctx->splat = sp; ctx->sort_rows = sr; ctx->bound_r = br;
     ctx->cap = cap;
+    if (ctx->edit_state) TRY(edit_ensure_alloc(ctx));           // the state store's allocation follows the resident capacity
     for (int i = 0; i < GS_MAX_LANES; i++) if (ctx->lanes[i]) { ctx->lanes[i]->have_sort = false; ctx->lanes[i]->sorted = nullptr; }
     return ensure_lane_scratch(ctx, cap);                       // lane 0 now; the other lanes when they are next used
 }
@@ -302,6 +318,7 @@ static int collect_status(gs_ctx *lane, bool *overflowed, GsShareTally &tally, u
     lane->stats.acc_frames = c->acc_frames; lane->stats.acc_sorted = c->acc_sorted; lane->stats.acc_visible = c->acc_visible;
     lane->stats.acc_pairs = c->acc_pairs; lane->stats.sort_records = c->n_sorted;
     lane->stats.sort_mode = c->near_sorted;
+    lane->stats.n_hidden = lane->sort_hidden;
     if (c->n_pairs_frame) { ctx->last_pairs = c->n_pairs_frame; ctx->last_visible = c->n_visible; }
     if (c->n_pairs_frame) __atomic_store_n(&ctx->run_hint, c->n_runs, __ATOMIC_RELAXED);
     if (c->n_pairs_frame) {                                     // sizing hint for the next frames' pair sort (any lane's worker may read it)
@@ -851,6 +868,7 @@ GS_API int gs_destroy(gs_ctx *ctx)
         if (ctx->lanes[i]) { free_frame_resources(ctx->lanes[i]); delete ctx->lanes[i]; ctx->lanes[i] = nullptr; }
     free_frame_resources(ctx);
     dev_free(ctx->splat); dev_free(ctx->sort_rows); dev_free(ctx->bound_r); dev_free(ctx->pow10tab); dev_free(ctx->sh);
+    dev_free(ctx->edit_state); dev_free(ctx->edit_cnt);
     dev_free(ctx->scene_depth); dev_free(ctx->scene_rgba);
     if (ctx->ev_sort) (void)hipEventDestroy(ctx->ev_sort);
     delete ctx;
@@ -862,6 +880,8 @@ GS_API int gs_clear(gs_ctx *ctx)
     CHECK_CTX(ctx);
     GS_HIP(hipSetDevice(ctx->device));
     TRY(drain_all(ctx));
+    if (ctx->edit_state && ctx->edit_n) GS_HIP(hipMemset(ctx->edit_state, 0, ctx->edit_n));   // (the allocation stays, all zero: a store grows zero-filled)
+    ctx->edit_n = 0; ctx->edit_hidden = 0;
     ctx->n = 0; ctx->sh_n = 0; ctx->sh_deg = 0; ctx->renderable = true; ctx->pair_hint = 0; ctx->run_hint = 0; ctx->last_pairs = 0; ctx->last_visible = 0;
     gs_share_reset_clear(ctx->share);
     ctx->near_stash_off = false; ctx->near_spec = false; ctx->near_spec_hold = 0; ctx->near_spec_backoff = 0; ctx->near_spec_miss_credit = 0;
@@ -1147,7 +1167,7 @@ static int sort_common(gs_ctx *ctx, const float view[4], const float *cutout16, 
         LANE_HIP(L, hipMemcpyAsync(L->ctl_host, L->ctl, sizeof(GsControl), hipMemcpyDeviceToHost, L->stream));
         LANE_HIP(L, hipStreamSynchronize(L->stream));
         const uint32_t V = L->ctl_host->n_kept;
-        L->stats.n_sorted = V; L->sorted_n_host = V;
+        L->stats.n_sorted = V; L->sorted_n_host = V; L->stats.n_hidden = L->sort_hidden;
         if (out_n) *out_n = V;
         if (out_idx && V) GS_HIP(hipMemcpy(out_idx, L->sorted, (size_t)V * 4, hipMemcpyDeviceToHost));
     }
@@ -1212,7 +1232,7 @@ GS_API int gs_sort_poll(gs_ctx *ctx, int wait, uint32_t *out_idx, uint32_t *out_
         B = L;
     }
     const uint32_t V = B->ctl_host->n_kept;
-    B->have_sort = true; B->stats.n_sorted = V; B->sorted_n_host = V;
+    B->have_sort = true; B->stats.n_sorted = V; B->sorted_n_host = V; B->stats.n_hidden = B->sort_hidden;
     if (out_n) *out_n = V;
     if (out_idx && V) GS_HIP(hipMemcpy(out_idx, B->sorted, (size_t)V * 4, hipMemcpyDeviceToHost));
     // the new order is the one the draws use from here on (the reply handler, index.js:201-207)
@@ -1658,6 +1678,173 @@ GS_API int gs_pick(gs_ctx *ctx, const gs_render_params *p, const int32_t *xy, si
     return GS_OK;
 }
 
+// ---- editing the resident cloud (include/gs_splat.h; kernels: gs_edit.hip).  The state store is the owner's, like the SH store; a sort
+// is handed the pointer and the length when it is launched (gs_sort.hip: run_sort), so the lanes hold nothing.
+// Before a change: every lane idle (frames in flight read the store; drain_all marks logged frames stale), the allocation in place, and
+// the store grown to `rows` -- the bytes behind the old length are zero (the allocation is zero-filled, and whoever shortens the store
+// clears what it gives up).
+static int edit_begin(gs_ctx *ctx, size_t rows)
+{
+    GS_HIP(hipSetDevice(ctx->device));
+    TRY(drain_all(ctx));
+    TRY(edit_ensure_alloc(ctx));
+    if (rows > ctx->edit_n) ctx->edit_n = rows;
+    return GS_OK;
+}
+// after a change: the hidden count, and no lane's order survives (as after a push)
+static int edit_end(gs_ctx *ctx)
+{
+    for (int i = 0; i < GS_MAX_LANES; i++) if (ctx->lanes[i]) ctx->lanes[i]->have_sort = false;
+    if (ctx->pend_lane > 0) ctx->pend_n = (size_t)-1;            // a sort begun before the change is run again when it is collected
+    return gs_edit_count_hidden(ctx, ctx->edit_state, ctx->edit_n, &ctx->edit_hidden);
+}
+
+GS_API int gs_set_state(gs_ctx *ctx, size_t first, const uint8_t *states, size_t n)
+{
+    CHECK_CTX(ctx);
+    if (first > ctx->n || n > ctx->n - first) FAIL(GS_E_BADARG, "gs_set_state: states [%zu, %zu) of %zu splats", first, first + n, ctx->n);
+    if (n == 0) return GS_OK;
+    if (!states) FAIL(GS_E_BADARG, "gs_set_state: states is NULL");
+    TRY(edit_begin(ctx, first + n));
+    GS_HIP(hipMemcpy(ctx->edit_state + first, states, n, hipMemcpyHostToDevice));
+    return edit_end(ctx);
+}
+
+GS_API int gs_set_state_ids(gs_ctx *ctx, const uint32_t *ids, size_t n, uint8_t set_bits, uint8_t clear_bits)
+{
+    CHECK_CTX(ctx);
+    if (n == 0) return GS_OK;
+    if (!ids) FAIL(GS_E_BADARG, "gs_set_state_ids: ids is NULL");
+    for (size_t k = 0; k < n; k++) if (ids[k] >= ctx->n) FAIL(GS_E_BADARG, "gs_set_state_ids: id %u (entry %zu) of %zu splats", ids[k], k, ctx->n);
+    TRY(edit_begin(ctx, ctx->n));
+    uint32_t *dev = nullptr;
+    TRY(dev_alloc(ctx, &dev, n));
+    int rc = GS_OK;
+    const hipError_t e = hipMemcpy(dev, ids, n * sizeof(uint32_t), hipMemcpyHostToDevice);
+    if (e != hipSuccess) { snprintf(GS_ERRBUF(ctx), GS_ERRLEN, "upload failed: %s", hipGetErrorString(e)); rc = GS_E_HIP; }
+    if (rc == GS_OK) rc = gs_edit_apply_ids(ctx, dev, n, set_bits, clear_bits);
+    dev_free(dev);
+    const int rc2 = edit_end(ctx);
+    return rc != GS_OK ? rc : rc2;
+}
+
+GS_API int gs_state_count(const gs_ctx *ctx, size_t *rows, size_t *hidden)
+{
+    if (!ctx) return GS_E_BADARG;
+    if (rows) *rows = ctx->edit_n;
+    if (hidden) *hidden = ctx->edit_hidden;
+    return GS_OK;
+}
+
+GS_API int gs_select_box(gs_ctx *ctx, const float box16[16], uint8_t set_bits, uint8_t clear_bits, uint32_t flags, size_t *out_hit)
+{
+    CHECK_CTX(ctx);
+    if (!box16) FAIL(GS_E_BADARG, "gs_select_box: box16 is NULL");
+    if (flags & ~GS_SELECT_INVERT) FAIL(GS_E_BADARG, "gs_select_box: unknown flags %#x", flags);
+    if (out_hit) *out_hit = 0;
+    if (!ctx->n) return GS_OK;
+    TRY(edit_begin(ctx, ctx->n));
+    const int rc = gs_edit_select_box(ctx, box16, set_bits, clear_bits, (flags & GS_SELECT_INVERT) != 0, out_hit);
+    const int rc2 = edit_end(ctx);
+    return rc != GS_OK ? rc : rc2;
+}
+
+GS_API int gs_select_sphere(gs_ctx *ctx, const float centre[3], float radius, uint8_t set_bits, uint8_t clear_bits, uint32_t flags, size_t *out_hit)
+{
+    CHECK_CTX(ctx);
+    if (!centre) FAIL(GS_E_BADARG, "gs_select_sphere: centre is NULL");
+    if (flags & ~GS_SELECT_INVERT) FAIL(GS_E_BADARG, "gs_select_sphere: unknown flags %#x", flags);
+    if (!ctx->renderable && ctx->n) FAIL(GS_E_STATE, "context was fed worker matrices only (gs_push_matrices): no positions in the rows' space");
+    if (out_hit) *out_hit = 0;
+    if (!ctx->n) return GS_OK;
+    TRY(edit_begin(ctx, ctx->n));
+    const int rc = gs_edit_select_sphere(ctx, centre, radius, set_bits, clear_bits, (flags & GS_SELECT_INVERT) != 0, out_hit);
+    const int rc2 = edit_end(ctx);
+    return rc != GS_OK ? rc : rc2;
+}
+
+GS_API int gs_select_rect(gs_ctx *ctx, const gs_render_params *p, const int32_t rect[4], uint8_t set_bits, uint8_t clear_bits, uint32_t flags, size_t *out_hit)
+{
+    CHECK_CTX(ctx);
+    if (!p || !rect) FAIL(GS_E_BADARG, "gs_select_rect: NULL argument");
+    if (flags & ~GS_SELECT_INVERT) FAIL(GS_E_BADARG, "gs_select_rect: unknown flags %#x", flags);
+    if (!ctx->renderable && ctx->n) FAIL(GS_E_STATE, "context was fed worker matrices only (gs_push_matrices): it can sort but not project");
+    gs_render_params q = *p;
+    q.x0 = 0; q.x1 = p->fb_width;
+    GsFrameUniforms u;
+    TRY(gs_fill_uniforms(ctx, &q, u));
+    if (out_hit) *out_hit = 0;
+    GS_HIP(hipSetDevice(ctx->device));
+    TRY(drain_all(ctx));                                         // (the current frame's lane is idle and its have_sort is the worker's last word)
+    gs_ctx *L = ctx->lanes[ctx->cur];
+    if (!ctx->n || !L->have_sort || !L->sorted) FAIL(GS_E_STATE, "gs_select_rect: no completed sort to select from");
+    // the WHOLE order: a near-only or a strip sort is run again in full first (what gs_download(GS_BUF_SORTED) does for the former)
+    if (L->sort_near_req || L->sv_has_strip) TRY(lane_rc(ctx, L, gs_run_sort(L, L->sv_view, L->sv_has_cutout ? L->sv_cutout : nullptr, nullptr, 0)));
+    TRY(edit_begin(ctx, ctx->n));
+    const int rc = gs_edit_select_rect(ctx, L, u, rect, set_bits, clear_bits, (flags & GS_SELECT_INVERT) != 0, out_hit);
+    const int rc2 = edit_end(ctx);
+    return rc != GS_OK ? rc : rc2;
+}
+
+GS_API int gs_compact(gs_ctx *ctx, uint32_t *out_old_index, size_t *out_n)
+{
+    CHECK_CTX(ctx);
+    if (out_n) *out_n = ctx->n;
+    if (!ctx->edit_hidden) {                                     // nothing hidden: nothing to do
+        if (out_old_index) for (size_t k = 0; k < ctx->n; k++) out_old_index[k] = (uint32_t)k;
+        return GS_OK;
+    }
+    GS_HIP(hipSetDevice(ctx->device));
+    TRY(drain_all(ctx));
+    // fresh arrays of the same capacity (the resident bytes are held twice until the swap below)
+    const size_t sh_q = ctx->sh_n ? 3 * (size_t)gsm::sh_channel_stride(ctx->sh_deg) / 4 : 0;   // 16-byte words per SH row
+    GsCompactTo to = { nullptr, nullptr, nullptr, nullptr, nullptr, nullptr };
+    int rc = dev_alloc(ctx, &to.splat, ctx->cap * 2);
+    if (rc == GS_OK) rc = dev_alloc(ctx, &to.sort_rows, ctx->cap);
+    if (rc == GS_OK) rc = dev_alloc(ctx, &to.bound_r, ctx->cap);
+    if (rc == GS_OK) rc = dev_alloc(ctx, &to.state, ctx->edit_cap);
+    if (rc == GS_OK) rc = dev_alloc(ctx, &to.old_index, ctx->n);
+    if (rc == GS_OK && sh_q) rc = dev_alloc(ctx, &to.sh, ctx->sh_cap * sh_q * 4);
+    if (rc == GS_OK && hipMemset(to.state, 0, ctx->edit_cap) != hipSuccess) { snprintf(GS_ERRBUF(ctx), GS_ERRLEN, "gs_compact: clearing the new state store failed"); rc = GS_E_HIP; }
+    // how many of the splats that have an SH row are hidden (the store ends at or before gs_count(): bytes beyond it are state 0)
+    size_t sh_hidden = 0, kept = 0;
+    if (rc == GS_OK && sh_q) rc = gs_edit_count_hidden(ctx, ctx->edit_state, ctx->sh_n < ctx->edit_n ? ctx->sh_n : ctx->edit_n, &sh_hidden);
+    if (rc == GS_OK) rc = gs_edit_compact(ctx, to, &kept);
+    if (rc == GS_OK && sh_q) rc = gs_edit_compact_sh(ctx, to, sh_q, ctx->sh_n - sh_hidden);
+    if (rc == GS_OK && kept != ctx->n - ctx->edit_hidden) { snprintf(GS_ERRBUF(ctx), GS_ERRLEN, "gs_compact: kept %zu splats, expected %zu", kept, ctx->n - ctx->edit_hidden); rc = GS_E_HIP; }
+    if (rc == GS_OK && out_old_index && kept && hipMemcpy(out_old_index, to.old_index, kept * sizeof(uint32_t), hipMemcpyDeviceToHost) != hipSuccess) {
+        snprintf(GS_ERRBUF(ctx), GS_ERRLEN, "gs_compact: download of the index map failed"); rc = GS_E_HIP;
+    }
+    if (rc != GS_OK) {
+        dev_free(to.splat); dev_free(to.sort_rows); dev_free(to.bound_r); dev_free(to.state); dev_free(to.old_index); dev_free(to.sh);
+        return rc;
+    }
+    dev_free(ctx->splat); dev_free(ctx->sort_rows); dev_free(ctx->bound_r); dev_free(ctx->edit_state); dev_free(to.old_index);
+    ctx->splat = to.splat; ctx->sort_rows = to.sort_rows; ctx->bound_r = to.bound_r; ctx->edit_state = to.state;
+    if (sh_q) { dev_free(ctx->sh); ctx->sh = to.sh; ctx->sh_n -= sh_hidden; }
+    ctx->edit_n -= ctx->edit_hidden; ctx->edit_hidden = 0;       // (every hidden splat lay inside the store; stable order: a prefix stays a prefix)
+    ctx->n = kept; ctx->stats.n_splats = kept;
+    if (!kept) { ctx->renderable = true; ctx->sh_n = 0; ctx->sh_deg = 0; }   // (an empty context, as after gs_clear)
+    // what gs_clear resets about shares and hints: they were measured on another cloud
+    ctx->pair_hint = 0; ctx->run_hint = 0; ctx->last_pairs = 0; ctx->last_visible = 0;
+    gs_share_reset_clear(ctx->share);
+    ctx->near_stash_off = false; ctx->near_spec = false; ctx->near_spec_hold = 0; ctx->near_spec_backoff = 0; ctx->near_spec_miss_credit = 0;
+    for (int i = 0; i < GS_MAX_LANES; i++) {
+        gs_ctx *L = ctx->lanes[i];
+        if (!L) continue;
+        L->have_sort = false; L->sorted = nullptr;
+        memset(&L->stats, 0, sizeof L->stats);
+    }
+    ctx->stats.n_splats = kept;
+    refresh_lanes(ctx);
+    ctx->cur = 0; ctx->rot = 0; ctx->cur_async = false;
+    // a sort posted before the call: run again over the kept splats when it is collected (as after any other edit); nothing kept: the
+    // empty context's reply [0] is owed (index.js:588-590)
+    if (ctx->pend_lane > 0) { if (kept) ctx->pend_n = (size_t)-1; else ctx->pend_lane = -1; }
+    if (out_n) *out_n = kept;
+    return GS_OK;
+}
+
 GS_API int gs_set_scene(gs_ctx *ctx, const float *depth, const uint8_t *rgba, int fb_width, int fb_height)
 {
     CHECK_CTX(ctx);
@@ -2022,6 +2209,11 @@ GS_API int gs_download(gs_ctx *ctx, int which, void *out, size_t nbytes)
         if (nbytes > ctx->n * 16 || nbytes % 16) FAIL(GS_E_BADARG, "buffer %d holds %zu bytes, %zu requested", which, ctx->n * 16, nbytes);
         if (nbytes) GS_HIP(hipMemcpy2D(out, 16, (const char *)ctx->splat + (which == GS_BUF_COV_COLOR ? 16 : 0), 32, 16, nbytes / 16,
                                         hipMemcpyDeviceToHost));
+        return GS_OK;
+    }
+    if (which == GS_BUF_STATE) {
+        if (nbytes > ctx->edit_n) FAIL(GS_E_BADARG, "buffer %d holds %zu bytes, %zu requested", which, ctx->edit_n, nbytes);
+        if (nbytes) GS_HIP(hipMemcpy(out, ctx->edit_state, nbytes, hipMemcpyDeviceToHost));
         return GS_OK;
     }
     if (which == GS_BUF_SH) {                                    // tight rows out of the padded store

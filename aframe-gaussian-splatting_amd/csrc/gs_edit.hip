@@ -1,0 +1,300 @@
+// gs_edit.hip -- editing the resident cloud (include/gs_splat.h: "editing the resident cloud"): the kernels behind the per-splat state
+// store -- counting, id lists, region selection (box, sphere, screen rectangle) -- and the stable compaction of gs_compact.
+//
+// None of this is a per-frame path: every kernel is one streaming pass over the rows (or over the order), its counts go to two device
+// words through one atomic per workgroup, and every launcher waits for its kernel and hands the count back on the host.  What a frame
+// pays for a state store is ONE byte load per splat in the depth pass (gs_sort.hip: the HID instantiations).
+#include "gs_internal.h"
+
+namespace {
+
+#define GS_EDIT_IPT 8u                                           // items per thread: consecutive ones (a thread's items keep their order)
+#define GS_EDIT_CHUNK (GS_EDIT_IPT * GS_BLOCK)                   // items per workgroup step
+#define GS_EDIT_GRID 2048u                                       // workgroups at most for the grid-strided kernels
+
+__device__ __forceinline__ uint32_t wave_sum(uint32_t v)
+{
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
+    return v;
+}
+// one atomic per workgroup: every thread calls it (barriers inside)
+__device__ __forceinline__ void block_count(uint32_t mine, uint32_t *__restrict__ out)
+{
+    __shared__ uint32_t s_w[GS_BLOCK / 64];
+    const uint32_t t = wave_sum(mine);
+    if ((threadIdx.x & 63) == 0) s_w[threadIdx.x >> 6] = t;
+    __syncthreads();
+    if (threadIdx.x == 0) { const uint32_t s = s_w[0] + s_w[1] + s_w[2] + s_w[3]; if (s) atomicAdd(out, s); }
+}
+// exclusive scan of one value per thread over the workgroup (256 threads), in thread order; total: the sum (every thread calls it)
+__device__ __forceinline__ uint32_t block_excl_scan(uint32_t v, uint32_t *s_w /* [GS_BLOCK / 64] */, uint32_t &total)
+{
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    uint32_t inc = v;
+    for (int d = 1; d < 64; d <<= 1) { const uint32_t t = __shfl_up(inc, d, 64); if (lane >= d) inc += t; }
+    __syncthreads();                                               // (s_w may still be read from the previous call)
+    if (lane == 63) s_w[w] = inc;
+    __syncthreads();
+    uint32_t base = 0;
+    for (int k = 0; k < w; k++) base += s_w[k];
+    total = s_w[0] + s_w[1] + s_w[2] + s_w[3];
+    return base + inc - v;
+}
+
+__global__ __launch_bounds__(GS_BLOCK) void k_edit_count_hidden(const uint8_t *__restrict__ state, uint32_t n, uint32_t *__restrict__ out)
+{
+    uint32_t c = 0;
+    for (uint32_t i = blockIdx.x * GS_BLOCK + threadIdx.x; i < n; i += gridDim.x * GS_BLOCK) c += state[i] & GS_STATE_HIDDEN;
+    block_count(c, out);
+}
+
+// (a duplicate id: both threads write the value the rule gives -- the rule is idempotent)
+__global__ __launch_bounds__(GS_BLOCK) void k_edit_apply_ids(uint8_t *__restrict__ state, uint32_t rows, const uint32_t *__restrict__ ids, uint32_t n,
+                                                             uint32_t set, uint32_t clear)
+{
+    for (uint32_t k = blockIdx.x * GS_BLOCK + threadIdx.x; k < n; k += gridDim.x * GS_BLOCK) {
+        const uint32_t id = ids[k];
+        if (id < rows) state[id] = (uint8_t)((state[id] & ~clear) | set);
+    }
+}
+
+struct BoxUniforms { double c[16]; int affine; };                 // widened on the host (exact), as gs_sort.hip's SortUniforms
+__global__ __launch_bounds__(GS_BLOCK) void k_edit_select_box(const float4 *__restrict__ rows, uint32_t n, BoxUniforms b, uint8_t *__restrict__ state,
+                                                              uint32_t set, uint32_t clear, uint32_t invert, uint32_t *__restrict__ hit)
+{
+    uint32_t c = 0;
+    for (uint32_t i = blockIdx.x * GS_BLOCK + threadIdx.x; i < n; i += gridDim.x * GS_BLOCK) {
+        const float4 m = rows[i];
+        // the depth pass' own test (index.js:526-545)
+        const bool inside = b.affine ? gsm::in_cutout_affine(b.c, m.x, m.y, m.z) : gsm::in_cutout(b.c, m.x, m.y, m.z);
+        if (inside != (invert != 0u)) { state[i] = (uint8_t)((state[i] & ~clear) | set); c++; }
+    }
+    block_count(c, hit);
+}
+
+__global__ __launch_bounds__(GS_BLOCK) void k_edit_select_sphere(const uint4 *__restrict__ splat, uint32_t n, double cx, double cy, double cz, double r2,
+                                                                 uint8_t *__restrict__ state, uint32_t set, uint32_t clear, uint32_t invert, uint32_t *__restrict__ hit)
+{
+    uint32_t c = 0;
+    for (uint32_t i = blockIdx.x * GS_BLOCK + threadIdx.x; i < n; i += gridDim.x * GS_BLOCK) {
+        const uint4 cs = splat[2 * (size_t)i];                       // the packed centre (x, y, -z): index.js:350-354
+        const double dx = (double)__uint_as_float(cs.x) - cx, dy = (double)__uint_as_float(cs.y) - cy, dz = (double)(-__uint_as_float(cs.z)) - cz;
+        const double d2 = (dx * dx + dy * dy) + dz * dz;             // (un-fused: the library is built with -ffp-contract=off)
+        const bool inside = d2 <= r2;                                // (NaN: outside)
+        if (inside != (invert != 0u)) { state[i] = (uint8_t)((state[i] & ~clear) | set); c++; }
+    }
+    block_count(c, hit);
+}
+
+struct RectUniforms { float mv[16], proj[16]; float focal, vw, vh; float x0, y0, x1, y1, hm1; };   // the rectangle clipped to the frame; hm1 = fb_height - 1
+__global__ __launch_bounds__(GS_BLOCK) void k_edit_select_rect(const uint32_t *__restrict__ sorted, const GsControl *__restrict__ ctl, uint32_t n,
+                                                               const uint4 *__restrict__ splat, RectUniforms u, uint8_t *__restrict__ state,
+                                                               uint32_t set, uint32_t clear, uint32_t invert, uint32_t *__restrict__ hit)
+{
+    const uint32_t V = ctl->n_kept < n ? ctl->n_kept : n;           // the whole order: V positions, every value an index below n
+    uint32_t c = 0;
+    for (uint32_t j = blockIdx.x * GS_BLOCK + threadIdx.x; j < V; j += gridDim.x * GS_BLOCK) {
+        const uint32_t idx = sorted[j];
+        if (idx >= n) continue;
+        const uint4 cs4 = splat[2 * (size_t)idx], cc4 = splat[2 * (size_t)idx + 1];
+        const float cs[4] = { __uint_as_float(cs4.x), __uint_as_float(cs4.y), __uint_as_float(cs4.z), __uint_as_float(cs4.w) };
+        const uint32_t cc[4] = { cc4.x, cc4.y, cc4.z, cc4.w };
+        gsm::Projected p; gsm::ProjExtra x;
+        bool inside = false;
+        if (gsm::project_splat(cs, cc, u.mv, u.proj, u.focal, u.vw, u.vh, p, x)) {   // what k_project calls, with the frame's uniforms
+            const float px = floorf(p.cx), py = u.hm1 - floorf(p.cy);   // GL rows (y up) -> image rows (top-down); NaN compares false
+            inside = px >= u.x0 && px < u.x1 && py >= u.y0 && py < u.y1;
+        }
+        if (inside != (invert != 0u)) { state[idx] = (uint8_t)((state[idx] & ~clear) | set); c++; }
+    }
+    block_count(c, hit);
+}
+
+// ---- gs_compact: flags -> offsets -> scatter.  A workgroup owns GS_EDIT_CHUNK consecutive splats, a thread GS_EDIT_IPT consecutive ones
+__device__ __forceinline__ bool edit_kept(const uint8_t *__restrict__ state, uint32_t rows, uint32_t i, uint32_t n)
+{
+    return i < n && !(i < rows && (state[i] & GS_STATE_HIDDEN));
+}
+__global__ __launch_bounds__(GS_BLOCK) void k_compact_count(const uint8_t *__restrict__ state, uint32_t rows, uint32_t n, uint32_t *__restrict__ blk)
+{
+    __shared__ uint32_t s_c;
+    if (threadIdx.x == 0) s_c = 0;
+    __syncthreads();
+    uint32_t c = 0;
+    const uint32_t i0 = blockIdx.x * GS_EDIT_CHUNK + threadIdx.x * GS_EDIT_IPT;
+    for (uint32_t j = 0; j < GS_EDIT_IPT; j++) c += edit_kept(state, rows, i0 + j, n) ? 1u : 0u;
+    c = wave_sum(c);
+    if ((threadIdx.x & 63) == 0 && c) atomicAdd(&s_c, c);
+    __syncthreads();
+    if (threadIdx.x == 0) blk[blockIdx.x] = s_c;
+}
+// one workgroup: blk[0, nblk) -> their exclusive sums in place, blk[nblk] = the total
+__global__ __launch_bounds__(GS_BLOCK) void k_compact_offsets(uint32_t *__restrict__ blk, uint32_t nblk)
+{
+    __shared__ uint32_t s_w[GS_BLOCK / 64];
+    uint32_t carry = 0;
+    for (uint32_t b0 = 0; b0 < nblk; b0 += GS_BLOCK) {
+        const uint32_t b = b0 + threadIdx.x;
+        const uint32_t v = b < nblk ? blk[b] : 0u;
+        uint32_t total;
+        const uint32_t ex = block_excl_scan(v, s_w, total);
+        if (b < nblk) blk[b] = carry + ex;
+        carry += total;
+    }
+    if (threadIdx.x == 0) blk[nblk] = carry;
+}
+__global__ __launch_bounds__(GS_BLOCK) void k_compact_scatter(const uint8_t *__restrict__ state, uint32_t rows, uint32_t n, const uint32_t *__restrict__ blk,
+                                                              const uint4 *__restrict__ splat, const float4 *__restrict__ sort_rows, const float *__restrict__ bound_r,
+                                                              uint32_t renderable, uint4 *__restrict__ o_splat, float4 *__restrict__ o_rows, float *__restrict__ o_bound,
+                                                              uint8_t *__restrict__ o_state, uint32_t *__restrict__ o_old)
+{
+    __shared__ uint32_t s_w[GS_BLOCK / 64];
+    const uint32_t i0 = blockIdx.x * GS_EDIT_CHUNK + threadIdx.x * GS_EDIT_IPT;
+    bool keep[GS_EDIT_IPT];
+    uint32_t c = 0;
+#pragma unroll
+    for (uint32_t j = 0; j < GS_EDIT_IPT; j++) { keep[j] = edit_kept(state, rows, i0 + j, n); c += keep[j] ? 1u : 0u; }
+    uint32_t total;
+    uint32_t k = blk[blockIdx.x] + block_excl_scan(c, s_w, total);  // the new index of this thread's first kept splat (k + kept < blk[nblk] <= n)
+#pragma unroll
+    for (uint32_t j = 0; j < GS_EDIT_IPT; j++) {
+        if (!keep[j]) continue;
+        const uint32_t i = i0 + j;
+        if (renderable) { o_splat[2 * (size_t)k] = splat[2 * (size_t)i]; o_splat[2 * (size_t)k + 1] = splat[2 * (size_t)i + 1]; }
+        o_rows[k] = sort_rows[i];
+        o_bound[k] = bound_r[i];
+        o_state[k] = i < rows ? state[i] : (uint8_t)0;               // (the hidden bit is clear: the splat was kept)
+        o_old[k] = i;
+        k++;
+    }
+}
+// the SH rows of the kept splats among those that have one: new row k < sh_kept is old row old[k] (a prefix stays a prefix: stable order)
+__global__ __launch_bounds__(GS_BLOCK) void k_compact_sh(const uint4 *__restrict__ sh, const uint32_t *__restrict__ old, uint32_t sh_kept, uint32_t sh_n, uint32_t row_q,
+                                                         uint4 *__restrict__ o_sh)
+{
+    const size_t words = (size_t)sh_kept * row_q;
+    for (size_t t = (size_t)blockIdx.x * GS_BLOCK + threadIdx.x; t < words; t += (size_t)gridDim.x * GS_BLOCK) {
+        const uint32_t k = (uint32_t)(t / row_q), q = (uint32_t)(t % row_q);
+        const uint32_t i = old[k];
+        if (i < sh_n) o_sh[t] = sh[(size_t)i * row_q + q];
+    }
+}
+
+uint32_t stream_grid(size_t n)
+{
+    const uint32_t g = gs_div_up(n ? n : 1, GS_BLOCK);
+    return g > GS_EDIT_GRID ? GS_EDIT_GRID : g;
+}
+
+int counters(gs_ctx *ctx)
+{
+    if (!ctx->edit_cnt) GS_HIP(hipMalloc((void **)&ctx->edit_cnt, 2 * sizeof(uint32_t)));
+    GS_HIP(hipMemsetAsync(ctx->edit_cnt, 0, 2 * sizeof(uint32_t), ctx->stream));
+    return GS_OK;
+}
+int read_counter(gs_ctx *ctx, size_t *out)
+{
+    uint32_t v = 0;
+    GS_HIP(hipGetLastError());
+    GS_HIP(hipMemcpyAsync(&v, ctx->edit_cnt, sizeof v, hipMemcpyDeviceToHost, ctx->stream));
+    GS_HIP(hipStreamSynchronize(ctx->stream));
+    if (out) *out = v;
+    return GS_OK;
+}
+
+}  // namespace
+
+int gs_edit_count_hidden(gs_ctx *ctx, const uint8_t *state, size_t n, size_t *out)
+{
+    *out = 0;
+    if (!n) return GS_OK;
+    int rc = counters(ctx);
+    if (rc != GS_OK) return rc;
+    hipLaunchKernelGGL(k_edit_count_hidden, dim3(stream_grid(n)), dim3(GS_BLOCK), 0, ctx->stream, state, (uint32_t)n, ctx->edit_cnt);
+    return read_counter(ctx, out);
+}
+
+int gs_edit_apply_ids(gs_ctx *ctx, const uint32_t *ids_dev, size_t n, uint8_t set, uint8_t clear)
+{
+    if (!n) return GS_OK;
+    hipLaunchKernelGGL(k_edit_apply_ids, dim3(stream_grid(n)), dim3(GS_BLOCK), 0, ctx->stream, ctx->edit_state, (uint32_t)ctx->edit_n, ids_dev, (uint32_t)n,
+                       (uint32_t)set, (uint32_t)clear);
+    GS_HIP(hipGetLastError());
+    GS_HIP(hipStreamSynchronize(ctx->stream));
+    return GS_OK;
+}
+
+int gs_edit_select_box(gs_ctx *ctx, const float box16[16], uint8_t set, uint8_t clear, bool invert, size_t *hit)
+{
+    int rc = counters(ctx);
+    if (rc != GS_OK) return rc;
+    BoxUniforms b;
+    for (int i = 0; i < 16; i++) b.c[i] = (double)box16[i];
+    b.affine = (b.c[3] == 0.0 && b.c[7] == 0.0 && b.c[11] == 0.0 && b.c[15] == 1.0) ? 1 : 0;   // (gs_sort.hip: fill_sort_uniforms)
+    hipLaunchKernelGGL(k_edit_select_box, dim3(stream_grid(ctx->n)), dim3(GS_BLOCK), 0, ctx->stream, (const float4 *)ctx->sort_rows, (uint32_t)ctx->n, b,
+                       ctx->edit_state, (uint32_t)set, (uint32_t)clear, invert ? 1u : 0u, ctx->edit_cnt);
+    return read_counter(ctx, hit);
+}
+
+int gs_edit_select_sphere(gs_ctx *ctx, const float centre[3], float radius, uint8_t set, uint8_t clear, bool invert, size_t *hit)
+{
+    int rc = counters(ctx);
+    if (rc != GS_OK) return rc;
+    const double r2 = (double)radius * (double)radius;
+    hipLaunchKernelGGL(k_edit_select_sphere, dim3(stream_grid(ctx->n)), dim3(GS_BLOCK), 0, ctx->stream, (const uint4 *)ctx->splat, (uint32_t)ctx->n,
+                       (double)centre[0], (double)centre[1], (double)centre[2], r2, ctx->edit_state, (uint32_t)set, (uint32_t)clear, invert ? 1u : 0u, ctx->edit_cnt);
+    return read_counter(ctx, hit);
+}
+
+int gs_edit_select_rect(gs_ctx *ctx, gs_ctx *L, const GsFrameUniforms &f, const int32_t rect[4], uint8_t set, uint8_t clear, bool invert, size_t *hit)
+{
+    int rc = counters(ctx);
+    if (rc != GS_OK) return rc;
+    RectUniforms u;
+    memcpy(u.mv, f.mv, sizeof u.mv); memcpy(u.proj, f.proj, sizeof u.proj);
+    u.focal = f.focal; u.vw = f.vw; u.vh = f.vh;
+    const int32_t x0 = rect[0] > 0 ? rect[0] : 0, y0 = rect[1] > 0 ? rect[1] : 0;
+    const int32_t x1 = rect[2] < f.W ? rect[2] : f.W, y1 = rect[3] < f.H ? rect[3] : f.H;
+    u.x0 = (float)x0; u.y0 = (float)y0; u.x1 = (float)x1; u.y1 = (float)y1; u.hm1 = (float)(f.H - 1);
+    // (the lane's stream holds the order; the owner's stream is idle and the lanes were drained: one stream suffices)
+    GS_HIP(hipStreamSynchronize(ctx->stream));
+    hipLaunchKernelGGL(k_edit_select_rect, dim3(stream_grid(ctx->n)), dim3(GS_BLOCK), 0, L->stream, (const uint32_t *)L->sorted, (const GsControl *)L->ctl,
+                       (uint32_t)ctx->n, (const uint4 *)ctx->splat, u, ctx->edit_state, (uint32_t)set, (uint32_t)clear, invert ? 1u : 0u, ctx->edit_cnt);
+    GS_HIP(hipGetLastError());
+    GS_HIP(hipStreamSynchronize(L->stream));
+    return read_counter(ctx, hit);
+}
+
+int gs_edit_compact(gs_ctx *ctx, const GsCompactTo &to, size_t *kept)
+{
+    const uint32_t n = (uint32_t)ctx->n, rows = (uint32_t)ctx->edit_n;
+    const uint32_t nblk = gs_div_up(n, GS_EDIT_CHUNK);
+    uint32_t *blk = nullptr;
+    GS_HIP(hipMalloc((void **)&blk, ((size_t)nblk + 1) * sizeof(uint32_t)));
+    hipStream_t st = ctx->stream;
+    hipLaunchKernelGGL(k_compact_count, dim3(nblk), dim3(GS_BLOCK), 0, st, (const uint8_t *)ctx->edit_state, rows, n, blk);
+    hipLaunchKernelGGL(k_compact_offsets, dim3(1), dim3(GS_BLOCK), 0, st, blk, nblk);
+    hipLaunchKernelGGL(k_compact_scatter, dim3(nblk), dim3(GS_BLOCK), 0, st, (const uint8_t *)ctx->edit_state, rows, n, (const uint32_t *)blk,
+                       (const uint4 *)ctx->splat, (const float4 *)ctx->sort_rows, (const float *)ctx->bound_r, ctx->renderable ? 1u : 0u,
+                       to.splat, to.sort_rows, to.bound_r, to.state, to.old_index);
+    uint32_t total = 0;
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = hipMemcpyAsync(&total, blk + nblk, sizeof total, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    (void)hipFree(blk);
+    if (e != hipSuccess) { snprintf(GS_ERRBUF(ctx), GS_ERRLEN, "gs_compact failed: %s", hipGetErrorString(e)); return GS_E_HIP; }
+    *kept = total;
+    return GS_OK;
+}
+
+// (separate: the number of SH rows that stay is known on the host only after the scatter)
+int gs_edit_compact_sh(gs_ctx *ctx, const GsCompactTo &to, size_t sh_words, size_t sh_kept)
+{
+    if (!sh_kept || !to.sh) return GS_OK;
+    hipLaunchKernelGGL(k_compact_sh, dim3(stream_grid(sh_kept * sh_words)), dim3(GS_BLOCK), 0, ctx->stream, (const uint4 *)ctx->sh, (const uint32_t *)to.old_index,
+                       (uint32_t)sh_kept, (uint32_t)ctx->sh_n, (uint32_t)sh_words, reinterpret_cast<uint4 *>(to.sh));
+    GS_HIP(hipGetLastError());
+    GS_HIP(hipStreamSynchronize(ctx->stream));
+    return GS_OK;
+}

@@ -204,6 +204,12 @@ struct gs_ctx {
     // every channel padded to whole 16-byte words (gs_sh.h: sh_channel_stride)
     float *sh; size_t sh_n, sh_cap; int sh_deg;   // rows stored / rows allocated / their degree (0 while empty)
     int sh_opt;                    // GS_OPT_SH_DEGREE
+    // the state store (owner only; gs_set_state ..., gs_edit.hip): one byte per splat, parallel to the splats.  The allocation always holds
+    // `cap` bytes (the depth pass loads a byte with every row, index clamped to n - 1), of which the first edit_n are the store
+    uint8_t *edit_state; size_t edit_n, edit_cap;
+    size_t edit_hidden;            // bytes of the store with GS_STATE_HIDDEN (counted on the GPU by every call that changes the store)
+    uint32_t *edit_cnt;            // two device words the editing kernels count into
+    uint32_t sort_hidden;          // lane: edit_hidden when this lane's last sort ran (gs_stats::n_hidden)
     int aa_opt;                    // GS_OPT_ANTIALIAS (owner; taken per frame by gs_fill_uniforms)
 
     // sort scratch (sized by cap)
@@ -418,6 +424,21 @@ int gs_run_sort(gs_ctx *ctx, const float view[4], const float *cutout16, const G
 // what the lane's order was made from and how much of it exists (a render that needs more sorts again in full by itself)
 void gs_remember_sort(gs_ctx *L, const float view[4], const float *cutout16, const GsSortStrip *strip, uint32_t near_req);
 int gs_run_sort2(gs_ctx *const S[2], const float *const view[2], const float *const cutout16[2], const GsSortStrip *const strip[2], const uint32_t near_req[2]);   // the same sequence for two frames per launch
+// ---- gs_edit.hip (the state store's kernels; every call leaves the owner's stream idle and returns counts on the host)
+// bytes of state[0, n) with GS_STATE_HIDDEN
+int gs_edit_count_hidden(gs_ctx *ctx, const uint8_t *state, size_t n, size_t *out);
+// state[id] = (state[id] & ~clear) | set for n ids in device memory (all < the store's length)
+int gs_edit_apply_ids(gs_ctx *ctx, const uint32_t *ids_dev, size_t n, uint8_t set, uint8_t clear);
+// region rules over the owner's rows (the store already spans ctx->n); *hit = the splats the rule was applied to
+int gs_edit_select_box(gs_ctx *ctx, const float box16[16], uint8_t set, uint8_t clear, bool invert, size_t *hit);
+int gs_edit_select_sphere(gs_ctx *ctx, const float centre[3], float radius, uint8_t set, uint8_t clear, bool invert, size_t *hit);
+// ... and over the whole order lane L holds (its control block says how long it is), projected with the uniforms u
+int gs_edit_select_rect(gs_ctx *ctx, gs_ctx *L, const GsFrameUniforms &u, const int32_t rect[4], uint8_t set, uint8_t clear, bool invert, size_t *hit);
+// stable compaction of the owner's resident arrays into `to` (allocated by the caller for ctx->cap splats; sh may be null); *kept = splats written
+struct GsCompactTo { uint4 *splat; float4 *sort_rows; float *bound_r; uint8_t *state; float *sh; uint32_t *old_index; };
+int gs_edit_compact(gs_ctx *ctx, const GsCompactTo &to, size_t *kept);
+// ... and then the SH rows of the kept splats: new row k < sh_kept = old row to.old_index[k], sh_words 16-byte words each
+int gs_edit_compact_sh(gs_ctx *ctx, const GsCompactTo &to, size_t sh_words, size_t sh_kept);
 // ---- gs_render.hip
 int gs_run_render(gs_ctx *ctx, const GsFrameUniforms &u, uint8_t *device_out);
 int gs_run_round1(gs_ctx *ctx, const GsFrameUniforms &u, uint8_t *device_out);

@@ -216,6 +216,49 @@ GS_API int gs_multi_push_sh(gs_multi *m, const float *sh_rows, size_t nrows, int
     return run_all(m, [sh_rows, nrows, degree](gs_ctx *c, int) { return gs_push_sh(c, sh_rows, nrows, degree); });
 }
 
+// ---- editing (gs_splat.h): the call on every device; hit counts and the index map are device 0's
+GS_API int gs_multi_set_state(gs_multi *m, size_t first, const uint8_t *states, size_t n)
+{
+    if (!m) return GS_E_BADARG;
+    m->have_sort = false;
+    return run_all(m, [first, states, n](gs_ctx *c, int) { return gs_set_state(c, first, states, n); });
+}
+
+GS_API int gs_multi_set_state_ids(gs_multi *m, const uint32_t *ids, size_t n, uint8_t set_bits, uint8_t clear_bits)
+{
+    if (!m) return GS_E_BADARG;
+    m->have_sort = false;
+    return run_all(m, [ids, n, set_bits, clear_bits](gs_ctx *c, int) { return gs_set_state_ids(c, ids, n, set_bits, clear_bits); });
+}
+
+GS_API int gs_multi_select_box(gs_multi *m, const float box16[16], uint8_t set_bits, uint8_t clear_bits, uint32_t flags, size_t *out_hit)
+{
+    if (!m) return GS_E_BADARG;
+    m->have_sort = false;
+    return run_all(m, [=](gs_ctx *c, int i) { return gs_select_box(c, box16, set_bits, clear_bits, flags, i == 0 ? out_hit : nullptr); });
+}
+
+GS_API int gs_multi_select_sphere(gs_multi *m, const float centre[3], float radius, uint8_t set_bits, uint8_t clear_bits, uint32_t flags, size_t *out_hit)
+{
+    if (!m) return GS_E_BADARG;
+    m->have_sort = false;
+    return run_all(m, [=](gs_ctx *c, int i) { return gs_select_sphere(c, centre, radius, set_bits, clear_bits, flags, i == 0 ? out_hit : nullptr); });
+}
+
+GS_API int gs_multi_select_rect(gs_multi *m, const gs_render_params *p, const int32_t rect[4], uint8_t set_bits, uint8_t clear_bits, uint32_t flags, size_t *out_hit)
+{
+    if (!m) return GS_E_BADARG;
+    m->have_sort = false;
+    return run_all(m, [=](gs_ctx *c, int i) { return gs_select_rect(c, p, rect, set_bits, clear_bits, flags, i == 0 ? out_hit : nullptr); });
+}
+
+GS_API int gs_multi_compact(gs_multi *m, uint32_t *out_old_index, size_t *out_n)
+{
+    if (!m) return GS_E_BADARG;
+    m->have_sort = false;
+    return run_all(m, [=](gs_ctx *c, int i) { return gs_compact(c, i == 0 ? out_old_index : nullptr, i == 0 ? out_n : nullptr); });
+}
+
 GS_API size_t gs_multi_count(const gs_multi *m) { return (m && !m->f.empty()) ? gs_count(m->f[0]->ctx) : 0; }
 
 GS_API int gs_multi_set_option(gs_multi *m, int option, int64_t value)

@@ -17,6 +17,9 @@ struct SortUniforms {                                            // widened on t
     int has_strip;
 };
 // gs_sort_for: rows 0, 1, 2 of gsModelViewMatrix, rows 0, 3 of gsProjectionMatrix, and the strip in pixels
+// the per-splat state store (gs_set_state ...; gs_edit.hip): a splat whose byte has GS_STATE_HIDDEN counts as outside the cutout.  Read by the
+// HID instantiations only -- a context whose store is empty launches the others, which never look at it
+struct HiddenArgs { const uint8_t *state; uint32_t rows; };      // rows: the store's length (<= n; the allocation holds n bytes at least)
 struct StripUniforms { float mvr0[4], mvr1[4], mvr2[4], pr0[4], pr1[4], pr3[4]; float focal, norm_a, half_w, sx0, sx1, half_h, sy1; };   // (sy1 > 0: rows [0, sy1) tested too)
 // the depth kernel's chunking is its own (no histogram depends on it)
 #ifndef GS_DEPTH_IPT
@@ -162,11 +165,12 @@ __device__ __forceinline__ bool strip_may_touch(const StripUniforms &s, float x,
         __syncthreads();                                                                                                         \
     } while (0)
 
-template <bool STRIP, bool SPEC>                                  // (instantiations: the strip test / the stash must not cost the plain sort registers)
+template <bool STRIP, bool SPEC, bool HID = false>                // (instantiations: the strip test / the stash / the state bytes must not cost the plain sort registers)
 __device__ __forceinline__ void k_sort_depth_body(const float4 *__restrict__ rows, const float *__restrict__ bound_r, uint32_t n, const SortUniforms &u, const StripUniforms &su,
                                                   float *__restrict__ depth_out, unsigned long long *__restrict__ part_min,
                                                   unsigned long long *__restrict__ part_max, uint32_t *__restrict__ part_cnt, DepthHist dh,
-                                                  uint2 *__restrict__ spec_stash, uint32_t *__restrict__ spec_cnt, const uint32_t *__restrict__ bin_hint, GsControl *ctl)
+                                                  uint2 *__restrict__ spec_stash, uint32_t *__restrict__ spec_cnt, const uint32_t *__restrict__ bin_hint, GsControl *ctl,
+                                                  HiddenArgs hid = HiddenArgs{ nullptr, 0u })
 {
     __shared__ unsigned long long s_min, s_max;
     __shared__ uint32_t s_cnt;
@@ -188,6 +192,7 @@ __device__ __forceinline__ void k_sort_depth_body(const float4 *__restrict__ row
     for (uint32_t c = blockIdx.x; c < nchunks; c += gridDim.x) {
         float4 mm[GS_DEPTH_IPT];                                     // all loads first: their latencies overlap
         float sg[GS_DEPTH_IPT];
+        uint8_t hs[HID ? GS_DEPTH_IPT : 1];
 #pragma unroll
         for (int r = 0; r < GS_DEPTH_IPT; r++) {
             const uint32_t i = c * DCHUNK + r * GS_BLOCK + threadIdx.x;
@@ -196,6 +201,7 @@ __device__ __forceinline__ void k_sort_depth_body(const float4 *__restrict__ row
             const uint32_t ic = i < n ? i : n - 1u;
             mm[r] = rows[ic];
             sg[r] = STRIP ? bound_r[ic] : 0.0f;
+            if (HID) hs[r] = hid.state[ic];                              // (with the rows: same index, same clamp)
         }
         uint32_t fb[GS_DEPTH_IPT];
         bool sp[GS_DEPTH_IPT];
@@ -207,7 +213,8 @@ __device__ __forceinline__ void k_sort_depth_body(const float4 *__restrict__ row
             if (i < n) {
                 const float4 m = mm[r];
                 const double d = gsm::view_depth(u.view, m.x, m.y, m.z);
-                const bool inside = u.has_cutout ? (u.has_cutout == 2 ? gsm::in_cutout_affine(u.cutout, m.x, m.y, m.z) : gsm::in_cutout(u.cutout, m.x, m.y, m.z)) : true;
+                bool inside = u.has_cutout ? (u.has_cutout == 2 ? gsm::in_cutout_affine(u.cutout, m.x, m.y, m.z) : gsm::in_cutout(u.cutout, m.x, m.y, m.z)) : true;
+                if (HID && i < hid.rows && (hs[r] & GS_STATE_HIDDEN)) inside = false;   // a hidden splat is a splat outside the cutout (index.js:548)
                 const bool keep = gsm::sort_keep(d, m.w, inside);
                 // the bucket scale comes from EVERY splat the reference keeps (index.js:552-553), so a strip's order is the
                 // reference's order restricted to the strip's splats; only those are handed on
@@ -245,6 +252,16 @@ __global__ __launch_bounds__(GS_BLOCK) void k_sort_depth(const float4 *__restric
 {
     k_sort_depth_body<STRIP, SPEC>(rows, bound_r, n, u, su, depth_out, part_min, part_max, part_cnt, dh, spec_stash, spec_cnt, bin_hint, ctl);
 }
+// ... and with the state store (a kernel of its own: the one above keeps its argument list)
+template <bool STRIP, bool SPEC>
+__global__ __launch_bounds__(GS_BLOCK) void k_sort_depth_hid(const float4 *__restrict__ rows, const float *__restrict__ bound_r, uint32_t n, SortUniforms u, StripUniforms su,
+                                                             float *__restrict__ depth_out, unsigned long long *__restrict__ part_min,
+                                                             unsigned long long *__restrict__ part_max, uint32_t *__restrict__ part_cnt, DepthHist dh,
+                                                             uint2 *__restrict__ spec_stash, uint32_t *__restrict__ spec_cnt, const uint32_t *__restrict__ bin_hint, GsControl *ctl,
+                                                             HiddenArgs hid)
+{
+    k_sort_depth_body<STRIP, SPEC, true>(rows, bound_r, n, u, su, depth_out, part_min, part_max, part_cnt, dh, spec_stash, spec_cnt, bin_hint, ctl, hid);
+}
 
 // The same pass for the two frames of a pair (GS_OPT_FRAME_BATCH) in ONE sweep over the splats: at 20 M splats the sort rows are
 // 320 MB of the 400 MB this pass streams per frame, and both frames read the same rows -- one read, two view rows / cutout
@@ -254,13 +271,13 @@ struct SpecArgs { uint2 *stash; uint32_t *cnt; const uint32_t *bin_hint; GsContr
 #ifndef GS_DEPTH_PAIR_MIN_N
 #define GS_DEPTH_PAIR_MIN_N (1u << 22)   // paired sorts of fewer splats run k_sort_depth's body twice (run_sort<2>)
 #endif
-template <bool STRIP, bool SPEC>
-__global__ __launch_bounds__(GS_BLOCK) void k_sort_depth_pair(const float4 *__restrict__ rows, const float *__restrict__ bound_r, uint32_t n,
-                                                              SortUniforms u0, SortUniforms u1, StripUniforms su0, StripUniforms su1,
+template <bool STRIP, bool SPEC, bool HID>
+__device__ __forceinline__ void k_sort_depth_pair_body(const float4 *__restrict__ rows, const float *__restrict__ bound_r, uint32_t n,
+                                                              const SortUniforms &u0, const SortUniforms &u1, const StripUniforms &su0, const StripUniforms &su1,
                                                               float *__restrict__ depth0, float *__restrict__ depth1,
                                                               unsigned long long *__restrict__ pmin0, unsigned long long *__restrict__ pmax0, uint32_t *__restrict__ pcnt0,
                                                               unsigned long long *__restrict__ pmin1, unsigned long long *__restrict__ pmax1, uint32_t *__restrict__ pcnt1,
-                                                              DepthHist dh0, DepthHist dh1, SpecArgs sa0, SpecArgs sa1)
+                                                              DepthHist dh0, DepthHist dh1, SpecArgs sa0, SpecArgs sa1, HiddenArgs hid)
 {
     __shared__ unsigned long long s_min[2], s_max[2];
     __shared__ uint32_t s_cnt[2];
@@ -280,6 +297,7 @@ __global__ __launch_bounds__(GS_BLOCK) void k_sort_depth_pair(const float4 *__re
     for (uint32_t c = blockIdx.x; c < nchunks; c += gridDim.x) {
         float4 mm[GS_DEPTH_IPT];
         float sg[GS_DEPTH_IPT];
+        uint8_t hs[HID ? GS_DEPTH_IPT : 1];
 #pragma unroll
         for (int r = 0; r < GS_DEPTH_IPT; r++) {
             const uint32_t i = c * DCHUNK + r * GS_BLOCK + threadIdx.x;
@@ -288,6 +306,7 @@ __global__ __launch_bounds__(GS_BLOCK) void k_sort_depth_pair(const float4 *__re
             const uint32_t ic = i < n ? i : n - 1u;
             mm[r] = rows[ic];
             sg[r] = STRIP ? bound_r[ic] : 0.0f;
+            if (HID) hs[r] = hid.state[ic];                              // (with the rows: same index, same clamp)
         }
         uint32_t fb0[GS_DEPTH_IPT], fb1[GS_DEPTH_IPT];
         bool sp0[GS_DEPTH_IPT], sp1[GS_DEPTH_IPT];
@@ -298,9 +317,10 @@ __global__ __launch_bounds__(GS_BLOCK) void k_sort_depth_pair(const float4 *__re
             const uint32_t i = c * DCHUNK + r * GS_BLOCK + threadIdx.x;
             if (i < n) {
                 const float4 m = mm[r];
+                const bool shown = !(HID && i < hid.rows && (hs[r] & GS_STATE_HIDDEN));   // (one store for both frames)
 #define GS_DEPTH_ONE(U, SU, OUT, MN, MX, CNT, DH, SDH, FB, SP, LIM) do {                                                \
                     const double d = gsm::view_depth(U.view, m.x, m.y, m.z);                                               \
-                    const bool inside = U.has_cutout ? (U.has_cutout == 2 ? gsm::in_cutout_affine(U.cutout, m.x, m.y, m.z) : gsm::in_cutout(U.cutout, m.x, m.y, m.z)) : true; \
+                    const bool inside = shown && (U.has_cutout ? (U.has_cutout == 2 ? gsm::in_cutout_affine(U.cutout, m.x, m.y, m.z) : gsm::in_cutout(U.cutout, m.x, m.y, m.z)) : true); \
                     const bool keep = gsm::sort_keep(d, m.w, inside);                                                      \
                     const bool mine = keep && (!STRIP || strip_may_touch(SU, m.x, m.y, m.z, sg[r]));            \
                     if (!SPEC) OUT[i] = mine ? (float)d : INFINITY;                                                        \
@@ -334,6 +354,27 @@ __global__ __launch_bounds__(GS_BLOCK) void k_sort_depth_pair(const float4 *__re
         pmin1[blockIdx.x] = s_min[1]; pmax1[blockIdx.x] = s_max[1]; pcnt1[blockIdx.x] = s_cnt[1];
     }
     depth_hist_end(dh0, s_dh0); depth_hist_end(dh1, s_dh1);
+}
+template <bool STRIP, bool SPEC>
+__global__ __launch_bounds__(GS_BLOCK) void k_sort_depth_pair(const float4 *__restrict__ rows, const float *__restrict__ bound_r, uint32_t n,
+                                                              SortUniforms u0, SortUniforms u1, StripUniforms su0, StripUniforms su1,
+                                                              float *__restrict__ depth0, float *__restrict__ depth1,
+                                                              unsigned long long *__restrict__ pmin0, unsigned long long *__restrict__ pmax0, uint32_t *__restrict__ pcnt0,
+                                                              unsigned long long *__restrict__ pmin1, unsigned long long *__restrict__ pmax1, uint32_t *__restrict__ pcnt1,
+                                                              DepthHist dh0, DepthHist dh1, SpecArgs sa0, SpecArgs sa1)
+{
+    k_sort_depth_pair_body<STRIP, SPEC, false>(rows, bound_r, n, u0, u1, su0, su1, depth0, depth1, pmin0, pmax0, pcnt0, pmin1, pmax1, pcnt1, dh0, dh1, sa0, sa1, HiddenArgs{ nullptr, 0u });
+}
+// ... and with the state store (a kernel of its own, as k_sort_depth_hid: the one above keeps its argument list)
+template <bool STRIP, bool SPEC>
+__global__ __launch_bounds__(GS_BLOCK) void k_sort_depth_pair_hid(const float4 *__restrict__ rows, const float *__restrict__ bound_r, uint32_t n,
+                                                              SortUniforms u0, SortUniforms u1, StripUniforms su0, StripUniforms su1,
+                                                              float *__restrict__ depth0, float *__restrict__ depth1,
+                                                              unsigned long long *__restrict__ pmin0, unsigned long long *__restrict__ pmax0, uint32_t *__restrict__ pcnt0,
+                                                              unsigned long long *__restrict__ pmin1, unsigned long long *__restrict__ pmax1, uint32_t *__restrict__ pcnt1,
+                                                              DepthHist dh0, DepthHist dh1, SpecArgs sa0, SpecArgs sa1, HiddenArgs hid)
+{
+    k_sort_depth_pair_body<STRIP, SPEC, true>(rows, bound_r, n, u0, u1, su0, su1, depth0, depth1, pmin0, pmax0, pcnt0, pmin1, pmax1, pcnt1, dh0, dh1, sa0, sa1, hid);
 }
 
 // pass 2 (index.js:558-561): 16-bit bucket of the stored depth; culled -> GS_RADIX_SKIP, dropped bucket -> GS_CULLED_KEY.
@@ -848,6 +889,7 @@ template <int NW> GS_BODY(F_near_stash, (k_near_stash<NW>), (k_near_stash_body<N
 GS_BODY(F_near_gather, (k_near_gather), (k_near_gather_body));
 template <int NW, bool COMPACT, bool NEAR, bool MSD = false> GS_BODY(F_sort_bucket, (k_sort_bucket<NW, COMPACT, NEAR, MSD>), (k_sort_bucket_body<NW, COMPACT, NEAR, MSD>));
 template <bool STRIP, bool SPEC> GS_BODY(F_sort_depth, (k_sort_depth<STRIP, SPEC>), (k_sort_depth_body<STRIP, SPEC>));
+template <bool STRIP, bool SPEC> GS_BODY(F_sort_depth_hid, (k_sort_depth_hid<STRIP, SPEC>), (k_sort_depth_body<STRIP, SPEC, true>));
 
 }  // namespace
 
@@ -971,6 +1013,11 @@ static int run_sort(gs_ctx *const S[], const float *const view[], const float *c
     const bool stash = near && stash_ok;
     const bool spec = stash && spec_ok;
     uint32_t *const bin_hint = &gs_root(ctx)->ctl->near_bin_hint;
+    // the owner's state store (edits drain every lane first: nothing changes it under a sort).  Empty: the kernels of a context that never edits
+    const gs_ctx *const R = gs_root(ctx);
+    const HiddenArgs hid = { R->edit_n ? R->edit_state : nullptr, R->edit_n ? (uint32_t)R->edit_n : 0u };
+    const bool hidden = hid.rows != 0u;
+    for (int k = 0; k < NF; k++) S[k]->sort_hidden = hidden ? (uint32_t)R->edit_hidden : 0u;
 
     // ---- the depth pass: the ONE step whose forms for one frame and for a pair differ (everything behind it goes through gs_launch<NF>)
     if constexpr (NF == 1) {
@@ -978,8 +1025,14 @@ static int run_sort(gs_ctx *const S[], const float *const view[], const float *c
         const size_t dlds = near ? GS_DEPTH_BINS * sizeof(uint32_t) : 0u;
 #define GS_DEPTH1(ST, SP) hipLaunchKernelGGL((k_sort_depth<ST, SP>), dim3(gd), dim3(GS_BLOCK), dlds, st, ctx->sort_rows, ctx->bound_r, n, u[0], su[0], ctx->depth, \
                                              ctx->part_min, ctx->part_max, ctx->part_cnt, dh[0], ctx->kv_b, ctx->hist, (const uint32_t *)bin_hint, ctx->ctl)
-        if (spec) { if (strips) GS_DEPTH1(true, true); else GS_DEPTH1(false, true); }
+#define GS_DEPTH1H(ST, SP) hipLaunchKernelGGL((k_sort_depth_hid<ST, SP>), dim3(gd), dim3(GS_BLOCK), dlds, st, ctx->sort_rows, ctx->bound_r, n, u[0], su[0], ctx->depth, \
+                                              ctx->part_min, ctx->part_max, ctx->part_cnt, dh[0], ctx->kv_b, ctx->hist, (const uint32_t *)bin_hint, ctx->ctl, hid)
+        if (hidden) {
+            if (spec) { if (strips) GS_DEPTH1H(true, true); else GS_DEPTH1H(false, true); }
+            else { if (strips) GS_DEPTH1H(true, false); else GS_DEPTH1H(false, false); }
+        } else if (spec) { if (strips) GS_DEPTH1(true, true); else GS_DEPTH1(false, true); }
         else { if (strips) GS_DEPTH1(true, false); else GS_DEPTH1(false, false); }
+#undef GS_DEPTH1H
 #undef GS_DEPTH1
     } else {
         // ONE sweep computes both frames' depths: the rows are read once (the lanes of a context alias the owner's resident arrays)
@@ -994,18 +1047,29 @@ static int run_sort(gs_ctx *const S[], const float *const view[], const float *c
                 return gs_pack_make((const float4 *)S[k]->sort_rows, (const float *)S[k]->bound_r, n, u[k], su[k], S[k]->depth, S[k]->part_min, S[k]->part_max, S[k]->part_cnt,
                                     dh[k], (uint2 *)nullptr, (uint32_t *)nullptr, (const uint32_t *)bin_hint, S[k]->ctl);
             };
-            if (strips) gs_launch<2, F_sort_depth<true, false>, GS_BLOCK>(gd, st, 0, args); else gs_launch<2, F_sort_depth<false, false>, GS_BLOCK>(gd, st, 0, args);
+            const auto args_hid = [&](int k) {
+                return gs_pack_make((const float4 *)S[k]->sort_rows, (const float *)S[k]->bound_r, n, u[k], su[k], S[k]->depth, S[k]->part_min, S[k]->part_max, S[k]->part_cnt,
+                                    dh[k], (uint2 *)nullptr, (uint32_t *)nullptr, (const uint32_t *)bin_hint, S[k]->ctl, hid);
+            };
+            if (hidden) { if (strips) gs_launch<2, F_sort_depth_hid<true, false>, GS_BLOCK>(gd, st, 0, args_hid); else gs_launch<2, F_sort_depth_hid<false, false>, GS_BLOCK>(gd, st, 0, args_hid); }
+            else if (strips) gs_launch<2, F_sort_depth<true, false>, GS_BLOCK>(gd, st, 0, args); else gs_launch<2, F_sort_depth<false, false>, GS_BLOCK>(gd, st, 0, args);
         } else {
             // (c) a long or speculative pair: k_sort_depth_pair, LDS for two depth histograms when the sorts are near-only
             const size_t dlds = near ? 2u * GS_DEPTH_BINS * sizeof(uint32_t) : 0u;
             SpecArgs sa[2];
             for (int k = 0; k < 2; k++) { sa[k].stash = S[k]->kv_b; sa[k].cnt = S[k]->hist; sa[k].bin_hint = bin_hint; sa[k].ctl = S[k]->ctl; }
-#define GS_DEPTHP(ST, SP) hipLaunchKernelGGL((k_sort_depth_pair<ST, SP>), dim3(gd), dim3(GS_BLOCK), dlds, st, (const float4 *)S[0]->sort_rows, (const float *)S[0]->bound_r, n,  \
-                                             u[0], u[1], su[0], su[1], S[0]->depth, S[1]->depth, S[0]->part_min, S[0]->part_max, S[0]->part_cnt,             \
-                                             S[1]->part_min, S[1]->part_max, S[1]->part_cnt, dh[0], dh[1], sa[0], sa[1])
-            if (spec) { if (strips) GS_DEPTHP(true, true); else GS_DEPTHP(false, true); }
+#define GS_DEPTHP_ARGS (const float4 *)S[0]->sort_rows, (const float *)S[0]->bound_r, n, u[0], u[1], su[0], su[1], S[0]->depth, S[1]->depth, S[0]->part_min, S[0]->part_max, S[0]->part_cnt, \
+                      S[1]->part_min, S[1]->part_max, S[1]->part_cnt, dh[0], dh[1], sa[0], sa[1]
+#define GS_DEPTHP(ST, SP) hipLaunchKernelGGL((k_sort_depth_pair<ST, SP>), dim3(gd), dim3(GS_BLOCK), dlds, st, GS_DEPTHP_ARGS)
+#define GS_DEPTHPH(ST, SP) hipLaunchKernelGGL((k_sort_depth_pair_hid<ST, SP>), dim3(gd), dim3(GS_BLOCK), dlds, st, GS_DEPTHP_ARGS, hid)
+            if (hidden) {
+                if (spec) { if (strips) GS_DEPTHPH(true, true); else GS_DEPTHPH(false, true); }
+                else { if (strips) GS_DEPTHPH(true, false); else GS_DEPTHPH(false, false); }
+            } else if (spec) { if (strips) GS_DEPTHP(true, true); else GS_DEPTHP(false, true); }
             else { if (strips) GS_DEPTHP(true, false); else GS_DEPTHP(false, false); }
 #undef GS_DEPTHP
+#undef GS_DEPTHPH
+#undef GS_DEPTHP_ARGS
         }
     }
     // ---- end of the depth pass

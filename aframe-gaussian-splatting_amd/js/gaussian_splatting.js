@@ -239,6 +239,38 @@ class GaussianSplatting {
     return hit;
   }
 
+  // Editing the resident cloud (gs_splat.h: one state byte per splat; 1 = hidden, 2 = selected).  A hidden splat leaves every sort, so
+  // it is gone from the next tick's order on; the draws until then use the last completed order, as in the reference (index.js:201-207).
+  // ids are what pick().index and renderSurface().id hold.
+  hideSplats(ids) { return native.setStateIds(this.handle, ids instanceof Uint32Array ? ids : Uint32Array.from(ids), 1, 0); }
+  // (clears the hidden bit alone -- the selected bit and the caller's six stay: the all-zero affine matrix maps every position into
+  // the unit box, NaN positions included, so the box rule with clear = 1 reaches every splat)
+  showAll() { return native.selectBox(this.handle, [0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 1], 0, 1, 0); }
+  // entityOrMatrix: an entity / object3D whose unit box is the region (what cutoutEntity takes), or the 16 numbers of the
+  // object-to-unit-box matrix tick builds for it.  opts.hide: hide the splats instead of selecting them; opts.invert: those outside.
+  selectBox(entityOrMatrix, opts) {
+    const o = opts || {};
+    let box = entityOrMatrix;
+    if (box && (box.object3D || box.matrixWorld)) {
+      const obj = box.object3D || box;
+      box = native.tickUniforms(elementsOf(this.camera.matrixWorld), elementsOf(this.object.matrixWorld), elementsOf(obj.matrixWorld)).cutout;
+    }
+    return native.selectBox(this.handle, box, o.hide ? 1 : 2, 0, o.invert ? 1 : 0);
+  }
+  // pixels of the CURRENT frame's drawing buffer (the view of the last render / frame call), row 0 = top; among what that view draws
+  selectRect(x0, y0, x1, y1, opts) {
+    const v = this._lastView, o = opts || {};
+    if (!v) throw new Error('selectRect: no frame has been drawn yet');
+    return native.selectRect(this.handle, this._renderParams(v.camera, v.viewport, v.options), [x0, y0, x1, y1], o.hide ? 1 : 2, 0, o.invert ? 1 : 0);
+  }
+  // real deletion of the hidden splats (the GPU holds the cloud twice for the duration of the call) -> Uint32Array: the old index of
+  // every splat that stays
+  deleteHidden() {
+    const old = native.compact(this.handle);
+    this.loadedVertexCount = native.count(this.handle);
+    return old;
+  }
+
   _renderParams(camera, viewport, options) {
     this._lastView = { camera, viewport, options };
     const proj = this.getProjectionMatrix(camera).elements;

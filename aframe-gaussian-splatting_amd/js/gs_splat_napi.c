@@ -505,6 +505,131 @@ static napi_value fn_pick(napi_env env, napi_callback_info info)
     return arr;
 }
 
+/* ---- editing the resident cloud (gs_splat.h): states, region selection, deletion.  Bits: 1 = hidden, 2 = selected. */
+static int get_u32(napi_env env, napi_value v, uint32_t *out)
+{
+    if (is_nullish(env, v)) { *out = 0; return 1; }
+    return napi_get_value_uint32(env, v, out) == napi_ok;
+}
+static napi_value make_count(napi_env env, size_t n)
+{
+    napi_value r;
+    NAPI_OK(napi_create_double(env, (double)n, &r));
+    return r;
+}
+
+/* setState(h, first, Uint8Array states) */
+static napi_value fn_set_state(napi_env env, napi_callback_info info)
+{
+    napi_value argv[3];
+    if (!get_args(env, info, 3, argv, NULL)) return NULL;
+    gs_ctx *ctx = get_ctx(env, argv[0]); if (!ctx) return NULL;
+    double first = 0;
+    NAPI_OK(napi_get_value_double(env, argv[1], &first));
+    void *data; size_t len;
+    if (first < 0 || !get_bytes(env, argv[2], &data, &len)) { napi_throw_type_error(env, NULL, "setState: (handle, first, Uint8Array)"); return NULL; }
+    int rc = gs_set_state(ctx, (size_t)first, (const uint8_t *)data, len);
+    if (rc != GS_OK) return throw_gs(env, ctx, rc);
+    return make_count(env, len);
+}
+
+/* setStateIds(h, Uint32Array ids, setBits, clearBits) */
+static napi_value fn_set_state_ids(napi_env env, napi_callback_info info)
+{
+    napi_value argv[4];
+    if (!get_args(env, info, 4, argv, NULL)) return NULL;
+    gs_ctx *ctx = get_ctx(env, argv[0]); if (!ctx) return NULL;
+    bool is_ta = false;
+    napi_typedarray_type tt; size_t len = 0; void *data = NULL;
+    uint32_t set = 0, clear = 0;
+    if (napi_is_typedarray(env, argv[1], &is_ta) != napi_ok || !is_ta ||
+        napi_get_typedarray_info(env, argv[1], &tt, &len, &data, NULL, NULL) != napi_ok || tt != napi_uint32_array ||
+        !get_u32(env, argv[2], &set) || !get_u32(env, argv[3], &clear)) {
+        napi_throw_type_error(env, NULL, "setStateIds: (handle, Uint32Array ids, setBits, clearBits)");
+        return NULL;
+    }
+    int rc = gs_set_state_ids(ctx, (const uint32_t *)data, len, (uint8_t)set, (uint8_t)clear);
+    if (rc != GS_OK) return throw_gs(env, ctx, rc);
+    return make_count(env, len);
+}
+
+/* selectBox(h, box16, setBits, clearBits, flags) / selectSphere(h, centre3, radius, setBits, clearBits, flags) -> splats hit */
+static napi_value fn_select_box(napi_env env, napi_callback_info info)
+{
+    napi_value argv[5];
+    if (!get_args(env, info, 5, argv, NULL)) return NULL;
+    gs_ctx *ctx = get_ctx(env, argv[0]); if (!ctx) return NULL;
+    float box[16];
+    uint32_t set = 0, clear = 0, flags = 0;
+    if (!get_floats(env, argv[1], box, 16) || !get_u32(env, argv[2], &set) || !get_u32(env, argv[3], &clear) || !get_u32(env, argv[4], &flags)) {
+        napi_throw_type_error(env, NULL, "selectBox: (handle, box16, setBits, clearBits, flags)");
+        return NULL;
+    }
+    size_t hit = 0;
+    int rc = gs_select_box(ctx, box, (uint8_t)set, (uint8_t)clear, flags, &hit);
+    if (rc != GS_OK) return throw_gs(env, ctx, rc);
+    return make_count(env, hit);
+}
+static napi_value fn_select_sphere(napi_env env, napi_callback_info info)
+{
+    napi_value argv[6];
+    if (!get_args(env, info, 6, argv, NULL)) return NULL;
+    gs_ctx *ctx = get_ctx(env, argv[0]); if (!ctx) return NULL;
+    float c[3];
+    double radius = 0;
+    uint32_t set = 0, clear = 0, flags = 0;
+    if (!get_floats(env, argv[1], c, 3) || napi_get_value_double(env, argv[2], &radius) != napi_ok || !get_u32(env, argv[3], &set) ||
+        !get_u32(env, argv[4], &clear) || !get_u32(env, argv[5], &flags)) {
+        napi_throw_type_error(env, NULL, "selectSphere: (handle, centre3, radius, setBits, clearBits, flags)");
+        return NULL;
+    }
+    size_t hit = 0;
+    int rc = gs_select_sphere(ctx, c, (float)radius, (uint8_t)set, (uint8_t)clear, flags, &hit);
+    if (rc != GS_OK) return throw_gs(env, ctx, rc);
+    return make_count(env, hit);
+}
+
+/* selectRect(h, params, [x0, y0, x1, y1], setBits, clearBits, flags) -> positions of the order hit */
+static napi_value fn_select_rect(napi_env env, napi_callback_info info)
+{
+    napi_value argv[6];
+    if (!get_args(env, info, 6, argv, NULL)) return NULL;
+    gs_ctx *ctx = get_ctx(env, argv[0]); if (!ctx) return NULL;
+    gs_render_params p;
+    double r[4];
+    uint32_t set = 0, clear = 0, flags = 0;
+    if (!fill_params(env, argv[1], &p) || !get_doubles(env, argv[2], r, 4) || !get_u32(env, argv[3], &set) || !get_u32(env, argv[4], &clear) ||
+        !get_u32(env, argv[5], &flags)) {
+        napi_throw_type_error(env, NULL, "selectRect: (handle, params, [x0, y0, x1, y1], setBits, clearBits, flags)");
+        return NULL;
+    }
+    int32_t rect[4];
+    for (int k = 0; k < 4; k++) {                                 /* (a double that is NaN or outside int32 must not reach the cast) */
+        if (!(r[k] == r[k])) { napi_throw_range_error(env, NULL, "selectRect: the rectangle holds a NaN"); return NULL; }
+        rect[k] = r[k] <= -2147483648.0 ? INT32_MIN : (r[k] >= 2147483647.0 ? INT32_MAX : (int32_t)r[k]);
+    }
+    size_t hit = 0;
+    int rc = gs_select_rect(ctx, &p, rect, (uint8_t)set, (uint8_t)clear, flags, &hit);
+    if (rc != GS_OK) return throw_gs(env, ctx, rc);
+    return make_count(env, hit);
+}
+
+/* compact(h) -> Uint32Array: the old index of every splat that stays */
+static napi_value fn_compact(napi_env env, napi_callback_info info)
+{
+    napi_value argv[1];
+    if (!get_args(env, info, 1, argv, NULL)) return NULL;
+    gs_ctx *ctx = get_ctx(env, argv[0]); if (!ctx) return NULL;
+    const size_t before = gs_count(ctx);
+    napi_value ab, ta; void *data = NULL;
+    NAPI_OK(napi_create_arraybuffer(env, (before ? before : 1) * 4, &data, &ab));
+    size_t n = 0;
+    int rc = gs_compact(ctx, (uint32_t *)data, &n);
+    if (rc != GS_OK) return throw_gs(env, ctx, rc);
+    NAPI_OK(napi_create_typedarray(env, napi_uint32_array, n, ab, 0, &ta));
+    return ta;
+}
+
 /* page-locked framebuffers handed to JavaScript as external ArrayBuffers: gs_render copies into them at PCIe speed and the
  * same memory is reused frame after frame (no per-call allocation, no extra copy) */
 static void frame_finalize(napi_env env, void *data, void *hint) { (void)env; (void)hint; gs_host_free(data); }
@@ -837,7 +962,7 @@ static napi_value fn_stats(napi_env env, napi_callback_info info)
     PUT("msBin", s.ms_bin); PUT("msBlend", s.ms_blend); PUT("msRender", s.ms_render);
     PUT("accFrames", s.acc_frames); PUT("unsatTiles", s.unsat_tiles); PUT("nearPermille", s.near_permille); PUT("sortRecords", s.sort_records);
     PUT("retriedFrames", s.retried_frames); PUT("specSorts", s.spec_sorts); PUT("specMisses", s.spec_misses); PUT("needSplats", s.need_splats); PUT("sortMode", s.sort_mode); PUT("subtile", s.subtile);
-    PUT("shDegree", s.sh_degree); PUT("surface", s.surface); PUT("antialias", s.antialias);
+    PUT("shDegree", s.sh_degree); PUT("surface", s.surface); PUT("antialias", s.antialias); PUT("nHidden", s.n_hidden);
 #undef PUT
     return o;
 }
@@ -1144,6 +1269,8 @@ static napi_value init(napi_env env, napi_value exports)
         { "sortGathered", fn_sort_gathered }, { "renderGathered", fn_render_gathered }, { "readGathered", fn_read_gathered }, { "setScene", fn_set_scene }, { "stats", fn_stats }, { "setOption", fn_set_option },
         { "modelViewMatrix", fn_model_view }, { "projectionMatrix", fn_projection }, { "tickUniforms", fn_tick },
         { "scaledSize", fn_scaled_size },
+        { "setState", fn_set_state }, { "setStateIds", fn_set_state_ids }, { "selectBox", fn_select_box }, { "selectSphere", fn_select_sphere },
+        { "selectRect", fn_select_rect }, { "compact", fn_compact },
         { "createMulti", fn_create_multi }, { "multiDestroy", fn_multi_destroy }, { "multiPushSplat", fn_multi_push_splat },
         { "multiLoadPly", fn_multi_load_ply }, { "multiClear", fn_multi_clear }, { "multiCount", fn_multi_count },
         { "multiSetOption", fn_multi_set_option }, { "multiSort", fn_multi_sort }, { "multiRender", fn_multi_render },

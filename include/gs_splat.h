@@ -232,6 +232,60 @@ GS_API int gs_render_surface_device(gs_ctx *ctx, const gs_render_params *p, void
 typedef struct gs_hit { uint32_t id; float depth; float alpha; float pos[3]; } gs_hit;
 GS_API int gs_pick(gs_ctx *ctx, const gs_render_params *p, const int32_t *xy, size_t npoints, gs_hit *out);
 
+/* ---- editing the resident cloud (no reference counterpart: the worker only ever appends, index.js:573-586; the one cull the reference
+ * has is the single cutoutEntity box, evaluated again in every sort, index.js:525-554) ------------------------------------------------
+ * One STATE byte per splat, parallel to the splats like the SH rows.  A splat whose byte has GS_STATE_HIDDEN is, in every depth sort,
+ * a splat outside the cutout (`cutoutArea == false`, index.js:548): not kept, not counted, no part in minDepth / maxDepth -- so the
+ * order of a context with the set H hidden is exactly the reference's order of the scene without the rows of H (indices of the full
+ * scene).  Nothing downstream knows about states: the order does not contain the splat, so projection, binning, every blend path,
+ * surface frames and gs_pick never see it.  This holds for gs_sort, gs_sort_for, gs_sort_begin / gs_sort_poll, gs_sort_gathered, the
+ * rank that sorts under GS_OPT_SORT_SHARE and the whole-order sorts a render or gs_download(GS_BUF_SORTED) runs by itself.
+ *   - GS_STATE_SELECTED changes no pixel: it is the caller's mark (what a later call hides, shows or reads back).  Bits 2..7 belong to
+ *     the caller and are kept untouched by the library.
+ *   - Splats beyond the store's length have state 0 (progressive loading keeps working); gs_clear empties the store.  While the store
+ *     is empty the sorts launch the very kernels of a context that never edits.
+ *   - Every call that changes the store behaves like a push: frames in flight are drained first, every lane's order is dropped (a
+ *     render before the next sort draws the background only, as after a push), and gs_sync() does not draw frames of before the change again by itself.
+ *     A state change takes effect at the NEXT sort: a draw uses the last completed order (index.js:201-207).
+ *   - gs_stats.n_hidden: the hidden splats the last collected sort skipped.
+ * Out of scope: a highlight colour for selected splats (a projection variant), lasso or mask-image selection, in-place edits of a
+ * splat's position or colour, undo. */
+#define GS_STATE_HIDDEN 1u
+#define GS_STATE_SELECTED 2u
+#define GS_SELECT_INVERT 1u      /* region calls: apply the rule to the splats NOT in the region */
+/* states[0, n) -> splats [first, first + n); the store grows to first + n, zero-filled.  first + n > gs_count(): GS_E_BADARG. */
+GS_API int gs_set_state(gs_ctx *ctx, size_t first, const uint8_t *states, size_t n);
+/* state = (state & ~clear_bits) | set_bits for the listed splats -- ids as gs_pick and the surface id plane return them.  A duplicate
+ * id is harmless; an id >= gs_count() is GS_E_BADARG and changes nothing.  The store grows to gs_count(). */
+GS_API int gs_set_state_ids(gs_ctx *ctx, const uint32_t *ids, size_t n, uint8_t set_bits, uint8_t clear_bits);
+/* the store's length and the number of hidden splats in it (counted on the GPU when the store last changed) */
+GS_API int gs_state_count(const gs_ctx *ctx, size_t *rows, size_t *hidden);
+/* Region selection on the GPU, one streaming kernel each: state = (state & ~clear_bits) | set_bits for the splats in the region (with
+ * GS_SELECT_INVERT in flags: for those not in it); *out_hit (optional) = the splats the rule was applied to.  The store grows to gs_count().
+ *   box     the matrix and the f64 arithmetic of gs_sort's cutout16 on the sort rows (index.js:526-545): a position whose comparisons are
+ *           all false (NaN) is inside, as in the reference.  Works on a context fed with gs_push_matrices.
+ *   sphere  centre in the rows' object space, as a .splat row stores it; in f64, un-fused: d2 = (dx*dx + dy*dy) + dz*dz, inside iff
+ *           d2 <= (double)radius * (double)radius (a NaN d2 is outside).  Matrices-only context: GS_E_STATE.
+ *   rect    screen space, among what is drawn: rect = { x0, y0, x1, y1 } in pixels of the frame `p` describes, row 0 = top, clipped to the
+ *           frame (p->x0 / x1 are ignored).  Walks the last completed WHOLE order (sorting again in full first if the last sort was
+ *           near-only or for a strip, as gs_download(GS_BUF_SORTED) does) and takes a splat iff the projection of that frame accepts it
+ *           (the very function the render calls), x0 <= floor(cx) < x1 and y0 <= fb_height - 1 - floor(cy) < y1.  Hidden splats are not
+ *           in the order and so are never hit; INVERT: the splats of the order that are not in the rectangle.  *out_hit counts positions
+ *           of the order.  No completed order, or a matrices-only context: GS_E_STATE. */
+GS_API int gs_select_box(gs_ctx *ctx, const float box16[16], uint8_t set_bits, uint8_t clear_bits, uint32_t flags, size_t *out_hit);
+GS_API int gs_select_sphere(gs_ctx *ctx, const float centre[3], float radius, uint8_t set_bits, uint8_t clear_bits, uint32_t flags, size_t *out_hit);
+GS_API int gs_select_rect(gs_ctx *ctx, const gs_render_params *p, const int32_t rect[4], uint8_t set_bits, uint8_t clear_bits, uint32_t flags,
+                          size_t *out_hit);
+/* Real deletion: every hidden splat leaves the resident arrays (both 16-byte records, the sort rows, the strip bounds, the SH rows of
+ * the kept splats among those that have one, the states -- hidden bit gone by definition, the other bits travel with the splat), in
+ * stable order.  out_old_index (optional, capacity gs_count() BEFORE the call): out_old_index[k] = the old index of new splat k;
+ * *out_n (optional) = gs_count() afterwards.  The arrays are compacted into fresh ones that are then swapped in: for the duration of
+ * the call the resident bytes are held TWICE.  Afterwards the context is indistinguishable from one that was pushed the kept rows
+ * (orders, hints and measured shares are dropped as by gs_clear).  A sort posted with gs_sort_begin and not yet collected is run
+ * again over the kept splats when gs_sort_poll collects it (nothing kept: its reply is the empty context's [0]).  Nothing hidden:
+ * nothing happens (*out_n = gs_count()). */
+GS_API int gs_compact(gs_ctx *ctx, uint32_t *out_old_index, size_t *out_n);
+
 /* Scene compositing inputs (reference: the splat mesh is drawn in three.js' transparent pass with depthTest: true,
  * depthWrite: false over the opaque scene, index.js:177-181): an optional window-space depth buffer of that scene
  * (GL convention: 0 = near plane, 1 = far plane; a fragment survives iff its depth zndc*0.5+0.5 <= the buffer, LEQUAL)
@@ -344,6 +398,15 @@ GS_API int gs_multi_clear(gs_multi *m);                                         
 GS_API int gs_multi_push_splat(gs_multi *m, const void *rows, size_t nrows);         /* gs_push_splat, uploads in parallel */
 GS_API int gs_multi_load_ply(gs_multi *m, const void *bytes, size_t nbytes);
 GS_API int gs_multi_push_sh(gs_multi *m, const float *sh_rows, size_t nrows, int degree);   /* gs_push_sh on every device     */
+/* the editing calls on every device; hit counts and the index map are those of devices[0] (every device holds the same splats; a
+ * gs_multi_select_rect walks each device's own whole order of the same view) */
+GS_API int gs_multi_set_state(gs_multi *m, size_t first, const uint8_t *states, size_t n);
+GS_API int gs_multi_set_state_ids(gs_multi *m, const uint32_t *ids, size_t n, uint8_t set_bits, uint8_t clear_bits);
+GS_API int gs_multi_select_box(gs_multi *m, const float box16[16], uint8_t set_bits, uint8_t clear_bits, uint32_t flags, size_t *out_hit);
+GS_API int gs_multi_select_sphere(gs_multi *m, const float centre[3], float radius, uint8_t set_bits, uint8_t clear_bits, uint32_t flags, size_t *out_hit);
+GS_API int gs_multi_select_rect(gs_multi *m, const gs_render_params *p, const int32_t rect[4], uint8_t set_bits, uint8_t clear_bits, uint32_t flags,
+                                size_t *out_hit);
+GS_API int gs_multi_compact(gs_multi *m, uint32_t *out_old_index, size_t *out_n);
 GS_API size_t gs_multi_count(const gs_multi *m);
 GS_API int gs_multi_set_option(gs_multi *m, int option, int64_t value);              /* gs_set_option on every device     */
 /* tick + worker sort for the frame `views` describe (one view, or the two XR eyes with the head camera's view row, index.js:441):
@@ -472,6 +535,8 @@ typedef struct gs_stats {
                              (asked for, or a strip of more than 256 tile columns or rows, or a row-count table beyond its limit); a frame
                              that runs no round (nothing resident) reports what its round would have taken                             */
     uint32_t sh_degree;   /* the spherical-harmonics degree the last frame's projection evaluated (GS_OPT_SH_DEGREE): 0 = packed byte colours   */
+    uint32_t n_hidden;    /* hidden splats (GS_STATE_HIDDEN) the last collected sort skipped (in front of `surface`: every field that a build
+                             without the editing calls has keeps its place up to here)                                                  */
     uint32_t surface;     /* 1 if the last frame wrote surface planes (gs_render_surface, gs_pick)                                        */
     uint32_t antialias;   /* 1 if the last frame's projection compensated its opacities (GS_OPT_ANTIALIAS)                                */
 } gs_stats;
@@ -560,6 +625,7 @@ GS_API int gs_get_stats(gs_ctx *ctx, gs_stats *out);
 #define GS_BUF_UNSAT_MASK 7   /* tiles_y x ceil(tiles_x / 32) u32: one bit per tile the first binning round of the last render left
                                  unsaturated (measurement aid)                                                         */
 #define GS_BUF_SH 8           /* rows x 3 (D+1)^2 f32  the SH store, tight rows as pushed (gs_sh_count: rows and D)                   */
+#define GS_BUF_STATE 9        /* rows u8     the state store (gs_state_count: rows)                                                      */
 GS_API int gs_download(gs_ctx *ctx, int which, void *out, size_t nbytes);
 
 #ifdef __cplusplus
