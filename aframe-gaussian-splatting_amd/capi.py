@@ -27,6 +27,7 @@ OPT_SUBTILE = 17
 OPT_ROW_WALK = 18
 OPT_SH_DEGREE = 19
 OPT_ANTIALIAS = 20
+OPT_SEG_COUNT = 21
 TRANSPORT_RCCL, TRANSPORT_INPROC = 0, 1
 COMM_ID_BYTES = 128
 BUF_CENTER_SCALE, BUF_COV_COLOR, BUF_SORT_ROWS, BUF_SORTED, BUF_PROJECTED, BUF_TILE_COUNT, BUF_TILE_STATS, BUF_UNSAT_MASK = 0, 1, 2, 3, 4, 5, 6, 7
@@ -73,7 +74,8 @@ class Stats(C.Structure):
                 ("acc_pairs", C.c_uint64), ("unsat_tiles", C.c_uint32), ("near_permille", C.c_uint32),
                 ("sort_records", C.c_uint32), ("retried_frames", C.c_uint32), ("spec_sorts", C.c_uint32), ("spec_misses", C.c_uint32), ("need_splats", C.c_uint32),
                 ("sort_mode", C.c_uint32), ("subtile", C.c_uint32), ("row_walk", C.c_uint32),
-                ("binning", C.c_uint32), ("sh_degree", C.c_uint32), ("n_hidden", C.c_uint32), ("surface", C.c_uint32), ("antialias", C.c_uint32)]
+                ("binning", C.c_uint32), ("sh_degree", C.c_uint32), ("n_hidden", C.c_uint32), ("surface", C.c_uint32), ("antialias", C.c_uint32),
+                ("seg_count", C.c_uint32), ("n_runs", C.c_uint32)]
 
     def as_dict(self):
         return {n: getattr(self, n) for n, _ in self._fields_}

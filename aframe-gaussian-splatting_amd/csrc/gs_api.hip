@@ -319,6 +319,7 @@ static int collect_status(gs_ctx *lane, bool *overflowed, GsShareTally &tally, u
     lane->stats.acc_pairs = c->acc_pairs; lane->stats.sort_records = c->n_sorted;
     lane->stats.sort_mode = c->near_sorted;
     lane->stats.n_hidden = lane->sort_hidden;
+    lane->stats.n_runs = c->n_runs;
     if (c->n_pairs_frame) { ctx->last_pairs = c->n_pairs_frame; ctx->last_visible = c->n_visible; }
     if (c->n_pairs_frame) __atomic_store_n(&ctx->run_hint, c->n_runs, __ATOMIC_RELAXED);
     if (c->n_pairs_frame) {                                     // sizing hint for the next frames' pair sort (any lane's worker may read it)
@@ -841,7 +842,7 @@ GS_API int gs_create(int device, gs_ctx **out)
     if (!ctx) { snprintf(g_create_err, sizeof g_create_err, "out of host memory"); return GS_E_OOM; }
     memset(ctx, 0, sizeof *ctx);
     ctx->device = device; ctx->renderable = true; ctx->t_eps = 1.0f / 1024.0f; gs_share_reset_create(ctx->share);
-    ctx->lanes[0] = ctx; ctx->pipe_depth = 3; ctx->enqueue_threads = true; ctx->frame_batch = 1; ctx->exec = ctx; ctx->sort_near_opt = 1; ctx->auto_retry = true; ctx->subtile_opt = 1; ctx->row_walk_opt = 1;
+    ctx->lanes[0] = ctx; ctx->pipe_depth = 3; ctx->enqueue_threads = true; ctx->frame_batch = 1; ctx->exec = ctx; ctx->sort_near_opt = 1; ctx->auto_retry = true; ctx->subtile_opt = 1; ctx->row_walk_opt = 1; ctx->seg_count_opt = 1;
     { const char *e = getenv("GS_SPEC_STASH"); ctx->near_spec_opt = !(e && e[0] == '0'); }   // (A/B: near-only sorts without the speculative stash)
 #define CREATE_HIP(call) do { hipError_t _e = (call); if (_e != hipSuccess) {                                              \
         snprintf(g_create_err, sizeof g_create_err, "%s failed: %s", #call, hipGetErrorString(_e)); gs_destroy(ctx);      \
@@ -2150,6 +2151,12 @@ GS_API int gs_set_option(gs_ctx *ctx, int option, int64_t value)
     case GS_OPT_ROW_WALK:
         if (value < 0 || value > 2) FAIL(GS_E_BADARG, "row walk: 0 (off), 1 (where splats are large) or 2 (always)");
         ctx->row_walk_opt = (int)value;
+        return GS_OK;
+    case GS_OPT_SEG_COUNT:
+        if (value < 0 || value > 2) FAIL(GS_E_BADARG, "segment counts: 0 (never), 1 (where tile rows hold many runs) or 2 (always)");
+        GS_HIP(hipSetDevice(ctx->device));
+        TRY(drain_all(ctx));                                         // (the lanes' enqueue threads read it where they launch a round)
+        ctx->seg_count_opt = (int)value;
         return GS_OK;
     case GS_OPT_SH_DEGREE:
         if (value < 0 || value > GS_SH_MAX_DEGREE) FAIL(GS_E_BADARG, "spherical-harmonics degree: 0 (off) to 3");

@@ -262,6 +262,10 @@ struct gs_ctx {
     int bin_mode;                           // owner: GS_OPT_BINNING
     int subtile_opt;                        // owner: GS_OPT_SUBTILE (0 off, 1 where the last collected frames' splats were small, 2 always)
     int row_walk_opt;                       // owner: GS_OPT_ROW_WALK (0 off, 1 where the last collected frames' splats were large, 2 always)
+    int seg_count_opt;                      // owner: GS_OPT_SEG_COUNT (0 never, 1 where the last collected frame held many runs per tile row, 2 always)
+                                            // (read with a plain load by the lanes' enqueue threads, run_round_spans: gs_set_option drains every lane
+                                            // before it stores, so no frame is being launched while the value changes -- unlike run_hint, which
+                                            // collections store while frames are in flight and which is therefore read atomically)
     uint32_t last_pairs, last_visible;      // owner: I and Vp of the last collected frame (what GS_OPT_SUBTILE = 1 decides on)
     uint2 *tile_range; size_t tile_cap;     // per tile [start,end) into the sorted pair list
     uint8_t *fb; size_t fb_cap;             // RGBA8 strip

@@ -2078,7 +2078,11 @@ int run_round_spans(gs_ctx *const S[], const GsFrameUniforms U[], uint8_t *const
     // frames of many runs per tile row (many small splats: a cut-out scene, the cloud seen from outside, tiles that do not saturate)
     // count their segments in a launch of their own; frames of few (the headline pose: 3 000 per row) let every k_lists item count its
     // row itself -- one launch less.  Decided from the runs of the last collected frame: a matter of speed only, the lists are the same.
-    const bool segc = ROUND == 0 && __atomic_load_n(&gs_root(ctx)->run_hint, __ATOMIC_RELAXED) > GS_SEGC_RUNS_PER_ROW * (uint32_t)u.tiles_y;
+    // GS_OPT_SEG_COUNT: 0 never, 2 in every such round 0 (what the tests force), 1 the rule above.
+    const int segc_opt = gs_root(ctx)->seg_count_opt;
+    const bool segc = ROUND == 0 && segc_opt != 0 &&
+                      (segc_opt == 2 || __atomic_load_n(&gs_root(ctx)->run_hint, __ATOMIC_RELAXED) > GS_SEGC_RUNS_PER_ROW * (uint32_t)u.tiles_y);
+    if (segc) for (int k = 0; k < NF; k++) S[k]->stats.seg_count = 1u;   // (gs_stats: read once the lane has drained)
     if (segc)
         gs_launch<NF, F_seg_count<ROUND>, GS_BLOCK>(gl, st, 0, [&](int k) {
             return gs_pack_make((const uint32_t *)geom[k], (const uint2 *)S[k]->row_tot, S[k]->seg_diff, V[k], (const GsControl *)S[k]->ctl, (uint32_t)S[k]->pair_cap); });
@@ -2182,6 +2186,7 @@ int gs_run_render2(gs_ctx *const S[2], const GsFrameUniforms U[2], uint8_t *cons
     gs_ctx *ctx = S[0];
     const GsFrameUniforms &u = U[0];
     uint8_t *out[2] = { device_out[0] ? device_out[0] : S[0]->fb, device_out[1] ? device_out[1] : S[1]->fb };
+    S[0]->stats.seg_count = 0; S[1]->stats.seg_count = 0;         // (run_round_spans sets it where round 0 launches k_seg_count)
     GS_PROF_RECORD(ctx, 2);
     const bool two_rounds = u.near_count != 0xFFFFFFFFu;
     int rc = run_round<0, 2>(S, U, out, !two_rounds || u.skip_round1);
@@ -2210,6 +2215,7 @@ int gs_run_render(gs_ctx *ctx, const GsFrameUniforms &u, uint8_t *device_out)
     uint8_t *const out = device_out ? device_out : ctx->fb;
     hipStream_t st = ctx->stream;
 
+    ctx->stats.seg_count = 0;                                      // (run_round_spans sets it where round 0 launches k_seg_count)
     GS_PROF_RECORD(ctx, 2);
     if (u.flags & GS_RENDER_COUNT_FRAGS) GS_HIP(hipMemsetAsync(&ctx->ctl->n_frags, 0, sizeof(unsigned long long), st));
     if (Vmax && ctx->have_sort) {

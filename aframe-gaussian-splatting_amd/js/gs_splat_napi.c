@@ -963,6 +963,7 @@ static napi_value fn_stats(napi_env env, napi_callback_info info)
     PUT("accFrames", s.acc_frames); PUT("unsatTiles", s.unsat_tiles); PUT("nearPermille", s.near_permille); PUT("sortRecords", s.sort_records);
     PUT("retriedFrames", s.retried_frames); PUT("specSorts", s.spec_sorts); PUT("specMisses", s.spec_misses); PUT("needSplats", s.need_splats); PUT("sortMode", s.sort_mode); PUT("subtile", s.subtile);
     PUT("shDegree", s.sh_degree); PUT("surface", s.surface); PUT("antialias", s.antialias); PUT("nHidden", s.n_hidden);
+    PUT("segCount", s.seg_count); PUT("nRuns", s.n_runs);
 #undef PUT
     return o;
 }

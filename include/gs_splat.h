@@ -539,6 +539,12 @@ typedef struct gs_stats {
                              without the editing calls has keeps its place up to here)                                                  */
     uint32_t surface;     /* 1 if the last frame wrote surface planes (gs_render_surface, gs_pick)                                        */
     uint32_t antialias;   /* 1 if the last frame's projection compensated its opacities (GS_OPT_ANTIALIAS)                                */
+    uint32_t seg_count;   /* 1 if the last frame's first binning round counted its runs per (tile row, segment) in a launch of its own
+                             (k_seg_count + the k_lists form that adds those counts up: GS_OPT_SEG_COUNT); 0 where every k_lists item counted
+                             its row itself, and for rounds that build no span lists (row walk, pair records, nothing resident)            */
+    uint32_t n_runs;      /* tile-row runs of the last collected frame, both rounds (span-list binning: a splat meets a tile row in one run of
+                             tiles); what GS_OPT_SEG_COUNT 1 and GS_OPT_ROW_WALK 1 decide from.  A pair-record frame leaves it as it was.
+                             (These two sit at the end: every older field keeps its offset.)                                              */
 } gs_stats;
 
 #define GS_OPT_PROFILE 1        /* 1: bracket every stage with HIP events on the frame's stream (7 per frame); 2: only
@@ -607,6 +613,16 @@ typedef struct gs_stats {
                                    written, counted and binned.  The colour word keeps the packed alpha byte.  Taken per frame (each eye, each
                                    strip), may change between frames; combines with GS_OPT_SH_DEGREE; paired frames (GS_OPT_FRAME_BATCH) share
                                    the setting.  Any other value: GS_E_BADARG.  gs_antialias_factor evaluates c on the host.        */
+#define GS_OPT_SEG_COUNT 21      /* how round 0 of a span-list frame that builds tile lists counts the runs that cover a tile column (same lists, same
+                                   pixels, bit for bit, whatever the value).  A tile row's runs are cut into at most 16 segments, one k_lists
+                                   workgroup each, and each needs per column the runs before its segment and in the whole row.  Either every
+                                   workgroup counts its whole row itself, or a launch of its own (k_seg_count) leaves one difference array per
+                                   segment and k_lists adds them up -- less work where rows hold many runs, one launch more where they hold few.
+                                   0: never the separate launch; 1 (default): in frames that follow a collected frame of more than 4096 runs per
+                                   tile row (gs_stats.n_runs; a fresh or cleared context has none: its first frame takes none); 2: always.
+                                   The second binning round, row-walk rounds (GS_OPT_ROW_WALK) and pair-record rounds (GS_OPT_BINNING 1, strips
+                                   beyond 256 tile columns or rows) are unaffected.  gs_stats.seg_count says what a frame took.  Any other
+                                   value: GS_E_BADARG.                                                                               */
 #define GS_OPT_ENQUEUE_THREADS 7 /* default 1: gs_sort() (without an output array) and gs_render_device(GS_RENDER_ASYNC) hand the
                                    frame to a worker thread of its pipeline lane, which does the ~18 kernel launches, so the
                                    launches of the frames in flight run in parallel; failures surface at gs_sync().  0: the

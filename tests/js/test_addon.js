@@ -114,6 +114,20 @@ comp.loadData(camera, object, null, scenePath, 100003).then((n) => {
   const strip = comp.render(camera, { width: Number(W), height: Number(H), x0: 16, x1: 48 });
   ok(strip.length === 32 * H * 4, 'strip size');
   ok(comp.render(camera, { width: Number(W), height: Number(H) }) === img, 'the frame buffer is reused (page-locked, no per-call allocation)');
+  {
+    // GS_OPT_SEG_COUNT (21) and the two statistics at the end of gs_stats: segCount, nRuns.  (GS_OPT_ROW_WALK 18 off meanwhile: a walked
+    // frame builds no lists and counts no segments.)
+    const first = Uint8Array.from(img), s0 = comp.stats();
+    ok((s0.segCount === 0 || s0.segCount === 1) && s0.nRuns > 0 && s0.nRuns <= s0.nPairs, 'stats(): segCount ' + s0.segCount + ', nRuns ' + s0.nRuns);
+    native.setOption(comp.handle, 18, 0); native.setOption(comp.handle, 21, 2);
+    ok(same(comp.render(camera, { width: Number(W), height: Number(H) }), first) && comp.stats().segCount === 1, 'setOption(21, 2): same frame, segCount 1');
+    native.setOption(comp.handle, 21, 0);
+    ok(same(comp.render(camera, { width: Number(W), height: Number(H) }), first) && comp.stats().segCount === 0, 'setOption(21, 0): same frame, segCount 0');
+    let refused = false;
+    try { native.setOption(comp.handle, 21, 3); } catch (e) { refused = e.code === 'GS-1'; }
+    ok(refused, 'setOption(21, 3) is GS_E_BADARG');
+    native.setOption(comp.handle, 21, 1); native.setOption(comp.handle, 18, 1);
+  }
   // ---- the reference's rhythm: fire-and-forget sort, single flight (index.js:201-207, 438-455): tick posts the sort, the frames drawn
   // until its reply arrives use the last COMPLETED order, the reply installs the new one.  Pose A = the order held now; pose B = the
   // entity turned by 70 degrees.

@@ -101,7 +101,7 @@ def test_symbol_option_and_stats_field():
     L = capi.load()
     assert hasattr(L, "gs_antialias_factor") and "gs_antialias_factor" in capi.EXPORTS
     assert capi.OPT_ANTIALIAS == 20
-    assert capi.Stats._fields_[-1] == ("antialias", C.c_uint32) and capi.Stats._fields_[-2][0] == "surface"
+    assert capi.Stats._fields_[-3] == ("antialias", C.c_uint32) and capi.Stats._fields_[-4][0] == "surface"    # (seg_count and n_runs follow)
     out = C.c_float(7.0)
     cov = (C.c_float * 3)(1.0, 0.0, 1.0)
     assert L.gs_antialias_factor(None, C.byref(out)) == capi.E_BADARG

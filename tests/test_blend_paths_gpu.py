@@ -105,18 +105,22 @@ def draw(scene, path, views=((0, None),), flags=0, opts=(), bg=(0.0, 0.0, 0.0, 1
     return out, idx, st
 
 
-def list_lengths(scene):
-    """(tiles_y, tiles_x) list length per tile, from the lists path (GS_OPT_RECORD_STAGED, GS_BUF_TILE_STATS)."""
-    tx, ty = (scene.W + 15) // 16, (scene.H + 15) // 16
+def tile_lengths(c, scene, x0=0, x1=None):
+    """(tiles_y, tiles_x) list length per tile of the strip [x0, x1) that context c drew last with GS_OPT_RECORD_STAGED set (GS_BUF_TILE_STATS)."""
+    tx, ty = ((x1 or scene.W) - x0 + 15) // 16, (scene.H + 15) // 16
+    return c.download(capi.BUF_TILE_STATS, tx * ty, np.uint32, 2)[:, 1].reshape(ty, tx)
+
+
+def list_lengths(scene, path="lists", x0=0, x1=None):
+    """(tiles_y, tiles_x) list length per tile, from the lists path (GS_OPT_RECORD_STAGED, GS_BUF_TILE_STATS) or another one that builds lists."""
     with capi.Context(0) as c:
-        force_path(c, "lists")
+        force_path(c, path)
         c.set_option(capi.OPT_RECORD_STAGED, 1)
         c.push_splat(scene.rows)
         c.sort(scene.cam["view"])
-        c.render(scene.params())
-        assert_path(c, "lists")
-        ts = c.download(capi.BUF_TILE_STATS, tx * ty, np.uint32, 2)
-    return ts[:, 1].reshape(ty, tx)
+        c.render(scene.params(x0, x1))
+        assert_path(c, path)
+        return tile_lengths(c, scene, x0, x1)
 
 
 def compare_paths(scene, views, paths=EXACT + ("split",), tag="", oracle_views=None, **kw):

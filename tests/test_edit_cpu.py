@@ -45,7 +45,7 @@ def test_stats_carry_n_hidden_where_the_header_puts_it():
     fields = re.search(r"typedef struct gs_stats \{(.*?)\} gs_stats;", _header(), re.S).group(1)
     declared = re.findall(r"\b(\w+)\s*(?:,|;)", re.sub(r"/\*.*?\*/", "", fields, flags=re.S))
     assert "n_hidden" in names and names == declared
-    assert dict(capi.Stats._fields_)["n_hidden"] is C.c_uint32 and names[-3:] == ["n_hidden", "surface", "antialias"]
+    assert dict(capi.Stats._fields_)["n_hidden"] is C.c_uint32 and names[-5:] == ["n_hidden", "surface", "antialias", "seg_count", "n_runs"]
 
 
 def test_null_context_is_refused_without_a_gpu():

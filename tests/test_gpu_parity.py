@@ -46,14 +46,16 @@ def pix_check(tag, got, want, tol=PIXEL_TOL_LSB):
 # The blend paths, each forced by options (nothing left to the per-frame automatic choices) and proven by the statistics of the frame
 # that ran it: a test that names a path fails if the library silently drew that frame another way.
 PATH_OPTIONS = {
-    "lists": {capi.OPT_BINNING: 0, capi.OPT_ROW_WALK: 0, capi.OPT_SUBTILE: 0},
+    "lists": {capi.OPT_BINNING: 0, capi.OPT_ROW_WALK: 0, capi.OPT_SUBTILE: 0, capi.OPT_SEG_COUNT: 0},
+    "segc": {capi.OPT_BINNING: 0, capi.OPT_ROW_WALK: 0, capi.OPT_SUBTILE: 0, capi.OPT_SEG_COUNT: 2},   # lists, segments counted by k_seg_count
     "walk": {capi.OPT_BINNING: 0, capi.OPT_ROW_WALK: 2, capi.OPT_SUBTILE: 0},
     "subtile": {capi.OPT_BINNING: 0, capi.OPT_ROW_WALK: 0, capi.OPT_SUBTILE: 2},
     "pairs": {capi.OPT_BINNING: 1, capi.OPT_ROW_WALK: 0, capi.OPT_SUBTILE: 0},
     "split": {capi.OPT_BINNING: 0, capi.OPT_ROW_WALK: 0, capi.OPT_SUBTILE: 0, capi.OPT_BLEND_SPLIT: 1},
 }
 PATH_PROOF = {
-    "lists": {"row_walk": 0, "subtile": 0, "binning": 0},
+    "lists": {"row_walk": 0, "subtile": 0, "binning": 0, "seg_count": 0},
+    "segc": {"row_walk": 0, "subtile": 0, "binning": 0, "seg_count": 1},
     "walk": {"row_walk": 1, "subtile": 0, "binning": 0},
     "subtile": {"row_walk": 0, "subtile": 1},
     "pairs": {"row_walk": 0, "binning": 1},
@@ -70,7 +72,7 @@ def force_path(c, path, near_permille=1000):
 
 
 def assert_path(c, path, tag=""):
-    """The last frame of context c ran the named path (gs_stats: row_walk, subtile, binning)."""
+    """The last frame of context c ran the named path (gs_stats: row_walk, subtile, binning, seg_count)."""
     st = c.stats()
     got = {k: st[k] for k in PATH_PROOF[path]}
     assert got == PATH_PROOF[path], (tag, path, got)
