@@ -28,6 +28,8 @@ OPT_ROW_WALK = 18
 OPT_SH_DEGREE = 19
 OPT_ANTIALIAS = 20
 OPT_SEG_COUNT = 21
+OPT_SORT_NEAR_FORCE = 22
+SORT_WHOLE, SORT_HISTOGRAM, SORT_SPEC, SORT_TAIL, SORT_STASH = 0, 1, 2, 3, 4     # gs_sort_info.form
 TRANSPORT_RCCL, TRANSPORT_INPROC = 0, 1
 COMM_ID_BYTES = 128
 BUF_CENTER_SCALE, BUF_COV_COLOR, BUF_SORT_ROWS, BUF_SORTED, BUF_PROJECTED, BUF_TILE_COUNT, BUF_TILE_STATS, BUF_UNSAT_MASK = 0, 1, 2, 3, 4, 5, 6, 7
@@ -51,6 +53,7 @@ EXPORTS = [
     "gs_render_surface", "gs_render_surface_device", "gs_pick",
     "gs_antialias_factor",
     "gs_set_state", "gs_set_state_ids", "gs_state_count", "gs_select_box", "gs_select_sphere", "gs_select_rect", "gs_compact",
+    "gs_sort_inspect",
     "gs_multi_set_state", "gs_multi_set_state_ids", "gs_multi_select_box", "gs_multi_select_sphere", "gs_multi_select_rect", "gs_multi_compact",
 ]
 SURFACE_NONE = 0xFFFFFFFF          # gs_surface.id / gs_hit.id where the transmittance never falls below one half
@@ -79,6 +82,15 @@ class Stats(C.Structure):
 
     def as_dict(self):
         return {n: getattr(self, n) for n, _ in self._fields_}
+
+
+class SortInfo(C.Structure):
+    _fields_ = [("form", C.c_uint32), ("near_req", C.c_uint32), ("n_kept", C.c_uint32), ("n_valid", C.c_uint32), ("n_records", C.c_uint32),
+                ("order_incomplete", C.c_uint32), ("near_overflow", C.c_uint32), ("spec_fail", C.c_uint32), ("threshold_bin", C.c_uint32),
+                ("reserved", C.c_uint32 * 3)]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_ if n != "reserved"}
 
 
 class Surface(C.Structure):
@@ -215,6 +227,8 @@ def load(build_if_missing=True):
             getattr(L, pre + "compact").argtypes = [vp, vp, szp]
         L.gs_state_count.argtypes = [vp, szp, szp]
     L.gs_download.argtypes = [vp, i32, vp, sz]
+    if hasattr(L, "gs_sort_inspect"):
+        L.gs_sort_inspect.argtypes = [vp, C.POINTER(SortInfo), vp, sz]
     L.gs_comm_unique_id.argtypes = [vp, vp]
     L.gs_comm_init.argtypes = [vp, vp, i32, i32]
     L.gs_comm_destroy.argtypes = [vp]
@@ -731,6 +745,14 @@ class Context:
         s = Stats()
         self._ck(self._L.gs_get_stats(self._h, C.byref(s)))
         return s.as_dict()
+
+    def sort_inspect(self, want_indices=True):
+        """gs_sort_inspect: the current lane's order as it lies -> (info dict, uint32[n_records] or None); also collects that sort for the
+        near-only forms' bookkeeping (include/gs_splat.h)"""
+        info = SortInfo()
+        out = np.zeros(max(self.count(), 1), np.uint32) if want_indices else None
+        self._ck(self._L.gs_sort_inspect(self._h, C.byref(info), _p(out), 0 if out is None else out.size))
+        return info.as_dict(), (None if out is None else out[:info.n_records].copy())
 
     def download(self, which, count, dtype, width):
         out = np.zeros((count, width), dtype)

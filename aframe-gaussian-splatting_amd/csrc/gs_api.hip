@@ -308,6 +308,36 @@ static void decide_share(gs_ctx *ctx /* owner */, float frac_used, const GsShare
     seed_need_words(ctx, need, idle_only);
 }
 
+// What a collected sort says about the near-only forms (a collection: collect_status below, or gs_sort_inspect): a stash that overflowed,
+// a threshold-bin hint that exists now, a speculative stash that failed.  spec_failed: the caller backs off once for all its lanes
+// (gs_sync); null: here
+static int collect_near_sort(gs_ctx *lane, const GsControl *c, uint32_t *spec_failed)
+{
+    gs_ctx *ctx = gs_root(lane);
+    if (c->near_overflow) {
+        // a chunk of a near-only sort had more survivors than its stash holds (the frame was flagged and is drawn again from a
+        // whole sort): this context keeps to the whole-length passes from now on
+        __atomic_store_n(&ctx->near_stash_off, true, __ATOMIC_RELAXED);   // (the lanes' enqueue threads read these flags while they launch sorts)
+        GS_HIP(hipMemsetAsync(&lane->ctl->near_overflow, 0, sizeof(uint32_t), lane->stream));
+    }
+    if (c->near_sorted == 1u || c->near_sorted == 2u) {          // (3: a tail sort -- no threshold, no hint)
+        __atomic_store_n(&ctx->near_spec, true, __ATOMIC_RELAXED);    // a near-only sort has run: the threshold-bin hint exists (gs_near_spec_ok)
+        const uint32_t h = __atomic_load_n(&ctx->near_spec_hold, __ATOMIC_RELAXED);
+        if (h) __atomic_store_n(&ctx->near_spec_hold, h - 1u, __ATOMIC_RELAXED);
+    }
+    if (c->near_sorted == 2u) { ctx->stats.spec_sorts++; if (ctx->near_spec_miss_credit) ctx->near_spec_miss_credit--; }
+    if (c->spec_fail) {
+        // a near-only sort could not vouch for the candidates its depth pass had stashed (the frame was flagged and is drawn again
+        // from a whole sort).  1: the hint was behind -- it is exact now; 2: a stash overflowed / the depth range does not suit the path
+        ctx->stats.spec_misses++;
+        // (the frames a gs_sync collects were sorted by ONE hint: the lanes that missed it together -- a camera jump -- are one event)
+        if (spec_failed) { if (c->spec_fail > *spec_failed) *spec_failed = c->spec_fail; }
+        else gs_spec_back_off(ctx, c->spec_fail == 2u);
+        GS_HIP(hipMemsetAsync(&lane->ctl->spec_fail, 0, sizeof(uint32_t), lane->stream));
+    }
+    return GS_OK;
+}
+
 // after a stream sync: publish the counters of the last completed frame, hand what they say about the share of splats binned first
 // to the policy (gs_share.h) and react to pair-buffer overflow
 static int collect_status(gs_ctx *lane, bool *overflowed, GsShareTally &tally, uint32_t *spec_failed)
@@ -336,27 +366,7 @@ static int collect_status(gs_ctx *lane, bool *overflowed, GsShareTally &tally, u
     obs.unsat_events = c->unsat_events; obs.acc_frames = c->acc_frames; obs.round1_missed = c->round1_missed;
     obs.order_incomplete = c->order_incomplete; obs.n_kept = c->n_kept; obs.tiles = lane->stats.n_tiles != 0;
     gs_share_observe(ctx->share, lane->share_lane, obs, tally);
-    if (c->near_overflow) {
-        // a chunk of a near-only sort had more survivors than its stash holds (the frame was flagged and is drawn again from a
-        // whole sort): this context keeps to the whole-length passes from now on
-        __atomic_store_n(&ctx->near_stash_off, true, __ATOMIC_RELAXED);   // (the lanes' enqueue threads read these flags while they launch sorts)
-        GS_HIP(hipMemsetAsync(&lane->ctl->near_overflow, 0, sizeof(uint32_t), lane->stream));
-    }
-    if (c->near_sorted == 1u || c->near_sorted == 2u) {          // (3: a tail sort -- no threshold, no hint)
-        __atomic_store_n(&ctx->near_spec, true, __ATOMIC_RELAXED);    // a near-only sort has run: the threshold-bin hint exists (gs_near_spec_ok)
-        const uint32_t h = __atomic_load_n(&ctx->near_spec_hold, __ATOMIC_RELAXED);
-        if (h) __atomic_store_n(&ctx->near_spec_hold, h - 1u, __ATOMIC_RELAXED);
-    }
-    if (c->near_sorted == 2u) { ctx->stats.spec_sorts++; if (ctx->near_spec_miss_credit) ctx->near_spec_miss_credit--; }
-    if (c->spec_fail) {
-        // a near-only sort could not vouch for the candidates its depth pass had stashed (the frame was flagged and is drawn again
-        // from a whole sort).  1: the hint was behind -- it is exact now; 2: a stash overflowed / the depth range does not suit the path
-        ctx->stats.spec_misses++;
-        // (the frames a gs_sync collects were sorted by ONE hint: the lanes that missed it together -- a camera jump -- are one event)
-        if (spec_failed) { if (c->spec_fail > *spec_failed) *spec_failed = c->spec_fail; }
-        else gs_spec_back_off(ctx, c->spec_fail == 2u);
-        GS_HIP(hipMemsetAsync(&lane->ctl->spec_fail, 0, sizeof(uint32_t), lane->stream));
-    }
+    TRY(collect_near_sort(lane, c, spec_failed));
     lane->stats.unsat_tiles = lane->share_lane.last_two_rounds ? c->unsat_round0 : 0;
     lane->stats.near_permille = (uint32_t)(ctx->share.near_frac * 1000.0f + 0.5f);
     *overflowed = c->overflow_sticky != 0;
@@ -423,6 +433,11 @@ static uint32_t sort_near_request(const gs_ctx *ctx /* owner */)
     // (a cutout or a strip that keeps little more than the frame reads anyway: the histogram and the threshold would buy nothing)
     if (ctx->sort_near_opt == 1 && ctx->share.last_kept && (double)nc * 2.0 > (double)ctx->share.last_kept) return 0;
     return nc;
+}
+// GS_OPT_SORT_NEAR_FORCE: the request itself, behind what a near-only sort cannot do without (compact records, a renderable context)
+static uint32_t sort_near_forced(const gs_ctx *ctx /* owner */)
+{
+    return (ctx->renderable && !ctx->wide_pairs && ctx->n <= ((size_t)1 << 25)) ? ctx->sort_near_force : 0u;
 }
 static inline bool sort_covers(uint32_t near_req, const GsFrameUniforms &u)
 {
@@ -1143,7 +1158,7 @@ static int sort_common(gs_ctx *ctx, const float view[4], const float *cutout16, 
         if (ctx->share.share_kind && ctx->share.share_kind != kind && ctx->share.near_fixed_permille <= 0) { gs_share_reset_kind_switch(ctx->share); reseed_lanes(ctx); }
         ctx->share.share_kind = kind;
     }
-    const uint32_t near_req = (out_idx || out_n) ? 0u : sort_near_request(ctx);     // (the caller wants the order itself: all of it)
+    const uint32_t near_req = (out_idx || out_n) ? 0u : (ctx->sort_near_force ? sort_near_forced(ctx) : sort_near_request(ctx));     // (the caller wants the order itself: all of it)
     // (a context that has not measured its share yet draws its next frame synchronously -- gs_render_uniforms --: its sort on the caller's
     // thread then, not on an enqueue thread that was created a moment ago and has to be woken first: 0.14 ms of that call's 0.7)
     // (... at most two sorts in a row: a context whose frames never measure -- counting renders -- keeps its threads)
@@ -2172,6 +2187,12 @@ GS_API int gs_set_option(gs_ctx *ctx, int option, int64_t value)
         TRY(drain_all(ctx));
         ctx->sort_near_opt = (int)value;
         return GS_OK;
+    case GS_OPT_SORT_NEAR_FORCE:
+        if (value < 0 || value > 0xFFFFFFFFll) FAIL(GS_E_BADARG, "forced near-only sorts: 0 (the policy decides) or the positions every sort without an index list is asked for");
+        GS_HIP(hipSetDevice(ctx->device));
+        TRY(drain_all(ctx));
+        ctx->sort_near_force = (uint32_t)value;
+        return GS_OK;
     default: FAIL(GS_E_BADARG, "unknown option %d", option);
     }
 }
@@ -2198,6 +2219,39 @@ GS_API int gs_get_stats(gs_ctx *ctx, gs_stats *out)
     s.retried_frames = ctx->stats.retried_frames; s.spec_sorts = ctx->stats.spec_sorts; s.spec_misses = ctx->stats.spec_misses; s.need_splats = ctx->stats.need_splats;
     s.near_permille = (uint32_t)(ctx->share.near_frac * 1000.0f + 0.5f);
     *out = s;
+    return GS_OK;
+}
+
+GS_API int gs_sort_inspect(gs_ctx *ctx, gs_sort_info *info, uint32_t *out_idx, size_t cap)
+{
+    CHECK_CTX(ctx);
+    if (!info) FAIL(GS_E_BADARG, "gs_sort_inspect: info is NULL");
+    memset(info, 0, sizeof *info);
+    GS_HIP(hipSetDevice(ctx->device));
+    gs_ctx *L = ctx->lanes[ctx->cur];
+    TRY(lane_rc(ctx, L, lane_drain(L)));
+    if (!L->have_sort || !ctx->n) FAIL(GS_E_STATE, "gs_sort_inspect: the current frame's lane holds no order");
+    LANE_HIP(L, hipMemcpyAsync(L->ctl_host, L->ctl, sizeof(GsControl), hipMemcpyDeviceToHost, L->stream));
+    LANE_HIP(L, hipStreamSynchronize(L->stream));
+    const GsControl *c = L->ctl_host;
+    const bool whole = L->sort_form == 0u;
+    info->form = L->sort_form; info->near_req = L->sort_near_req;
+    info->n_kept = c->n_kept;
+    info->n_valid = whole ? (ctx->wide_pairs || ctx->n > ((size_t)1 << 25) ? c->n_kept : c->n_sorted) : c->n_valid;
+    info->n_records = whole ? c->n_kept : c->n_sorted;
+    info->order_incomplete = c->order_incomplete; info->near_overflow = c->near_overflow; info->spec_fail = c->spec_fail;
+    GS_HIP(hipMemcpy(&info->threshold_bin, &ctx->ctl->near_bin_hint, sizeof(uint32_t), hipMemcpyDeviceToHost));   // (the owner's block: any lane's kernels write it)
+    const bool fits = !out_idx || cap >= info->n_records;
+    if (fits && out_idx && info->n_records) GS_HIP(hipMemcpy(out_idx, L->sorted, (size_t)info->n_records * 4, hipMemcpyDeviceToHost));
+    // the collection (the near-only sorts' bookkeeping alone).  An incomplete order: what a synchronous frame does -- flags down, a whole sort
+    TRY(collect_near_sort(L, c, nullptr));
+    if (c->order_incomplete) {
+        LANE_HIP(L, hipMemsetAsync(&L->ctl->order_incomplete, 0, sizeof(uint32_t), L->stream));
+        LANE_HIP(L, hipMemsetAsync(&L->ctl->round1_missed, 0, sizeof(uint32_t), L->stream));
+        TRY(lane_rc(ctx, L, ensure_full_sort(L)));
+        LANE_HIP(L, hipStreamSynchronize(L->stream));
+    }
+    if (!fits) FAIL(GS_E_BADARG, "gs_sort_inspect: the lane holds %u entries, room for %zu", info->n_records, cap);
     return GS_OK;
 }
 

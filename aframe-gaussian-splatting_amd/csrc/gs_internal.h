@@ -224,7 +224,9 @@ struct gs_ctx {
     // one and clears the one the previous sort filled), the request the last sort of this lane ran with (0 = whole order) and its arguments
     uint32_t *dhist[2]; int dh_next; uint32_t *dh_dirty;
     uint32_t sort_near_req;
-    bool no_tail_sort;             // lane: this sort's near-only form must hold AT MOST ~2 x near_req records (the shared sort's exchange buffer): the histogram form, not a tail sort
+    uint32_t sort_form;            // lane: the form run_sort gave the lane's last sort (gs_sort_info::form; near_sorted is 1 for histogram and stash alike)
+    uint32_t sort_near_force;      // owner: GS_OPT_SORT_NEAR_FORCE (0 = the policy decides)
+    bool no_tail_sort;            // lane: this sort's near-only form must hold AT MOST ~2 x near_req records (the shared sort's exchange buffer): the histogram form, not a tail sort
     uint32_t status_seq, status_base; // lane: renders handed to the lane so far (which word of the ring the next one gets) / its value when the first frame of the collection under way was queued
     uint32_t *status_cur;          // lane: the word of the render handed over last (gs_frame_status_device)
     float sv_view[4], sv_cutout[16]; bool sv_has_cutout, sv_has_strip; GsSortStrip sv_strip;

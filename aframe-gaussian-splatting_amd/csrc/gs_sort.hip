@@ -1013,6 +1013,7 @@ static int run_sort(gs_ctx *const S[], const float *const view[], const float *c
     const bool stash = near && stash_ok;
     const bool spec = stash && spec_ok;
     uint32_t *const bin_hint = &gs_root(ctx)->ctl->near_bin_hint;
+    for (int k = 0; k < NF; k++) S[k]->sort_form = spec ? 2u : (stash ? 4u : (near ? 1u : (tail[k] ? 3u : 0u)));   // (gs_sort_inspect)
     // the owner's state store (edits drain every lane first: nothing changes it under a sort).  Empty: the kernels of a context that never edits
     const gs_ctx *const R = gs_root(ctx);
     const HiddenArgs hid = { R->edit_n ? R->edit_state : nullptr, R->edit_n ? (uint32_t)R->edit_n : 0u };

@@ -627,8 +627,42 @@ typedef struct gs_stats {
                                    frame to a worker thread of its pipeline lane, which does the ~18 kernel launches, so the
                                    launches of the frames in flight run in parallel; failures surface at gs_sync().  0: the
                                    calling thread launches everything itself                                            */
+#define GS_OPT_SORT_NEAR_FORCE 22 /* a test hook (tests/test_near_sort_gpu.py), host only.  P > 0: a gs_sort / gs_sort_for that is not asked for the
+                                   index list runs as a near-only sort of the nearest P positions whatever the share policy says -- share settled or
+                                   not, GS_OPT_SORT_NEAR, the size thresholds and the last kept count are not looked at.  What a near-only sort needs
+                                   stays required: compact records (no GS_OPT_WIDE_PAIRS, at most 2^25 splats) and a renderable context; without
+                                   them the sort is a whole one.  The form is chosen from the size as always (gs_sort_info.form).  Frames drawn
+                                   from such an order are right without further ado: a frame that reads more of the order than the lane holds
+                                   sorts again in full first, as after any near-only sort.  0 (default): the policy decides.  Negative values, and
+                                   values beyond 2^32 - 1: GS_E_BADARG.                                                              */
 GS_API int gs_set_option(gs_ctx *ctx, int option, int64_t value);
 GS_API int gs_get_stats(gs_ctx *ctx, gs_stats *out);
+
+/* The order of the current frame's lane AS IT LIES (a test hook; gs_download(GS_BUF_SORTED) sorts again in full first): waits for the lane,
+   reads its control block and copies the n_records entries the lane's last sort left -- the whole order's positions
+   [n_valid - n_records, n_valid) after a near-only sort, all n_kept positions (zero tail included) after a whole one.
+   out_idx may be NULL (the counts only); cap: the entries out_idx has room for (fewer than n_records: GS_E_BADARG, info is filled).
+   GS_E_STATE if the lane holds no order.
+   The call is also a COLLECTION of that sort as far as the near-only sorts' own bookkeeping goes (what gs_sync / a synchronous frame
+   do with near_overflow, spec_fail and the threshold-bin hint; the share policy sees nothing of it): after a sort whose chunk stash
+   overflowed the context keeps to the histogram form, after a collected histogram / stash / spec sort the next one may take the spec
+   form, a failed spec sort backs the form off.  An order reported incomplete is replaced by a whole sort of the same view before the
+   call returns (the flags are cleared), so the lane never keeps an order a frame must not be drawn from. */
+typedef struct gs_sort_info {
+    uint32_t form;             /* 0 whole order, 1 histogram (threshold bucket from the depth histogram, whole-length passes), 2 spec (candidates
+                                  stashed by the depth pass), 3 tail (cut at a segment boundary), 4 stash (survivors through per-chunk stashes) */
+    uint32_t near_req;         /* positions the lane's sort was asked for (0: all) */
+    uint32_t n_kept;           /* V: splats that survive the sort's culls */
+    uint32_t n_valid;          /* V': of those, the ones with a bucket inside the table (whole order, 8-byte records: not counted, = V) */
+    uint32_t n_records;        /* P: entries the lane holds */
+    uint32_t order_incomplete; /* the lane does not hold what it claims (a stash overflowed, the spec form could not vouch for its candidates) */
+    uint32_t near_overflow;    /* a chunk of the stash form had more survivors than its stash holds */
+    uint32_t spec_fail;        /* spec form: 1 the threshold-bin hint was behind, 2 a candidate stash overflowed / the depth range does not suit it */
+    uint32_t threshold_bin;    /* the context's threshold depth bin (sign-less f32 depth bits >> 20) as the last histogram / stash / spec sort of
+                                  any lane left it: what the next spec sort's depth pass goes by */
+    uint32_t reserved[3];
+} gs_sort_info;
+GS_API int gs_sort_inspect(gs_ctx *ctx, gs_sort_info *info, uint32_t *out_idx, size_t cap);
 
 /* Copy a device-resident array back to the host (parity tests / debugging). */
 #define GS_BUF_CENTER_SCALE 0 /* N x 4 f32   centerAndScaleData                                         */

@@ -9,6 +9,12 @@ Steps (lists, JSON-able; an array argument is a numpy array in process and the n
     ["wide", 0 | 1]                      GS_OPT_WIDE_PAIRS
     ["sort", view, cutout | None, out]   gs_sort -> the list `out`
     ["posted", view, cutout | None, out] gs_sort_begin + gs_sort_poll(wait) -> the list `out`
+and for tests/test_near_sort_gpu.py (renderable rows; the lane's order as it lies):
+    ["splat", rows4]                     the same rows as 32-byte .splat records (scale = size three times, alpha 255): a renderable context
+    ["state", first, states]             gs_set_state
+    ["opt", option, value]               gs_set_option
+    ["rows", out]                        the resident sort rows, as uint32 words -> `out`
+    ["near", view, cutout | None, out]   gs_sort without a list + gs_sort_inspect -> `out`: the INFO_FIELDS words, then the lane's records
 """
 import json
 import os
@@ -26,6 +32,33 @@ def expand(rows4):
     return m
 
 
+INFO_FIELDS = ("form", "near_req", "n_kept", "n_valid", "n_records", "order_incomplete", "near_overflow", "spec_fail", "threshold_bin")
+
+
+def splat_rows(rows4):
+    """rows (x, y, z, size) -> .splat records whose sort row is exactly that row (index.js:396-401: position, max scale * alpha / 255)"""
+    rows4 = np.ascontiguousarray(rows4, np.float32).reshape(-1, 4)
+    rec = np.zeros(rows4.shape[0], dtype=[("p", "<f4", 3), ("s", "<f4", 3), ("c", "u1", 4), ("q", "u1", 4)])
+    rec["p"] = rows4[:, :3]
+    rec["p"][:, 2] = -rows4[:, 2]                                   # (index.js:350-354: the row holds -z)
+    rec["s"] = rows4[:, 3:4]
+    rec["c"] = (200, 180, 160, 255)
+    rec["q"] = (255, 128, 128, 128)
+    return rec.view(np.uint8).reshape(-1, 32)
+
+
+def near_sort(c, view, cut=None):
+    """gs_sort without a list, then the lane's order as it lies -> INFO_FIELDS words + records"""
+    c.sort(view, cut, want_indices=False)
+    info, rec = c.sort_inspect()
+    return np.concatenate([np.array([info[k] for k in INFO_FIELDS], np.uint32), rec])
+
+
+def decode(words):
+    k = len(INFO_FIELDS)
+    return {f: int(w) for f, w in zip(INFO_FIELDS, words[:k])}, words[k:]
+
+
 def run_job(capi, steps, load=lambda a: a):
     """-> {out name: uint32 list} of the job's sorting steps, in one fresh context"""
     got = {}
@@ -36,6 +69,19 @@ def run_job(capi, steps, load=lambda a: a):
                 rows4 = np.ascontiguousarray(load(st[1]), np.float32).reshape(-1, 4)
                 for o in range(0, rows4.shape[0], PUSH_ROWS):
                     c.push_matrices(expand(rows4[o:o + PUSH_ROWS]))
+            elif op == "splat":
+                rows4 = np.ascontiguousarray(load(st[1]), np.float32).reshape(-1, 4)
+                for o in range(0, rows4.shape[0], PUSH_ROWS):
+                    c.push_splat(splat_rows(rows4[o:o + PUSH_ROWS]))
+            elif op == "state":
+                c.set_state(int(st[1]), load(st[2]))
+            elif op == "opt":
+                c.set_option(int(st[1]), int(st[2]))
+            elif op == "rows":
+                got[st[1]] = c.download(capi.BUF_SORT_ROWS, c.count(), np.float32, 4).view(np.uint32).reshape(-1)
+            elif op == "near":
+                assert st[3] not in got, st[3]
+                got[st[3]] = near_sort(c, load(st[1]), None if st[2] is None else load(st[2]))
             elif op == "clear":
                 c.clear()
             elif op == "wide":

@@ -36,8 +36,7 @@ takes 0.6 .. 0.8 s, the size switches 0.12 .. 0.18 s each (both references of 3 
 sort on short inputs, one at a time) with 62 contexts between them.
 
 Not covered here (so that nobody assumes it):
-  - the near-only forms (tail, histogram, stash): gs_download of the order sorts again in full, so their lists cannot be observed
-    without a new entry point -- a feature, not a test;
+  - the near-only forms (tail, histogram, stash, spec): tests/test_near_sort_gpu.py, through gs_sort_inspect;
   - paired sorts: their lists are only visible through frames, which test_blend_paths_gpu.py and test_as_benched.py compare;
   - strip sorts (gs_sort_for)."""
 import functools
@@ -228,7 +227,7 @@ def run_child(jobs, d, limit=180):
             np.save(os.path.join(d, names[id(a)] + ".npy"), a)
         return names[id(a)]
 
-    outs = [st[3] for steps in jobs for st in steps if st[0] in ("sort", "posted")]
+    outs = [st[3] for steps in jobs for st in steps if st[0] in ("sort", "posted", "near")] + [st[1] for steps in jobs for st in steps if st[0] == "rows"]
     assert len(set(outs)) == len(outs), "output names must be unique over a child's jobs"
     with open(os.path.join(d, "jobs.json"), "w") as f:
         json.dump([[[ref(x) for x in st] for st in steps] for steps in jobs], f)
