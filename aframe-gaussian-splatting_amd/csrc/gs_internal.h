@@ -4,6 +4,7 @@
 #include <stdint.h>
 #include <stdio.h>
 #include <string.h>
+#include <type_traits>
 #include "../../include/gs_splat.h"
 #include "gs_device_math.h"
 #include "gs_share.h"
@@ -88,7 +89,7 @@ struct GsControl {
     uint32_t vis_total;            // visible splats of the current binning round (k_pairs_check)
     uint32_t near_overflow;        // sticky: a near-only sort's survivors did not fit a chunk's stash (host clears; the frame is also
                                    // flagged order_incomplete + round1_missed: it is drawn again from a whole sort)
-    uint32_t spec_fail;            // sticky: a near-only sort whose depth pass stashed the candidates itself (k_sort_depth<.., SPEC>) could not vouch for
+    uint32_t spec_fail;            // sticky: a near-only sort whose depth pass stashed the candidates itself (k_sort_depth<.., SPEC, ..> / k_sort_depth_pair<.., SPEC, ..>) could not vouch for
                                    // them -- 1: the threshold hint was behind (transient), 2: a stash overflowed / the depth range does not suit
                                    // the path (the context stops using it); the frame is flagged order_incomplete + round1_missed (host clears)
     uint32_t spec_dbg;             // (GS_DEBUG_NEAR) exact threshold bin << 16 | the limit of a chunk that failed the check
@@ -156,7 +157,7 @@ struct GsFrameUniforms {           // per-render constants, passed by value to k
     float *surf_depth;
     float *surf_alpha;
     uint32_t surface;              // != 0: a surface frame -- tile lists, k_blend_surf
-    // anti-aliased splats (GS_OPT_ANTIALIAS; behind everything else once more).  Read by the host only: it picks k_project_aa
+    // anti-aliased splats (GS_OPT_ANTIALIAS; behind everything else once more).  Read by the host only: it picks k_project<.., AA>
     uint32_t antialias;            // != 0: this frame's projection writes alpha * antialias_factor into its records
 };
 
@@ -386,6 +387,8 @@ template <int NF, class F, int NT, int TWIN_MINW = 0, class Args> static inline 
         else hipLaunchKernelGGL((k_twin<F, NT, P>), dim3(grid_x, 2), dim3(NT), lds, st, a);
     }
 }
+// a run-time flag as a template argument: gs_flag(scene, [&](auto SC) { ... decltype(SC)::value ... })
+template <class Fn> static inline void gs_flag(bool on, const Fn &fn) { if (on) fn(std::true_type()); else fn(std::false_type()); }
 
 // ---- gs_prims.hip
 // One stable LSD radix pass over n = *n_ptr items on digit (key >> shift) & (2^bits-1), for NF frames (S[k]: the lane whose histogram

@@ -23,7 +23,6 @@
 //
 // The fixed-function rasteriser + ROP of the reference have no structural counterpart; parity is defined at
 // the pixel level against oracle/gs_oracle.c (docs/LAB_NOTES.md "Pixel parity argument").
-#include <type_traits>
 #include "gs_internal.h"
 #include "gs_sh.h"
 
@@ -140,7 +139,7 @@ __device__ __forceinline__ uint32_t sh_colour_word(const GsFrameUniforms &u, uin
 
 // AA (anti-aliased splats, GS_OPT_ANTIALIAS): the record's alpha float is alpha * gsm::antialias_factor -- the one word that differs; the
 // splat is written, counted and binned whatever the factor (0 included), so geometry, coverage and every count stay what they are.
-template <int ROUND, bool RUNS, bool SH = false, bool AA = false>
+template <int ROUND, bool RUNS, bool SH, bool AA>
 __device__ __forceinline__ void k_project_body(const uint32_t *__restrict__ sorted, const uint4 *__restrict__ splat,
                                                const GsFrameUniforms &u, gsm::Projected *__restrict__ proj, uint2 *__restrict__ rect,
                                                uint32_t *__restrict__ tile_count, uint32_t *__restrict__ spine,
@@ -273,36 +272,15 @@ __device__ __forceinline__ void k_project_body(const uint32_t *__restrict__ sort
     if (threadIdx.x == 0) part_vis[blockIdx.x] = s_vis;
 }
 
-template <int ROUND, bool RUNS>
+// plain, with view-dependent colour (SH), with compensated opacity (AA), or both
+template <int ROUND, bool RUNS, bool SH, bool AA>
 __global__ __launch_bounds__(GS_BLOCK) void k_project(const uint32_t *__restrict__ sorted, const uint4 *__restrict__ splat,
                                                       GsFrameUniforms u, gsm::Projected *__restrict__ proj, uint2 *__restrict__ rect,
                                                       uint32_t *__restrict__ tile_count, uint32_t *__restrict__ spine,
                                                       uint32_t *__restrict__ part_vis, const uint32_t *__restrict__ mask,
                                                       float *__restrict__ zwin, GsControl *ctl)
 {
-    k_project_body<ROUND, RUNS>(sorted, splat, u, proj, rect, tile_count, spine, part_vis, mask, zwin, ctl);
-}
-
-// ... with view-dependent colour (a kernel of its own name: the instantiations above stay what they were)
-template <int ROUND, bool RUNS>
-__global__ __launch_bounds__(GS_BLOCK) void k_project_sh(const uint32_t *__restrict__ sorted, const uint4 *__restrict__ splat,
-                                                         GsFrameUniforms u, gsm::Projected *__restrict__ proj, uint2 *__restrict__ rect,
-                                                         uint32_t *__restrict__ tile_count, uint32_t *__restrict__ spine,
-                                                         uint32_t *__restrict__ part_vis, const uint32_t *__restrict__ mask,
-                                                         float *__restrict__ zwin, GsControl *ctl)
-{
-    k_project_body<ROUND, RUNS, true>(sorted, splat, u, proj, rect, tile_count, spine, part_vis, mask, zwin, ctl);
-}
-
-// ... with compensated opacity (GS_OPT_ANTIALIAS), with or without view-dependent colour (kernels of their own name again)
-template <int ROUND, bool RUNS, bool SH>
-__global__ __launch_bounds__(GS_BLOCK) void k_project_aa(const uint32_t *__restrict__ sorted, const uint4 *__restrict__ splat,
-                                                         GsFrameUniforms u, gsm::Projected *__restrict__ proj, uint2 *__restrict__ rect,
-                                                         uint32_t *__restrict__ tile_count, uint32_t *__restrict__ spine,
-                                                         uint32_t *__restrict__ part_vis, const uint32_t *__restrict__ mask,
-                                                         float *__restrict__ zwin, GsControl *ctl)
-{
-    k_project_body<ROUND, RUNS, SH, true>(sorted, splat, u, proj, rect, tile_count, spine, part_vis, mask, zwin, ctl);
+    k_project_body<ROUND, RUNS, SH, AA>(sorted, splat, u, proj, rect, tile_count, spine, part_vis, mask, zwin, ctl);
 }
 
 // One workgroup: exclusive scan of the per-chunk totals (spine) -> chunk base offsets, I = grand total (refused and
@@ -1902,9 +1880,7 @@ int bits_for(uint32_t n) { int b = 1; while (b < 32 && (1u << b) < n) b++; retur
 // The kernels of a round as body functors (gs_internal.h: GS_BODY), each with its plain kernel: what gs_launch<NF, F, ...> launches for one frame
 // (the plain kernel) and for a pair (k_twin<F, ...>).  A NEW KERNEL gets its body, its thin __global__ wrapper, one line here and one gs_launch
 // in the sequence below -- once, for both frame counts.
-template <int ROUND, bool RUNS> GS_BODY(F_project, (k_project<ROUND, RUNS>), (k_project_body<ROUND, RUNS>));
-template <int ROUND, bool RUNS> GS_BODY(F_project_sh, (k_project_sh<ROUND, RUNS>), (k_project_body<ROUND, RUNS, true>));
-template <int ROUND, bool RUNS, bool SH> GS_BODY(F_project_aa, (k_project_aa<ROUND, RUNS, SH>), (k_project_body<ROUND, RUNS, SH, true>));
+template <int ROUND, bool RUNS, bool SH, bool AA> GS_BODY(F_project, (k_project<ROUND, RUNS, SH, AA>), (k_project_body<ROUND, RUNS, SH, AA>));
 template <int ROUND> GS_BODY(F_row_scan, (k_row_scan<ROUND>), (k_row_scan_body<ROUND>));
 template <int ROUND> GS_BODY(F_emit_runs, (k_emit_runs<ROUND>), (k_emit_runs_body<ROUND>));
 template <int ROUND> GS_BODY(F_seg_count, (k_seg_count<ROUND>), (k_seg_count_body<ROUND>));
@@ -1917,9 +1893,6 @@ template <int ROUND, bool SCENE> GS_BODY(F_blend_px, (k_blend_px<ROUND, SCENE>),
 // single-frame only (gs_frames_batchable keeps such frames out of pairs; launch_blend<.., 2> refuses them): there is no twin kernel of these
 template <int ROUND, bool SCENE, bool SUB> GS_BODY(F_blend_count, (k_blend<true, ROUND, SCENE, SUB>), (k_blend_body<true, ROUND, SCENE, SUB>));
 template <int ROUND, bool SCENE> GS_BODY(F_blend_surf, (k_blend_surf<ROUND, SCENE>), (k_blend_body<false, ROUND, SCENE, false, false, true>));
-
-// a run-time flag as a template argument: gs_flag(scene, [&](auto SC) { ... decltype(SC)::value ... })
-template <class Fn> inline void gs_flag(bool on, const Fn &fn) { if (on) fn(std::true_type()); else fn(std::false_type()); }
 
 // The sequences below draw NF frames that take the same path, every kernel launched once: S[k] is frame k's lane (sibling lanes on ONE
 // stream -- S[0]'s --, each with its own scratch, control block and output), U[k] its uniforms, out[k] its image.  Whatever decides the PATH
@@ -2032,11 +2005,9 @@ void launch_project(gs_ctx *const S[], const GsFrameUniforms F[], uint32_t g)
         return gs_pack_make((const uint32_t *)S[k]->sorted, (const uint4 *)S[k]->splat, F[k], S[k]->proj, S[k]->rect, S[k]->tile_count, RUNS ? S[k]->row_cnt : S[k]->spine,
                             S[k]->part_vis, (const uint32_t *)S[k]->unsat_mask, S[k]->zwin, S[k]->ctl);
     };
-    if (F[0].antialias) {
-        if (F[0].sh_degree) gs_launch<NF, F_project_aa<ROUND, RUNS, true>, GS_BLOCK>(g, st, 0, args);
-        else gs_launch<NF, F_project_aa<ROUND, RUNS, false>, GS_BLOCK>(g, st, 0, args);
-    } else if (F[0].sh_degree) gs_launch<NF, F_project_sh<ROUND, RUNS>, GS_BLOCK>(g, st, 0, args);
-    else gs_launch<NF, F_project<ROUND, RUNS>, GS_BLOCK>(g, st, 0, args);
+    gs_flag(F[0].sh_degree != 0, [&](auto SH) { gs_flag(F[0].antialias != 0, [&](auto AA) {
+        gs_launch<NF, F_project<ROUND, RUNS, decltype(SH)::value, decltype(AA)::value>, GS_BLOCK>(g, st, 0, args);
+    }); });
 }
 
 // one round with span lists: project (+ row counts) -> row scan -> runs -> lists -> blend (row walk: no lists)
@@ -2233,19 +2204,14 @@ int gs_run_render(gs_ctx *ctx, const GsFrameUniforms &u, uint8_t *device_out)
         GS_HIP(hipMemsetAsync(ctx->tile_range, 0, sizeof(uint2) * ntiles, st));
         GsFrameUniforms ub = u; ub.near_count = 0xFFFFFFFFu;
         GS_PROF_RECORD(ctx, 3); GS_PROF_RECORD(ctx, 4);
-        if (ub.surface) {
-            if (ub.has_scene_rgba)
-                hipLaunchKernelGGL((k_blend_surf<0, true>), dim3(ntiles), dim3(64), 0, st, ctx->tile_range, ctx->pair_a, ctx->proj, ub, out,
+        gs_flag(ub.has_scene_rgba != 0, [&](auto SC) {
+            if (ub.surface)
+                hipLaunchKernelGGL((k_blend_surf<0, decltype(SC)::value>), dim3(ntiles), dim3(64), 0, st, ctx->tile_range, ctx->pair_a, ctx->proj, ub, out,
                                    ctx->state, ctx->unsat_mask, ctx->zwin, ctx->scene_depth, ctx->scene_rgba, ctx->ctl, (const uint32_t *)ctx->sorted);
             else
-                hipLaunchKernelGGL((k_blend_surf<0, false>), dim3(ntiles), dim3(64), 0, st, ctx->tile_range, ctx->pair_a, ctx->proj, ub, out,
-                                   ctx->state, ctx->unsat_mask, ctx->zwin, ctx->scene_depth, ctx->scene_rgba, ctx->ctl, (const uint32_t *)ctx->sorted);
-        } else if (ub.has_scene_rgba)
-            hipLaunchKernelGGL((k_blend<false, 0, true>), dim3(ntiles), dim3(64), 0, st, ctx->tile_range, ctx->pair_a, ctx->proj, ub, out,
-                               ctx->state, ctx->unsat_mask, ctx->zwin, ctx->scene_depth, ctx->scene_rgba, ctx->ctl);
-        else
-            hipLaunchKernelGGL((k_blend<false, 0, false>), dim3(ntiles), dim3(64), 0, st, ctx->tile_range, ctx->pair_a, ctx->proj, ub, out,
-                               ctx->state, ctx->unsat_mask, ctx->zwin, ctx->scene_depth, ctx->scene_rgba, ctx->ctl);
+                hipLaunchKernelGGL((k_blend<false, 0, decltype(SC)::value>), dim3(ntiles), dim3(64), 0, st, ctx->tile_range, ctx->pair_a, ctx->proj, ub, out,
+                                   ctx->state, ctx->unsat_mask, ctx->zwin, ctx->scene_depth, ctx->scene_rgba, ctx->ctl);
+        });
         GS_HIP(hipGetLastError());
         GS_PROF_RECORD(ctx, 5);
     }

@@ -7,7 +7,6 @@
 // neither counted nor scattered), so pass B runs over the V kept splats.  Kept splats whose bucket falls outside
 // [0,65535] (f32 rounding of the stored depth >> depth range) carry key 65536, sort behind every bucket and store 0 --
 // exactly like the reference's out-of-bounds typed-array writes leave 0 in the tail [V',V) of its result.
-#include <type_traits>
 #include "gs_internal.h"
 
 namespace {
@@ -135,67 +134,106 @@ __device__ __forceinline__ bool strip_may_touch(const StripUniforms &s, float x,
                                    // has not moved: the threshold BUCKET lies inside the next bin; the second is the margin for a moving camera)
 #endif
 #define GS_SPEC_GROUP 32u          // chunks (of 1024 items) one k_near_filter workgroup compacts: 4096 stash slots
-// the stash step of one chunk: ranks by (row, wavefront, lane) = index order
-#define GS_SPEC_STASH_STEP(SP, FB, SROW, STASH, CNT, CTL, LIMREC) do {                                                                     \
-        uint32_t bef_[GS_DEPTH_IPT];                                                                                             \
-        _Pragma("unroll") for (int r = 0; r < GS_DEPTH_IPT; r++) {                                                                \
-            const unsigned long long bal_ = __ballot(SP[r]);                                                                     \
-            bef_[r] = (uint32_t)__popcll(bal_ & ((1ull << (threadIdx.x & 63)) - 1ull));                                           \
-            if ((threadIdx.x & 63) == 0) SROW[r * 4 + (threadIdx.x >> 6)] = (uint32_t)__popcll(bal_);                              \
-        }                                                                                                                        \
-        __syncthreads();                                                                                                         \
-        if (threadIdx.x < 64) {                                                                                                  \
-            const uint32_t cv_ = threadIdx.x < 4u * GS_DEPTH_IPT ? SROW[threadIdx.x] : 0u;                                        \
-            uint32_t inc_ = cv_;                                                                                                 \
-            for (int d_ = 1; d_ < 64; d_ <<= 1) { const uint32_t t_ = __shfl_up(inc_, d_, 64); if ((int)threadIdx.x >= d_) inc_ += t_; } \
-            if (threadIdx.x < 4u * GS_DEPTH_IPT) SROW[threadIdx.x] = inc_ - cv_;                                                  \
-            const uint32_t total_ = __shfl(inc_, 63, 64);                                                                        \
-            if (threadIdx.x == 0) {                                                                                              \
-                CNT[c] = (total_ < GS_SPEC_SLOT ? total_ : GS_SPEC_SLOT) | (LIMREC << 16);   /* the bins THIS chunk was stashed by: checked per chunk */ \
-                if (total_ > GS_SPEC_SLOT) CTL->spec_fail = 2u;                                                                   \
-            }                                                                                                                    \
-        }                                                                                                                        \
-        __syncthreads();                                                                                                         \
-        _Pragma("unroll") for (int r = 0; r < GS_DEPTH_IPT; r++) {                                                                \
-            if (SP[r]) {                                                                                                         \
-                const uint32_t slot_ = SROW[r * 4 + (threadIdx.x >> 6)] + bef_[r];                                                \
-                if (slot_ < GS_SPEC_SLOT) STASH[(size_t)c * GS_SPEC_SLOT + slot_] = make_uint2(FB[r], c * DCHUNK + r * GS_BLOCK + threadIdx.x); \
-            }                                                                                                                    \
-        }                                                                                                                        \
-        __syncthreads();                                                                                                         \
-    } while (0)
 
-template <bool STRIP, bool SPEC, bool HID = false>                // (instantiations: the strip test / the stash / the state bytes must not cost the plain sort registers)
-__device__ __forceinline__ void k_sort_depth_body(const float4 *__restrict__ rows, const float *__restrict__ bound_r, uint32_t n, const SortUniforms &u, const StripUniforms &su,
-                                                  float *__restrict__ depth_out, unsigned long long *__restrict__ part_min,
-                                                  unsigned long long *__restrict__ part_max, uint32_t *__restrict__ part_cnt, DepthHist dh,
-                                                  uint2 *__restrict__ spec_stash, uint32_t *__restrict__ spec_cnt, const uint32_t *__restrict__ bin_hint, GsControl *ctl,
-                                                  HiddenArgs hid = HiddenArgs{ nullptr, 0u })
+// What belongs to ONE view of the pass: its uniforms, where its depths, partials and histogram go, and (SPEC) its stash
+struct DepthView {
+    SortUniforms u; StripUniforms su;
+    float *depth; unsigned long long *part_min, *part_max; uint32_t *part_cnt; DepthHist dh;
+    uint2 *stash; uint32_t *cnt; const uint32_t *bin_hint; GsControl *ctl;     // SPEC: candidates, per-chunk counts, the threshold-bin hint
+};
+template <int NV> struct DepthViews { DepthView v[NV]; };        // the views of one sweep over the splats
+// ... and what a thread carries for one view: min / max / count of what it kept, and (SPEC) the chunk's depth bits and stash flags
+struct DepthAcc { double mn, mx; uint32_t cnt, lim, rec; uint32_t fb[GS_DEPTH_IPT]; bool sp[GS_DEPTH_IPT]; };
+constexpr uint32_t GS_DEPTH_CHUNK = GS_DEPTH_IPT * GS_BLOCK;     // this pass' own chunking (no histogram depends on it)
+
+// item r of a chunk (splat i: row m, bound sigma; shown = not hidden) as view v sees it
+template <bool STRIP, bool SPEC>
+__device__ __forceinline__ void depth_view_step(const DepthView &v, const float4 m, float sigma, bool shown, uint32_t i, int r, uint32_t *s_dh, DepthAcc &a)
 {
-    __shared__ unsigned long long s_min, s_max;
-    __shared__ uint32_t s_cnt;
-    __shared__ uint32_t s_srow[SPEC ? 4 * GS_DEPTH_IPT : 1];
-    // the bins this workgroup stashes: up to the last sort's threshold bin + pad.  The hint is one word shared by the context's lanes
-    // and may change while this kernel runs: every chunk records the limit it was stashed by, and the filter checks chunk by chunk
-    const uint32_t hint_ = SPEC ? *bin_hint : 0u;
-    const uint32_t spec_lim = (SPEC && hint_ != 0xFFFFFFFFu) ? hint_ + GS_SPEC_PAD : 0u, spec_rec = (SPEC && hint_ != 0xFFFFFFFFu) ? spec_lim : 0xFFFFu;
-    extern __shared__ uint32_t s_dh[];                           // GS_DEPTH_BINS words for a near-only sort, none otherwise (LDS the other frames' blends can use)
-    if (threadIdx.x == 0) { s_min = ~0ull; s_max = 0ull; s_cnt = 0; }
-    depth_hist_begin(dh, s_dh);
+    const double d = gsm::view_depth(v.u.view, m.x, m.y, m.z);
+    // a hidden splat is a splat outside the cutout (index.js:548)
+    const bool inside = shown && (v.u.has_cutout ? (v.u.has_cutout == 2 ? gsm::in_cutout_affine(v.u.cutout, m.x, m.y, m.z) : gsm::in_cutout(v.u.cutout, m.x, m.y, m.z)) : true);
+    const bool keep = gsm::sort_keep(d, m.w, inside);
+    // the bucket scale comes from EVERY splat the reference keeps (index.js:552-553), so a strip's order is the
+    // reference's order restricted to the strip's splats; only those are handed on
+    const bool mine = keep && (!STRIP || strip_may_touch(v.su, m.x, m.y, m.z, sigma));
+    if (!SPEC) v.depth[i] = mine ? (float)d : INFINITY;
+    if (mine && v.dh.fill) atomicAdd(&s_dh[depth_bin((float)d)], 1u);
+    if (SPEC) { a.fb[r] = __float_as_uint((float)d); a.sp[r] = mine && depth_bin((float)d) <= a.lim; }
+    if (keep) {
+        a.mn = min_f64(a.mn, d); a.mx = max_f64(a.mx, d);
+        if (mine) a.cnt++;
+    }
+}
+
+// the stash step of chunk c for one view: ranks by (row, wavefront, lane) = index order
+__device__ __forceinline__ void spec_stash_step(const DepthView &v, const DepthAcc &a, uint32_t c, uint32_t *s_srow)
+{
+    uint32_t bef[GS_DEPTH_IPT];
+#pragma unroll
+    for (int r = 0; r < GS_DEPTH_IPT; r++) {
+        const unsigned long long bal = __ballot(a.sp[r]);
+        bef[r] = (uint32_t)__popcll(bal & ((1ull << (threadIdx.x & 63)) - 1ull));
+        if ((threadIdx.x & 63) == 0) s_srow[r * 4 + (threadIdx.x >> 6)] = (uint32_t)__popcll(bal);
+    }
     __syncthreads();
-    constexpr uint32_t DCHUNK = GS_DEPTH_IPT * GS_BLOCK;         // this kernel's own chunking (no histogram depends on it)
-    const uint32_t nchunks = (n + DCHUNK - 1) / DCHUNK;
+    if (threadIdx.x < 64) {
+        const uint32_t cv = threadIdx.x < 4u * GS_DEPTH_IPT ? s_srow[threadIdx.x] : 0u;
+        uint32_t inc = cv;
+        for (int d = 1; d < 64; d <<= 1) { const uint32_t t = __shfl_up(inc, d, 64); if ((int)threadIdx.x >= d) inc += t; }
+        if (threadIdx.x < 4u * GS_DEPTH_IPT) s_srow[threadIdx.x] = inc - cv;
+        const uint32_t total = __shfl(inc, 63, 64);
+        if (threadIdx.x == 0) {
+            v.cnt[c] = (total < GS_SPEC_SLOT ? total : GS_SPEC_SLOT) | (a.rec << 16);   // the bins THIS chunk was stashed by: checked per chunk
+            if (total > GS_SPEC_SLOT) v.ctl->spec_fail = 2u;
+        }
+    }
+    __syncthreads();
+#pragma unroll
+    for (int r = 0; r < GS_DEPTH_IPT; r++) {
+        if (a.sp[r]) {
+            const uint32_t slot = s_srow[r * 4 + (threadIdx.x >> 6)] + bef[r];
+            if (slot < GS_SPEC_SLOT) v.stash[(size_t)c * GS_SPEC_SLOT + slot] = make_uint2(a.fb[r], c * GS_DEPTH_CHUNK + r * GS_BLOCK + threadIdx.x);
+        }
+    }
+    __syncthreads();
+}
+
+// The pass for NV views in ONE sweep over the splats: rows, bounds and state bytes are loaded once per item, then every view takes its
+// step.  NV = 2 is the two frames of a pair (GS_OPT_FRAME_BATCH): at 20 M splats the sort rows are 320 MB of the 400 MB this pass
+// streams per frame, and both frames read the same rows -- one read, two view rows / cutout matrices, two depth arrays and two sets
+// of partials (20 M @ 4K: 2464 -> 2606 frames/s; no difference at 1 M, where the rows are cache-resident).
+// (instantiations: the strip test / the stash / the state bytes must not cost the plain sort registers)
+template <int NV, bool STRIP, bool SPEC, bool HID>
+__device__ __forceinline__ void k_sort_depth_body(const float4 *__restrict__ rows, const float *__restrict__ bound_r, uint32_t n, const DepthViews<NV> &vs, HiddenArgs hid)
+{
+    __shared__ unsigned long long s_min[NV], s_max[NV];
+    __shared__ uint32_t s_cnt[NV];
+    __shared__ uint32_t s_srow[NV][SPEC ? 4 * GS_DEPTH_IPT : 1];
+    extern __shared__ uint32_t s_dh[];                           // GS_DEPTH_BINS words per view for a near-only sort, none otherwise (LDS the other frames' blends can use)
     // min / max of the kept depths as doubles (kept depths are finite and negative: sort_keep), encoded once per wavefront at the end
     // -- on the ordered-u64 encoding a splat cost two 64-bit compares and four selects
-    double mn = INFINITY, mx = -INFINITY;
-    uint32_t cnt = 0;
+    DepthAcc acc[NV];
+#pragma unroll
+    for (int k = 0; k < NV; k++) {
+        // the bins this workgroup stashes: up to the last sort's threshold bin + pad.  The hint is one word shared by the context's lanes
+        // and may change while this kernel runs: every chunk records the limit it was stashed by, and the filter checks chunk by chunk
+        const uint32_t hint = SPEC ? *vs.v[k].bin_hint : 0u;
+        acc[k].lim = (SPEC && hint != 0xFFFFFFFFu) ? hint + GS_SPEC_PAD : 0u;
+        acc[k].rec = (SPEC && hint != 0xFFFFFFFFu) ? acc[k].lim : 0xFFFFu;
+        acc[k].mn = INFINITY; acc[k].mx = -INFINITY; acc[k].cnt = 0;
+        depth_hist_begin(vs.v[k].dh, s_dh + k * GS_DEPTH_BINS);
+    }
+    if (threadIdx.x < NV) { s_min[threadIdx.x] = ~0ull; s_max[threadIdx.x] = 0ull; s_cnt[threadIdx.x] = 0; }
+    __syncthreads();
+    const uint32_t nchunks = (n + GS_DEPTH_CHUNK - 1) / GS_DEPTH_CHUNK;
     for (uint32_t c = blockIdx.x; c < nchunks; c += gridDim.x) {
         float4 mm[GS_DEPTH_IPT];                                     // all loads first: their latencies overlap
         float sg[GS_DEPTH_IPT];
         uint8_t hs[HID ? GS_DEPTH_IPT : 1];
 #pragma unroll
         for (int r = 0; r < GS_DEPTH_IPT; r++) {
-            const uint32_t i = c * DCHUNK + r * GS_BLOCK + threadIdx.x;
+            const uint32_t i = c * GS_DEPTH_CHUNK + r * GS_BLOCK + threadIdx.x;
             // (unconditional, the index clamped: a conditional load put each item's wait and f64 conversions into its own branch, so the
             // four loads of a thread went out one after the other; items beyond n are dropped below)
             const uint32_t ic = i < n ? i : n - 1u;
@@ -203,178 +241,62 @@ __device__ __forceinline__ void k_sort_depth_body(const float4 *__restrict__ row
             sg[r] = STRIP ? bound_r[ic] : 0.0f;
             if (HID) hs[r] = hid.state[ic];                              // (with the rows: same index, same clamp)
         }
-        uint32_t fb[GS_DEPTH_IPT];
-        bool sp[GS_DEPTH_IPT];
 #pragma unroll
-        for (int r = 0; r < GS_DEPTH_IPT; r++) { fb[r] = 0u; sp[r] = false; }
+        for (int k = 0; k < NV; k++) {
+#pragma unroll
+            for (int r = 0; r < GS_DEPTH_IPT; r++) { acc[k].fb[r] = 0u; acc[k].sp[r] = false; }
+        }
 #pragma unroll
         for (int r = 0; r < GS_DEPTH_IPT; r++) {
-            const uint32_t i = c * DCHUNK + r * GS_BLOCK + threadIdx.x;
+            const uint32_t i = c * GS_DEPTH_CHUNK + r * GS_BLOCK + threadIdx.x;
             if (i < n) {
-                const float4 m = mm[r];
-                const double d = gsm::view_depth(u.view, m.x, m.y, m.z);
-                bool inside = u.has_cutout ? (u.has_cutout == 2 ? gsm::in_cutout_affine(u.cutout, m.x, m.y, m.z) : gsm::in_cutout(u.cutout, m.x, m.y, m.z)) : true;
-                if (HID && i < hid.rows && (hs[r] & GS_STATE_HIDDEN)) inside = false;   // a hidden splat is a splat outside the cutout (index.js:548)
-                const bool keep = gsm::sort_keep(d, m.w, inside);
-                // the bucket scale comes from EVERY splat the reference keeps (index.js:552-553), so a strip's order is the
-                // reference's order restricted to the strip's splats; only those are handed on
-                const bool mine = keep && (!STRIP || strip_may_touch(su, m.x, m.y, m.z, sg[r]));
-                if (!SPEC) depth_out[i] = mine ? (float)d : INFINITY;
-                if (mine && dh.fill) atomicAdd(&s_dh[depth_bin((float)d)], 1u);
-                if (SPEC) { fb[r] = __float_as_uint((float)d); sp[r] = mine && depth_bin((float)d) <= spec_lim; }
-                if (keep) {
-                    mn = min_f64(mn, d); mx = max_f64(mx, d);
-                    if (mine) cnt++;
-                }
+                const bool shown = !(HID && i < hid.rows && (hs[r] & GS_STATE_HIDDEN));   // (one state load for all views)
+#pragma unroll
+                for (int k = 0; k < NV; k++) depth_view_step<STRIP, SPEC>(vs.v[k], mm[r], sg[r], shown, i, r, s_dh + k * GS_DEPTH_BINS, acc[k]);
             }
         }
-        if (SPEC) GS_SPEC_STASH_STEP(sp, fb, s_srow, spec_stash, spec_cnt, ctl, spec_rec);
+        if (SPEC) {
+#pragma unroll
+            for (int k = 0; k < NV; k++) spec_stash_step(vs.v[k], acc[k], c, s_srow[k]);
+        }
     }
 #pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) {                           // wavefront butterfly, then one LDS atomic per wave
-        const double omn = shfl_xor_f64(mn, m), omx = shfl_xor_f64(mx, m);
-        mn = omn < mn ? omn : mn; mx = omx > mx ? omx : mx;
-        cnt += __shfl_xor(cnt, m, 64);
+    for (int m = 32; m >= 1; m >>= 1) {                           // wavefront butterfly, then one LDS atomic per wave and view
+#pragma unroll
+        for (int k = 0; k < NV; k++) {
+            const double omn = shfl_xor_f64(acc[k].mn, m), omx = shfl_xor_f64(acc[k].mx, m);
+            acc[k].mn = omn < acc[k].mn ? omn : acc[k].mn; acc[k].mx = omx > acc[k].mx ? omx : acc[k].mx;
+            acc[k].cnt += __shfl_xor(acc[k].cnt, m, 64);
+        }
     }
-    if ((threadIdx.x & 63) == 0 && mx > -INFINITY) {              // (the wave kept something)
-        atomicMin(&s_min, gsm::f64_to_ordered(mn)); atomicMax(&s_max, gsm::f64_to_ordered(mx)); atomicAdd(&s_cnt, cnt);
+#pragma unroll
+    for (int k = 0; k < NV; k++) {
+        if ((threadIdx.x & 63) == 0 && acc[k].mx > -INFINITY) {   // (the wave kept something)
+            atomicMin(&s_min[k], gsm::f64_to_ordered(acc[k].mn)); atomicMax(&s_max[k], gsm::f64_to_ordered(acc[k].mx)); atomicAdd(&s_cnt[k], acc[k].cnt);
+        }
     }
     __syncthreads();
-    if (threadIdx.x == 0) { part_min[blockIdx.x] = s_min; part_max[blockIdx.x] = s_max; part_cnt[blockIdx.x] = s_cnt; }
-    depth_hist_end(dh, s_dh);
+#pragma unroll
+    for (int k = 0; k < NV; k++) {
+        if (threadIdx.x == 0) { vs.v[k].part_min[blockIdx.x] = s_min[k]; vs.v[k].part_max[blockIdx.x] = s_max[k]; vs.v[k].part_cnt[blockIdx.x] = s_cnt[k]; }
+        depth_hist_end(vs.v[k].dh, s_dh + k * GS_DEPTH_BINS);
+    }
 }
 
-template <bool STRIP, bool SPEC>
-__global__ __launch_bounds__(GS_BLOCK) void k_sort_depth(const float4 *__restrict__ rows, const float *__restrict__ bound_r, uint32_t n, SortUniforms u, StripUniforms su,
-                                                         float *__restrict__ depth_out, unsigned long long *__restrict__ part_min,
-                                                         unsigned long long *__restrict__ part_max, uint32_t *__restrict__ part_cnt, DepthHist dh,
-                                                         uint2 *__restrict__ spec_stash, uint32_t *__restrict__ spec_cnt, const uint32_t *__restrict__ bin_hint, GsControl *ctl)
+// one view per sweep: a single frame, and -- twinned by gs_launch<2, ..> -- the frames of a short pair (run_sort)
+template <bool STRIP, bool SPEC, bool HID>
+__global__ __launch_bounds__(GS_BLOCK) void k_sort_depth(const float4 *__restrict__ rows, const float *__restrict__ bound_r, uint32_t n, DepthViews<1> vs, HiddenArgs hid)
 {
-    k_sort_depth_body<STRIP, SPEC>(rows, bound_r, n, u, su, depth_out, part_min, part_max, part_cnt, dh, spec_stash, spec_cnt, bin_hint, ctl);
+    k_sort_depth_body<1, STRIP, SPEC, HID>(rows, bound_r, n, vs, hid);
 }
-// ... and with the state store (a kernel of its own: the one above keeps its argument list)
-template <bool STRIP, bool SPEC>
-__global__ __launch_bounds__(GS_BLOCK) void k_sort_depth_hid(const float4 *__restrict__ rows, const float *__restrict__ bound_r, uint32_t n, SortUniforms u, StripUniforms su,
-                                                             float *__restrict__ depth_out, unsigned long long *__restrict__ part_min,
-                                                             unsigned long long *__restrict__ part_max, uint32_t *__restrict__ part_cnt, DepthHist dh,
-                                                             uint2 *__restrict__ spec_stash, uint32_t *__restrict__ spec_cnt, const uint32_t *__restrict__ bin_hint, GsControl *ctl,
-                                                             HiddenArgs hid)
-{
-    k_sort_depth_body<STRIP, SPEC, true>(rows, bound_r, n, u, su, depth_out, part_min, part_max, part_cnt, dh, spec_stash, spec_cnt, bin_hint, ctl, hid);
-}
-
-// The same pass for the two frames of a pair (GS_OPT_FRAME_BATCH) in ONE sweep over the splats: at 20 M splats the sort rows are
-// 320 MB of the 400 MB this pass streams per frame, and both frames read the same rows -- one read, two view rows / cutout
-// matrices, two depth arrays and two sets of partials (20 M @ 4K: 2464 -> 2606 frames/s; no difference at 1 M, where the rows
-// are cache-resident).  Per frame exactly the arithmetic of k_sort_depth.
-struct SpecArgs { uint2 *stash; uint32_t *cnt; const uint32_t *bin_hint; GsControl *ctl; };
+// both views of a pair in one sweep
 #ifndef GS_DEPTH_PAIR_MIN_N
 #define GS_DEPTH_PAIR_MIN_N (1u << 22)   // paired sorts of fewer splats run k_sort_depth's body twice (run_sort<2>)
 #endif
 template <bool STRIP, bool SPEC, bool HID>
-__device__ __forceinline__ void k_sort_depth_pair_body(const float4 *__restrict__ rows, const float *__restrict__ bound_r, uint32_t n,
-                                                              const SortUniforms &u0, const SortUniforms &u1, const StripUniforms &su0, const StripUniforms &su1,
-                                                              float *__restrict__ depth0, float *__restrict__ depth1,
-                                                              unsigned long long *__restrict__ pmin0, unsigned long long *__restrict__ pmax0, uint32_t *__restrict__ pcnt0,
-                                                              unsigned long long *__restrict__ pmin1, unsigned long long *__restrict__ pmax1, uint32_t *__restrict__ pcnt1,
-                                                              DepthHist dh0, DepthHist dh1, SpecArgs sa0, SpecArgs sa1, HiddenArgs hid)
+__global__ __launch_bounds__(GS_BLOCK) void k_sort_depth_pair(const float4 *__restrict__ rows, const float *__restrict__ bound_r, uint32_t n, DepthViews<2> vs, HiddenArgs hid)
 {
-    __shared__ unsigned long long s_min[2], s_max[2];
-    __shared__ uint32_t s_cnt[2];
-    __shared__ uint32_t s_srow0[SPEC ? 4 * GS_DEPTH_IPT : 1], s_srow1[SPEC ? 4 * GS_DEPTH_IPT : 1];
-    const uint32_t h0_ = SPEC ? *sa0.bin_hint : 0u, h1_ = SPEC ? *sa1.bin_hint : 0u;
-    const uint32_t lim0 = (SPEC && h0_ != 0xFFFFFFFFu) ? h0_ + GS_SPEC_PAD : 0u, rec0 = (SPEC && h0_ != 0xFFFFFFFFu) ? lim0 : 0xFFFFu;
-    const uint32_t lim1 = (SPEC && h1_ != 0xFFFFFFFFu) ? h1_ + GS_SPEC_PAD : 0u, rec1 = (SPEC && h1_ != 0xFFFFFFFFu) ? lim1 : 0xFFFFu;
-    extern __shared__ uint32_t s_dh0[];                          // 2 x GS_DEPTH_BINS words for near-only sorts, none otherwise
-    uint32_t *const s_dh1 = s_dh0 + GS_DEPTH_BINS;
-    if (threadIdx.x < 2) { s_min[threadIdx.x] = ~0ull; s_max[threadIdx.x] = 0ull; s_cnt[threadIdx.x] = 0; }
-    depth_hist_begin(dh0, s_dh0); depth_hist_begin(dh1, s_dh1);
-    __syncthreads();
-    constexpr uint32_t DCHUNK = GS_DEPTH_IPT * GS_BLOCK;
-    const uint32_t nchunks = (n + DCHUNK - 1) / DCHUNK;
-    double mn0 = INFINITY, mx0 = -INFINITY, mn1 = INFINITY, mx1 = -INFINITY;
-    uint32_t cnt0 = 0, cnt1 = 0;
-    for (uint32_t c = blockIdx.x; c < nchunks; c += gridDim.x) {
-        float4 mm[GS_DEPTH_IPT];
-        float sg[GS_DEPTH_IPT];
-        uint8_t hs[HID ? GS_DEPTH_IPT : 1];
-#pragma unroll
-        for (int r = 0; r < GS_DEPTH_IPT; r++) {
-            const uint32_t i = c * DCHUNK + r * GS_BLOCK + threadIdx.x;
-            // (unconditional, the index clamped: a conditional load put each item's wait and f64 conversions into its own branch, so the
-            // four loads of a thread went out one after the other; items beyond n are dropped below)
-            const uint32_t ic = i < n ? i : n - 1u;
-            mm[r] = rows[ic];
-            sg[r] = STRIP ? bound_r[ic] : 0.0f;
-            if (HID) hs[r] = hid.state[ic];                              // (with the rows: same index, same clamp)
-        }
-        uint32_t fb0[GS_DEPTH_IPT], fb1[GS_DEPTH_IPT];
-        bool sp0[GS_DEPTH_IPT], sp1[GS_DEPTH_IPT];
-#pragma unroll
-        for (int r = 0; r < GS_DEPTH_IPT; r++) { fb0[r] = fb1[r] = 0u; sp0[r] = sp1[r] = false; }
-#pragma unroll
-        for (int r = 0; r < GS_DEPTH_IPT; r++) {
-            const uint32_t i = c * DCHUNK + r * GS_BLOCK + threadIdx.x;
-            if (i < n) {
-                const float4 m = mm[r];
-                const bool shown = !(HID && i < hid.rows && (hs[r] & GS_STATE_HIDDEN));   // (one store for both frames)
-#define GS_DEPTH_ONE(U, SU, OUT, MN, MX, CNT, DH, SDH, FB, SP, LIM) do {                                                \
-                    const double d = gsm::view_depth(U.view, m.x, m.y, m.z);                                               \
-                    const bool inside = shown && (U.has_cutout ? (U.has_cutout == 2 ? gsm::in_cutout_affine(U.cutout, m.x, m.y, m.z) : gsm::in_cutout(U.cutout, m.x, m.y, m.z)) : true); \
-                    const bool keep = gsm::sort_keep(d, m.w, inside);                                                      \
-                    const bool mine = keep && (!STRIP || strip_may_touch(SU, m.x, m.y, m.z, sg[r]));            \
-                    if (!SPEC) OUT[i] = mine ? (float)d : INFINITY;                                                        \
-                    if (mine && DH.fill) atomicAdd(&SDH[depth_bin((float)d)], 1u);                                         \
-                    if (SPEC) { FB[r] = __float_as_uint((float)d); SP[r] = mine && depth_bin((float)d) <= LIM; }           \
-                    if (keep) { MN = min_f64(MN, d); MX = max_f64(MX, d); if (mine) CNT++; }                                 \
-                } while (0)
-                GS_DEPTH_ONE(u0, su0, depth0, mn0, mx0, cnt0, dh0, s_dh0, fb0, sp0, lim0);
-                GS_DEPTH_ONE(u1, su1, depth1, mn1, mx1, cnt1, dh1, s_dh1, fb1, sp1, lim1);
-#undef GS_DEPTH_ONE
-            }
-        }
-        if (SPEC) {
-            GS_SPEC_STASH_STEP(sp0, fb0, s_srow0, sa0.stash, sa0.cnt, sa0.ctl, rec0);
-            GS_SPEC_STASH_STEP(sp1, fb1, s_srow1, sa1.stash, sa1.cnt, sa1.ctl, rec1);
-        }
-    }
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) {
-        const double a0 = shfl_xor_f64(mn0, m), b0 = shfl_xor_f64(mx0, m), a1 = shfl_xor_f64(mn1, m), b1 = shfl_xor_f64(mx1, m);
-        mn0 = a0 < mn0 ? a0 : mn0; mx0 = b0 > mx0 ? b0 : mx0; mn1 = a1 < mn1 ? a1 : mn1; mx1 = b1 > mx1 ? b1 : mx1;
-        cnt0 += __shfl_xor(cnt0, m, 64); cnt1 += __shfl_xor(cnt1, m, 64);
-    }
-    if ((threadIdx.x & 63) == 0) {
-        if (mx0 > -INFINITY) { atomicMin(&s_min[0], gsm::f64_to_ordered(mn0)); atomicMax(&s_max[0], gsm::f64_to_ordered(mx0)); atomicAdd(&s_cnt[0], cnt0); }
-        if (mx1 > -INFINITY) { atomicMin(&s_min[1], gsm::f64_to_ordered(mn1)); atomicMax(&s_max[1], gsm::f64_to_ordered(mx1)); atomicAdd(&s_cnt[1], cnt1); }
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        pmin0[blockIdx.x] = s_min[0]; pmax0[blockIdx.x] = s_max[0]; pcnt0[blockIdx.x] = s_cnt[0];
-        pmin1[blockIdx.x] = s_min[1]; pmax1[blockIdx.x] = s_max[1]; pcnt1[blockIdx.x] = s_cnt[1];
-    }
-    depth_hist_end(dh0, s_dh0); depth_hist_end(dh1, s_dh1);
-}
-template <bool STRIP, bool SPEC>
-__global__ __launch_bounds__(GS_BLOCK) void k_sort_depth_pair(const float4 *__restrict__ rows, const float *__restrict__ bound_r, uint32_t n,
-                                                              SortUniforms u0, SortUniforms u1, StripUniforms su0, StripUniforms su1,
-                                                              float *__restrict__ depth0, float *__restrict__ depth1,
-                                                              unsigned long long *__restrict__ pmin0, unsigned long long *__restrict__ pmax0, uint32_t *__restrict__ pcnt0,
-                                                              unsigned long long *__restrict__ pmin1, unsigned long long *__restrict__ pmax1, uint32_t *__restrict__ pcnt1,
-                                                              DepthHist dh0, DepthHist dh1, SpecArgs sa0, SpecArgs sa1)
-{
-    k_sort_depth_pair_body<STRIP, SPEC, false>(rows, bound_r, n, u0, u1, su0, su1, depth0, depth1, pmin0, pmax0, pcnt0, pmin1, pmax1, pcnt1, dh0, dh1, sa0, sa1, HiddenArgs{ nullptr, 0u });
-}
-// ... and with the state store (a kernel of its own, as k_sort_depth_hid: the one above keeps its argument list)
-template <bool STRIP, bool SPEC>
-__global__ __launch_bounds__(GS_BLOCK) void k_sort_depth_pair_hid(const float4 *__restrict__ rows, const float *__restrict__ bound_r, uint32_t n,
-                                                              SortUniforms u0, SortUniforms u1, StripUniforms su0, StripUniforms su1,
-                                                              float *__restrict__ depth0, float *__restrict__ depth1,
-                                                              unsigned long long *__restrict__ pmin0, unsigned long long *__restrict__ pmax0, uint32_t *__restrict__ pcnt0,
-                                                              unsigned long long *__restrict__ pmin1, unsigned long long *__restrict__ pmax1, uint32_t *__restrict__ pcnt1,
-                                                              DepthHist dh0, DepthHist dh1, SpecArgs sa0, SpecArgs sa1, HiddenArgs hid)
-{
-    k_sort_depth_pair_body<STRIP, SPEC, true>(rows, bound_r, n, u0, u1, su0, su1, depth0, depth1, pmin0, pmax0, pcnt0, pmin1, pmax1, pcnt1, dh0, dh1, sa0, sa1, hid);
+    k_sort_depth_body<2, STRIP, SPEC, HID>(rows, bound_r, n, vs, hid);
 }
 
 // pass 2 (index.js:558-561): 16-bit bucket of the stored depth; culled -> GS_RADIX_SKIP, dropped bucket -> GS_CULLED_KEY.
@@ -888,8 +810,7 @@ GS_BODY(F_near_gather_groups, (k_near_gather_groups), (k_near_gather_groups_body
 template <int NW> GS_BODY(F_near_stash, (k_near_stash<NW>), (k_near_stash_body<NW>));
 GS_BODY(F_near_gather, (k_near_gather), (k_near_gather_body));
 template <int NW, bool COMPACT, bool NEAR, bool MSD = false> GS_BODY(F_sort_bucket, (k_sort_bucket<NW, COMPACT, NEAR, MSD>), (k_sort_bucket_body<NW, COMPACT, NEAR, MSD>));
-template <bool STRIP, bool SPEC> GS_BODY(F_sort_depth, (k_sort_depth<STRIP, SPEC>), (k_sort_depth_body<STRIP, SPEC>));
-template <bool STRIP, bool SPEC> GS_BODY(F_sort_depth_hid, (k_sort_depth_hid<STRIP, SPEC>), (k_sort_depth_body<STRIP, SPEC, true>));
+template <bool STRIP, bool SPEC, bool HID> GS_BODY(F_sort_depth, (k_sort_depth<STRIP, SPEC, HID>), (k_sort_depth_body<1, STRIP, SPEC, HID>));
 
 }  // namespace
 
@@ -1020,59 +941,27 @@ static int run_sort(gs_ctx *const S[], const float *const view[], const float *c
     const bool hidden = hid.rows != 0u;
     for (int k = 0; k < NF; k++) S[k]->sort_hidden = hidden ? (uint32_t)R->edit_hidden : 0u;
 
-    // ---- the depth pass: the ONE step whose forms for one frame and for a pair differ (everything behind it goes through gs_launch<NF>)
-    if constexpr (NF == 1) {
-        // (a) one frame: k_sort_depth, LDS for one depth histogram when the sort is near-only
-        const size_t dlds = near ? GS_DEPTH_BINS * sizeof(uint32_t) : 0u;
-#define GS_DEPTH1(ST, SP) hipLaunchKernelGGL((k_sort_depth<ST, SP>), dim3(gd), dim3(GS_BLOCK), dlds, st, ctx->sort_rows, ctx->bound_r, n, u[0], su[0], ctx->depth, \
-                                             ctx->part_min, ctx->part_max, ctx->part_cnt, dh[0], ctx->kv_b, ctx->hist, (const uint32_t *)bin_hint, ctx->ctl)
-#define GS_DEPTH1H(ST, SP) hipLaunchKernelGGL((k_sort_depth_hid<ST, SP>), dim3(gd), dim3(GS_BLOCK), dlds, st, ctx->sort_rows, ctx->bound_r, n, u[0], su[0], ctx->depth, \
-                                              ctx->part_min, ctx->part_max, ctx->part_cnt, dh[0], ctx->kv_b, ctx->hist, (const uint32_t *)bin_hint, ctx->ctl, hid)
-        if (hidden) {
-            if (spec) { if (strips) GS_DEPTH1H(true, true); else GS_DEPTH1H(false, true); }
-            else { if (strips) GS_DEPTH1H(true, false); else GS_DEPTH1H(false, false); }
-        } else if (spec) { if (strips) GS_DEPTH1(true, true); else GS_DEPTH1(false, true); }
-        else { if (strips) GS_DEPTH1(true, false); else GS_DEPTH1(false, false); }
-#undef GS_DEPTH1H
-#undef GS_DEPTH1
-    } else {
-        // ONE sweep computes both frames' depths: the rows are read once (the lanes of a context alias the owner's resident arrays)
-        if (S[0]->sort_rows != S[1]->sort_rows) { snprintf(GS_ERRBUF(ctx), GS_ERRLEN, "paired sort: the two lanes hold different splat arrays"); return GS_E_STATE; }
-        // ... where one sweep saves memory traffic: inputs the caches do not hold.  Below GS_DEPTH_PAIR_MIN_N splats the rows stay resident
-        // between the two frames' reads, and the one-sweep kernel pays for holding two frames' uniforms (two view rows, two cut-out matrices,
-        // two strips' 31 words each: more than the scalar registers hold -- the compiler parks them in lanes of a vector register, and 39 % of
-        // that kernel's vector instructions at 1 M splats were v_readlane)
-        if (!near && !spec && n < GS_DEPTH_PAIR_MIN_N) {
-            // (b) a short pair: k_sort_depth's body twice, blockIdx.y = the frame (never near-only here: no histogram in LDS)
-            const auto args = [&](int k) {
-                return gs_pack_make((const float4 *)S[k]->sort_rows, (const float *)S[k]->bound_r, n, u[k], su[k], S[k]->depth, S[k]->part_min, S[k]->part_max, S[k]->part_cnt,
-                                    dh[k], (uint2 *)nullptr, (uint32_t *)nullptr, (const uint32_t *)bin_hint, S[k]->ctl);
-            };
-            const auto args_hid = [&](int k) {
-                return gs_pack_make((const float4 *)S[k]->sort_rows, (const float *)S[k]->bound_r, n, u[k], su[k], S[k]->depth, S[k]->part_min, S[k]->part_max, S[k]->part_cnt,
-                                    dh[k], (uint2 *)nullptr, (uint32_t *)nullptr, (const uint32_t *)bin_hint, S[k]->ctl, hid);
-            };
-            if (hidden) { if (strips) gs_launch<2, F_sort_depth_hid<true, false>, GS_BLOCK>(gd, st, 0, args_hid); else gs_launch<2, F_sort_depth_hid<false, false>, GS_BLOCK>(gd, st, 0, args_hid); }
-            else if (strips) gs_launch<2, F_sort_depth<true, false>, GS_BLOCK>(gd, st, 0, args); else gs_launch<2, F_sort_depth<false, false>, GS_BLOCK>(gd, st, 0, args);
-        } else {
-            // (c) a long or speculative pair: k_sort_depth_pair, LDS for two depth histograms when the sorts are near-only
-            const size_t dlds = near ? 2u * GS_DEPTH_BINS * sizeof(uint32_t) : 0u;
-            SpecArgs sa[2];
-            for (int k = 0; k < 2; k++) { sa[k].stash = S[k]->kv_b; sa[k].cnt = S[k]->hist; sa[k].bin_hint = bin_hint; sa[k].ctl = S[k]->ctl; }
-#define GS_DEPTHP_ARGS (const float4 *)S[0]->sort_rows, (const float *)S[0]->bound_r, n, u[0], u[1], su[0], su[1], S[0]->depth, S[1]->depth, S[0]->part_min, S[0]->part_max, S[0]->part_cnt, \
-                      S[1]->part_min, S[1]->part_max, S[1]->part_cnt, dh[0], dh[1], sa[0], sa[1]
-#define GS_DEPTHP(ST, SP) hipLaunchKernelGGL((k_sort_depth_pair<ST, SP>), dim3(gd), dim3(GS_BLOCK), dlds, st, GS_DEPTHP_ARGS)
-#define GS_DEPTHPH(ST, SP) hipLaunchKernelGGL((k_sort_depth_pair_hid<ST, SP>), dim3(gd), dim3(GS_BLOCK), dlds, st, GS_DEPTHP_ARGS, hid)
-            if (hidden) {
-                if (spec) { if (strips) GS_DEPTHPH(true, true); else GS_DEPTHPH(false, true); }
-                else { if (strips) GS_DEPTHPH(true, false); else GS_DEPTHPH(false, false); }
-            } else if (spec) { if (strips) GS_DEPTHP(true, true); else GS_DEPTHP(false, true); }
-            else { if (strips) GS_DEPTHP(true, false); else GS_DEPTHP(false, false); }
-#undef GS_DEPTHP
-#undef GS_DEPTHPH
-#undef GS_DEPTHP_ARGS
+    // ---- the depth pass: one view per sweep (k_sort_depth: a single frame, and twice through gs_launch<2> for a short pair), or both views of a
+    // pair in ONE sweep (k_sort_depth_pair: the rows are read once -- the lanes of a context alias the owner's resident arrays)
+    if (NF == 2 && S[0]->sort_rows != S[NF - 1]->sort_rows) { snprintf(GS_ERRBUF(ctx), GS_ERRLEN, "paired sort: the two lanes hold different splat arrays"); return GS_E_STATE; }
+    DepthViews<NF> dv;
+    for (int k = 0; k < NF; k++) dv.v[k] = DepthView{ u[k], su[k], S[k]->depth, S[k]->part_min, S[k]->part_max, S[k]->part_cnt, dh[k], S[k]->kv_b, S[k]->hist, bin_hint, S[k]->ctl };
+    // ... where one sweep saves memory traffic: inputs the caches do not hold.  Below GS_DEPTH_PAIR_MIN_N splats the rows stay resident
+    // between the two frames' reads, and the one-sweep kernel pays for holding two frames' uniforms (two view rows, two cut-out matrices,
+    // two strips' 31 words each: more than the scalar registers hold -- the compiler parks them in lanes of a vector register, and 39 % of
+    // that kernel's vector instructions at 1 M splats were v_readlane).  Near-only and speculative pairs always take the one sweep: a twin
+    // has no histogram in LDS and no stash
+    const bool sweep2 = NF == 2 && (near || spec || n >= GS_DEPTH_PAIR_MIN_N);
+    const size_t dlds = near ? (sweep2 ? 2u : 1u) * GS_DEPTH_BINS * sizeof(uint32_t) : 0u;   // one depth histogram per view of the sweep
+    gs_flag(strips, [&](auto ST) { gs_flag(spec, [&](auto SP) { gs_flag(hidden, [&](auto HD) {
+        constexpr bool STRIP = decltype(ST)::value, SPEC = decltype(SP)::value, HID = decltype(HD)::value;
+        if constexpr (NF == 2) {
+            if (sweep2) { hipLaunchKernelGGL((k_sort_depth_pair<STRIP, SPEC, HID>), dim3(gd), dim3(GS_BLOCK), dlds, st, (const float4 *)ctx->sort_rows, (const float *)ctx->bound_r, n, dv, hid); return; }
         }
-    }
+        if constexpr (NF == 1 || !SPEC)                             // (no twin stashes: spec implies sweep2)
+            gs_launch<NF, F_sort_depth<STRIP, SPEC, HID>, GS_BLOCK>(gd, st, dlds, [&](int k) {
+                return gs_pack_make((const float4 *)S[k]->sort_rows, (const float *)S[k]->bound_r, n, DepthViews<1>{ { dv.v[k] } }, hid); });
+    }); }); });
     // ---- end of the depth pass
 
     GsRadixIO io[NF];

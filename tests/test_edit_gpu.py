@@ -349,9 +349,9 @@ def test_multi_world2_select_and_compact():
 
 
 def test_long_paired_depth_pass():
-    """n > GS_DEPTH_PAIR_MIN_N: two queued frames that go out as a pair run k_sort_depth_pair_hid, one sweep for both frames.  Whether a
+    """n > GS_DEPTH_PAIR_MIN_N: two queued frames that go out as a pair run k_sort_depth_pair<.., HID>, one sweep for both frames.  Whether a
     pair forms depends on both frames waiting in the lane's queue when its thread looks (a matter of timing), and no statistic says
-    which depth kernel ran: frames that went out alone match through k_sort_depth_hid just as well.  What this case guarantees is the
+    which depth kernel ran: frames that went out alone match through k_sort_depth<.., HID> just as well.  What this case guarantees is the
     size and the call pattern at which the paired kernel is the one that runs whenever a pair forms."""
     n = PAIR_MIN_N + 1000
     rows = cached_rows("make_splat_rows_fast", n).reshape(n, 32)

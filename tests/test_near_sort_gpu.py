@@ -20,7 +20,7 @@ Forms and how they are reached (run_sort chooses as always):
                a view whose threshold bin is more than GS_SPEC_PAD bins past the hint.
 The long cloud is built once: three independent depth layouts on its x, y and z columns, chosen by the view row.
 
-Not covered here: the paired depth pass (k_sort_depth_pair with histograms) and the shared sort's no_tail_sort lane -- reached only through
+Not covered here: the paired depth pass (k_sort_depth_pair<..>: two views with a histogram each) and the shared sort's no_tail_sort lane -- reached only through
 queued pairs and several contexts, they stay with the 6 M-splat frame tests of test_gpu_parity.py.  The gather's workgroups take one group
 of GS_GATHER_CHUNKS chunks each at this size (a workgroup takes several only beyond 33 M splats); the spread survivors cross every seam
 between groups.  Frames after a forced sort: the tail form at 4096 splats, and the stash form's overflow at the long cloud; the histogram

@@ -72,7 +72,7 @@ def main():
             kern[k] = row
         frames = info.get("frames_queued")
         tot = sum(r["hbm_bytes"] * r["launches"] for r in kern.values())
-        # the pipelined, paired frames alone (k_twin<...> / k_sort_depth_pair launches cover two frames each): what a frame of the
+        # the pipelined, paired frames alone (k_twin<...> / k_sort_depth_pair<...> launches cover two frames each): what a frame of the
         # steady loop moves -- the process' synchronous settling frames (whole sorts, both binning rounds) are not in it
         paired = {k: r for k, r in kern.items() if k.startswith("k_twin") or "_pair<" in k}
         bl = [r["launches"] for k, r in paired.items() if "F_blend<0" in k]
