@@ -1112,8 +1112,16 @@ __global__ __launch_bounds__(GS_BLOCK) void k_lists(const uint32_t *__restrict__
 #define GS_BLEND_BATCH 64
 #endif
 #ifndef GS_BLEND_FACTOR
-#define GS_BLEND_FACTOR 1           // the coverage test of plain frames' whole-batch walk as a factor (GS_BLEND_APPLY_W)
-#endif
+#define GS_BLEND_FACTOR 2           // the coverage test of plain frames as a factor (GS_BLEND_APPLY_W): 0 compare / select (GS_BLEND_APPLY),
+#endif                              // 1 w = clamp((qm - q) * 1e30 + 1), 2 w = clamp(q * -1e30 + c): one packed fma per pixel pair
+// GS_BLEND_FACTOR 2: the per-pixel constant c of a pixel inside the strip, the ONE float with 0 < c - 4 K < K ulp(4) for K = (float)1e30
+// (the float next above 4 K; floats are 2^78 = 3.0e23 apart there, K ulp(4) = 4.8e23).  The fma rounds once, so q * -K + c is >= 3.0e23
+// for every float q <= 4 and <= -1.7e23 for every float q > 4: clamped, exactly 1 and exactly 0.  A pixel outside has c = -1: q is a sum
+// of squares, q * -K - 1 <= -1.  -inf -> 0 and NaN -> 0 under clamp, as form 1.  tests/host_check/blend_factor.cpp finds this constant by
+// itself and compares the three forms on every float; tests/test_blend_factor_cpu.py holds the literal below to what it prints.
+#define GS_BLEND_W_K 1.0e30f
+#define GS_BLEND_W_C_IN 0x1.93e596p+101f
+#define GS_BLEND_W_C_OUT -1.0f
 typedef float f2 __attribute__((ext_vector_type(2)));            // two pixels per packed-fp32 instruction (v_pk_*_f32)
 __device__ __forceinline__ f2 fma2(f2 a, f2 b, f2 c) { return __builtin_elementwise_fma(a, b, c); }
 // fma2(a, (f2)(b.x), (f2)(c.x)) / fma2(a, (f2)(b.y), (f2)(c.y)): both halves of the result take the LOW / HIGH words of b and c
@@ -1254,6 +1262,9 @@ __device__ __forceinline__ void k_blend_body(const uint2 *__restrict__ tile_rang
     const f2 qmA = { (row_in && xb < u.x1b) ? 4.0f : -1.0f, (row_in && xb + 1 < u.x1b) ? 4.0f : -1.0f };
     const f2 qmB = { (row_in && xb + 2 < u.x1b) ? 4.0f : -1.0f, (row_in && xb + 3 < u.x1b) ? 4.0f : -1.0f };
     f2 TA = { qmA.x > 0.0f ? 1.0f : 0.0f, qmA.y > 0.0f ? 1.0f : 0.0f }, TB = { qmB.x > 0.0f ? 1.0f : 0.0f, qmB.y > 0.0f ? 1.0f : 0.0f };
+    // (GS_BLEND_FACTOR 2: the constant that stands for qm in the factor form of the step; qm itself then lives only where the step compares)
+    const f2 cwA = { qmA.x > 0.0f ? GS_BLEND_W_C_IN : GS_BLEND_W_C_OUT, qmA.y > 0.0f ? GS_BLEND_W_C_IN : GS_BLEND_W_C_OUT };
+    const f2 cwB = { qmB.x > 0.0f ? GS_BLEND_W_C_IN : GS_BLEND_W_C_OUT, qmB.y > 0.0f ? GS_BLEND_W_C_IN : GS_BLEND_W_C_OUT };
     f2 crA = { 0, 0 }, crB = { 0, 0 }, cgA = { 0, 0 }, cgB = { 0, 0 }, cbA = { 0, 0 }, cbB = { 0, 0 };
     // opaque scene depth under each of the lane's 4 pixels (+inf = nothing in front of the far plane)
     float zb0 = 3.0e38f, zb1 = 3.0e38f, zb2 = 3.0e38f, zb3 = 3.0e38f;
@@ -1274,9 +1285,15 @@ __device__ __forceinline__ void k_blend_body(const uint2 *__restrict__ tile_rang
     // A lane leaves the list when all four of its pixels are below the threshold (checked after every list entry, so the
     // point of exit depends on the list alone -- not on batching or on the split into rounds); until then every pixel of
     // the lane keeps blending: what a pixel below the threshold still receives is < t_eps in total.
+    // (as compiled: v_max_f32, v_max3_f32, v_cmp -- the compiler regroups the four-way maximum by itself: a maximum is exact in any
+    // grouping, and T is never NaN here -- it starts at 0, 1 or a saved T, and a step adds -alpha * e to it with e = exp(A) * w * T in
+    // [0, T]: k_project's records are finite, so q is finite or +inf, exp(A) in [0, 1] -- so there is nothing left to write by hand)
 #define GS_LANE_LIVE() (fmaxf(fmaxf(TA.x, TA.y), fmaxf(TB.x, TB.y)) >= t_eps)
-    f2 kbig = { 1.0e30f, 1.0e30f }, kone = { 1.0f, 1.0f };         // (GS_BLEND_APPLY_W; the empty asm keeps them in registers: as literals the
-    asm volatile("" : "+v"(kbig), "+v"(kone));                     // compiler builds each pair again in front of every use, 2 moves per entry)
+    f2 kbig = { GS_BLEND_W_K, GS_BLEND_W_K }, kone = { 1.0f, 1.0f };   // (GS_BLEND_APPLY_W; the empty asm keeps them in registers: as literals the
+    if (GS_BLEND_FACTOR == 2 && !COUNT && !SCENE && !SURF) {       // compiler builds each pair again in front of every use, 2 moves per entry)
+        kbig = -kbig;                                              // form 2 multiplies by -K and needs no 1; the kernels that compare keep
+        asm volatile("" : "+v"(kbig));                             // the statement they had, and with it their code
+    } else asm volatile("" : "+v"(kbig), "+v"(kone));
     bool live = GS_LANE_LIVE();
     uint32_t nfr = 0, staged = 0, evaluated = 0;
     // SURF: the sorted position and window depth of each pixel's surface (none yet), and the slot latched in the batch under way
@@ -1431,13 +1448,19 @@ __device__ __forceinline__ void k_blend_body(const uint2 *__restrict__ tile_rang
         // floats that differ differ by 2^-22 at least near 4: times 1e30 that is +-2e23), and exp(A) * w is exp(A) or +0 -- the values the
         // selects produce, so T and the colours see the same operations.  What goes is the skip of a step no lane's pixel passes
         // (rare: lane utilisation 0.85 at the headline pose, and a step of the block lists serves sixteen blocks with sixteen entries), 2 of
-        // the 39 vector instructions per entry.
+        // the 39 vector instructions per entry.  GS_BLEND_FACTOR 2: the same w from ONE fma, clamp(q * -1e30 + c) with the per-pixel
+        // constant c in qm's place (GS_BLEND_W_C_IN: why it is the same w for every q) -- 2 more, 35 per entry.
+#if GS_BLEND_FACTOR == 2
+#define GS_BLEND_W(qA, qB) const f2 wA = fma2_clamp(qA, kbig, cwA), wB = fma2_clamp(qB, kbig, cwB);
+#else
+#define GS_BLEND_W(qA, qB) const f2 wA = fma2_clamp(qmA - qA, kbig, kone), wB = fma2_clamp(qmB - qB, kbig, kone);
+#endif
 #define GS_BLEND_APPLY_W(qA, qB, EB)                                                                                   \
                 if (live) {                                                                                            \
                     const float2 cl_ = *reinterpret_cast<const float2 *>((EB) + 32);                                   \
                     const float2 ch_ = *reinterpret_cast<const float2 *>((EB) + 40);                                   \
                     const float nalpha = cl_.x;                                                                        \
-                    const f2 wA = fma2_clamp(qmA - qA, kbig, kone), wB = fma2_clamp(qmB - qB, kbig, kone);             \
+                    GS_BLEND_W(qA, qB)                                                                                 \
                     const f2 tA = qA * (f2)(-1.44269502f), tB = qB * (f2)(-1.44269502f);                                \
                     const f2 EA = { __builtin_amdgcn_exp2f(tA.x), __builtin_amdgcn_exp2f(tA.y) };                      \
                     const f2 EB_ = { __builtin_amdgcn_exp2f(tB.x), __builtin_amdgcn_exp2f(tB.y) };                     \
@@ -1502,6 +1525,7 @@ __device__ __forceinline__ void k_blend_body(const uint2 *__restrict__ tile_rang
             if (u.record_staged == 2) evaluated += min(vo / 48u + 2u, nb);   // list entries this lane evaluated (measurement aid)
         }
 #undef GS_BLEND_APPLY_W
+#undef GS_BLEND_W
 #undef GS_BLEND_APPLY
 #undef GS_BLEND_Q
         if (SURF) {
