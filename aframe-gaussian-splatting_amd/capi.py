@@ -29,6 +29,7 @@ OPT_SH_DEGREE = 19
 OPT_ANTIALIAS = 20
 OPT_SEG_COUNT = 21
 OPT_SORT_NEAR_FORCE = 22
+OPT_HIGHLIGHT = 23
 SORT_WHOLE, SORT_HISTOGRAM, SORT_SPEC, SORT_TAIL, SORT_STASH = 0, 1, 2, 3, 4     # gs_sort_info.form
 TRANSPORT_RCCL, TRANSPORT_INPROC = 0, 1
 COMM_ID_BYTES = 128
@@ -55,6 +56,7 @@ EXPORTS = [
     "gs_set_state", "gs_set_state_ids", "gs_state_count", "gs_select_box", "gs_select_sphere", "gs_select_rect", "gs_compact",
     "gs_sort_inspect",
     "gs_multi_set_state", "gs_multi_set_state_ids", "gs_multi_select_box", "gs_multi_select_sphere", "gs_multi_select_rect", "gs_multi_compact",
+    "gs_select_mask", "gs_multi_select_mask", "gs_mask_polygon", "gs_highlight_info", "gs_highlight_word",
 ]
 SURFACE_NONE = 0xFFFFFFFF          # gs_surface.id / gs_hit.id where the transmittance never falls below one half
 
@@ -226,6 +228,13 @@ def load(build_if_missing=True):
             getattr(L, pre + "select_rect").argtypes = [vp, C.POINTER(RenderParams), vp, u8, u8, C.c_uint32, szp]
             getattr(L, pre + "compact").argtypes = [vp, vp, szp]
         L.gs_state_count.argtypes = [vp, szp, szp]
+    if hasattr(L, "gs_select_mask"):                           # (an older build loaded through GS_SPLAT_LIB for an A/B run has none)
+        u8, szp = C.c_uint8, C.POINTER(sz)
+        for pre in ("gs_", "gs_multi_"):
+            getattr(L, pre + "select_mask").argtypes = [vp, C.POINTER(RenderParams), vp, sz, vp, u8, u8, C.c_uint32, szp]
+        L.gs_mask_polygon.argtypes = [vp, sz, i32, i32, vp, sz]
+        L.gs_highlight_info.argtypes = [vp, u32p, u32p]
+        L.gs_highlight_word.argtypes = [C.c_uint32, C.c_uint32, u32p]
     L.gs_download.argtypes = [vp, i32, vp, sz]
     if hasattr(L, "gs_sort_inspect"):
         L.gs_sort_inspect.argtypes = [vp, C.POINTER(SortInfo), vp, sz]
@@ -414,6 +423,56 @@ def antialias_factor(cov):
     return out.reshape(c.shape[:-1]) if c.ndim > 1 else out[0]
 
 
+def highlight_option(rgb, weight):
+    """the value of OPT_HIGHLIGHT for a colour (r, g, b) and a weight, bytes each: R | G << 8 | B << 16 | W << 24"""
+    r, g, b = (int(v) & 255 for v in rgb)
+    return r | g << 8 | b << 16 | (int(weight) & 255) << 24
+
+
+def highlight_word(rgba, option_value):
+    """gs_highlight_word: the colour word(s) R | G << 8 | B << 16 | A << 24 of selected splats under OPT_HIGHLIGHT = option_value, by the
+    kernel's own function (one value, or an array of them)"""
+    w = np.ascontiguousarray(rgba, np.uint32)
+    flat, out = w.reshape(-1), C.c_uint32(0)
+    res = np.zeros(flat.size, np.uint32)
+    f = load().gs_highlight_word
+    for i in range(flat.size):
+        rc = f(int(flat[i]), int(option_value) & 0xFFFFFFFF, C.byref(out))
+        if rc != GS_OK:
+            raise GsError(rc, "gs_highlight_word: bad argument")
+        res[i] = out.value
+    return res.reshape(w.shape) if w.ndim else res[0]
+
+
+def mask_polygon(points, width, height, out=None):
+    """gs_mask_polygon: even-odd fill of the closed polygon `points` (n x (x, y), pixels, row 0 = top) -> uint8[height, width] of 0 / 1.
+    out: a C-contiguous uint8 array of `height` rows to fill instead (its row length is the stride; bytes beyond `width` stay)."""
+    pts = np.ascontiguousarray(points, np.float32).reshape(-1, 2)
+    if out is None:
+        out = np.zeros((int(height), int(width)), np.uint8)
+    if out.dtype != np.uint8 or out.ndim != 2 or not out.flags.c_contiguous or out.shape[0] != int(height):
+        raise ValueError("out: a C-contiguous uint8 array of `height` rows expected")
+    rc = load().gs_mask_polygon(_p(pts) if len(pts) else None, len(pts), int(width), int(height), _p(out), out.shape[1])
+    if rc != GS_OK:
+        raise GsError(rc, "gs_mask_polygon: bad argument")
+    return out
+
+
+def _mask_args(params, mask, depth_max):
+    """(mask as rows of bytes, its stride, the depth plane or None) for gs_select_mask: a uint8 view with padded rows is passed as it is"""
+    m = np.asarray(mask)
+    if m.dtype != np.uint8 or m.ndim != 2 or m.strides[1] != 1 or m.strides[0] < m.shape[1]:
+        m = np.ascontiguousarray(mask, np.uint8)
+    if m.ndim != 2 or m.shape != (params.fb_height, params.fb_width):
+        raise ValueError("mask: fb_height x fb_width bytes expected")
+    d = None
+    if depth_max is not None:
+        d = np.ascontiguousarray(depth_max, np.float32)
+        if d.shape != (params.fb_height, params.fb_width):
+            raise ValueError("depth_max: fb_height x fb_width float32 expected")
+    return m, m.strides[0], d
+
+
 def make_params(mv, proj, width, height, x0=0, x1=None, focal_=0.0, background=(0.0, 0.0, 0.0, 1.0), flags=0):
     p = RenderParams()
     p.model_view[:] = [float(v) for v in np.asarray(mv, np.float32)]
@@ -534,6 +593,20 @@ class Context:
         hit = C.c_size_t(0)
         self._ck(self._L.gs_select_rect(self._h, C.byref(params), _p(r), int(set_bits), int(clear_bits), int(flags), C.byref(hit)))
         return hit.value
+
+    def select_mask(self, params, mask, depth_max=None, set_bits=0, clear_bits=0, flags=0):
+        """mask: uint8[fb_height, fb_width] (a view with padded rows is passed with its stride), non-zero = inside; depth_max: optional
+        float32[fb_height, fb_width] of window depths (the depth plane of render_surface: visible splats only) -> positions hit"""
+        m, stride, d = _mask_args(params, mask, depth_max)
+        hit = C.c_size_t(0)
+        self._ck(self._L.gs_select_mask(self._h, C.byref(params), _p(m), stride, _p(d), int(set_bits), int(clear_bits), int(flags), C.byref(hit)))
+        return hit.value
+
+    def highlight_info(self):
+        """(the value of OPT_HIGHLIGHT, 1 if the last frame was projected by the highlighting kernels)"""
+        v, last = C.c_uint32(0), C.c_uint32(0)
+        self._ck(self._L.gs_highlight_info(self._h, C.byref(v), C.byref(last)))
+        return v.value, last.value
 
     def compact(self):
         """gs_compact: delete the hidden splats -> uint32[count afterwards], the old index of every splat that stays"""
@@ -800,6 +873,15 @@ class Multi:
             raise GsError(rc, self._L.gs_last_error(h).decode())
         return s.as_dict()
 
+    def ctx_highlight_info(self, i):
+        """gs_highlight_info of the context on devices[i] (call sync() first)"""
+        v, last = C.c_uint32(0), C.c_uint32(0)
+        h = self._L.gs_multi_ctx(self._h, int(i))
+        rc = self._L.gs_highlight_info(h, C.byref(v), C.byref(last))
+        if rc != GS_OK:
+            raise GsError(rc, self._L.gs_last_error(h).decode())
+        return v.value, last.value
+
     def clear(self):
         self._ck(self._L.gs_multi_clear(self._h))
 
@@ -847,6 +929,13 @@ class Multi:
         r = np.ascontiguousarray(rect, np.int32).reshape(4)
         hit = C.c_size_t(0)
         self._ck(self._L.gs_multi_select_rect(self._h, C.byref(params), _p(r), int(set_bits), int(clear_bits), int(flags), C.byref(hit)))
+        return hit.value
+
+    def select_mask(self, params, mask, depth_max=None, set_bits=0, clear_bits=0, flags=0):
+        """Context.select_mask on every device -> the positions hit on devices[0]"""
+        m, stride, d = _mask_args(params, mask, depth_max)
+        hit = C.c_size_t(0)
+        self._ck(self._L.gs_multi_select_mask(self._h, C.byref(params), _p(m), stride, _p(d), int(set_bits), int(clear_bits), int(flags), C.byref(hit)))
         return hit.value
 
     def compact(self):

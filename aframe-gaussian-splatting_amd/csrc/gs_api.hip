@@ -884,7 +884,7 @@ GS_API int gs_destroy(gs_ctx *ctx)
         if (ctx->lanes[i]) { free_frame_resources(ctx->lanes[i]); delete ctx->lanes[i]; ctx->lanes[i] = nullptr; }
     free_frame_resources(ctx);
     dev_free(ctx->splat); dev_free(ctx->sort_rows); dev_free(ctx->bound_r); dev_free(ctx->pow10tab); dev_free(ctx->sh);
-    dev_free(ctx->edit_state); dev_free(ctx->edit_cnt);
+    dev_free(ctx->edit_state); dev_free(ctx->edit_cnt); dev_free(ctx->mask_buf);
     dev_free(ctx->scene_depth); dev_free(ctx->scene_rgba);
     if (ctx->ev_sort) (void)hipEventDestroy(ctx->ev_sort);
     delete ctx;
@@ -1364,6 +1364,9 @@ int gs_fill_uniforms(gs_ctx *ctx /* owner: options, adaptive share, scene */, co
     }
     u.surf_id = nullptr; u.surf_depth = nullptr; u.surf_alpha = nullptr; u.surface = 0;   // (gs_render_surface sets them)
     u.antialias = ctx->aa_opt ? 1u : 0u;                            // compensated opacity (GS_OPT_ANTIALIAS), per frame like the SH degree
+    // highlighted selection (GS_OPT_HIGHLIGHT), per frame too: only with a weight AND a store -- a context that never edits keeps its kernels
+    const bool hl = (ctx->hl_opt >> 24) != 0u && ctx->edit_n != 0 && ctx->edit_state;
+    u.highlight = hl ? ctx->hl_opt : 0u; u.hl_rows = hl ? (uint32_t)ctx->edit_n : 0u; u.hl_state = hl ? ctx->edit_state : nullptr;
     return GS_OK;
 }
 
@@ -1522,6 +1525,7 @@ int gs_render_uniforms(gs_ctx *ctx, const GsFrameUniforms &u_in, void *device_rg
     L->stats.sh_degree = u.sh_degree;
     L->stats.surface = u.surface ? 1u : 0u;
     L->stats.antialias = u.antialias ? 1u : 0u;
+    L->hl_frame = u.highlight ? 1u : 0u;
     u.need_seed = L->share_lane.need_seed_pending; L->share_lane.need_seed_pending = 0;  // (a seed for the lane's need words travels with its next frame)
     bool async = (u.flags & GS_RENDER_ASYNC) && !(u.flags & GS_RENDER_COUNT_FRAGS);
     // A context that has not MEASURED its share yet (fresh, cleared, the share un-pinned) draws its first two-round frame synchronously
@@ -1800,6 +1804,64 @@ GS_API int gs_select_rect(gs_ctx *ctx, const gs_render_params *p, const int32_t 
     const int rc = gs_edit_select_rect(ctx, L, u, rect, set_bits, clear_bits, (flags & GS_SELECT_INVERT) != 0, out_hit);
     const int rc2 = edit_end(ctx);
     return rc != GS_OK ? rc : rc2;
+}
+
+// gs_select_mask's inputs on the device, in the owner's grow-only scratch, on its stream: the mask as tight rows of W bytes and -- 256-byte
+// aligned behind it, at depth_at -- the depth plane.  An editor action, not a frame path: pageable memory, one copy each
+static int mask_upload(gs_ctx *ctx, const uint8_t *mask, size_t stride, const float *depth_max, size_t W, size_t H, size_t depth_at)
+{
+    const size_t need = depth_at + (depth_max ? W * H * sizeof(float) : 0);
+    if (need > ctx->mask_cap_bytes) {
+        dev_free(ctx->mask_buf); ctx->mask_buf = nullptr; ctx->mask_cap_bytes = 0;
+        TRY(dev_alloc(ctx, &ctx->mask_buf, need));
+        ctx->mask_cap_bytes = need;
+    }
+    if (stride == W) GS_HIP(hipMemcpyAsync(ctx->mask_buf, mask, W * H, hipMemcpyHostToDevice, ctx->stream));
+    else GS_HIP(hipMemcpy2DAsync(ctx->mask_buf, W, mask, stride, W, H, hipMemcpyHostToDevice, ctx->stream));
+    if (depth_max) GS_HIP(hipMemcpyAsync(ctx->mask_buf + depth_at, depth_max, W * H * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
+    return GS_OK;
+}
+
+GS_API int gs_select_mask(gs_ctx *ctx, const gs_render_params *p, const uint8_t *mask, size_t mask_stride, const float *depth_max, uint8_t set_bits,
+                          uint8_t clear_bits, uint32_t flags, size_t *out_hit)
+{
+    CHECK_CTX(ctx);
+    if (!p || !mask) FAIL(GS_E_BADARG, "gs_select_mask: NULL argument");
+    if (flags & ~GS_SELECT_INVERT) FAIL(GS_E_BADARG, "gs_select_mask: unknown flags %#x", flags);
+    if (!ctx->renderable && ctx->n) FAIL(GS_E_STATE, "context was fed worker matrices only (gs_push_matrices): it can sort but not project");
+    gs_render_params q = *p;
+    q.x0 = 0; q.x1 = p->fb_width;
+    GsFrameUniforms u;
+    TRY(gs_fill_uniforms(ctx, &q, u));
+    const size_t W = (size_t)u.W, H = (size_t)u.H;
+    if (mask_stride && mask_stride < W) FAIL(GS_E_BADARG, "gs_select_mask: stride %zu smaller than a row (%zu bytes)", mask_stride, W);
+    if (out_hit) *out_hit = 0;
+    GS_HIP(hipSetDevice(ctx->device));
+    TRY(drain_all(ctx));                                         // (the current frame's lane is idle and its have_sort is the worker's last word)
+    gs_ctx *L = ctx->lanes[ctx->cur];
+    if (!ctx->n || !L->have_sort || !L->sorted) FAIL(GS_E_STATE, "gs_select_mask: no completed sort to select from");
+    // the WHOLE order, as gs_select_rect
+    if (L->sort_near_req || L->sv_has_strip) TRY(lane_rc(ctx, L, gs_run_sort(L, L->sv_view, L->sv_has_cutout ? L->sv_cutout : nullptr, nullptr, 0)));
+    TRY(edit_begin(ctx, ctx->n));
+    const size_t depth_at = (W * H + 255) & ~(size_t)255;
+    int rc = mask_upload(ctx, mask, mask_stride ? mask_stride : W, depth_max, W, H, depth_at);
+    if (rc == GS_OK) rc = gs_edit_select_mask(ctx, L, u, ctx->mask_buf, depth_max ? reinterpret_cast<const float *>(ctx->mask_buf + depth_at) : nullptr, set_bits,
+                                              clear_bits, (flags & GS_SELECT_INVERT) != 0, out_hit);
+    if (rc != GS_OK) (void)hipStreamSynchronize(ctx->stream);     // (no copy out of the caller's memory is left behind)
+    const int rc2 = edit_end(ctx);
+    return rc != GS_OK ? rc : rc2;
+}
+
+GS_API int gs_highlight_info(const gs_ctx *ctx, uint32_t *option_value, uint32_t *last_frame)
+{
+    if (!ctx) return GS_E_BADARG;
+    if (option_value) *option_value = ctx->hl_opt;
+    if (last_frame) {
+        gs_ctx *c = const_cast<gs_ctx *>(ctx);
+        for (int i = 0; i < GS_MAX_LANES; i++) if (c->lanes[i]) (void)lane_drain(c->lanes[i]);   // (as gs_get_stats: what the workers were handed is settled)
+        *last_frame = c->lanes[c->cur]->hl_frame;
+    }
+    return GS_OK;
 }
 
 GS_API int gs_compact(gs_ctx *ctx, uint32_t *out_old_index, size_t *out_n)
@@ -2180,6 +2242,10 @@ GS_API int gs_set_option(gs_ctx *ctx, int option, int64_t value)
     case GS_OPT_ANTIALIAS:
         if (value != 0 && value != 1) FAIL(GS_E_BADARG, "anti-aliased splats: 0 (off) or 1 (opacity compensated for the 0.3 px^2 dilation)");
         ctx->aa_opt = (int)value;
+        return GS_OK;
+    case GS_OPT_HIGHLIGHT:
+        if (value < 0 || value > 0xFFFFFFFFll) FAIL(GS_E_BADARG, "highlight: R | G << 8 | B << 16 | W << 24 (W = 0: off)");
+        ctx->hl_opt = (uint32_t)value;
         return GS_OK;
     case GS_OPT_SORT_NEAR:
         if (value < 0 || value > 2) FAIL(GS_E_BADARG, "near-only sorts: 0 (off), 1 (scenes of 4 M splats and more) or 2 (always)");

@@ -228,6 +228,19 @@ GS_HD float antialias_factor(float cov00, float cov01, float cov11, float l1, fl
     r = fminf(fmaxf(r, 0.0f), 1.0f);
     return sqrtf(r);
 }
+// Highlight colour of a selected splat (GS_OPT_HIGHLIGHT): hl = R | G << 8 | B << 16 | W << 24.  Each colour byte c of the word goes W / 255
+// of the way to the highlight's byte h, in unsigned integers: c' = (c * (255 - W) + h * W + 127) / 255, truncating (at most 255 * 255 + 127:
+// no overflow; W = 255 gives h exactly, W = 0 gives c).  The alpha byte stays.
+GS_HD uint32_t highlight_word(uint32_t rgba, uint32_t hl)
+{
+    const uint32_t w = hl >> 24, iw = 255u - w;
+    uint32_t out = rgba & 0xFF000000u;
+    for (uint32_t s = 0; s < 24u; s += 8u) {
+        const uint32_t c = (rgba >> s) & 0xFFu, h = (hl >> s) & 0xFFu;
+        out |= ((c * iw + h * w + 127u) / 255u) << s;
+    }
+    return out;
+}
 // the eigenvalues project_splat draws cov = {cov00, cov01, cov11} with (its very lines)
 GS_HD void dilated_eigenvalues(float cov00, float cov01, float cov11, float &l1, float &l2)
 {

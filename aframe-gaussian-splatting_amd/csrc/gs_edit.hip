@@ -1,5 +1,5 @@
 // gs_edit.hip -- editing the resident cloud (include/gs_splat.h: "editing the resident cloud"): the kernels behind the per-splat state
-// store -- counting, id lists, region selection (box, sphere, screen rectangle) -- and the stable compaction of gs_compact.
+// store -- counting, id lists, region selection (box, sphere, screen rectangle, mask image) -- and the stable compaction of gs_compact.
 //
 // None of this is a per-frame path: every kernel is one streaming pass over the rows (or over the order), its counts go to two device
 // words through one atomic per workgroup, and every launcher waits for its kernel and hands the count back on the host.  What a frame
@@ -105,6 +105,38 @@ __global__ __launch_bounds__(GS_BLOCK) void k_edit_select_rect(const uint32_t *_
         if (gsm::project_splat(cs, cc, u.mv, u.proj, u.focal, u.vw, u.vh, p, x)) {   // what k_project calls, with the frame's uniforms
             const float px = floorf(p.cx), py = u.hm1 - floorf(p.cy);   // GL rows (y up) -> image rows (top-down); NaN compares false
             inside = px >= u.x0 && px < u.x1 && py >= u.y0 && py < u.y1;
+        }
+        if (inside != (invert != 0u)) { state[idx] = (uint8_t)((state[idx] & ~clear) | set); c++; }
+    }
+    block_count(c, hit);
+}
+
+// The same walk against a mask image: one byte per pixel, tight rows of W, row 0 = top (non-zero = inside), and an optional plane of window
+// depths, tight too: a position is taken iff its centre's pixel lies in the frame, the mask is set there and -- with a plane -- the depth
+// k_project writes to zwin is <= the plane's value there (a NaN on either side: not taken)
+struct MaskUniforms { float mv[16], proj[16]; float focal, vw, vh; int32_t W, H; };
+__global__ __launch_bounds__(GS_BLOCK) void k_edit_select_mask(const uint32_t *__restrict__ sorted, const GsControl *__restrict__ ctl, uint32_t n,
+                                                               const uint4 *__restrict__ splat, MaskUniforms u, const uint8_t *__restrict__ mask,
+                                                               const float *__restrict__ depth_max, uint8_t *__restrict__ state,
+                                                               uint32_t set, uint32_t clear, uint32_t invert, uint32_t *__restrict__ hit)
+{
+    const uint32_t V = ctl->n_kept < n ? ctl->n_kept : n;           // the whole order: V positions, every value an index below n
+    uint32_t c = 0;
+    for (uint32_t j = blockIdx.x * GS_BLOCK + threadIdx.x; j < V; j += gridDim.x * GS_BLOCK) {
+        const uint32_t idx = sorted[j];
+        if (idx >= n) continue;
+        const uint4 cs4 = splat[2 * (size_t)idx], cc4 = splat[2 * (size_t)idx + 1];
+        const float cs[4] = { __uint_as_float(cs4.x), __uint_as_float(cs4.y), __uint_as_float(cs4.z), __uint_as_float(cs4.w) };
+        const uint32_t cc[4] = { cc4.x, cc4.y, cc4.z, cc4.w };
+        gsm::Projected p; gsm::ProjExtra x;
+        bool inside = false;
+        if (gsm::project_splat(cs, cc, u.mv, u.proj, u.focal, u.vw, u.vh, p, x)) {   // what k_project calls, with the frame's uniforms
+            const float fx = floorf(p.cx), fy = floorf(p.cy);
+            if (fx >= 0.0f && fx < (float)u.W && fy >= 0.0f && fy < (float)u.H) {     // (NaN compares false; inside the frame: exact integers)
+                const size_t px = (size_t)(u.H - 1 - (int32_t)fy) * (size_t)u.W + (size_t)(int32_t)fx;   // GL rows (y up) -> image rows (top-down)
+                inside = mask[px] != 0;
+                if (inside && depth_max) inside = x.zndc * 0.5f + 0.5f <= depth_max[px];   // k_project's zwin
+            }
         }
         if (inside != (invert != 0u)) { state[idx] = (uint8_t)((state[idx] & ~clear) | set); c++; }
     }
@@ -261,6 +293,24 @@ int gs_edit_select_rect(gs_ctx *ctx, gs_ctx *L, const GsFrameUniforms &f, const 
     GS_HIP(hipStreamSynchronize(ctx->stream));
     hipLaunchKernelGGL(k_edit_select_rect, dim3(stream_grid(ctx->n)), dim3(GS_BLOCK), 0, L->stream, (const uint32_t *)L->sorted, (const GsControl *)L->ctl,
                        (uint32_t)ctx->n, (const uint4 *)ctx->splat, u, ctx->edit_state, (uint32_t)set, (uint32_t)clear, invert ? 1u : 0u, ctx->edit_cnt);
+    GS_HIP(hipGetLastError());
+    GS_HIP(hipStreamSynchronize(L->stream));
+    return read_counter(ctx, hit);
+}
+
+int gs_edit_select_mask(gs_ctx *ctx, gs_ctx *L, const GsFrameUniforms &f, const uint8_t *mask_dev, const float *depth_dev, uint8_t set, uint8_t clear,
+                        bool invert, size_t *hit)
+{
+    int rc = counters(ctx);
+    if (rc != GS_OK) return rc;
+    MaskUniforms u;
+    memcpy(u.mv, f.mv, sizeof u.mv); memcpy(u.proj, f.proj, sizeof u.proj);
+    u.focal = f.focal; u.vw = f.vw; u.vh = f.vh; u.W = f.W; u.H = f.H;
+    // (the uploads and the counters went to the owner's stream; the lane's stream holds the order: as gs_edit_select_rect)
+    GS_HIP(hipStreamSynchronize(ctx->stream));
+    hipLaunchKernelGGL(k_edit_select_mask, dim3(stream_grid(ctx->n)), dim3(GS_BLOCK), 0, L->stream, (const uint32_t *)L->sorted, (const GsControl *)L->ctl,
+                       (uint32_t)ctx->n, (const uint4 *)ctx->splat, u, mask_dev, depth_dev, ctx->edit_state, (uint32_t)set, (uint32_t)clear, invert ? 1u : 0u,
+                       ctx->edit_cnt);
     GS_HIP(hipGetLastError());
     GS_HIP(hipStreamSynchronize(L->stream));
     return read_counter(ctx, hit);

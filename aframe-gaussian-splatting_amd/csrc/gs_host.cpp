@@ -347,6 +347,34 @@ GS_API int gs_antialias_factor(const float cov[3], float *out_c)
     return GS_OK;
 }
 
+GS_API int gs_highlight_word(uint32_t rgba, uint32_t option_value, uint32_t *out)
+{
+    if (!out) return GS_E_BADARG;
+    *out = (option_value >> 24) ? gsm::highlight_word(rgba, option_value) : rgba;   // (W = 0: the option is off)
+    return GS_OK;
+}
+
+// even-odd fill, pixel centres, f64; the crossing test's operations in the header's order (un-fused: -ffp-contract=off)
+GS_API int gs_mask_polygon(const float *xy, size_t npoints, int fb_width, int fb_height, uint8_t *mask_out, size_t stride)
+{
+    if (!mask_out || (!xy && npoints) || fb_width <= 0 || fb_height <= 0 || (stride && stride < (size_t)fb_width)) return GS_E_BADARG;
+    const size_t st = stride ? stride : (size_t)fb_width;
+    for (int y = 0; y < fb_height; y++) memset(mask_out + (size_t)y * st, 0, (size_t)fb_width);
+    if (npoints < 3) return GS_OK;
+    for (int y = 0; y < fb_height; y++) {
+        const double py = (double)y + 0.5;
+        uint8_t *row = mask_out + (size_t)y * st;
+        for (size_t k = 0; k < npoints; k++) {
+            const size_t k1 = k + 1 < npoints ? k + 1 : 0;
+            const double xa = (double)xy[2 * k], ya = (double)xy[2 * k + 1], xb = (double)xy[2 * k1], yb = (double)xy[2 * k1 + 1];
+            if ((ya <= py) == (yb <= py)) continue;               // the edge does not cross this row of centres
+            const double xc = xa + (py - ya) * (xb - xa) / (yb - ya);
+            for (int x = 0; x < fb_width; x++) if ((double)x + 0.5 < xc) row[x] ^= 1u;
+        }
+    }
+    return GS_OK;
+}
+
 GS_API int gs_camera_in_object(const float model_view[16], double out[3])
 {
     if (!model_view || !out) return GS_E_BADARG;

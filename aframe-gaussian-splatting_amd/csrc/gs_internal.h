@@ -159,6 +159,10 @@ struct GsFrameUniforms {           // per-render constants, passed by value to k
     uint32_t surface;              // != 0: a surface frame -- tile lists, k_blend_surf
     // anti-aliased splats (GS_OPT_ANTIALIAS; behind everything else once more).  Read by the host only: it picks k_project<.., AA>
     uint32_t antialias;            // != 0: this frame's projection writes alpha * antialias_factor into its records
+    // highlighted selection (GS_OPT_HIGHLIGHT; at the very end).  The host picks k_project<.., HL> iff highlight != 0; only that kernel reads the store
+    uint32_t highlight;            // R | G << 8 | B << 16 | W << 24; 0 unless the option's W > 0 AND the state store is non-empty
+    uint32_t hl_rows;              // the state store's length: splats beyond it have state 0
+    const uint8_t *hl_state;       // the store (the owner's edit_state)
 };
 
 struct GsLaneWorker;
@@ -212,6 +216,9 @@ struct gs_ctx {
     uint32_t *edit_cnt;            // two device words the editing kernels count into
     uint32_t sort_hidden;          // lane: edit_hidden when this lane's last sort ran (gs_stats::n_hidden)
     int aa_opt;                    // GS_OPT_ANTIALIAS (owner; taken per frame by gs_fill_uniforms)
+    uint32_t hl_opt;               // GS_OPT_HIGHLIGHT (owner; taken per frame by gs_fill_uniforms)
+    uint32_t hl_frame;             // lane: 1 if the lane's last frame was projected by an HL instantiation (gs_highlight_info; kept out of gs_stats)
+    uint8_t *mask_buf; size_t mask_cap_bytes;   // owner: gs_select_mask's mask and depth plane on the device (grow-only scratch)
 
     // sort scratch (sized by cap)
     float *depth;                  // stored f32 depth or +inf for culled
@@ -443,6 +450,9 @@ int gs_edit_select_box(gs_ctx *ctx, const float box16[16], uint8_t set, uint8_t 
 int gs_edit_select_sphere(gs_ctx *ctx, const float centre[3], float radius, uint8_t set, uint8_t clear, bool invert, size_t *hit);
 // ... and over the whole order lane L holds (its control block says how long it is), projected with the uniforms u
 int gs_edit_select_rect(gs_ctx *ctx, gs_ctx *L, const GsFrameUniforms &u, const int32_t rect[4], uint8_t set, uint8_t clear, bool invert, size_t *hit);
+// ... against a mask image in device memory (tight rows of u.W bytes, row 0 = top) and an optional plane of window depths (tight, may be null)
+int gs_edit_select_mask(gs_ctx *ctx, gs_ctx *L, const GsFrameUniforms &u, const uint8_t *mask_dev, const float *depth_dev, uint8_t set, uint8_t clear,
+                        bool invert, size_t *hit);
 // stable compaction of the owner's resident arrays into `to` (allocated by the caller for ctx->cap splats; sh may be null); *kept = splats written
 struct GsCompactTo { uint4 *splat; float4 *sort_rows; float *bound_r; uint8_t *state; float *sh; uint32_t *old_index; };
 int gs_edit_compact(gs_ctx *ctx, const GsCompactTo &to, size_t *kept);

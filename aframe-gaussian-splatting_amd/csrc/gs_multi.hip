@@ -252,6 +252,14 @@ GS_API int gs_multi_select_rect(gs_multi *m, const gs_render_params *p, const in
     return run_all(m, [=](gs_ctx *c, int i) { return gs_select_rect(c, p, rect, set_bits, clear_bits, flags, i == 0 ? out_hit : nullptr); });
 }
 
+GS_API int gs_multi_select_mask(gs_multi *m, const gs_render_params *p, const uint8_t *mask, size_t mask_stride, const float *depth_max, uint8_t set_bits,
+                                uint8_t clear_bits, uint32_t flags, size_t *out_hit)
+{
+    if (!m) return GS_E_BADARG;
+    m->have_sort = false;
+    return run_all(m, [=](gs_ctx *c, int i) { return gs_select_mask(c, p, mask, mask_stride, depth_max, set_bits, clear_bits, flags, i == 0 ? out_hit : nullptr); });
+}
+
 GS_API int gs_multi_compact(gs_multi *m, uint32_t *out_old_index, size_t *out_n)
 {
     if (!m) return GS_E_BADARG;

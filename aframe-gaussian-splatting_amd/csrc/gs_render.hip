@@ -139,7 +139,9 @@ __device__ __forceinline__ uint32_t sh_colour_word(const GsFrameUniforms &u, uin
 
 // AA (anti-aliased splats, GS_OPT_ANTIALIAS): the record's alpha float is alpha * gsm::antialias_factor -- the one word that differs; the
 // splat is written, counted and binned whatever the factor (0 included), so geometry, coverage and every count stay what they are.
-template <int ROUND, bool RUNS, bool SH, bool AA>
+// HL (highlighted selection, GS_OPT_HIGHLIGHT): a splat that writes its record and whose state byte has GS_STATE_SELECTED blends the RGB
+// bytes of its colour word -- after SH -- towards the frame's highlight colour (gsm::highlight_word); one byte load per record written.
+template <int ROUND, bool RUNS, bool SH, bool AA, bool HL>
 __device__ __forceinline__ void k_project_body(const uint32_t *__restrict__ sorted, const uint4 *__restrict__ splat,
                                                const GsFrameUniforms &u, gsm::Projected *__restrict__ proj, uint2 *__restrict__ rect,
                                                uint32_t *__restrict__ tile_count, uint32_t *__restrict__ spine,
@@ -189,7 +191,9 @@ __device__ __forceinline__ void k_project_body(const uint32_t *__restrict__ sort
                     if (!RUNS || ty1 - ty0 >= 2) rect[j] = make_uint2(tx0 | (ty0 << 16), tx1 | (ty1 << 16));   // (RUNS, one or two tile rows: the runs themselves, below)
                     float4 *dst = reinterpret_cast<float4 *>(proj + j);
                     dst[0] = make_float4(p.cx, p.cy, p.ax, p.ay);
-                    dst[1] = make_float4(p.bx, p.by, __uint_as_float(SH ? sh_colour_word(u, idx, cs, p.rgba) : p.rgba), AA ? p.alpha * x.aa : p.alpha);
+                    uint32_t rgba = SH ? sh_colour_word(u, idx, cs, p.rgba) : p.rgba;
+                    if (HL && idx < u.hl_rows && (u.hl_state[idx] & GS_STATE_SELECTED)) rgba = gsm::highlight_word(rgba, u.highlight);
+                    dst[1] = make_float4(p.bx, p.by, __uint_as_float(rgba), AA ? p.alpha * x.aa : p.alpha);
                     if (u.has_depth | u.surface) zwin[j] = x.zndc * 0.5f + 0.5f;   // gl_FragCoord.z of every fragment of the quad (a surface frame's depth plane)
                     if (ty1 - ty0 >= 2) {
                         // three or more tile rows: counted cooperatively, one lane per row -- by 16-lane groups up to 16 rows
@@ -272,15 +276,15 @@ __device__ __forceinline__ void k_project_body(const uint32_t *__restrict__ sort
     if (threadIdx.x == 0) part_vis[blockIdx.x] = s_vis;
 }
 
-// plain, with view-dependent colour (SH), with compensated opacity (AA), or both
-template <int ROUND, bool RUNS, bool SH, bool AA>
+// plain, with view-dependent colour (SH), with compensated opacity (AA), with the selection highlighted (HL), or any of them together
+template <int ROUND, bool RUNS, bool SH, bool AA, bool HL>
 __global__ __launch_bounds__(GS_BLOCK) void k_project(const uint32_t *__restrict__ sorted, const uint4 *__restrict__ splat,
                                                       GsFrameUniforms u, gsm::Projected *__restrict__ proj, uint2 *__restrict__ rect,
                                                       uint32_t *__restrict__ tile_count, uint32_t *__restrict__ spine,
                                                       uint32_t *__restrict__ part_vis, const uint32_t *__restrict__ mask,
                                                       float *__restrict__ zwin, GsControl *ctl)
 {
-    k_project_body<ROUND, RUNS, SH, AA>(sorted, splat, u, proj, rect, tile_count, spine, part_vis, mask, zwin, ctl);
+    k_project_body<ROUND, RUNS, SH, AA, HL>(sorted, splat, u, proj, rect, tile_count, spine, part_vis, mask, zwin, ctl);
 }
 
 // One workgroup: exclusive scan of the per-chunk totals (spine) -> chunk base offsets, I = grand total (refused and
@@ -1904,7 +1908,7 @@ int bits_for(uint32_t n) { int b = 1; while (b < 32 && (1u << b) < n) b++; retur
 // The kernels of a round as body functors (gs_internal.h: GS_BODY), each with its plain kernel: what gs_launch<NF, F, ...> launches for one frame
 // (the plain kernel) and for a pair (k_twin<F, ...>).  A NEW KERNEL gets its body, its thin __global__ wrapper, one line here and one gs_launch
 // in the sequence below -- once, for both frame counts.
-template <int ROUND, bool RUNS, bool SH, bool AA> GS_BODY(F_project, (k_project<ROUND, RUNS, SH, AA>), (k_project_body<ROUND, RUNS, SH, AA>));
+template <int ROUND, bool RUNS, bool SH, bool AA, bool HL> GS_BODY(F_project, (k_project<ROUND, RUNS, SH, AA, HL>), (k_project_body<ROUND, RUNS, SH, AA, HL>));
 template <int ROUND> GS_BODY(F_row_scan, (k_row_scan<ROUND>), (k_row_scan_body<ROUND>));
 template <int ROUND> GS_BODY(F_emit_runs, (k_emit_runs<ROUND>), (k_emit_runs_body<ROUND>));
 template <int ROUND> GS_BODY(F_seg_count, (k_seg_count<ROUND>), (k_seg_count_body<ROUND>));
@@ -2018,7 +2022,8 @@ bool row_walk_round(const GsFrameUniforms &u)
     return ROUND == 0 && u.row_walk && !(u.flags & GS_RENDER_COUNT_FRAGS) && !u.record_staged && !u.subtile && !u.split_min;
 }
 
-// the projection of a round: plain, with view-dependent colour (GS_OPT_SH_DEGREE), with compensated opacity (GS_OPT_ANTIALIAS), or both.
+// the projection of a round: plain, with view-dependent colour (GS_OPT_SH_DEGREE), with compensated opacity (GS_OPT_ANTIALIAS), with the selection highlighted
+// (GS_OPT_HIGHLIGHT and a non-empty state store), or any of them together.
 // RUNS: a span-list round (row counts per 256-splat chunk) / the pair records (tiles touched per chunk: the spine).  F[k]: the frame as
 // the kernel sees it
 template <int ROUND, bool RUNS, int NF>
@@ -2029,9 +2034,9 @@ void launch_project(gs_ctx *const S[], const GsFrameUniforms F[], uint32_t g)
         return gs_pack_make((const uint32_t *)S[k]->sorted, (const uint4 *)S[k]->splat, F[k], S[k]->proj, S[k]->rect, S[k]->tile_count, RUNS ? S[k]->row_cnt : S[k]->spine,
                             S[k]->part_vis, (const uint32_t *)S[k]->unsat_mask, S[k]->zwin, S[k]->ctl);
     };
-    gs_flag(F[0].sh_degree != 0, [&](auto SH) { gs_flag(F[0].antialias != 0, [&](auto AA) {
-        gs_launch<NF, F_project<ROUND, RUNS, decltype(SH)::value, decltype(AA)::value>, GS_BLOCK>(g, st, 0, args);
-    }); });
+    gs_flag(F[0].sh_degree != 0, [&](auto SH) { gs_flag(F[0].antialias != 0, [&](auto AA) { gs_flag(F[0].highlight != 0, [&](auto HL) {
+        gs_launch<NF, F_project<ROUND, RUNS, decltype(SH)::value, decltype(AA)::value, decltype(HL)::value>, GS_BLOCK>(g, st, 0, args);
+    }); }); });
 }
 
 // one round with span lists: project (+ row counts) -> row scan -> runs -> lists -> blend (row walk: no lists)
@@ -2173,7 +2178,7 @@ bool gs_frames_batchable(const GsFrameUniforms &a, const GsFrameUniforms &b)
     return a.near_count == b.near_count && a.skip_round1 == b.skip_round1 && a.W == b.W && a.H == b.H && a.x0 == b.x0 && a.x1 == b.x1 &&
            a.flags == b.flags && !(a.flags & (GS_RENDER_COUNT_FRAGS | GS_RENDER_COUNT_EVALUATED)) && !a.record_staged && !b.record_staged &&
            a.split_min == b.split_min && a.subtile == b.subtile && a.row_walk == b.row_walk && a.has_depth == b.has_depth && a.has_scene_rgba == b.has_scene_rgba && a.t_eps == b.t_eps &&
-           a.sh_degree == b.sh_degree && a.antialias == b.antialias && !a.surface && !b.surface;
+           a.sh_degree == b.sh_degree && a.antialias == b.antialias && a.highlight == b.highlight && !a.surface && !b.surface;
 }
 
 int gs_run_render2(gs_ctx *const S[2], const GsFrameUniforms U[2], uint8_t *const device_out[2])

@@ -27,6 +27,7 @@ const schema = {                                   // index.js:2-7
 };
 const OPT_SH_DEGREE = 19;
 const OPT_ANTIALIAS = 20;
+const OPT_HIGHLIGHT = 23;
 const ROW_LENGTH = 3 * 4 + 3 * 4 + 4 + 4;          // index.js:227
 
 function elementsOf(m) { return m && m.elements ? m.elements : m; }
@@ -263,6 +264,32 @@ class GaussianSplatting {
     if (!v) throw new Error('selectRect: no frame has been drawn yet');
     return native.selectRect(this.handle, this._renderParams(v.camera, v.viewport, v.options), [x0, y0, x1, y1], o.hide ? 1 : 2, 0, o.invert ? 1 : 0);
   }
+  // Any screen-space region, as a mask image over the CURRENT frame's drawing buffer: Uint8Array(width * height), row 0 = top, non-zero =
+  // inside.  opts.hide / opts.invert as above; opts.visibleOnly: only what that view shows -- the frame's surface is drawn
+  // (renderSurface) and its depth plane limits the selection to the surface splats and what lies in front of them.
+  selectMask(mask, opts) {
+    const v = this._lastView, o = opts || {};
+    if (!v) throw new Error('selectMask: no frame has been drawn yet');
+    const whole = { width: v.viewport.width, height: v.viewport.height };
+    const depth = o.visibleOnly ? this.renderSurface(v.camera, whole, v.options).depth : null;
+    const p = this._renderParams(v.camera, whole, v.options);
+    this._lastView = v;
+    return native.selectMask(this.handle, p, mask, depth, o.hide ? 1 : 2, 0, o.invert ? 1 : 0);
+  }
+  // A lasso: points = [x, y, x, y, ...] or [[x, y], ...] in pixels of that buffer, closed by itself, even-odd fill at pixel centres
+  selectLasso(points, opts) {
+    const v = this._lastView;
+    if (!v) throw new Error('selectLasso: no frame has been drawn yet');
+    const flat = Array.isArray(points) && Array.isArray(points[0]) ? [].concat(...points) : points;
+    return this.selectMask(native.maskPolygon(flat, v.viewport.width, v.viewport.height), opts);
+  }
+  // Show the selection: every frame tints the selected splats towards color ([r, g, b] bytes) by weight / 255 (GS_OPT_HIGHLIGHT; only
+  // the colour word of a selected splat's projected record changes).  weight 0 or no arguments: off.  Takes effect with the next draw.
+  highlightSelected(color, weight) {
+    const c = color || [0, 0, 0], w = color ? (weight === undefined ? 128 : weight) : 0;
+    native.setOption(this.handle, OPT_HIGHLIGHT, ((c[0] & 255) | (c[1] & 255) << 8 | (c[2] & 255) << 16) + (w & 255) * 16777216);
+  }
+  highlightInfo() { return native.highlightInfo(this.handle); }
   // real deletion of the hidden splats (the GPU holds the cloud twice for the duration of the call) -> Uint32Array: the old index of
   // every splat that stays
   deleteHidden() {

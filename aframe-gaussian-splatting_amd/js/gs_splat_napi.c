@@ -614,6 +614,76 @@ static napi_value fn_select_rect(napi_env env, napi_callback_info info)
     return make_count(env, hit);
 }
 
+/* selectMask(h, params, Uint8Array mask (fbWidth x fbHeight, tight, row 0 = top), Float32Array depthMax | null, setBits, clearBits, flags)
+ * -> positions of the order hit */
+static napi_value fn_select_mask(napi_env env, napi_callback_info info)
+{
+    napi_value argv[7];
+    if (!get_args(env, info, 7, argv, NULL)) return NULL;
+    gs_ctx *ctx = get_ctx(env, argv[0]); if (!ctx) return NULL;
+    gs_render_params p;
+    uint32_t set = 0, clear = 0, flags = 0;
+    void *mask = NULL, *depth = NULL; size_t mlen = 0, dlen = 0;
+    if (!fill_params(env, argv[1], &p) || !get_bytes(env, argv[2], &mask, &mlen) || (!is_nullish(env, argv[3]) && !get_bytes(env, argv[3], &depth, &dlen)) ||
+        !get_u32(env, argv[4], &set) || !get_u32(env, argv[5], &clear) || !get_u32(env, argv[6], &flags)) {
+        napi_throw_type_error(env, NULL, "selectMask: (handle, params, Uint8Array mask, Float32Array depthMax | null, setBits, clearBits, flags)");
+        return NULL;
+    }
+    if (p.fb_width <= 0 || p.fb_height <= 0) { napi_throw_range_error(env, NULL, "selectMask: empty frame"); return NULL; }
+    const size_t px = (size_t)p.fb_width * (size_t)p.fb_height;
+    if (mlen < px || (depth && dlen < px * 4)) { napi_throw_range_error(env, NULL, "selectMask: mask or depth plane smaller than the frame"); return NULL; }
+    size_t hit = 0;
+    int rc = gs_select_mask(ctx, &p, (const uint8_t *)mask, 0, (const float *)depth, (uint8_t)set, (uint8_t)clear, flags, &hit);
+    if (rc != GS_OK) return throw_gs(env, ctx, rc);
+    return make_count(env, hit);
+}
+
+/* maskPolygon(points (Float32Array | Array of x, y, x, y, ...), width, height) -> Uint8Array(width * height) of 0 / 1 (no context) */
+static napi_value fn_mask_polygon(napi_env env, napi_callback_info info)
+{
+    napi_value argv[3]; int32_t w = 0, h = 0; uint32_t n = 0;
+    if (!get_args(env, info, 3, argv, NULL)) return NULL;
+    napi_value lenv;
+    if (napi_get_named_property(env, argv[0], "length", &lenv) != napi_ok || napi_get_value_uint32(env, lenv, &n) != napi_ok ||
+        napi_get_value_int32(env, argv[1], &w) != napi_ok || napi_get_value_int32(env, argv[2], &h) != napi_ok) {
+        napi_throw_type_error(env, NULL, "maskPolygon: (points [x, y, ...], width, height)");
+        return NULL;
+    }
+    if (w <= 0 || h <= 0 || (n & 1u)) { napi_throw_range_error(env, NULL, "maskPolygon: bad size, or an odd number of coordinates"); return NULL; }
+    double *d = (double *)malloc((n ? n : 1) * sizeof(double));
+    float *xy = (float *)malloc((n ? n : 1) * sizeof(float));
+    if (!d || !xy || (n && !get_doubles(env, argv[0], d, n))) {
+        free(d); free(xy);
+        napi_throw_type_error(env, NULL, "maskPolygon: points must be numbers");
+        return NULL;
+    }
+    for (uint32_t i = 0; i < n; i++) xy[i] = (float)d[i];
+    free(d);
+    napi_value ab, ta; void *out = NULL;
+    if (napi_create_arraybuffer(env, (size_t)w * (size_t)h, &out, &ab) != napi_ok) { free(xy); napi_throw_error(env, NULL, "maskPolygon: out of memory"); return NULL; }
+    int rc = gs_mask_polygon(xy, n / 2, w, h, (uint8_t *)out, 0);
+    free(xy);
+    if (rc != GS_OK) { napi_throw_error(env, NULL, "maskPolygon: bad argument"); return NULL; }
+    NAPI_OK(napi_create_typedarray(env, napi_uint8_array, (size_t)w * (size_t)h, ab, 0, &ta));
+    return ta;
+}
+
+/* highlightInfo(h) -> { value, lastFrame } */
+static napi_value fn_highlight_info(napi_env env, napi_callback_info info)
+{
+    napi_value argv[1];
+    if (!get_args(env, info, 1, argv, NULL)) return NULL;
+    gs_ctx *ctx = get_ctx(env, argv[0]); if (!ctx) return NULL;
+    uint32_t value = 0, last = 0;
+    int rc = gs_highlight_info(ctx, &value, &last);
+    if (rc != GS_OK) return throw_gs(env, ctx, rc);
+    napi_value o, v;
+    NAPI_OK(napi_create_object(env, &o));
+    NAPI_OK(napi_create_uint32(env, value, &v)); NAPI_OK(napi_set_named_property(env, o, "value", v));
+    NAPI_OK(napi_create_uint32(env, last, &v)); NAPI_OK(napi_set_named_property(env, o, "lastFrame", v));
+    return o;
+}
+
 /* compact(h) -> Uint32Array: the old index of every splat that stays */
 static napi_value fn_compact(napi_env env, napi_callback_info info)
 {
@@ -1272,6 +1342,7 @@ static napi_value init(napi_env env, napi_value exports)
         { "scaledSize", fn_scaled_size },
         { "setState", fn_set_state }, { "setStateIds", fn_set_state_ids }, { "selectBox", fn_select_box }, { "selectSphere", fn_select_sphere },
         { "selectRect", fn_select_rect }, { "compact", fn_compact },
+        { "selectMask", fn_select_mask }, { "maskPolygon", fn_mask_polygon }, { "highlightInfo", fn_highlight_info },
         { "createMulti", fn_create_multi }, { "multiDestroy", fn_multi_destroy }, { "multiPushSplat", fn_multi_push_splat },
         { "multiLoadPly", fn_multi_load_ply }, { "multiClear", fn_multi_clear }, { "multiCount", fn_multi_count },
         { "multiSetOption", fn_multi_set_option }, { "multiSort", fn_multi_sort }, { "multiRender", fn_multi_render },

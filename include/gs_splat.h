@@ -240,16 +240,15 @@ GS_API int gs_pick(gs_ctx *ctx, const gs_render_params *p, const int32_t *xy, si
  * scene).  Nothing downstream knows about states: the order does not contain the splat, so projection, binning, every blend path,
  * surface frames and gs_pick never see it.  This holds for gs_sort, gs_sort_for, gs_sort_begin / gs_sort_poll, gs_sort_gathered, the
  * rank that sorts under GS_OPT_SORT_SHARE and the whole-order sorts a render or gs_download(GS_BUF_SORTED) runs by itself.
- *   - GS_STATE_SELECTED changes no pixel: it is the caller's mark (what a later call hides, shows or reads back).  Bits 2..7 belong to
- *     the caller and are kept untouched by the library.
+ *   - GS_STATE_SELECTED changes no pixel by itself: it is the caller's mark (what a later call hides, shows or reads back), and what
+ *     GS_OPT_HIGHLIGHT tints.  Bits 2..7 belong to the caller and are kept untouched by the library.
  *   - Splats beyond the store's length have state 0 (progressive loading keeps working); gs_clear empties the store.  While the store
  *     is empty the sorts launch the very kernels of a context that never edits.
  *   - Every call that changes the store behaves like a push: frames in flight are drained first, every lane's order is dropped (a
  *     render before the next sort draws the background only, as after a push), and gs_sync() does not draw frames of before the change again by itself.
  *     A state change takes effect at the NEXT sort: a draw uses the last completed order (index.js:201-207).
  *   - gs_stats.n_hidden: the hidden splats the last collected sort skipped.
- * Out of scope: a highlight colour for selected splats (a projection variant), lasso or mask-image selection, in-place edits of a
- * splat's position or colour, undo. */
+ * Out of scope: in-place edits of a splat's position or colour, undo. */
 #define GS_STATE_HIDDEN 1u
 #define GS_STATE_SELECTED 2u
 #define GS_SELECT_INVERT 1u      /* region calls: apply the rule to the splats NOT in the region */
@@ -276,6 +275,30 @@ GS_API int gs_select_box(gs_ctx *ctx, const float box16[16], uint8_t set_bits, u
 GS_API int gs_select_sphere(gs_ctx *ctx, const float centre[3], float radius, uint8_t set_bits, uint8_t clear_bits, uint32_t flags, size_t *out_hit);
 GS_API int gs_select_rect(gs_ctx *ctx, const gs_render_params *p, const int32_t rect[4], uint8_t set_bits, uint8_t clear_bits, uint32_t flags,
                           size_t *out_hit);
+/*   mask    screen space like rect, any shape: mask = fb_width x fb_height bytes in HOST memory, row 0 = top, mask_stride bytes per row
+ *           (0 = tight; a non-zero stride below fb_width: GS_E_BADARG), non-zero = the pixel is in the region.  depth_max (optional):
+ *           fb_width x fb_height f32, tight, window depths in the convention of gs_set_scene and the surface depth plane.  Walks the
+ *           whole order as rect does and takes a position iff the projection of that frame accepts the splat, col = floor(cx) lies in
+ *           [0, fb_width), row = fb_height - 1 - floor(cy) lies in [0, fb_height), mask[row][col] != 0 and -- with depth_max --
+ *           zndc * 0.5f + 0.5f <= depth_max[row][col] (f32, the value the projection writes for depth tests; a NaN on either side is
+ *           false).  Passing the depth plane of gs_render_surface of the same frame selects what is visible: the surface splats and
+ *           what lies in front of them; a caller who wants slack adds it to the plane.  INVERT, *out_hit and the errors: as rect; NULL
+ *           mask or p: GS_E_BADARG.  Mask and plane are uploaded for the call (the context keeps the device buffer, grow-only). */
+GS_API int gs_select_mask(gs_ctx *ctx, const gs_render_params *p, const uint8_t *mask, size_t mask_stride, const float *depth_max, uint8_t set_bits,
+                          uint8_t clear_bits, uint32_t flags, size_t *out_hit);
+/* A lasso as a mask, on the host (no context, no GPU): even-odd fill of the closed polygon xy = npoints x (x, y) in pixels, row 0 = top,
+ * the last vertex joins the first.  mask_out: fb_height rows of `stride` bytes (0 = tight); the first fb_width bytes of every row are
+ * written 1 or 0, bytes beyond them stay untouched.  Pixel (x, y) is tested at its centre (px, py) = (x + 0.5, y + 0.5), all in f64,
+ * un-fused: an edge a -> b counts iff (ya <= py) != (yb <= py) and px < xa + (py - ya) * (xb - xa) / (yb - ya), evaluated in that
+ * order; the pixel is 1 iff the count is odd.  npoints < 3: an all-zero mask, GS_OK.  NULL pointers, non-positive sizes, a non-zero
+ * stride below fb_width: GS_E_BADARG. */
+GS_API int gs_mask_polygon(const float *xy, size_t npoints, int fb_width, int fb_height, uint8_t *mask_out, size_t stride);
+/* GS_OPT_HIGHLIGHT as it stands (*option_value) and whether the last frame of the current frame's lane was projected by the
+ * highlighting kernels (*last_frame: 1 / 0; 0 while the option is off or the store is empty).  Either pointer may be NULL. */
+GS_API int gs_highlight_info(const gs_ctx *ctx, uint32_t *option_value, uint32_t *last_frame);
+/* The colour word GS_OPT_HIGHLIGHT = option_value gives a selected splat whose word is rgba (R | G << 8 | B << 16 | A << 24), by the
+ * kernel's own function; W = 0 returns rgba.  out NULL: GS_E_BADARG. */
+GS_API int gs_highlight_word(uint32_t rgba, uint32_t option_value, uint32_t *out);
 /* Real deletion: every hidden splat leaves the resident arrays (both 16-byte records, the sort rows, the strip bounds, the SH rows of
  * the kept splats among those that have one, the states -- hidden bit gone by definition, the other bits travel with the splat), in
  * stable order.  out_old_index (optional, capacity gs_count() BEFORE the call): out_old_index[k] = the old index of new splat k;
@@ -406,6 +429,8 @@ GS_API int gs_multi_select_box(gs_multi *m, const float box16[16], uint8_t set_b
 GS_API int gs_multi_select_sphere(gs_multi *m, const float centre[3], float radius, uint8_t set_bits, uint8_t clear_bits, uint32_t flags, size_t *out_hit);
 GS_API int gs_multi_select_rect(gs_multi *m, const gs_render_params *p, const int32_t rect[4], uint8_t set_bits, uint8_t clear_bits, uint32_t flags,
                                 size_t *out_hit);
+GS_API int gs_multi_select_mask(gs_multi *m, const gs_render_params *p, const uint8_t *mask, size_t mask_stride, const float *depth_max, uint8_t set_bits,
+                                uint8_t clear_bits, uint32_t flags, size_t *out_hit);
 GS_API int gs_multi_compact(gs_multi *m, uint32_t *out_old_index, size_t *out_n);
 GS_API size_t gs_multi_count(const gs_multi *m);
 GS_API int gs_multi_set_option(gs_multi *m, int option, int64_t value);              /* gs_set_option on every device     */
@@ -635,6 +660,21 @@ typedef struct gs_stats {
                                    from such an order are right without further ado: a frame that reads more of the order than the lane holds
                                    sorts again in full first, as after any near-only sort.  0 (default): the policy decides.  Negative values, and
                                    values beyond 2^32 - 1: GS_E_BADARG.                                                              */
+#define GS_OPT_HIGHLIGHT 23      /* a highlight colour for the selected splats.  value = R | G << 8 | B << 16 | W << 24 (u32): the colour and its
+                                   weight W; W = 0 (default: 0) switches the option off whatever the colour bytes are.  With W > 0 and a non-empty
+                                   state store, every frame's projection changes the colour word of each splat it writes a record for whose
+                                   index is below the store's length and whose byte has GS_STATE_SELECTED: for each of the three colour bytes
+                                     c' = (c * (255 - W) + h * W + 127) / 255      (unsigned integers, truncating; h = R, G or B)
+                                   AFTER the spherical-harmonics colour where GS_OPT_SH_DEGREE is active; independent of GS_OPT_ANTIALIAS.  The
+                                   alpha byte and the alpha float stay.  Only that word changes: geometry, coverage, runs, lists and every
+                                   count are those of a frame without the option, and every binning and blend path, surface frames and
+                                   gs_pick, strips, gathered and gs_multi frames see the record only.  Splats beyond the store are never
+                                   highlighted; hidden ones are not in the order.  Taken per frame like GS_OPT_ANTIALIAS (each eye, each
+                                   strip); changing it drops no order, while state changes take effect at the next sort as always; paired
+                                   frames (GS_OPT_FRAME_BATCH) share the value.  While the option is off or the store is empty a frame
+                                   launches the kernels it launches without the option (gs_highlight_info says what a frame took;
+                                   gs_highlight_word evaluates the rule on the host).  Negative values and values beyond 2^32 - 1:
+                                   GS_E_BADARG.                                                                                     */
 GS_API int gs_set_option(gs_ctx *ctx, int option, int64_t value);
 GS_API int gs_get_stats(gs_ctx *ctx, gs_stats *out);
 
