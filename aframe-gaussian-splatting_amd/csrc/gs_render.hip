@@ -782,7 +782,10 @@ __device__ __forceinline__ void round_books(GsControl *ctl, unsigned long long I
 // The runs of one chunk of 256 sorted positions, each to its tile row's segment (see above).  The traversal is k_project's:
 // splats of one or two tile rows by their own thread, of up to 16 rows by 16 lanes, beyond by a wavefront -- twice, once to build
 // the occupancy words and once to write.
-template <int ROUND>
+// W16 (round 0 of a row-walk frame: nothing but blend<0, .., WALK> reads these runs): the run's geometry as ONE 16-bit word, first
+// tile column | (tiles - 1) << 8 -- columns are < 256 and a run is at most 256 tiles long -- at halfword `slot` of run_geom, i.e. in
+// the first half of the array the 32-bit words fill; run_ref as ever.
+template <int ROUND, bool W16 = false>
 __device__ __forceinline__ void k_emit_runs_body(const gsm::Projected *__restrict__ proj, const uint2 *__restrict__ rect,
                                                  const uint32_t *__restrict__ tile_count, const uint32_t *__restrict__ row_cnt,
                                                  const uint2 *__restrict__ row_tot, const GsFrameUniforms &u,
@@ -871,7 +874,9 @@ __device__ __forceinline__ void k_emit_runs_body(const gsm::Projected *__restric
             uint32_t rank_ = (uint32_t)__popcll(s_m[TY][wq_] & ((1ull << ((T) & 63u)) - 1ull));                                   \
             for (uint32_t k_ = 0; k_ < wq_; k_++) rank_ += (uint32_t)__popcll(s_m[TY][k_]);                                       \
             const uint32_t slot_ = s_base[TY] + rank_;                                                                            \
-            run_geom[slot_] = (A) | ((N) << 16); run_ref[slot_] = j_lo + c * GS_BLOCK + (T); } while (0)
+            if (W16) reinterpret_cast<uint16_t *>(run_geom)[slot_] = (uint16_t)((A) | (((N) - 1u) << 8));                          \
+            else run_geom[slot_] = (A) | ((N) << 16);                                                                             \
+            run_ref[slot_] = j_lo + c * GS_BLOCK + (T); } while (0)
         GS_RUN_PASS(GS_RUN_WRITE);
 #undef GS_RUN_WRITE
 #undef GS_RUN_MARK
@@ -881,7 +886,7 @@ __device__ __forceinline__ void k_emit_runs_body(const gsm::Projected *__restric
     }
 }
 
-template <int ROUND>
+template <int ROUND, bool W16 = false>
 __global__ __launch_bounds__(GS_BLOCK) void k_emit_runs(const gsm::Projected *__restrict__ proj, const uint2 *__restrict__ rect,
                                                         const uint32_t *__restrict__ tile_count, const uint32_t *__restrict__ row_cnt,
                                                         const uint2 *__restrict__ row_tot, GsFrameUniforms u,
@@ -889,7 +894,8 @@ __global__ __launch_bounds__(GS_BLOCK) void k_emit_runs(const gsm::Projected *__
                                                         const uint32_t *__restrict__ mask, GsControl *ctl, uint32_t pair_cap, uint2 *__restrict__ row_runs,
                                                         const uint32_t *__restrict__ part_vis, uint32_t nparts, int last_round)
 {
-    k_emit_runs_body<ROUND>(proj, rect, tile_count, row_cnt, row_tot, u, run_geom, run_ref, mask, ctl, pair_cap, row_runs, part_vis, nparts, last_round);
+    static_assert(!W16 || ROUND == 0, "the row walk serves round 0");
+    k_emit_runs_body<ROUND, W16>(proj, rect, tile_count, row_cnt, row_tot, u, run_geom, run_ref, mask, ctl, pair_cap, row_runs, part_vis, nparts, last_round);
 }
 
 // Per item of k_lists -- (tile row, segment of the row's runs) -- the difference array of the segment's runs over the tile columns
@@ -1208,11 +1214,18 @@ __device__ __forceinline__ uint32_t subtile_mask(const float4 ra, const float bx
 // depthWrite off, index.js:179-180) and/or colour image (the destination the splats are blended over).
 // SUB: with the sub-tile lists (GS_OPT_SUBTILE; a kernel of its own: the lists cost 20 vector registers, i.e. a wave per SIMD)
 // WALK: the row walk (GS_OPT_ROW_WALK; round 0 of plain frames): no tile lists were built.  `tile_range` is then the table of every
-// tile row's (first run, runs) and `pairs` the run geometry (first tile column | length << 16), the runs' sorted positions u.walk_ref
-// words behind it.  The wave fills each batch itself from the end of its row's runs, 64 runs per step: a ballot of the runs that cover
-// its column, compacted by mbcnt into the batch's slots; a step with more hits than free slots takes the nearest ones and the next
-// step resumes right behind the last run taken.  Batches are thus the list's batches -- same entries, same slots, same order -- and
-// the images, exits and need records are the list path's, bit for bit; the walk stops where the list walk would (every lane left).
+// tile row's (first run, runs) and `pairs` the run geometry as 16-bit words, run i at halfword i (first tile column | (tiles - 1) << 8:
+// k_emit_runs_body<0, true>), the runs' sorted positions as 32-bit words u.walk_ref words behind the array's start.  The wave fills each
+// batch itself from the end of its row's runs, up to 128 runs per step: lane l loads the aligned dword D - l (D: the dword of the last run
+// not examined yet), i.e. runs 2 (D - l) and 2 (D - l) + 1.  Rows lie back to back in the array, so a step's first and last dword may hold
+// a run of the neighbouring row or one examined already: a half counts only if its INDEX lies in [row's first run, cursor).  Two ballots,
+// odd halves and even halves, of the runs that cover the column; a run's slot is the number of hits at larger indices (mbcnt over both
+// ballots, + its own odd half for an even one), and the slot keeps the run's index.  A step with more hits than free slots takes the
+// nearest ones, the cursor becomes the index of the run that took the last slot -- whichever half it is -- and the next batch resumes
+// right behind it; otherwise the cursor drops to the step's lowest dword.  The sorted position is read when the slot is staged, by the
+// lane that stages it (run_ref[index], then proj[j]): 8 % of the runs examined hit, so the scan loads 2 bytes per run and nothing else
+// (LAB_NOTES: 64 runs of 8 bytes per step before, +2.2 % frames/s).  Batches are the list's batches -- same entries, same slots, same
+// order -- and the images, exits and need records are the list path's, bit for bit; the walk stops where the list walk would (every lane left).
 // SURF: a surface frame (gs_render_surface): next to the colour the tile writes, per pixel, the list entry at which the transmittance
 // falls below one half -- the first entry with T_before >= 0.5 > T_after, the median of the blending weights -- as the splat's index
 // (`sorted` at the entry's position), its window depth (zwin) and the pixel's accumulated alpha 1 - T.  T never rises, so a pixel
@@ -1233,7 +1246,7 @@ __device__ __forceinline__ void k_blend_body(const uint2 *__restrict__ tile_rang
     __shared__ float4 s_ent[3 * (GS_BLEND_BATCH + 1)];
     __shared__ float s_z[GS_BLEND_BATCH + 2];                    // their window depths (SCENE only)
     __shared__ __attribute__((aligned(16))) uint8_t s_list[SUB ? GS_SUBTILE_GROUPS * GS_SUBTILE_STRIDE : 16];   // GS_OPT_SUBTILE: per 4x4-pixel block, the batch's entries (slots) that can reach it
-    __shared__ uint32_t s_j[SURF ? 2 * GS_BLEND_BATCH : WALK ? GS_BLEND_BATCH : 1];   // WALK: the batch's sorted positions, by slot; SURF: those, and the window depths behind them
+    __shared__ uint32_t s_j[SURF ? 2 * GS_BLEND_BATCH : WALK ? GS_BLEND_BATCH : 1];   // WALK: the batch's runs (their indices), by slot; SURF: those, and the window depths behind them
     static_assert(!WALK || (!COUNT && ROUND == 0 && !SUB), "the row walk serves round 0 of plain frames");
     static_assert(!SURF || (!COUNT && !SUB && !WALK), "a surface frame takes the tile lists");
     const int lane = threadIdx.x;
@@ -1318,27 +1331,31 @@ __device__ __forceinline__ void k_blend_body(const uint2 *__restrict__ tile_rang
             // the batch's entries: the nearest GS_BLEND_BATCH runs below the cursor that cover column tx (wave-uniform: nb, cur)
             nb = 0;
             do {
-                const uint32_t avail = cur - range.x;
-                bool hit = false;
-                uint32_t jr = 0;
-                if ((uint32_t)lane < avail) {
-                    const uint32_t i = cur - 1u - (uint32_t)lane, g = run_geom[i];
-                    jr = run_ref[i];
-                    hit = tx - (g & 0xFFFFu) < (g >> 16);
-                }
-                const unsigned long long bal = __ballot(hit);
-                const uint32_t pos = nb + __builtin_amdgcn_mbcnt_hi((uint32_t)(bal >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)bal, 0u));
-                if (hit && pos < GS_BLEND_BATCH) s_j[pos] = jr;
-                const uint32_t nh = (uint32_t)__popcll(bal);
+                // lane l takes dword D - l of the 16-bit run words, D the dword of run cur - 1: runs 2 (D - l) and 2 (D - l) + 1.  A row
+                // begins and ends anywhere in a dword, so each half counts by its INDEX in [range.x, cur); lanes beyond the array's
+                // first dword load it again and test nothing
+                const uint32_t D = (cur - 1u) >> 1, d = D - (uint32_t)lane, left = cur - range.x;
+                const bool in = (uint32_t)lane <= D;
+                const uint32_t g = run_geom[in ? d : 0u], i0 = 2u * d, i1 = i0 + 1u;
+                const bool hit1 = in && i1 - range.x < left && tx - ((g >> 16) & 0xFFu) <= (g >> 24);
+                const bool hit0 = in && i0 - range.x < left && tx - (g & 0xFFu) <= ((g >> 8) & 0xFFu);
+                // nearest first: a run's slot is nb + the hits at larger indices -- both halves of the lower lanes, and its own odd half
+                const unsigned long long bal1 = __ballot(hit1), bal0 = __ballot(hit0);
+                const uint32_t pos1 = __builtin_amdgcn_mbcnt_hi((uint32_t)(bal0 >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)bal0,
+                                      __builtin_amdgcn_mbcnt_hi((uint32_t)(bal1 >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)bal1, nb))));
+                const uint32_t pos0 = pos1 + (hit1 ? 1u : 0u);
+                if (hit1 && pos1 < GS_BLEND_BATCH) s_j[pos1] = i1;
+                if (hit0 && pos0 < GS_BLEND_BATCH) s_j[pos0] = i0;
+                const uint32_t nh = (uint32_t)__popcll(bal1) + (uint32_t)__popcll(bal0);
                 if (nb + nh > GS_BLEND_BATCH) {
-                    // more hits than free slots: the batch ends with the run of the lane that took the last slot, and the next batch
-                    // starts right behind it
-                    const unsigned long long last = __ballot(hit && pos == GS_BLEND_BATCH - 1u);
-                    cur -= (uint32_t)__ffsll((long long)last);
+                    // more hits than free slots: the batch ends with the run that took the last slot, whichever half of its lane's dword
+                    // it is, and the next batch starts right behind it
+                    const unsigned long long last1 = __ballot(hit1 && pos1 == GS_BLEND_BATCH - 1u), last0 = __ballot(hit0 && pos0 == GS_BLEND_BATCH - 1u);
+                    cur = last1 ? 2u * (D + 1u - (uint32_t)__ffsll((long long)last1)) + 1u : 2u * (D + 1u - (uint32_t)__ffsll((long long)last0));
                     nb = GS_BLEND_BATCH;
                 } else {
                     nb += nh;
-                    cur -= min(avail, 64u);
+                    cur = D >= 63u && 2u * (D - 63u) > range.x ? 2u * (D - 63u) : range.x;   // (the step's lowest dword is examined in full)
                 }
             } while (nb < GS_BLEND_BATCH && cur > range.x);
             if (nb == 0) break;                                     // (no run of the rest of the row covers the column)
@@ -1353,7 +1370,7 @@ __device__ __forceinline__ void k_blend_body(const uint2 *__restrict__ tile_rang
         for (int h = 0; h < GS_BLEND_BATCH / 64; h++) {            // nearest first: reverse the back-to-front list
             const uint32_t slot = h * 64 + lane;
             if (slot < nb) {
-                const uint32_t j = WALK ? s_j[slot] : span ? reinterpret_cast<const uint32_t *>(pairs)[end - 1 - slot] : reinterpret_cast<const uint2 *>(pairs)[end - 1 - slot].y;
+                const uint32_t j = WALK ? run_ref[s_j[slot]] : span ? reinterpret_cast<const uint32_t *>(pairs)[end - 1 - slot] : reinterpret_cast<const uint2 *>(pairs)[end - 1 - slot].y;
                 const float4 *src = reinterpret_cast<const float4 *>(proj + j);
                 const float4 ra = src[0], rb = src[1];
                 if (GS_BLEND_BATCH == 64) j_mine = j;
@@ -1910,7 +1927,7 @@ int bits_for(uint32_t n) { int b = 1; while (b < 32 && (1u << b) < n) b++; retur
 // in the sequence below -- once, for both frame counts.
 template <int ROUND, bool RUNS, bool SH, bool AA, bool HL> GS_BODY(F_project, (k_project<ROUND, RUNS, SH, AA, HL>), (k_project_body<ROUND, RUNS, SH, AA, HL>));
 template <int ROUND> GS_BODY(F_row_scan, (k_row_scan<ROUND>), (k_row_scan_body<ROUND>));
-template <int ROUND> GS_BODY(F_emit_runs, (k_emit_runs<ROUND>), (k_emit_runs_body<ROUND>));
+template <int ROUND, bool W16> GS_BODY(F_emit_runs, (k_emit_runs<ROUND, W16>), (k_emit_runs_body<ROUND, W16>));
 template <int ROUND> GS_BODY(F_seg_count, (k_seg_count<ROUND>), (k_seg_count_body<ROUND>));
 template <int ROUND, bool SEGC> GS_BODY(F_lists, (k_lists<ROUND, SEGC>), (k_lists_body<ROUND, SEGC>));
 template <int ROUND> GS_BODY(F_pairs_check, (k_pairs_check<ROUND>), (k_pairs_check_body<ROUND>));
@@ -2063,10 +2080,12 @@ int run_round_spans(gs_ctx *const S[], const GsFrameUniforms U[], uint8_t *const
     if (ROUND == 0) GS_PROF_RECORD(ctx, 3);
     gs_launch<NF, F_row_scan<ROUND>, GS_BLOCK>((uint32_t)u.tiles_y, st, 0, [&](int k) {
         return gs_pack_make(S[k]->row_cnt, S[k]->row_tot, (const GsControl *)S[k]->ctl, U[k].near_count, stride, (uint32_t)u.tiles_y, S[k]->unsat_mask, u.mask_words); });
-    gs_launch<NF, F_emit_runs<ROUND>, GS_BLOCK>(g, st, 0, [&](int k) {
-        return gs_pack_make((const gsm::Projected *)S[k]->proj, (const uint2 *)S[k]->rect, (const uint32_t *)S[k]->tile_count, (const uint32_t *)S[k]->row_cnt,
-                            (const uint2 *)S[k]->row_tot, V[k], geom[k], ref[k], (const uint32_t *)S[k]->unsat_mask, S[k]->ctl, (uint32_t)S[k]->pair_cap,
-                            S[k]->row_tot + GS_BLOCK, (const uint32_t *)S[k]->part_vis, g, last_round ? 1 : 0); });
+    // (a round that walks writes its runs' geometry as 16-bit words: k_emit_runs_body)
+    gs_flag(ROUND == 0 && V[0].row_walk, [&](auto W16) {
+        gs_launch<NF, F_emit_runs<ROUND, ROUND == 0 && decltype(W16)::value>, GS_BLOCK>(g, st, 0, [&](int k) {
+            return gs_pack_make((const gsm::Projected *)S[k]->proj, (const uint2 *)S[k]->rect, (const uint32_t *)S[k]->tile_count, (const uint32_t *)S[k]->row_cnt,
+                                (const uint2 *)S[k]->row_tot, V[k], geom[k], ref[k], (const uint32_t *)S[k]->unsat_mask, S[k]->ctl, (uint32_t)S[k]->pair_cap,
+                                S[k]->row_tot + GS_BLOCK, (const uint32_t *)S[k]->part_vis, g, last_round ? 1 : 0); }); });
     const void *fpairs[NF];
     if (V[0].row_walk) {
         GS_HIP(hipGetLastError());
