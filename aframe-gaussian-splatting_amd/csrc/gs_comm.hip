@@ -24,8 +24,8 @@
 #include <unistd.h>
 #include "gs_internal.h"
 
-extern "C" int gs_lane_call(gs_ctx *ctx, bool async, std::function<int(gs_ctx *)> call, bool always = false);   // gs_api.hip
-extern "C" int gs_sort_two_views(gs_ctx *ctx, const float view[4], const float *cutout16);       // gs_api.hip
+extern "C" int gs_lane_call(gs_ctx *ctx, bool async, std::function<int(gs_ctx *)> call, bool always = false);   // gs_frame.hip
+extern "C" int gs_sort_two_views(gs_ctx *ctx, const float view[4], const float *cutout16);       // gs_frame.hip
 
 // the slice of rccl.h this file needs (types only; the functions come from dlsym)
 typedef struct ncclComm *ncclComm_t;

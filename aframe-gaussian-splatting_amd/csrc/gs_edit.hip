@@ -4,7 +4,9 @@
 // None of this is a per-frame path: every kernel is one streaming pass over the rows (or over the order), its counts go to two device
 // words through one atomic per workgroup, and every launcher waits for its kernel and hands the count back on the host.  What a frame
 // pays for a state store is ONE byte load per splat in the depth pass (gs_sort.hip: the HID instantiations).
-#include "gs_internal.h"
+// Behind the launchers: the entry points of the C ABI that call them (gs_set_state ... gs_compact).
+#include "gs_lanes.h"
+#include "gs_sh.h"
 
 namespace {
 
@@ -348,3 +350,234 @@ int gs_edit_compact_sh(gs_ctx *ctx, const GsCompactTo &to, size_t sh_words, size
     GS_HIP(hipStreamSynchronize(ctx->stream));
     return GS_OK;
 }
+
+// ---- editing the resident cloud (include/gs_splat.h; kernels: above).  The state store is the owner's, like the SH store; a sort
+// is handed the pointer and the length when it is launched (gs_sort.hip: run_sort), so the lanes hold nothing.
+// Before a change: every lane idle (frames in flight read the store; drain_all marks logged frames stale), the allocation in place, and
+// the store grown to `rows` -- the bytes behind the old length are zero (the allocation is zero-filled, and whoever shortens the store
+// clears what it gives up).
+static int edit_begin(gs_ctx *ctx, size_t rows)
+{
+    GS_HIP(hipSetDevice(ctx->device));
+    TRY(drain_all(ctx));
+    TRY(edit_ensure_alloc(ctx));
+    if (rows > ctx->edit_n) ctx->edit_n = rows;
+    return GS_OK;
+}
+// after a change: the hidden count, and no lane's order survives (as after a push)
+static int edit_end(gs_ctx *ctx)
+{
+    for (int i = 0; i < GS_MAX_LANES; i++) if (ctx->lanes[i]) ctx->lanes[i]->have_sort = false;
+    if (ctx->pend_lane > 0) ctx->pend_n = (size_t)-1;            // a sort begun before the change is run again when it is collected
+    return gs_edit_count_hidden(ctx, ctx->edit_state, ctx->edit_n, &ctx->edit_hidden);
+}
+
+// one change of the store: `fn` between edit_begin and edit_end; its failure goes before the count's
+template <typename F> static int edit_apply(gs_ctx *ctx, size_t rows, F fn)
+{
+    TRY(edit_begin(ctx, rows));
+    const int rc = fn();
+    const int rc2 = edit_end(ctx);
+    return rc != GS_OK ? rc : rc2;
+}
+
+// gs_select_rect / gs_select_mask (`name`): the arguments both take (`what`: the rectangle, the mask) and the full-width frame the
+// selection is made in ...
+static int screen_select_begin(gs_ctx *ctx, const gs_render_params *p, const void *what, uint32_t flags, const char *name, GsFrameUniforms &u)
+{
+    if (!p || !what) FAIL(GS_E_BADARG, "%s: NULL argument", name);
+    if (flags & ~GS_SELECT_INVERT) FAIL(GS_E_BADARG, "%s: unknown flags %#x", name, flags);
+    if (!ctx->renderable && ctx->n) FAIL(GS_E_STATE, "context was fed worker matrices only (gs_push_matrices): it can sort but not project");
+    gs_render_params q = *p;
+    q.x0 = 0; q.x1 = p->fb_width;
+    return gs_fill_uniforms(ctx, &q, u);
+}
+// ... and, every lane idle, the WHOLE order on the current frame's lane: a near-only or a strip sort is run again in full first (what
+// gs_download(GS_BUF_SORTED) does for the former)
+static int screen_select_order(gs_ctx *ctx, const char *name, gs_ctx **lane)
+{
+    GS_HIP(hipSetDevice(ctx->device));
+    TRY(drain_all(ctx));                                         // (the current frame's lane is idle and its have_sort is the worker's last word)
+    gs_ctx *L = *lane = ctx->lanes[ctx->cur];
+    if (!ctx->n || !L->have_sort || !L->sorted) FAIL(GS_E_STATE, "%s: no completed sort to select from", name);
+    if (L->sort_near_req || L->sv_has_strip) TRY(lane_rc(ctx, L, gs_run_sort(L, L->sv_view, L->sv_has_cutout ? L->sv_cutout : nullptr, nullptr, 0)));
+    return GS_OK;
+}
+
+// gs_select_mask's inputs on the device, in the owner's grow-only scratch, on its stream: the mask as tight rows of W bytes and -- 256-byte
+// aligned behind it, at depth_at -- the depth plane.  An editor action, not a frame path: pageable memory, one copy each
+static int mask_upload(gs_ctx *ctx, const uint8_t *mask, size_t stride, const float *depth_max, size_t W, size_t H, size_t depth_at)
+{
+    const size_t need = depth_at + (depth_max ? W * H * sizeof(float) : 0);
+    if (need > ctx->mask_cap_bytes) {
+        dev_free(ctx->mask_buf); ctx->mask_buf = nullptr; ctx->mask_cap_bytes = 0;
+        TRY(dev_alloc(ctx, &ctx->mask_buf, need));
+        ctx->mask_cap_bytes = need;
+    }
+    if (stride == W) GS_HIP(hipMemcpyAsync(ctx->mask_buf, mask, W * H, hipMemcpyHostToDevice, ctx->stream));
+    else GS_HIP(hipMemcpy2DAsync(ctx->mask_buf, W, mask, stride, W, H, hipMemcpyHostToDevice, ctx->stream));
+    if (depth_max) GS_HIP(hipMemcpyAsync(ctx->mask_buf + depth_at, depth_max, W * H * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
+    return GS_OK;
+}
+
+extern "C" {
+
+GS_API int gs_set_state(gs_ctx *ctx, size_t first, const uint8_t *states, size_t n)
+{
+    CHECK_CTX(ctx);
+    if (first > ctx->n || n > ctx->n - first) FAIL(GS_E_BADARG, "gs_set_state: states [%zu, %zu) of %zu splats", first, first + n, ctx->n);
+    if (n == 0) return GS_OK;
+    if (!states) FAIL(GS_E_BADARG, "gs_set_state: states is NULL");
+    TRY(edit_begin(ctx, first + n));
+    GS_HIP(hipMemcpy(ctx->edit_state + first, states, n, hipMemcpyHostToDevice));
+    return edit_end(ctx);
+}
+
+GS_API int gs_set_state_ids(gs_ctx *ctx, const uint32_t *ids, size_t n, uint8_t set_bits, uint8_t clear_bits)
+{
+    CHECK_CTX(ctx);
+    if (n == 0) return GS_OK;
+    if (!ids) FAIL(GS_E_BADARG, "gs_set_state_ids: ids is NULL");
+    for (size_t k = 0; k < n; k++) if (ids[k] >= ctx->n) FAIL(GS_E_BADARG, "gs_set_state_ids: id %u (entry %zu) of %zu splats", ids[k], k, ctx->n);
+    TRY(edit_begin(ctx, ctx->n));
+    uint32_t *dev = nullptr;
+    TRY(dev_alloc(ctx, &dev, n));
+    int rc = GS_OK;
+    const hipError_t e = hipMemcpy(dev, ids, n * sizeof(uint32_t), hipMemcpyHostToDevice);
+    if (e != hipSuccess) { snprintf(GS_ERRBUF(ctx), GS_ERRLEN, "upload failed: %s", hipGetErrorString(e)); rc = GS_E_HIP; }
+    if (rc == GS_OK) rc = gs_edit_apply_ids(ctx, dev, n, set_bits, clear_bits);
+    dev_free(dev);
+    const int rc2 = edit_end(ctx);
+    return rc != GS_OK ? rc : rc2;
+}
+
+GS_API int gs_state_count(const gs_ctx *ctx, size_t *rows, size_t *hidden)
+{
+    if (!ctx) return GS_E_BADARG;
+    if (rows) *rows = ctx->edit_n;
+    if (hidden) *hidden = ctx->edit_hidden;
+    return GS_OK;
+}
+
+GS_API int gs_select_box(gs_ctx *ctx, const float box16[16], uint8_t set_bits, uint8_t clear_bits, uint32_t flags, size_t *out_hit)
+{
+    CHECK_CTX(ctx);
+    if (!box16) FAIL(GS_E_BADARG, "gs_select_box: box16 is NULL");
+    if (flags & ~GS_SELECT_INVERT) FAIL(GS_E_BADARG, "gs_select_box: unknown flags %#x", flags);
+    if (out_hit) *out_hit = 0;
+    if (!ctx->n) return GS_OK;
+    return edit_apply(ctx, ctx->n, [&] { return gs_edit_select_box(ctx, box16, set_bits, clear_bits, (flags & GS_SELECT_INVERT) != 0, out_hit); });
+}
+
+GS_API int gs_select_sphere(gs_ctx *ctx, const float centre[3], float radius, uint8_t set_bits, uint8_t clear_bits, uint32_t flags, size_t *out_hit)
+{
+    CHECK_CTX(ctx);
+    if (!centre) FAIL(GS_E_BADARG, "gs_select_sphere: centre is NULL");
+    if (flags & ~GS_SELECT_INVERT) FAIL(GS_E_BADARG, "gs_select_sphere: unknown flags %#x", flags);
+    if (!ctx->renderable && ctx->n) FAIL(GS_E_STATE, "context was fed worker matrices only (gs_push_matrices): no positions in the rows' space");
+    if (out_hit) *out_hit = 0;
+    if (!ctx->n) return GS_OK;
+    return edit_apply(ctx, ctx->n, [&] { return gs_edit_select_sphere(ctx, centre, radius, set_bits, clear_bits, (flags & GS_SELECT_INVERT) != 0, out_hit); });
+}
+
+GS_API int gs_select_rect(gs_ctx *ctx, const gs_render_params *p, const int32_t rect[4], uint8_t set_bits, uint8_t clear_bits, uint32_t flags, size_t *out_hit)
+{
+    CHECK_CTX(ctx);
+    GsFrameUniforms u;
+    gs_ctx *L = nullptr;
+    TRY(screen_select_begin(ctx, p, rect, flags, "gs_select_rect", u));
+    if (out_hit) *out_hit = 0;
+    TRY(screen_select_order(ctx, "gs_select_rect", &L));
+    return edit_apply(ctx, ctx->n, [&] { return gs_edit_select_rect(ctx, L, u, rect, set_bits, clear_bits, (flags & GS_SELECT_INVERT) != 0, out_hit); });
+}
+
+GS_API int gs_select_mask(gs_ctx *ctx, const gs_render_params *p, const uint8_t *mask, size_t mask_stride, const float *depth_max, uint8_t set_bits,
+                          uint8_t clear_bits, uint32_t flags, size_t *out_hit)
+{
+    CHECK_CTX(ctx);
+    GsFrameUniforms u;
+    gs_ctx *L = nullptr;
+    TRY(screen_select_begin(ctx, p, mask, flags, "gs_select_mask", u));
+    const size_t W = (size_t)u.W, H = (size_t)u.H;
+    if (mask_stride && mask_stride < W) FAIL(GS_E_BADARG, "gs_select_mask: stride %zu smaller than a row (%zu bytes)", mask_stride, W);
+    if (out_hit) *out_hit = 0;
+    TRY(screen_select_order(ctx, "gs_select_mask", &L));
+    return edit_apply(ctx, ctx->n, [&] {
+        const size_t depth_at = (W * H + 255) & ~(size_t)255;
+        int rc = mask_upload(ctx, mask, mask_stride ? mask_stride : W, depth_max, W, H, depth_at);
+        if (rc == GS_OK) rc = gs_edit_select_mask(ctx, L, u, ctx->mask_buf, depth_max ? reinterpret_cast<const float *>(ctx->mask_buf + depth_at) : nullptr, set_bits,
+                                                  clear_bits, (flags & GS_SELECT_INVERT) != 0, out_hit);
+        if (rc != GS_OK) (void)hipStreamSynchronize(ctx->stream);     // (no copy out of the caller's memory is left behind)
+        return rc;
+    });
+}
+
+GS_API int gs_highlight_info(const gs_ctx *ctx, uint32_t *option_value, uint32_t *last_frame)
+{
+    if (!ctx) return GS_E_BADARG;
+    if (option_value) *option_value = ctx->hl_opt;
+    if (last_frame) {
+        gs_ctx *c = const_cast<gs_ctx *>(ctx);
+        for (int i = 0; i < GS_MAX_LANES; i++) if (c->lanes[i]) (void)lane_drain(c->lanes[i]);   // (as gs_get_stats: what the workers were handed is settled)
+        *last_frame = c->lanes[c->cur]->hl_frame;
+    }
+    return GS_OK;
+}
+
+GS_API int gs_compact(gs_ctx *ctx, uint32_t *out_old_index, size_t *out_n)
+{
+    CHECK_CTX(ctx);
+    if (out_n) *out_n = ctx->n;
+    if (!ctx->edit_hidden) {                                     // nothing hidden: nothing to do
+        if (out_old_index) for (size_t k = 0; k < ctx->n; k++) out_old_index[k] = (uint32_t)k;
+        return GS_OK;
+    }
+    GS_HIP(hipSetDevice(ctx->device));
+    TRY(drain_all(ctx));
+    // fresh arrays of the same capacity (the resident bytes are held twice until the swap below)
+    const size_t sh_q = ctx->sh_n ? 3 * (size_t)gsm::sh_channel_stride(ctx->sh_deg) / 4 : 0;   // 16-byte words per SH row
+    GsCompactTo to = { nullptr, nullptr, nullptr, nullptr, nullptr, nullptr };
+    int rc = dev_alloc(ctx, &to.splat, ctx->cap * 2);
+    if (rc == GS_OK) rc = dev_alloc(ctx, &to.sort_rows, ctx->cap);
+    if (rc == GS_OK) rc = dev_alloc(ctx, &to.bound_r, ctx->cap);
+    if (rc == GS_OK) rc = dev_alloc(ctx, &to.state, ctx->edit_cap);
+    if (rc == GS_OK) rc = dev_alloc(ctx, &to.old_index, ctx->n);
+    if (rc == GS_OK && sh_q) rc = dev_alloc(ctx, &to.sh, ctx->sh_cap * sh_q * 4);
+    if (rc == GS_OK && hipMemset(to.state, 0, ctx->edit_cap) != hipSuccess) { snprintf(GS_ERRBUF(ctx), GS_ERRLEN, "gs_compact: clearing the new state store failed"); rc = GS_E_HIP; }
+    // how many of the splats that have an SH row are hidden (the store ends at or before gs_count(): bytes beyond it are state 0)
+    size_t sh_hidden = 0, kept = 0;
+    if (rc == GS_OK && sh_q) rc = gs_edit_count_hidden(ctx, ctx->edit_state, ctx->sh_n < ctx->edit_n ? ctx->sh_n : ctx->edit_n, &sh_hidden);
+    if (rc == GS_OK) rc = gs_edit_compact(ctx, to, &kept);
+    if (rc == GS_OK && sh_q) rc = gs_edit_compact_sh(ctx, to, sh_q, ctx->sh_n - sh_hidden);
+    if (rc == GS_OK && kept != ctx->n - ctx->edit_hidden) { snprintf(GS_ERRBUF(ctx), GS_ERRLEN, "gs_compact: kept %zu splats, expected %zu", kept, ctx->n - ctx->edit_hidden); rc = GS_E_HIP; }
+    if (rc == GS_OK && out_old_index && kept && hipMemcpy(out_old_index, to.old_index, kept * sizeof(uint32_t), hipMemcpyDeviceToHost) != hipSuccess) {
+        snprintf(GS_ERRBUF(ctx), GS_ERRLEN, "gs_compact: download of the index map failed"); rc = GS_E_HIP;
+    }
+    if (rc != GS_OK) {
+        dev_free(to.splat); dev_free(to.sort_rows); dev_free(to.bound_r); dev_free(to.state); dev_free(to.old_index); dev_free(to.sh);
+        return rc;
+    }
+    dev_free(ctx->splat); dev_free(ctx->sort_rows); dev_free(ctx->bound_r); dev_free(ctx->edit_state); dev_free(to.old_index);
+    ctx->splat = to.splat; ctx->sort_rows = to.sort_rows; ctx->bound_r = to.bound_r; ctx->edit_state = to.state;
+    if (sh_q) { dev_free(ctx->sh); ctx->sh = to.sh; ctx->sh_n -= sh_hidden; }
+    ctx->edit_n -= ctx->edit_hidden; ctx->edit_hidden = 0;       // (every hidden splat lay inside the store; stable order: a prefix stays a prefix)
+    ctx->n = kept; ctx->stats.n_splats = kept;
+    if (!kept) { ctx->renderable = true; ctx->sh_n = 0; ctx->sh_deg = 0; }   // (an empty context, as after gs_clear)
+    reset_cloud_measurements(ctx);
+    for (int i = 0; i < GS_MAX_LANES; i++) {
+        gs_ctx *L = ctx->lanes[i];
+        if (!L) continue;
+        L->have_sort = false; L->sorted = nullptr;
+        memset(&L->stats, 0, sizeof L->stats);
+    }
+    ctx->stats.n_splats = kept;
+    refresh_lanes(ctx);
+    set_current_lane(ctx, 0, 0);
+    // a sort posted before the call: run again over the kept splats when it is collected (as after any other edit); nothing kept: the
+    // empty context's reply [0] is owed (index.js:588-590)
+    if (ctx->pend_lane > 0) { if (kept) ctx->pend_n = (size_t)-1; else ctx->pend_lane = -1; }
+    if (out_n) *out_n = kept;
+    return GS_OK;
+}
+
+}  // extern "C"

@@ -24,7 +24,7 @@
 #define GS_RADIX_LARGE_N (3u << 20) // inputs expected to be longer than this take the long geometry
 #endif
 #define GS_RADIX_MAX_BINS 512      // up to 9-bit digits (depth key = 17 bits = 8 + 9)
-#define GS_TOUCH_PRIVATE_WORDS 16u   /* private dwords per lane a new lane's stream is made to allocate (gs_api.hip: k_touch_private) */
+#define GS_TOUCH_PRIVATE_WORDS 16u   /* private dwords per lane a new lane's stream is made to allocate (gs_lanes.hip: k_touch_private) */
 #define GS_STATUS_RING 64u             /* completion words per lane (GsControl::status_ring) */
 #define GS_NEED_WORDS 32u          // GsControl::need_near
 #define GS_MSD_GROUP 32u           // the MSD depth sort (gs_sort.hip): radix chunks per group row
@@ -100,7 +100,7 @@ struct GsControl {
     // read before its 256 pixels were saturated; the sorted position of that entry says how many of the NEAREST splats had to be binned
     // for the tile: V - position.  need_near[tile % GS_NEED_WORDS] = max over the tiles of the frames drawn since the host last cleared
     // it (one fire-and-forget atomicMax per tile, spread over 32 words: a single word serialises at ~11 ns per tile); 0xFFFFFFFF: a tile
-    // was not saturated by the whole order (sky: no share helps it).  The host sets near_count from the maximum (gs_api.hip).
+    // was not saturated by the whole order (sky: no share helps it).  The host sets near_count from the maximum (gs_frame.hip).
     uint32_t acc_frames;           // frames rendered since profiling was switched on
     unsigned long long acc_sorted, acc_visible, acc_pairs;   // sums of V, Vp, I over those frames
     // (a cache line of its own: atomics drop the line from the XCDs' L2s, and the counts above are read by every kernel.  A tile's wave
@@ -166,7 +166,7 @@ struct GsFrameUniforms {           // per-render constants, passed by value to k
 };
 
 struct GsLaneWorker;
-struct GsFrameLog;                 // gs_api.hip: what was asked of a lane since the last gs_sync (transparent re-rendering)
+struct GsFrameLog;                 // gs_lanes.h: what was asked of a lane since the last gs_sync (transparent re-rendering)
 struct gs_ctx {
     int device;
     hipStream_t stream;
@@ -320,7 +320,7 @@ struct gs_ctx {
     gs_stats stats;
 };
 
-// Where a failure message goes.  A lane's enqueue thread (gs_api.hip) points gs_tl_err at ITS OWN buffer: lane 0 is the
+// Where a failure message goes.  A lane's enqueue thread (gs_lanes.hip) points gs_tl_err at ITS OWN buffer: lane 0 is the
 // owner context itself, and the caller's thread may be writing or reading ctx->err at the same moment; lane_drain()
 // copies the worker's message into the lane's err on the caller's thread.
 extern thread_local char *gs_tl_err;
@@ -473,9 +473,9 @@ int gs_run_render2(gs_ctx *const S[2], const GsFrameUniforms U[2], uint8_t *cons
 namespace gsm { struct PlyLayout; }
 int gs_ply_rows_device(gs_ctx *ctx, const uint8_t *host_data, const gsm::PlyLayout &layout, size_t n, uint4 *rows_out, bool *had_nan);
 extern "C" int gs_ply_plan(const void *bytes, size_t nbytes, gsm::PlyLayout *layout, size_t *nrows, size_t *data_start, char *err, size_t errlen);
-// ---- gs_api.hip
+// ---- gs_frame.hip, gs_lanes.hip (what crosses between them, gs_edit.hip and gs_api.hip alone: gs_lanes.h)
 static inline gs_ctx *gs_root(gs_ctx *c) { return c->parent ? c->parent : c; }
-// (defined inside gs_api.hip's extern "C" block: C linkage, hidden visibility)
+// (defined inside gs_frame.hip's extern "C" block: C linkage, hidden visibility)
 extern "C" int gs_fill_uniforms(gs_ctx *ctx, const gs_render_params *p, GsFrameUniforms &u);
 // render the current frame's strip `u` on its lane (asynchronously if u.flags says so) into device_rgba / host_rgba
 extern "C" int gs_render_uniforms(gs_ctx *ctx, const GsFrameUniforms &u, void *device_rgba, uint8_t *host_rgba, size_t stride);

@@ -474,7 +474,7 @@ __device__ __forceinline__ void k_msd_scatter_body(const uint32_t *__restrict__ 
         uint32_t tot;
         uint32_t ex = block_excl_scan<NW>(tot_d, s_wave, &tot);
         // A TAIL sort (tail_req != 0: the frame reads the last tail_req positions of the order at most -- the nearest splats, one binning
-        // round, gs_api.hip: sort_near_request): the order is cut at a SEGMENT boundary, the start of the segment that holds position
+        // round, gs_frame.hip: sort_near_request): the order is cut at a SEGMENT boundary, the start of the segment that holds position
         // V' - tail_req.  The segments before it are neither scattered nor sorted; the records behind the cut are stored from slot 0
         // (k_project: near_sorted, j_base = n_valid - n_sorted).  The cut costs nothing: every workgroup has the digit totals in its hands
         // here -- where the near-only sorts of long inputs build a depth histogram and search it for a threshold (10 us at 1 M splats).

@@ -163,7 +163,7 @@ __device__ __forceinline__ void k_project_body(const uint32_t *__restrict__ sort
     if (threadIdx.x == 0) s_vis = 0;
     // the frame's completion word starts here (the first kernel of the frame's render; its sort may have left the order incomplete)
     if (ROUND == 0 && blockIdx.x == 0 && threadIdx.x == 0 && u.status) *u.status = ctl->order_incomplete ? 4u : 0u;
-    if (ROUND == 0 && blockIdx.x == 0 && u.need_seed && threadIdx.x < GS_NEED_WORDS) ctl->need_near[threadIdx.x] = u.need_seed == 1u ? 0u : u.need_seed;   // (the host's seed: gs_api.hip)
+    if (ROUND == 0 && blockIdx.x == 0 && u.need_seed && threadIdx.x < GS_NEED_WORDS) ctl->need_near[threadIdx.x] = u.need_seed == 1u ? 0u : u.need_seed;   // (the host's seed: gs_frame.hip)
     for (uint32_t c = blockIdx.x; c < nchunks; c += gridDim.x) {
         if (threadIdx.x == 0) { s_sum = 0; s_nbig = 0; s_nmid = 0; }
         if (RUNS) s_rc[threadIdx.x] = 0u;

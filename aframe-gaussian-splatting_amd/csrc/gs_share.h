@@ -1,5 +1,5 @@
 // The round-0 share policy: how much of the sorted order a frame's first binning round covers, whether its second round is left out,
-// and what the lanes' need words are seeded with.  Host-only plain C++17 -- no HIP, no gs_internal.h: gs_api.hip fills a GsShareObs
+// and what the lanes' need words are seeded with.  Host-only plain C++17 -- no HIP, no gs_internal.h: gs_frame.hip fills a GsShareObs
 // from each collected lane's GsControl, calls gs_share_observe per lane and gs_share_decide once per collection; tests/host_check/
 // compiles this header with g++ alone and replays recorded collections against it (tests/test_share_policy_cpu.py).
 // Every float expression here has a fixed type (f32 / f64), operation order and comparison direction: compile with -ffp-contract=off.

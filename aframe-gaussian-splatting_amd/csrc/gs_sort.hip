@@ -467,7 +467,7 @@ __global__ __launch_bounds__(64 * NW) void k_sort_bucket(const float *__restrict
 // one contiguous list (each workgroup sums the counts before its chunks itself: 20 KB of L2 reads at most, no scan launch), in
 // chunk order, i.e. in index order, and two stable passes over the P' records (9 + 7 bucket bits) give the order the
 // whole-length passes give.  A chunk with more survivors than its stash holds raises near_overflow + round1_missed: the frame
-// is drawn again from a whole sort and the context stops using the stash (gs_api.hip).
+// is drawn again from a whole sort and the context stops using the stash (gs_frame.hip).
 template <int NW>
 __device__ __forceinline__ void k_near_stash_body(const float *__restrict__ depth, uint32_t n, const unsigned long long *__restrict__ part_min,
                                                   const unsigned long long *__restrict__ part_max, const uint32_t *__restrict__ part_cnt, uint32_t nparts,

@@ -8,7 +8,7 @@ struct ShareBackend {
     GsShare S;
     struct Lane { GsShareLane L; bool exists, tiles, pending; } lanes[SHARE_REPLAY_LANES];
     size_t n;
-    uint32_t need_splats;                                          // gs_stats::need_splats as gs_api.hip fills it
+    uint32_t need_splats;                                          // gs_stats::need_splats as gs_frame.hip fills it
 
     void create() { memset(this, 0, sizeof *this); gs_share_reset_create(S); }
     void set_n(size_t v) { n = v; }

@@ -15,7 +15,7 @@
 //   pin P                            GS_OPT_NEAR_PERMILLE = P (0: the unpin reset)
 //   kind K                           a sort of kind K (1 whole, 2 strip): the kind-switch reset where it differs
 //   clear                            gs_clear
-//   cold SORTS FRAMES                the cold sorts / cold frames gs_api.hip has counted (only the resets touch them here)
+//   cold SORTS FRAMES                the cold sorts / cold frames gs_frame.hip has counted (only the resets touch them here)
 //   show                             print the state
 //   repeat N ... end                 (may nest)
 // A step that can change the policy state prints one line: script, frozen, pin, kind, clear and show the whole state and the outputs,
