@@ -350,9 +350,23 @@ struct EllipseRows { float invA, B, D4A, D, dy_r, pad; };   // D4A = 4*A
 // in the counting pass (k_project) and the writing pass (k_emit), which run this very code on the same stored
 // record.  They are not part of the pixel parity contract, so the 1-ulp hardware reciprocal / square root
 // (v_rcp_f32 / v_sqrt_f32, one instruction each) replace the ~15-instruction IEEE sequences here.
+// (a) is checked by tests/test_coverage_cpu.py: this header's host build, with the two operations moved by -1, 0 and +1 ulp in
+// all nine combinations (GS_HOST_CHECK_ULP, below), against frag_power <= 4.0f at every pixel centre, for tilted, thin, clamped and
+// grazing splats; and by tests/test_coverage_gpu.py on the hardware's own operations (fragment counts equal to the oracle's).
 #if defined(__HIP_DEVICE_COMPILE__)
 GS_HD float fast_rcp(float x) { return __builtin_amdgcn_rcpf(x); }
 GS_HD float fast_sqrt(float x) { return __builtin_amdgcn_sqrtf(x); }
+#elif defined(GS_HOST_CHECK_ULP)
+// tests/host_check only: the IEEE result moved by hc_ulp_rcp / hc_ulp_sqrt (-1, 0 or +1) units in the last place, the error the
+// hardware operations above are allowed.  Zeros, infinities and NaNs stay as they are.
+static thread_local int hc_ulp_rcp = 0, hc_ulp_sqrt = 0;
+static inline float hc_move_ulp(float r, int k)
+{
+    if (k == 0 || !(fabsf(r) > 0.0f) || !(fabsf(r) <= 3.402823466e+38f)) return r;
+    return nextafterf(r, k > 0 ? INFINITY : -INFINITY);
+}
+GS_HD float fast_rcp(float x) { return hc_move_ulp(1.0f / x, hc_ulp_rcp); }
+GS_HD float fast_sqrt(float x) { return hc_move_ulp(sqrtf(x), hc_ulp_sqrt); }
 #else
 GS_HD float fast_rcp(float x) { return 1.0f / x; }
 GS_HD float fast_sqrt(float x) { return sqrtf(x); }
@@ -394,6 +408,40 @@ GS_HD void splat_tile_row(const Projected &p, const EllipseRows &e, int ty, int 
     if (!(fi0 <= fi1)) { tx0 = 0; n = 0; return; }
     const uint32_t a = (uint32_t)((int)fi0 - x0) >> 4, b = (uint32_t)((int)fi1 - x0) >> 4;
     tx0 = a; n = b - a + 1;
+}
+
+// The 4x4-pixel blocks of the 16x16 tile at strip column tile_x0 (a pixel x, as a float), image rows r0 .. r0 + 15, that the splat
+// of record (cx, cy, ax, ay, bx, by) can reach (GS_OPT_SUBTILE, gs_render.hip): bit 4 * band + column, bands top-down.  The same
+// band arithmetic as splat_tile_row over the tile's four 4-row bands and 4-pixel columns: a superset of the pixels that pass q <= 4.
+#define GS_SUBTILE_BANDS 4          // row bands per tile: 4x4-pixel blocks, sixteen lists (eight lists of 4 x 8 pixels: the same frames/s, docs/LAB_NOTES.md)
+#define GS_SUBTILE_GROUPS (4 * GS_SUBTILE_BANDS)
+#define GS_SUBTILE_ROWS (16 / GS_SUBTILE_BANDS)
+GS_HD uint32_t subtile_mask(const float cx, const float cy, const float ax, const float ay, const float bx, const float by,
+                            const float tile_x0, const int r0, const int H)
+{
+    Projected p;
+    p.cx = cx; p.cy = cy; p.ax = ax; p.ay = ay; p.bx = bx; p.by = by;
+    EllipseRows e;
+    ellipse_rows_setup(p, e);
+    // half height of the ellipse, as ellipse_rows_setup's half width: 2 sqrt(A / D)
+    const float hh = 2.0f * fast_sqrt((0.25f * e.D4A) * fast_rcp(e.D));
+    if (!(hh >= 0.0f) || !(e.pad >= 0.0f)) return (1u << GS_SUBTILE_GROUPS) - 1u;   // (no such record leaves k_project; whole tile if one did)
+    uint32_t m = 0;
+#pragma unroll 1
+    for (int b = 0; b < GS_SUBTILE_BANDS; b++) {
+        // image rows r0 + ROWS b .. + ROWS - 1 (top-down); GL pixel-centre y of image row r is (H - 1 - r) + 0.5
+        const float ya = ((float)(H - 1 - (r0 + GS_SUBTILE_ROWS * b + GS_SUBTILE_ROWS - 1)) + 0.5f) - p.cy - e.pad, yb = ((float)(H - 1 - (r0 + GS_SUBTILE_ROWS * b)) + 0.5f) - p.cy + e.pad;
+        if (ya <= hh && yb >= -hh) {
+            float xmin, xmax;
+            ellipse_band_xrange(e, ya, yb, xmin, xmax);
+            const float fi0 = fmaxf(ceilf(p.cx + xmin - e.pad - 0.5f), tile_x0), fi1 = fminf(floorf(p.cx + xmax + e.pad - 0.5f), tile_x0 + 15.0f);
+            if (fi0 <= fi1) {
+                const uint32_t c0 = (uint32_t)(fi0 - tile_x0) >> 2, c1 = (uint32_t)(fi1 - tile_x0) >> 2;
+                m |= (((2u << c1) - 1u) & ~((1u << c0) - 1u)) << (4 * b);
+            }
+        }
+    }
+    return m;
 }
 
 }  // namespace gsm

@@ -1180,35 +1180,8 @@ __device__ __forceinline__ f2 fma2_hi0(f2 a, f2 b, f2 c)
 #endif
 #define GS_SUBTILE_STRIDE 68u       // bytes per block list: 64 entries + the inert pair behind them, banks 17 g + k / 4 apart
 #define GS_SUBTILE_INERT 64u        // the slot of the record no pixel passes
-#define GS_SUBTILE_BANDS 4          // row bands per tile: 4x4-pixel blocks, sixteen lists (eight lists of 4 x 8 pixels: the same frames/s, docs/LAB_NOTES.md)
-#define GS_SUBTILE_GROUPS (4 * GS_SUBTILE_BANDS)
-#define GS_SUBTILE_ROWS (16 / GS_SUBTILE_BANDS)
-__device__ __forceinline__ uint32_t subtile_mask(const float4 ra, const float bx, const float by, const float tile_x0, const int r0, const int H)
-{
-    gsm::Projected p;
-    p.cx = ra.x; p.cy = ra.y; p.ax = ra.z; p.ay = ra.w; p.bx = bx; p.by = by;
-    gsm::EllipseRows e;
-    gsm::ellipse_rows_setup(p, e);
-    // half height of the ellipse, as ellipse_rows_setup's half width: 2 sqrt(A / D)
-    const float hh = 2.0f * gsm::fast_sqrt((0.25f * e.D4A) * gsm::fast_rcp(e.D));
-    if (!(hh >= 0.0f) || !(e.pad >= 0.0f)) return (1u << GS_SUBTILE_GROUPS) - 1u;   // (no such record leaves k_project; whole tile if one did)
-    uint32_t m = 0;
-#pragma unroll 1
-    for (int b = 0; b < GS_SUBTILE_BANDS; b++) {
-        // image rows r0 + ROWS b .. + ROWS - 1 (top-down); GL pixel-centre y of image row r is (H - 1 - r) + 0.5
-        const float ya = ((float)(H - 1 - (r0 + GS_SUBTILE_ROWS * b + GS_SUBTILE_ROWS - 1)) + 0.5f) - p.cy - e.pad, yb = ((float)(H - 1 - (r0 + GS_SUBTILE_ROWS * b)) + 0.5f) - p.cy + e.pad;
-        if (ya <= hh && yb >= -hh) {
-            float xmin, xmax;
-            gsm::ellipse_band_xrange(e, ya, yb, xmin, xmax);
-            const float fi0 = fmaxf(ceilf(p.cx + xmin - e.pad - 0.5f), tile_x0), fi1 = fminf(floorf(p.cx + xmax + e.pad - 0.5f), tile_x0 + 15.0f);
-            if (fi0 <= fi1) {
-                const uint32_t c0 = (uint32_t)(fi0 - tile_x0) >> 2, c1 = (uint32_t)(fi1 - tile_x0) >> 2;
-                m |= (((2u << c1) - 1u) & ~((1u << c0) - 1u)) << (4 * b);
-            }
-        }
-    }
-    return m;
-}
+// (the blocks an entry can reach: gsm::subtile_mask, gs_device_math.h, with GS_SUBTILE_BANDS / _GROUPS / _ROWS -- there so that the CPU
+// tier can run it: tests/test_coverage_cpu.py)
 
 // SCENE: the opaque scene's depth buffer (fragment kept iff its window depth <= the buffer: depthTest LEQUAL,
 // depthWrite off, index.js:179-180) and/or colour image (the destination the splats are blended over).
@@ -1278,6 +1251,8 @@ __device__ __forceinline__ void k_blend_body(const uint2 *__restrict__ tile_rang
     // not written -- so that the lane leaves its list exactly where it does when the whole frame is drawn)
     const f2 qmA = { (row_in && xb < u.x1b) ? 4.0f : -1.0f, (row_in && xb + 1 < u.x1b) ? 4.0f : -1.0f };
     const f2 qmB = { (row_in && xb + 2 < u.x1b) ? 4.0f : -1.0f, (row_in && xb + 3 < u.x1b) ? 4.0f : -1.0f };
+    // (GS_RENDER_COUNT_FRAGS counts the strip's own pixels only: the up to three blended beyond x1 are no fragments of a reference that draws [x0, x1))
+    const uint32_t in0 = (COUNT && xb < u.x1) ? 1u : 0u, in1 = (COUNT && xb + 1 < u.x1) ? 1u : 0u, in2 = (COUNT && xb + 2 < u.x1) ? 1u : 0u, in3 = (COUNT && xb + 3 < u.x1) ? 1u : 0u;
     f2 TA = { qmA.x > 0.0f ? 1.0f : 0.0f, qmA.y > 0.0f ? 1.0f : 0.0f }, TB = { qmB.x > 0.0f ? 1.0f : 0.0f, qmB.y > 0.0f ? 1.0f : 0.0f };
     // (GS_BLEND_FACTOR 2: the constant that stands for qm in the factor form of the step; qm itself then lives only where the step compares)
     const f2 cwA = { qmA.x > 0.0f ? GS_BLEND_W_C_IN : GS_BLEND_W_C_OUT, qmA.y > 0.0f ? GS_BLEND_W_C_IN : GS_BLEND_W_C_OUT };
@@ -1374,7 +1349,7 @@ __device__ __forceinline__ void k_blend_body(const uint2 *__restrict__ tile_rang
                 const float4 *src = reinterpret_cast<const float4 *>(proj + j);
                 const float4 ra = src[0], rb = src[1];
                 if (GS_BLEND_BATCH == 64) j_mine = j;
-                if (SUB) m16 = subtile_mask(ra, rb.x, rb.y, (float)(u.x0 + (int)tx * GS_TILE), (int)ty * GS_TILE, u.H);
+                if (SUB) m16 = gsm::subtile_mask(ra.x, ra.y, ra.z, ra.w, rb.x, rb.y, (float)(u.x0 + (int)tx * GS_TILE), (int)ty * GS_TILE, u.H);
                 // (cx, cy, ax, bx | ay, by, -, -): the two coefficients a row shares with dy sit in one register pair, so that
                 // dy * (ay, by) is one packed multiplication, and so do the two that multiply dx
                 s_ent[3 * slot] = make_float4(ra.x, ra.y, ra.z, rb.x);
@@ -1455,7 +1430,7 @@ __device__ __forceinline__ void k_blend_body(const uint2 *__restrict__ tile_rang
                            pair's to a fresh register: the same packed fma, the selection written out) */              \
                         const f2 chv_ = { ch_.x, ch_.y };                                                              \
                         cbA = fma2_hi0(chv_, eA, cbA); cbB = fma2_hi0(chv_, eB, cbB);                                  \
-                        if (COUNT) nfr += (uint32_t)p0 + (uint32_t)p1 + (uint32_t)p2 + (uint32_t)p3;                   \
+                        if (COUNT) nfr += ((uint32_t)p0 & in0) + ((uint32_t)p1 & in1) + ((uint32_t)p2 & in2) + ((uint32_t)p3 & in3); \
                         if (SURF) {                                  /* the first slot behind which T < 0.5 */         \
                             const uint32_t s_ = (ss);                                                                  \
                             sfc0 = TA.x < 0.5f ? min(sfc0, s_) : sfc0; sfc1 = TA.y < 0.5f ? min(sfc1, s_) : sfc1;      \

@@ -3,6 +3,8 @@
 // oracle and the golden vectors in the CPU-only test tier.  Nothing here is
 // part of, linked into or reachable from the product library.
 #include <string.h>
+#include <atomic>
+#include <thread>
 #include <vector>
 #include "gs_device_math.h"
 #include "gs_ply.h"
@@ -106,4 +108,167 @@ size_t hc_cutout_affine_mismatches(const float *pos3, size_t n, const double *c1
 
 __attribute__((visibility("default")))
 void hc_js_exp(const double *x, size_t n, double *out) { for (size_t i = 0; i < n; i++) out[i] = gsm::js_exp(x[i]); }
+}
+
+// ---------------------------------------------------------------- coverage sweep (tests/test_coverage_cpu.py)
+// Records (cx, cy, s1, s2, theta): a screen ellipse with its centre at (cx, cy) (GL orientation, as Projected), semi-axes s1 >= s2
+// and its long axis at angle theta.  For each one the truth -- gsm::frag_power(dx, dy, ...) <= 4.0f at every pixel centre of the
+// strip, the blend's own function and comparison -- is brute-forced, and the two conservative bounds are held against it:
+//   tile check      every tile that holds a passing pixel lies in a tile row k_project visits (splat_pixel_bounds) and inside
+//                   that row's run [tx0, tx0 + n) (splat_tile_row);
+//   sub-tile check  in every such tile, every 4x4-pixel block that holds a passing pixel has its bit in gsm::subtile_mask.
+// Both in all nine settings of the emulated 1-ulp reciprocal and square root (GS_HOST_CHECK_ULP), or at the IEEE setting alone.
+
+namespace {
+
+void cov_record(const float *r, gsm::Projected &p, gsm::ProjExtra &x)
+{
+    // project_splat's own lines from its unit eigenvector (dvx, dvy) = (cos, sin) on, f32, in that order
+    const float s1 = r[2], s2 = r[3];
+    const float dvx = (float)cos((double)r[4]), dvy = (float)sin((double)r[4]);
+    memset(&p, 0, sizeof p); memset(&x, 0, sizeof x);
+    x.v1x = s1 * dvx; x.v1y = s1 * dvy;
+    x.v2x = s2 * dvy; x.v2y = s2 * -dvx;
+    p.cx = r[0]; p.cy = r[1];
+    const float n1 = x.v1x * x.v1x + x.v1y * x.v1y, n2 = x.v2x * x.v2x + x.v2y * x.v2y;
+    p.ax = x.v2x / n2; p.ay = x.v2y / n2;
+    p.bx = x.v1x / n1; p.by = x.v1y / n1;
+}
+
+// one image row of the truth.  (fmaf is correctly rounded whether it is the FMA instruction or libm's: the clones differ in speed only)
+__attribute__((target_clones("arch=haswell", "default"), flatten))
+void cov_pass_row(const gsm::Projected &p, float dy, int x0, int x1, uint8_t *pass)
+{
+    for (int i = x0; i < x1; i++) {
+        const float dx = ((float)i + 0.5f) - p.cx;
+        pass[i - x0] = gsm::frag_power(dx, dy, p.ax, p.ay, p.bx, p.by) <= 4.0f;
+    }
+}
+
+struct CovAcc {
+    int64_t tile_miss = 0, blk_miss = 0, claimed = 0, touched = 0, live = 0;
+    int64_t first[6] = { -1, 0, 0, 0, 0, 0 };          // record, pixel x, image row, ulp of rcp, ulp of sqrt, check (1 tile, 2 sub-tile)
+};
+
+// a passing pixel of tile (ty, tx), inside the blocks `bits` (bit 4 * band + column)
+void cov_find_pixel(const gsm::Projected &p, int H, int x0, int x1, int ty, int tx, uint32_t bits, int64_t &px, int64_t &row)
+{
+    for (int r = 16 * ty; r < 16 * ty + 16 && r < H; r++)
+        for (int i = x0 + 16 * tx; i < x0 + 16 * tx + 16 && i < x1; i++) {
+            if (!((bits >> (4 * ((r & 15) >> 2) + (((i - x0) & 15) >> 2))) & 1u)) continue;
+            const float dx = ((float)i + 0.5f) - p.cx, dy = ((float)(H - 1 - r) + 0.5f) - p.cy;
+            if (gsm::frag_power(dx, dy, p.ax, p.ay, p.bx, p.by) <= 4.0f) { px = i; row = r; return; }
+        }
+}
+
+void cov_one(const float *rec, int64_t ri, int H, int x0, int x1, int checks, int nine, CovAcc &acc,
+             std::vector<uint16_t> &blk, std::vector<uint8_t> &pass)
+{
+    gsm::Projected p; gsm::ProjExtra x;
+    cov_record(rec, p, x);
+    const int SW = x1 - x0, TX = (SW + 15) / 16, TY = (H + 15) / 16;
+    std::fill(blk.begin(), blk.begin() + (size_t)TX * TY, (uint16_t)0);
+    bool any = false;
+    for (int row = 0; row < H; row++) {
+        const float dy = ((float)(H - 1 - row) + 0.5f) - p.cy;
+        cov_pass_row(p, dy, x0, x1, pass.data());
+        uint16_t *b = blk.data() + (size_t)(row >> 4) * TX;
+        const int band = (row & 15) >> 2;
+        for (int i0 = 0; i0 < SW; i0 += 8) {
+            uint64_t w; memcpy(&w, pass.data() + i0, 8);               // (pass is padded with zeros to a multiple of 8)
+            if (!w) continue;
+            for (int i = i0; i < i0 + 8 && i < SW; i++)
+                if (pass[i]) { b[i >> 4] |= (uint16_t)(1u << (4 * band + ((i & 15) >> 2))); any = true; }
+        }
+    }
+    if (any) acc.live++;
+    // the tile rows k_project visits (gs_render.hip: its clamp of splat_pixel_bounds to the strip and the frame)
+    float xmin, xmax, ymin, ymax;
+    gsm::splat_pixel_bounds(p, x, xmin, xmax, ymin, ymax);
+    const float fx0 = fmaxf(xmin, (float)x0), fx1 = fminf(xmax, (float)(x1 - 1));
+    const float fy0 = fmaxf(ymin, 0.0f), fy1 = fminf(ymax, (float)(H - 1));
+    int ty0 = 0, ty1 = -1;
+    if (fx0 <= fx1 && fy0 <= fy1) { ty0 = (H - 1 - (int)fy1) / 16; ty1 = (H - 1 - (int)fy0) / 16; }
+    for (int s = 0; s < (nine ? 9 : 1); s++) {
+        static const int order[9][2] = { {0, 0}, {-1, -1}, {-1, 0}, {-1, 1}, {0, -1}, {0, 1}, {1, -1}, {1, 0}, {1, 1} };
+        const int ur = order[s][0], us = order[s][1];
+        gsm::hc_ulp_rcp = ur; gsm::hc_ulp_sqrt = us;
+        gsm::EllipseRows e; gsm::ellipse_rows_setup(p, e);
+        for (int ty = 0; ty < TY; ty++) {
+            uint32_t tx0 = 0, n = 0;
+            if (ty >= ty0 && ty <= ty1) gsm::splat_tile_row(p, e, ty, H, x0, x1, tx0, n);
+            if (s == 0) acc.claimed += n;
+            if (!any) continue;
+            for (int tx = 0; tx < TX; tx++) {
+                const uint32_t have = blk[(size_t)ty * TX + tx];
+                if (!have) continue;
+                if (s == 0) acc.touched++;
+                const bool in_run = (uint32_t)tx >= tx0 && (uint32_t)tx < tx0 + n;
+                int bad = 0; uint32_t bits = 0;
+                if ((checks & 1) && !in_run) { acc.tile_miss++; bad = 1; bits = have; }
+                if ((checks & 2) && in_run) {
+                    const uint32_t m = gsm::subtile_mask(p.cx, p.cy, p.ax, p.ay, p.bx, p.by, (float)(x0 + 16 * tx), 16 * ty, H);
+                    if (have & ~m) { acc.blk_miss += __builtin_popcount(have & ~m); bad = 2; bits = have & ~m; }
+                }
+                if (bad && acc.first[0] < 0) {
+                    acc.first[0] = ri; acc.first[3] = ur; acc.first[4] = us; acc.first[5] = bad;
+                    cov_find_pixel(p, H, x0, x1, ty, tx, bits, acc.first[1], acc.first[2]);
+                }
+            }
+        }
+    }
+    gsm::hc_ulp_rcp = 0; gsm::hc_ulp_sqrt = 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+// out[12]: misses, tile misses, block misses, tiles claimed and tiles touched (both at the IEEE setting), records with a passing
+// pixel, then the first offender (lowest record index): record, pixel x, image row, ulp of rcp, ulp of sqrt, check.  Returns misses.
+__attribute__((visibility("default")))
+int64_t hc_coverage_sweep(const float *recs, size_t n, int W, int H, int x0, int x1, int checks, int nine, int64_t *out)
+{
+    if (W <= 0 || H <= 0 || x0 < 0 || x1 > W || x0 >= x1) return -1;
+    unsigned nt = std::thread::hardware_concurrency();
+    nt = nt < 1 ? 1 : (nt > 16 ? 16 : nt);
+    std::vector<CovAcc> accs(nt);
+    std::atomic<size_t> next(0);
+    auto work = [&](unsigned t) {
+        const int TX = (x1 - x0 + 15) / 16, TY = (H + 15) / 16;
+        std::vector<uint16_t> blk((size_t)TX * TY);
+        std::vector<uint8_t> pass((size_t)(x1 - x0 + 15) & ~(size_t)7, 0);
+        for (;;) {
+            const size_t a = next.fetch_add(64);
+            if (a >= n) break;
+            for (size_t i = a; i < a + 64 && i < n; i++) cov_one(recs + 5 * i, (int64_t)i, H, x0, x1, checks, nine, accs[t], blk, pass);
+        }
+    };
+    std::vector<std::thread> th;
+    for (unsigned t = 1; t < nt; t++) th.emplace_back(work, t);
+    work(0);
+    for (auto &t : th) t.join();
+    memset(out, 0, 12 * sizeof(int64_t)); out[6] = -1;
+    for (const CovAcc &a : accs) {
+        out[1] += a.tile_miss; out[2] += a.blk_miss; out[3] += a.claimed; out[4] += a.touched; out[5] += a.live;
+        if (a.first[0] >= 0 && (out[6] < 0 || a.first[0] < out[6])) memcpy(out + 6, a.first, sizeof a.first);
+    }
+    out[0] = out[1] + out[2];
+    return out[0];
+}
+
+// the Projected record of each sweep record (cx, cy, ax, ay, bx, by) and, where px is given, frag_power at pixel (px[i], row[i])
+__attribute__((visibility("default")))
+void hc_coverage_records(const float *recs, size_t n, int H, float *out6, const int *px, const int *row, float *q)
+{
+    for (size_t i = 0; i < n; i++) {
+        gsm::Projected p; gsm::ProjExtra x;
+        cov_record(recs + 5 * i, p, x);
+        if (out6) { float *o = out6 + 6 * i; o[0] = p.cx; o[1] = p.cy; o[2] = p.ax; o[3] = p.ay; o[4] = p.bx; o[5] = p.by; }
+        if (px) {
+            const float dx = ((float)px[i] + 0.5f) - p.cx, dy = ((float)(H - 1 - row[i]) + 0.5f) - p.cy;
+            q[i] = gsm::frag_power(dx, dy, p.ax, p.ay, p.bx, p.by);
+        }
+    }
+}
 }
