@@ -372,6 +372,50 @@ GS_HD float fast_rcp(float x) { return 1.0f / x; }
 GS_HD float fast_sqrt(float x) { return sqrtf(x); }
 #endif
 
+// ---------------------------------------------------------------- reach test of gs_sort_for (gs_sort.hip: the STRIP depth kernels)
+// rows 0, 1, 2 of gsModelViewMatrix, rows 0, 1, 3 of gsProjectionMatrix, and the strip in pixels; filled on the host by
+// gs_fill_strip_uniforms (gs_strip_uniforms.h), which also derives norm_a >= ||mat3(gsModelViewMatrix)||_2
+struct StripUniforms { float mvr0[4], mvr1[4], mvr2[4], pr0[4], pr1[4], pr3[4]; float focal, norm_a, half_w, sx0, sx1, half_h, sy1; };   // (sy1 > 0: rows [0, sy1) tested too)
+
+// Can a fragment of the splat fall on pixel columns [sx0, sx1]?  Fragments live where |p| <= 2
+// (index.js:171-172): an ellipse with semi-axes 2 v1, 2 v2 around the projected centre, whose half-width in x is
+// 2 sqrt(v1x^2 + v2x^2) <= 2 |v1| = 2 min(sqrt(2 lambda1), 1024) (index.js:139-149), and
+// lambda1 <= (|J|_2 |A|_2 sigma_max)^2 + 0.3 with J the shader's Jacobian at the splat's camera-space position
+// (index.js:127-135; J J^T = (f/z)^2 [[1 + rx^2, -rx ry], [-rx ry, 1 + ry^2]], largest eigenvalue (f/z)^2 (1 + rx^2 + ry^2)).
+// Conservative by construction; the slack on top is 3 % + 3 pixels (reach = 2.06 ax + 3 against a half-width of at most 2 ax) and up
+// to 0.88 % in norm_a; NaN anywhere keeps the splat.
+// (fp32 with hardware rcp / sqrt: the test only has to err on the side of keeping, and that slack dwarfs the rounding; in
+// f64 -- divisions, a square root -- it cost more than the whole depth pass: 92 -> 158 us at 20 M splats.)
+// camz comes from the STRIP's own modelView row 2, not from the sort's view row: the two coincide for a mono frame, but an XR
+// eye is sorted with the head camera's view (index.js:441) and drawn with its own, possibly canted, matrix (index.js:185-187).
+// Checked by tests/test_reach_cpu.py: this header's host build, the reciprocal and the square root moved by -1, 0 and +1 ulp, against
+// frag_power <= 4.0f at every pixel centre of the strip; and by tests/test_reach_gpu.py on the hardware's own operations.
+GS_HD bool strip_may_touch(const StripUniforms &s, float x, float y, float z, float sigma)
+{
+    const float camz = fmaf(s.mvr2[2], z, fmaf(s.mvr2[1], y, s.mvr2[0] * x)) + s.mvr2[3];
+    const float camx = fmaf(s.mvr0[2], z, fmaf(s.mvr0[1], y, s.mvr0[0] * x)) + s.mvr0[3];
+    const float camy = fmaf(s.mvr1[2], z, fmaf(s.mvr1[1], y, s.mvr1[0] * x)) + s.mvr1[3];
+    const float cw = fmaf(s.pr3[2], camz, fmaf(s.pr3[1], camy, s.pr3[0] * camx)) + s.pr3[3];
+    const float cx = fmaf(s.pr0[2], camz, fmaf(s.pr0[1], camy, s.pr0[0] * camx)) + s.pr0[3];
+    if (!(cw > 0.0f)) return true;
+    const float xpx = fmaf(cx, fast_rcp(cw), 1.0f) * s.half_w;
+    const float iz = fast_rcp(camz), rx = camx * iz, ry = camy * iz;
+    const float jn = fabsf(s.focal * iz) * fast_sqrt(fmaf(rx, rx, fmaf(ry, ry, 1.0f)));
+    const float sd = jn * s.norm_a * sigma;
+    float ax = fast_sqrt(2.0f * fmaf(sd, sd, 0.3f));
+    if (!(ax < 1024.0f)) ax = 1024.0f;
+    const float reach = fmaf(2.06f, ax, 3.0f);
+    if (xpx + reach < s.sx0 || xpx - reach > s.sx1) return false;
+    // the rows of the frame (round 6: a strip is as tall as its frame, and gs_sort_for over the WHOLE frame is a frustum cull): the same
+    // bound serves both axes -- 2 sqrt(v1y^2 + v2y^2) <= 2 |v1| too
+    if (s.sy1 > 0.0f) {
+        const float cy = fmaf(s.pr1[2], camz, fmaf(s.pr1[1], camy, s.pr1[0] * camx)) + s.pr1[3];
+        const float ypx = fmaf(cy, fast_rcp(cw), 1.0f) * s.half_h;
+        if (ypx + reach < 0.0f || ypx - reach > s.sy1) return false;
+    }
+    return true;
+}
+
 GS_HD void ellipse_rows_setup(const Projected &p, EllipseRows &e)
 {
     const float A = p.ax * p.ax + p.bx * p.bx;

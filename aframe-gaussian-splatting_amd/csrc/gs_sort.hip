@@ -8,6 +8,7 @@
 // [0,65535] (f32 rounding of the stored depth >> depth range) carry key 65536, sort behind every bucket and store 0 --
 // exactly like the reference's out-of-bounds typed-array writes leave 0 in the tail [V',V) of its result.
 #include "gs_internal.h"
+#include "gs_strip_uniforms.h"
 
 namespace {
 
@@ -19,7 +20,7 @@ struct SortUniforms {                                            // widened on t
 // the per-splat state store (gs_set_state ...; gs_edit.hip): a splat whose byte has GS_STATE_HIDDEN counts as outside the cutout.  Read by the
 // HID instantiations only -- a context whose store is empty launches the others, which never look at it
 struct HiddenArgs { const uint8_t *state; uint32_t rows; };      // rows: the store's length (<= n; the allocation holds n bytes at least)
-struct StripUniforms { float mvr0[4], mvr1[4], mvr2[4], pr0[4], pr1[4], pr3[4]; float focal, norm_a, half_w, sx0, sx1, half_h, sy1; };   // (sy1 > 0: rows [0, sy1) tested too)
+using gsm::StripUniforms;                                        // (gs_device_math.h, with the reach test gsm::strip_may_touch)
 // the depth kernel's chunking is its own (no histogram depends on it)
 #ifndef GS_DEPTH_IPT
 #define GS_DEPTH_IPT 4             // items per thread and pass: 52 vector registers, 8 waves per SIMD (8 items: 92, 5 waves)
@@ -80,41 +81,7 @@ __device__ __forceinline__ void depth_hist_end(const DepthHist &dh, const uint32
 
 // pass 1 (index.js:517-555): depth, culls, f64 min/max of survivors.  16 B/splat in, 4 B/splat out.
 // Each workgroup leaves its (min, max, count) in a partial slot; no global atomics.
-// strip test of gs_sort_for: can a fragment of the splat fall on pixel columns [sx0, sx1]?  Fragments live where |p| <= 2
-// (index.js:171-172): an ellipse with semi-axes 2 v1, 2 v2 around the projected centre, whose half-width in x is
-// 2 sqrt(v1x^2 + v2x^2) <= 2 |v1| = 2 min(sqrt(2 lambda1), 1024) (index.js:139-149), and
-// lambda1 <= (|J|_2 |A|_2 sigma_max)^2 + 0.3 with J the shader's Jacobian at the splat's camera-space position
-// (index.js:127-135; J J^T = (f/z)^2 [[1 + rx^2, -rx ry], [-rx ry, 1 + ry^2]], largest eigenvalue (f/z)^2 (1 + rx^2 + ry^2)).
-// Conservative by construction, 1 % + 2 pixels of slack on top; NaN anywhere keeps the splat.
-// (fp32 with hardware rcp / sqrt: the test only has to err on the side of keeping, and 3 % + 3 pixels of slack dwarf the
-// rounding; in f64 -- divisions, a square root -- it cost more than the whole depth pass: 92 -> 158 us at 20 M splats.)
-// camz comes from the STRIP's own modelView row 2, not from the sort's view row: the two coincide for a mono frame, but an XR
-// eye is sorted with the head camera's view (index.js:441) and drawn with its own, possibly canted, matrix (index.js:185-187).
-__device__ __forceinline__ bool strip_may_touch(const StripUniforms &s, float x, float y, float z, float sigma)
-{
-    const float camz = fmaf(s.mvr2[2], z, fmaf(s.mvr2[1], y, s.mvr2[0] * x)) + s.mvr2[3];
-    const float camx = fmaf(s.mvr0[2], z, fmaf(s.mvr0[1], y, s.mvr0[0] * x)) + s.mvr0[3];
-    const float camy = fmaf(s.mvr1[2], z, fmaf(s.mvr1[1], y, s.mvr1[0] * x)) + s.mvr1[3];
-    const float cw = fmaf(s.pr3[2], camz, fmaf(s.pr3[1], camy, s.pr3[0] * camx)) + s.pr3[3];
-    const float cx = fmaf(s.pr0[2], camz, fmaf(s.pr0[1], camy, s.pr0[0] * camx)) + s.pr0[3];
-    if (!(cw > 0.0f)) return true;
-    const float xpx = fmaf(cx, __builtin_amdgcn_rcpf(cw), 1.0f) * s.half_w;
-    const float iz = __builtin_amdgcn_rcpf(camz), rx = camx * iz, ry = camy * iz;
-    const float jn = fabsf(s.focal * iz) * __builtin_amdgcn_sqrtf(fmaf(rx, rx, fmaf(ry, ry, 1.0f)));
-    const float sd = jn * s.norm_a * sigma;
-    float ax = __builtin_amdgcn_sqrtf(2.0f * fmaf(sd, sd, 0.3f));
-    if (!(ax < 1024.0f)) ax = 1024.0f;
-    const float reach = fmaf(2.06f, ax, 3.0f);
-    if (xpx + reach < s.sx0 || xpx - reach > s.sx1) return false;
-    // the rows of the frame (round 6: a strip is as tall as its frame, and gs_sort_for over the WHOLE frame is a frustum cull): the same
-    // bound serves both axes -- 2 sqrt(v1y^2 + v2y^2) <= 2 |v1| too
-    if (s.sy1 > 0.0f) {
-        const float cy = fmaf(s.pr1[2], camz, fmaf(s.pr1[1], camy, s.pr1[0] * camx)) + s.pr1[3];
-        const float ypx = fmaf(cy, __builtin_amdgcn_rcpf(cw), 1.0f) * s.half_h;
-        if (ypx + reach < 0.0f || ypx - reach > s.sy1) return false;
-    }
-    return true;
-}
+// (the strip test of gs_sort_for: gsm::strip_may_touch, gs_device_math.h)
 
 // SPEC (near-only sorts of long inputs, round 4): the pass hands the candidates on itself.  A near-only sort keeps the splats whose
 // bucket reaches a threshold that is only known after the pass (it comes from this pass' depth histogram and min / max) -- so the
@@ -156,7 +123,7 @@ __device__ __forceinline__ void depth_view_step(const DepthView &v, const float4
     const bool keep = gsm::sort_keep(d, m.w, inside);
     // the bucket scale comes from EVERY splat the reference keeps (index.js:552-553), so a strip's order is the
     // reference's order restricted to the strip's splats; only those are handed on
-    const bool mine = keep && (!STRIP || strip_may_touch(v.su, m.x, m.y, m.z, sigma));
+    const bool mine = keep && (!STRIP || gsm::strip_may_touch(v.su, m.x, m.y, m.z, sigma));
     if (!SPEC) v.depth[i] = mine ? (float)d : INFINITY;
     if (mine && v.dh.fill) atomicAdd(&s_dh[depth_bin((float)d)], 1u);
     if (SPEC) { a.fb[r] = __float_as_uint((float)d); a.sp[r] = mine && depth_bin((float)d) <= a.lim; }
@@ -1051,7 +1018,7 @@ int gs_run_sort2(gs_ctx *const S[2], const float *const view[2], const float *co
 }
 
 // the uniforms of one sort: view row and cutout matrix widened to f64; for a strip sort (gs_sort_for) the rows of the frame's
-// matrices the reach test needs and an upper bound of ||mat3(modelView)||_2
+// matrices the reach test needs and an upper bound of ||mat3(modelView)||_2 (gs_strip_uniforms.h)
 static void fill_sort_uniforms(const gs_ctx *ctx, const float view[4], const float *cutout16, const GsSortStrip *strip, SortUniforms &u, StripUniforms &su)
 {
     for (int i = 0; i < 4; i++) u.view[i] = (double)view[i];
@@ -1063,32 +1030,7 @@ static void fill_sort_uniforms(const gs_ctx *ctx, const float view[4], const flo
     u.has_strip = 0;
     memset(&su, 0, sizeof su);
     if (strip && ctx->renderable) {
-        const float *m = strip->mv, *p = strip->proj;
-        for (int k = 0; k < 4; k++) { su.mvr0[k] = m[4 * k]; su.mvr1[k] = m[4 * k + 1]; su.mvr2[k] = m[4 * k + 2]; su.pr0[k] = p[4 * k]; su.pr1[k] = p[4 * k + 1]; su.pr3[k] = p[4 * k + 3]; }
-        // spectral norm of A = mat3(gsModelViewMatrix): power iteration on A^T A (symmetric 3x3), bracketed from above by the
-        // Frobenius norm; a rigid pose with uniform scale s gives s
-        double ata[3][3], fro = 0.0;
-        for (int i = 0; i < 3; i++) for (int j = 0; j < 3; j++) {
-            ata[i][j] = 0.0;
-            for (int r = 0; r < 3; r++) ata[i][j] += (double)m[4 * i + r] * m[4 * j + r];
-        }
-        for (int i = 0; i < 3; i++) fro += ata[i][i];
-        double v[3] = { 1.0, 0.7, 0.4 }, lam = fro;
-        for (int it = 0; it < 64; it++) {
-            double w[3] = { 0, 0, 0 }, nn = 0.0;
-            for (int i = 0; i < 3; i++) { for (int j = 0; j < 3; j++) w[i] += ata[i][j] * v[j]; nn += w[i] * w[i]; }
-            nn = sqrt(nn);
-            if (!(nn > 0.0)) break;
-            for (int i = 0; i < 3; i++) v[i] = w[i] / nn;
-            lam = nn;
-        }
-        // (the iterate's Rayleigh quotient approaches the largest eigenvalue from below: 2 % on top, never above Frobenius)
-        double na = sqrt(lam) * 1.02;
-        if (!(na <= sqrt(fro) * 1.0001)) na = sqrt(fro) * 1.0001;
-        su.norm_a = (float)na * 1.0001f;
-        su.focal = strip->focal; su.half_w = 0.5f * strip->vw; su.sx0 = (float)strip->x0; su.sx1 = (float)strip->x1;
-        su.half_h = 0.5f * strip->vh; su.sy1 = strip->vh > 0.0f ? strip->vh : 0.0f;
-        u.has_strip = (su.norm_a == su.norm_a && su.focal > 0.0f && strip->x1 > strip->x0) ? 1 : 0;
+        u.has_strip = gs_fill_strip_uniforms(strip->mv, strip->proj, strip->focal, strip->vw, strip->vh, strip->x0, strip->x1, su);
     }
 
 }

@@ -9,6 +9,7 @@
 #include "gs_device_math.h"
 #include "gs_ply.h"
 #include "gs_host_tables.h"
+#include "gs_strip_uniforms.h"
 
 extern "C" {
 
@@ -270,5 +271,118 @@ void hc_coverage_records(const float *recs, size_t n, int H, float *out6, const 
             q[i] = gsm::frag_power(dx, dy, p.ax, p.ay, p.bx, p.by);
         }
     }
+}
+}
+
+// ---------------------------------------------------------------- reach sweep (tests/test_reach_cpu.py)
+// gs_sort_for's reach test (gsm::strip_may_touch with the uniforms of gs_fill_strip_uniforms) against the truth, per .splat row:
+//   truth   the row, packed (gsm::pack_row) and projected (gsm::project_splat), is visible and some pixel centre with column in
+//           [x0, x1) and row in [0, H) has gsm::frag_power <= 4.0f -- brute force over the strip's intersection with the ellipse's
+//           f64 bounding box widened by one pixel;
+//   miss    truth, and strip_may_touch says false in one of the nine (or the one IEEE) settings of the emulated reciprocal / square root.
+
+namespace {
+
+struct ReachAcc {
+    int64_t miss = 0, truth = 0, kept = 0, truth_kept = 0, idle_culled = 0;
+    int64_t first[5] = { -1, 0, 0, 0, 0 };             // row, pixel x, image row, ulp of rcp, ulp of sqrt
+};
+
+// the first passing pixel of the box, rows top-down; false if none
+bool reach_truth(const gsm::Projected &p, const gsm::ProjExtra &x, int H, int x0, int x1, std::vector<uint8_t> &pass, int64_t &px, int64_t &row)
+{
+    const double hw = 2.0 * sqrt((double)x.v1x * x.v1x + (double)x.v2x * x.v2x), hh = 2.0 * sqrt((double)x.v1y * x.v1y + (double)x.v2y * x.v2y);
+    if (!(hw == hw) || !(hh == hh) || !(p.cx == p.cx) || !(p.cy == p.cy)) return false;      // (no such record is visible)
+    // pixel i has its centre at i + 0.5; GL row g likewise; one more pixel on every side
+    const double fx0 = floor((double)p.cx - hw - 0.5) - 1.0, fx1 = ceil((double)p.cx + hw - 0.5) + 1.0;
+    const double fy0 = floor((double)p.cy - hh - 0.5) - 1.0, fy1 = ceil((double)p.cy + hh - 0.5) + 1.0;
+    const int i0 = (int)fmax(fx0, (double)x0), i1 = (int)fmin(fx1, (double)(x1 - 1));
+    const int g0 = (int)fmax(fy0, 0.0), g1 = (int)fmin(fy1, (double)(H - 1));
+    if (i0 > i1 || g0 > g1) return false;
+    for (int g = g1; g >= g0; g--) {
+        const float dy = ((float)g + 0.5f) - p.cy;
+        cov_pass_row(p, dy, i0, i1 + 1, pass.data());
+        for (int i = i0; i <= i1; i++) if (pass[i - i0]) { px = i; row = H - 1 - g; return true; }
+    }
+    return false;
+}
+
+}  // namespace
+
+extern "C" {
+
+__attribute__((visibility("default")))
+float hc_norm_bound(const float *mv16) { return gs_norm_bound(mv16); }
+
+// the uniforms as the library fills them (31 floats, the struct's layout); returns has_strip
+__attribute__((visibility("default")))
+int hc_strip_uniforms(const float *mv, const float *proj, float focal, float vw, float vh, int x0, int x1, float *su31)
+{
+    gsm::StripUniforms su;
+    const int has = gs_fill_strip_uniforms(mv, proj, focal, vw, vh, x0, x1, su);
+    static_assert(sizeof su == 31 * sizeof(float), "StripUniforms layout");
+    memcpy(su31, &su, sizeof su);
+    return has;
+}
+
+// rows: n x 32-byte .splat rows.  norm_a > 0 replaces the bound gs_fill_strip_uniforms derives (the test feeds the parent commit's
+// formula through the same strip_may_touch).  flags (n bytes, may be null): bit 0 truth, bit 1 kept at the IEEE setting, bit 2 visible.
+// out[10]: misses, truth, kept (IEEE), truth and kept, neither, then the first offender (lowest row): row, pixel x, image row, ulp of
+// rcp, ulp of sqrt.  Returns misses, -1 for a bad strip, -2 when has_strip is 0 (nothing is tested then: the sort keeps every splat).
+__attribute__((visibility("default")))
+int64_t hc_reach_sweep(const uint8_t *rows, size_t n, const float *mv, const float *proj, float focal, int W, int H, int x0, int x1,
+                       float norm_a, int nine, int64_t *out, uint8_t *flags)
+{
+    if (W <= 0 || H <= 0 || x0 < 0 || x1 > W || x0 >= x1) return -1;
+    gsm::StripUniforms su;
+    if (!gs_fill_strip_uniforms(mv, proj, focal, (float)W, (float)H, x0, x1, su)) return -2;
+    if (norm_a > 0.0f) su.norm_a = norm_a;
+    std::vector<double> tab(GS_POW10_ENTRIES);
+    gs_build_pow10_table(tab.data());
+    unsigned nt = std::thread::hardware_concurrency();
+    nt = nt < 1 ? 1 : (nt > 16 ? 16 : nt);
+    std::vector<ReachAcc> accs(nt);
+    std::atomic<size_t> next(0);
+    auto work = [&](unsigned t) {
+        ReachAcc &acc = accs[t];
+        std::vector<uint8_t> pass((size_t)(x1 - x0 + 15) & ~(size_t)7, 0);
+        for (;;) {
+            const size_t a = next.fetch_add(64);
+            if (a >= n) break;
+            for (size_t i = a; i < a + 64 && i < n; i++) {
+                uint32_t w[8]; memcpy(w, rows + 32 * i, 32);
+                gsm::PackOut o; gsm::pack_row(w, tab.data(), o);
+                const float mx = o.cs[3] * 32767.0f;                                            // k_pack's line (gs_pack.hip)
+                const float bound_r = (mx == mx && mx < 3.0e37f) ? sqrtf(3.0f * mx) * 1.001f : INFINITY;
+                gsm::Projected p; gsm::ProjExtra x;
+                memset(&p, 0, sizeof p); memset(&x, 0, sizeof x);
+                const bool vis = gsm::project_splat(o.cs, o.cc, mv, proj, focal, (float)W, (float)H, p, x);
+                int64_t px = 0, row = 0;
+                const bool truth = vis && reach_truth(p, x, H, x0, x1, pass, px, row);
+                gsm::hc_ulp_rcp = 0; gsm::hc_ulp_sqrt = 0;
+                const bool kept = gsm::strip_may_touch(su, o.sort_row[0], o.sort_row[1], o.sort_row[2], bound_r);
+                acc.truth += truth; acc.kept += kept; acc.truth_kept += truth && kept; acc.idle_culled += !truth && !kept;
+                if (flags) flags[i] = (uint8_t)((truth ? 1 : 0) | (kept ? 2 : 0) | (vis ? 4 : 0));
+                if (!truth) continue;
+                for (int s = 0; s < (nine ? 9 : 1); s++) {
+                    gsm::hc_ulp_rcp = s / 3 - 1 + (nine ? 0 : 1); gsm::hc_ulp_sqrt = s % 3 - 1 + (nine ? 0 : 1);
+                    if (gsm::strip_may_touch(su, o.sort_row[0], o.sort_row[1], o.sort_row[2], bound_r)) continue;
+                    acc.miss++;
+                    if (acc.first[0] < 0 || (int64_t)i < acc.first[0]) { acc.first[0] = (int64_t)i; acc.first[1] = px; acc.first[2] = row; acc.first[3] = gsm::hc_ulp_rcp; acc.first[4] = gsm::hc_ulp_sqrt; }
+                }
+                gsm::hc_ulp_rcp = 0; gsm::hc_ulp_sqrt = 0;
+            }
+        }
+    };
+    std::vector<std::thread> th;
+    for (unsigned t = 1; t < nt; t++) th.emplace_back(work, t);
+    work(0);
+    for (auto &t : th) t.join();
+    memset(out, 0, 10 * sizeof(int64_t)); out[5] = -1;
+    for (const ReachAcc &a : accs) {
+        out[0] += a.miss; out[1] += a.truth; out[2] += a.kept; out[3] += a.truth_kept; out[4] += a.idle_culled;
+        if (a.first[0] >= 0 && (out[5] < 0 || a.first[0] < out[5])) memcpy(out + 5, a.first, sizeof a.first);
+    }
+    return out[0];
 }
 }

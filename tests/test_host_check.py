@@ -18,7 +18,8 @@ CSRC = os.path.join(ROOT, "aframe-gaussian-splatting_amd", "csrc")
 @pytest.fixture(scope="module")
 def hc():
     so = os.path.join(HC_DIR, "libhost_check.so")
-    srcs = [os.path.join(HC_DIR, "host_check.cpp"), os.path.join(CSRC, "gs_device_math.h"), os.path.join(CSRC, "gs_host_tables.h")]
+    srcs = [os.path.join(HC_DIR, "host_check.cpp"), os.path.join(CSRC, "gs_device_math.h"), os.path.join(CSRC, "gs_host_tables.h"),
+            os.path.join(CSRC, "gs_strip_uniforms.h")]
     if not os.path.exists(so) or any(os.path.getmtime(s) > os.path.getmtime(so) for s in srcs):
         # GS_HOST_CHECK_ULP: fast_rcp / fast_sqrt take a -1 / 0 / +1 ulp error from two variables (0: IEEE, as before; test_coverage_cpu.py)
         subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-pthread", "-ffp-contract=off", "-fvisibility=hidden",
