@@ -38,6 +38,8 @@ BUF_SH = 8
 BUF_STATE = 9
 STATE_HIDDEN, STATE_SELECTED = 1, 2
 SELECT_INVERT = 1
+PROP_X, PROP_Y, PROP_Z, PROP_RED, PROP_GREEN, PROP_BLUE, PROP_ALPHA, PROP_SIZE2 = range(8)
+HIST_MAX_BINS = 4096
 
 EXPORTS = [
     "gs_create", "gs_destroy", "gs_last_error", "gs_version", "gs_device_count", "gs_clear", "gs_push_splat", "gs_push_matrices", "gs_load_ply",
@@ -57,6 +59,8 @@ EXPORTS = [
     "gs_sort_inspect",
     "gs_multi_set_state", "gs_multi_set_state_ids", "gs_multi_select_box", "gs_multi_select_sphere", "gs_multi_select_rect", "gs_multi_compact",
     "gs_select_mask", "gs_multi_select_mask", "gs_mask_polygon", "gs_highlight_info", "gs_highlight_word",
+    "gs_prop_eval", "gs_hist_bin", "gs_prop_range", "gs_histogram", "gs_select_range",
+    "gs_multi_prop_range", "gs_multi_histogram", "gs_multi_select_range",
 ]
 SURFACE_NONE = 0xFFFFFFFF          # gs_surface.id / gs_hit.id where the transmittance never falls below one half
 
@@ -235,6 +239,14 @@ def load(build_if_missing=True):
         L.gs_mask_polygon.argtypes = [vp, sz, i32, i32, vp, sz]
         L.gs_highlight_info.argtypes = [vp, u32p, u32p]
         L.gs_highlight_word.argtypes = [C.c_uint32, C.c_uint32, u32p]
+    if hasattr(L, "gs_histogram"):                             # (an older build loaded through GS_SPLAT_LIB for an A/B run has none)
+        u8, szp, f64 = C.c_uint8, C.POINTER(sz), C.c_double
+        L.gs_prop_eval.argtypes = [vp, vp, i32, vp]
+        L.gs_hist_bin.argtypes = [f64, f64, f64, C.c_uint32, C.POINTER(C.c_int32)]
+        for pre in ("gs_", "gs_multi_"):
+            getattr(L, pre + "prop_range").argtypes = [vp, i32, u8, u8, C.POINTER(f64), C.POINTER(f64), szp]
+            getattr(L, pre + "histogram").argtypes = [vp, i32, f64, f64, C.c_uint32, u8, u8, vp, vp]
+            getattr(L, pre + "select_range").argtypes = [vp, i32, f64, f64, u8, u8, C.c_uint32, szp]
     L.gs_download.argtypes = [vp, i32, vp, sz]
     if hasattr(L, "gs_sort_inspect"):
         L.gs_sort_inspect.argtypes = [vp, C.POINTER(SortInfo), vp, sz]
@@ -444,6 +456,37 @@ def highlight_word(rgba, option_value):
     return res.reshape(w.shape) if w.ndim else res[0]
 
 
+def prop_eval(cs, cc, prop):
+    """gs_prop_eval: the property `prop` (PROP_*) of packed records -- cs = float32[..., 4] and cc = uint32[..., 4], as BUF_CENTER_SCALE and
+    BUF_COV_COLOR hold them -- by the kernels' own function -> float64 (one value, or one per record)"""
+    a = np.ascontiguousarray(cs, np.float32)
+    b = np.ascontiguousarray(cc, np.uint32)
+    if a.shape[-1:] != (4,) or a.shape != b.shape:
+        raise ValueError("cs and cc: records of four words each, the same number of them")
+    ra, rb = a.reshape(-1, 4), b.reshape(-1, 4)
+    out = np.zeros(len(ra), np.float64)
+    f, pa, pb, po = load().gs_prop_eval, ra.ctypes.data, rb.ctypes.data, out.ctypes.data
+    for i in range(len(ra)):
+        rc = f(pa + 16 * i, pb + 16 * i, int(prop), po + 8 * i)
+        if rc != GS_OK:
+            raise GsError(rc, "gs_prop_eval: bad argument")
+    return out.reshape(a.shape[:-1]) if a.ndim > 1 else out[0]
+
+
+def hist_bin(v, lo, hi, nbins):
+    """gs_hist_bin: the bin(s) of the value(s) v in a histogram of nbins bins over [lo, hi] (-1 below, -2 above, -3 NaN) -> int32"""
+    vals = np.ascontiguousarray(v, np.float64)
+    flat, out = vals.reshape(-1), C.c_int32(0)
+    res = np.zeros(flat.size, np.int32)
+    f = load().gs_hist_bin
+    for i in range(flat.size):
+        rc = f(float(flat[i]), float(lo), float(hi), int(nbins), C.byref(out))
+        if rc != GS_OK:
+            raise GsError(rc, "gs_hist_bin: bad argument")
+        res[i] = out.value
+    return res.reshape(vals.shape) if vals.ndim else res[0]
+
+
 def mask_polygon(points, width, height, out=None):
     """gs_mask_polygon: even-odd fill of the closed polygon `points` (n x (x, y), pixels, row 0 = top) -> uint8[height, width] of 0 / 1.
     out: a C-contiguous uint8 array of `height` rows to fill instead (its row length is the stride; bytes beyond `width` stay)."""
@@ -607,6 +650,28 @@ class Context:
         v, last = C.c_uint32(0), C.c_uint32(0)
         self._ck(self._L.gs_highlight_info(self._h, C.byref(v), C.byref(last)))
         return v.value, last.value
+
+    # properties of the resident records (PROP_*): their range, a histogram, selection by value.  A splat takes part in the first two iff
+    # (state & state_mask) == state_value
+    def prop_range(self, prop, state_mask=0, state_value=0):
+        """-> (min, max, n): of the non-NaN values among the splats that pass (+inf, -inf: none), and how many pass"""
+        mn, mx, n = C.c_double(0), C.c_double(0), C.c_size_t(0)
+        self._ck(self._L.gs_prop_range(self._h, int(prop), int(state_mask), int(state_value), C.byref(mn), C.byref(mx), C.byref(n)))
+        return mn.value, mx.value, n.value
+
+    def histogram(self, prop, lo, hi, nbins, state_mask=0, state_value=0):
+        """-> (counts uint32[nbins], tally uint64[4] = passing, below lo, above hi, NaN)"""
+        nb = int(nbins)
+        counts = np.zeros(min(max(nb, 1), HIST_MAX_BINS), np.uint32)        # (a bin count out of range is the library's to refuse)
+        tally = np.zeros(4, np.uint64)
+        self._ck(self._L.gs_histogram(self._h, int(prop), float(lo), float(hi), nb & 0xFFFFFFFF, int(state_mask), int(state_value), _p(counts), _p(tally)))
+        return counts, tally
+
+    def select_range(self, prop, lo, hi, set_bits=0, clear_bits=0, flags=0):
+        """state = (state & ~clear_bits) | set_bits for the splats with lo <= value <= hi (SELECT_INVERT: the others) -> how many"""
+        hit = C.c_size_t(0)
+        self._ck(self._L.gs_select_range(self._h, int(prop), float(lo), float(hi), int(set_bits), int(clear_bits), int(flags), C.byref(hit)))
+        return hit.value
 
     def compact(self):
         """gs_compact: delete the hidden splats -> uint32[count afterwards], the old index of every splat that stays"""
@@ -936,6 +1001,28 @@ class Multi:
         m, stride, d = _mask_args(params, mask, depth_max)
         hit = C.c_size_t(0)
         self._ck(self._L.gs_multi_select_mask(self._h, C.byref(params), _p(m), stride, _p(d), int(set_bits), int(clear_bits), int(flags), C.byref(hit)))
+        return hit.value
+
+    # properties of the resident records (PROP_*): their range, a histogram, selection by value.  A splat takes part in the first two iff
+    # (state & state_mask) == state_value
+    def prop_range(self, prop, state_mask=0, state_value=0):
+        """-> (min, max, n): of the non-NaN values among the splats that pass (+inf, -inf: none), and how many pass"""
+        mn, mx, n = C.c_double(0), C.c_double(0), C.c_size_t(0)
+        self._ck(self._L.gs_multi_prop_range(self._h, int(prop), int(state_mask), int(state_value), C.byref(mn), C.byref(mx), C.byref(n)))
+        return mn.value, mx.value, n.value
+
+    def histogram(self, prop, lo, hi, nbins, state_mask=0, state_value=0):
+        """-> (counts uint32[nbins], tally uint64[4] = passing, below lo, above hi, NaN)"""
+        nb = int(nbins)
+        counts = np.zeros(min(max(nb, 1), HIST_MAX_BINS), np.uint32)        # (a bin count out of range is the library's to refuse)
+        tally = np.zeros(4, np.uint64)
+        self._ck(self._L.gs_multi_histogram(self._h, int(prop), float(lo), float(hi), nb & 0xFFFFFFFF, int(state_mask), int(state_value), _p(counts), _p(tally)))
+        return counts, tally
+
+    def select_range(self, prop, lo, hi, set_bits=0, clear_bits=0, flags=0):
+        """state = (state & ~clear_bits) | set_bits for the splats with lo <= value <= hi (SELECT_INVERT: the others) -> how many"""
+        hit = C.c_size_t(0)
+        self._ck(self._L.gs_multi_select_range(self._h, int(prop), float(lo), float(hi), int(set_bits), int(clear_bits), int(flags), C.byref(hit)))
         return hit.value
 
     def compact(self):

@@ -72,6 +72,8 @@ GS_API int gs_destroy(gs_ctx *ctx)
     dev_free(ctx->splat); dev_free(ctx->sort_rows); dev_free(ctx->bound_r); dev_free(ctx->pow10tab); dev_free(ctx->sh);
     dev_free(ctx->edit_state); dev_free(ctx->edit_cnt); dev_free(ctx->mask_buf);
     dev_free(ctx->scene_depth); dev_free(ctx->scene_rgba);
+    dev_free(ctx->prop_buf);
+    if (ctx->prop_stream) (void)hipStreamDestroy(ctx->prop_stream);
     if (ctx->ev_sort) (void)hipEventDestroy(ctx->ev_sort);
     delete ctx;
     return GS_OK;

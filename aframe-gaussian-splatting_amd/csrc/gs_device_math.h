@@ -241,6 +241,32 @@ GS_HD uint32_t highlight_word(uint32_t rgba, uint32_t hl)
     }
     return out;
 }
+// Per-splat properties (gs_prop_range / gs_histogram / gs_select_range, gs_splat.h: GS_PROP_*): one f64 per packed record, every
+// operation f64 and un-fused.  0..2: the centre in the rows' object space (the packed z is negated back, as gs_select_sphere reads it);
+// 3..6: the colour bytes; 7: the trace of the dequantised covariance -- the diagonal project_splat reads, summed as integers (exact),
+// one multiplication, no square root.  The caller has checked prop_valid; a position property never reads cc.
+GS_HD bool prop_valid(int prop) { return prop >= 0 && prop <= 7; }
+GS_HD bool prop_reads_cc(int prop) { return prop >= 3; }
+GS_HD double prop_value(const float cs[4], const uint32_t cc[4], int prop)
+{
+    if (prop == 0) return (double)cs[0];
+    if (prop == 1) return (double)cs[1];
+    if (prop == 2) return -(double)cs[2];
+    if (prop <= 6) return (double)((cc[3] >> (8u * (uint32_t)(prop - 3))) & 0xFFu);
+    const int32_t q11 = (int16_t)(cc[0] & 0xFFFF), q22 = (int16_t)(cc[1] >> 16), q33 = (int16_t)(cc[2] >> 16);
+    return ((double)q11 + (double)q22 + (double)q33) * (double)cs[3];
+}
+// The binning rule of gs_hist_bin: scale = (double)nbins / (hi - lo), formed ONCE on the host and handed to the kernel as it is.
+// -1: below lo, -2: above hi, -3: NaN; else min(floor((v - lo) * scale), nbins - 1), so v == hi lands in the last bin.  (A product
+// that is not below nbins lands there too -- with a range so narrow that the scale overflows, that includes the NaN of 0 * inf.)
+GS_HD int32_t hist_bin(double v, double lo, double hi, double scale, uint32_t nbins)
+{
+    if (v != v) return -3;
+    if (v < lo) return -1;
+    if (v > hi) return -2;
+    const double t = floor((v - lo) * scale);
+    return t < (double)nbins ? (int32_t)(int64_t)t : (int32_t)(nbins - 1u);
+}
 // the eigenvalues project_splat draws cov = {cov00, cov01, cov11} with (its very lines)
 GS_HD void dilated_eigenvalues(float cov00, float cov01, float cov11, float &l1, float &l2)
 {

@@ -1,9 +1,11 @@
 // gs_edit.hip -- editing the resident cloud (include/gs_splat.h: "editing the resident cloud"): the kernels behind the per-splat state
-// store -- counting, id lists, region selection (box, sphere, screen rectangle, mask image) -- and the stable compaction of gs_compact.
+// store -- counting, id lists, region selection (box, sphere, screen rectangle, mask image), selection by a property's value and the
+// properties' histogram and range -- and the stable compaction of gs_compact.
 //
 // None of this is a per-frame path: every kernel is one streaming pass over the rows (or over the order), its counts go to two device
 // words through one atomic per workgroup, and every launcher waits for its kernel and hands the count back on the host.  What a frame
 // pays for a state store is ONE byte load per splat in the depth pass (gs_sort.hip: the HID instantiations).
+// (The two reading passes, gs_prop_range and gs_histogram, run on a stream of their own and wait for their kernel alone.)
 // Behind the launchers: the entry points of the C ABI that call them (gs_set_state ... gs_compact).
 #include "gs_lanes.h"
 #include "gs_sh.h"
@@ -215,6 +217,121 @@ __global__ __launch_bounds__(GS_BLOCK) void k_compact_sh(const uint4 *__restrict
     }
 }
 
+// ---- per-splat properties (gs_splat.h: gs_prop_range / gs_histogram / gs_select_range).  One streaming pass each, grid-strided in whole
+// workgroup steps (every lane of a wave stays in the loop until the workgroup leaves it: the wave-wide votes below see all 64 lanes).
+// CC: the property reads the second half of the record (colour bytes, SIZE2); the position properties cost one 16-byte load per splat.
+template <bool CC> __device__ __forceinline__ double prop_load(const uint4 *__restrict__ splat, uint32_t i, int prop)
+{
+    const uint4 cs4 = splat[2 * (size_t)i];
+    uint4 cc4 = make_uint4(0u, 0u, 0u, 0u);
+    if (CC) cc4 = splat[2 * (size_t)i + 1];
+    const float cs[4] = { __uint_as_float(cs4.x), __uint_as_float(cs4.y), __uint_as_float(cs4.z), __uint_as_float(cs4.w) };
+    const uint32_t cc[4] = { cc4.x, cc4.y, cc4.z, cc4.w };
+    return gsm::prop_value(cs, cc, prop);
+}
+// the filter: rows = 0 when the mask is 0 or the store is empty (no byte is loaded then: a store that was never allocated is never read)
+__device__ __forceinline__ bool prop_passes(const uint8_t *__restrict__ state, uint32_t rows, uint32_t i, uint32_t mask, uint32_t value)
+{
+    const uint32_t st = i < rows ? (uint32_t)state[i] : 0u;
+    return (st & mask) == value;
+}
+
+template <bool CC>
+__global__ __launch_bounds__(GS_BLOCK) void k_prop_select(const uint4 *__restrict__ splat, uint32_t n, int prop, double lo, double hi, uint8_t *__restrict__ state,
+                                                          uint32_t set, uint32_t clear, uint32_t invert, uint32_t *__restrict__ hit)
+{
+    uint32_t c = 0;
+    for (uint32_t i = blockIdx.x * GS_BLOCK + threadIdx.x; i < n; i += gridDim.x * GS_BLOCK) {
+        const double v = prop_load<CC>(splat, i, prop);
+        const bool inside = lo <= v && v <= hi;                      // (NaN: outside)
+        if (inside != (invert != 0u)) { state[i] = (uint8_t)((state[i] & ~clear) | set); c++; }
+    }
+    block_count(c, hit);
+}
+
+// Per-workgroup partials, reduced on the host (as the depth pass' range: no f64 atomics on one address): part[blockIdx.x] = { min, max }
+// of the non-NaN values of the workgroup's passing splats (+inf, -inf where it saw none), cnt[blockIdx.x] = its passing splats.
+template <bool CC>
+__global__ __launch_bounds__(GS_BLOCK) void k_prop_range(const uint4 *__restrict__ splat, uint32_t n, int prop, const uint8_t *__restrict__ state, uint32_t rows,
+                                                         uint32_t mask, uint32_t value, double2 *__restrict__ part, uint32_t *__restrict__ cnt)
+{
+    __shared__ double s_mn[GS_BLOCK / 64], s_mx[GS_BLOCK / 64];
+    __shared__ uint32_t s_c[GS_BLOCK / 64];
+    double mn = INFINITY, mx = -INFINITY;
+    uint32_t c = 0;
+    for (uint32_t i = blockIdx.x * GS_BLOCK + threadIdx.x; i < n; i += gridDim.x * GS_BLOCK) {
+        if (!prop_passes(state, rows, i, mask, value)) continue;
+        const double v = prop_load<CC>(splat, i, prop);
+        c++;
+        if (v < mn) mn = v;                                          // (a NaN compares false twice)
+        if (v > mx) mx = v;
+    }
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) {
+        const double a = __shfl_xor(mn, m, 64), b = __shfl_xor(mx, m, 64);
+        if (a < mn) mn = a;
+        if (b > mx) mx = b;
+    }
+    c = wave_sum(c);
+    if ((threadIdx.x & 63) == 0) { s_mn[threadIdx.x >> 6] = mn; s_mx[threadIdx.x >> 6] = mx; s_c[threadIdx.x >> 6] = c; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (int w = 1; w < GS_BLOCK / 64; w++) { if (s_mn[w] < mn) mn = s_mn[w]; if (s_mx[w] > mx) mx = s_mx[w]; c += s_c[w]; }
+        part[blockIdx.x] = make_double2(mn, mx);
+        cnt[blockIdx.x] = c;
+    }
+}
+
+// The histogram: ONE table of nbins words in LDS per workgroup, cleared at the start and added to global memory at the end with one
+// atomic per non-empty bin, and equal bins of a wave COMBINED BEFORE they touch LDS.  Of the two ways to survive a pile-up (most alpha
+// bytes of a trained scene are 255: all 64 lanes of a wave want one word) this one was chosen because the pile-up is INSIDE a wave: the
+// 64 adds of one LDS instruction on one address are taken one after the other whichever table they go to, so a table per wave
+// changes nothing about them -- and four tables of 4096 words are the whole 64 KB of static LDS, with no room left for the tally.
+// Combining: up to GS_HIST_PEEL times, the first lane that still holds a bin names it, a vote finds every lane holding the same one, and
+// the first lane adds their number once.  A wave whose lanes agree is done after one round and one add; where the values are spread,
+// the rounds cost a few scalar instructions each and the lanes left over add 1 each, to words that are then mostly different.
+// out: nbins counts, then { passing, below, above, NaN }.
+#define GS_HIST_PEEL 4
+template <bool CC>
+__global__ __launch_bounds__(GS_BLOCK) void k_prop_hist(const uint4 *__restrict__ splat, uint32_t n, int prop, double lo, double hi, double scale, uint32_t nbins,
+                                                        const uint8_t *__restrict__ state, uint32_t rows, uint32_t mask, uint32_t value, uint32_t *__restrict__ out)
+{
+    __shared__ uint32_t s_h[GS_HIST_MAX_BINS];
+    __shared__ uint32_t s_t[4];
+    for (uint32_t b = threadIdx.x; b < nbins; b += GS_BLOCK) s_h[b] = 0;
+    if (threadIdx.x < 4) s_t[threadIdx.x] = 0;
+    __syncthreads();
+    const int lane = threadIdx.x & 63;
+    uint32_t passing = 0, below = 0, above = 0, nan = 0;
+    for (uint64_t base = (uint64_t)blockIdx.x * GS_BLOCK; base < n; base += (uint64_t)gridDim.x * GS_BLOCK) {
+        const uint64_t i64 = base + threadIdx.x;
+        const uint32_t i = (uint32_t)(i64 < n ? i64 : n);            // (i == n: no splat)
+        int32_t bin = -4;                                            // not a passing splat
+        if (i < n && prop_passes(state, rows, i, mask, value)) bin = gsm::hist_bin(prop_load<CC>(splat, i, prop), lo, hi, scale, nbins);
+        passing += bin != -4; below += bin == -1; above += bin == -2; nan += bin == -3;
+        unsigned long long todo = __ballot(bin >= 0);
+        for (int r = 0; r < GS_HIST_PEEL && todo; r++) {
+            const int first = __ffsll(todo) - 1;
+            const int32_t fb = __shfl(bin, first, 64);                // (>= 0: the lane was named by the vote)
+            const unsigned long long same = __ballot(bin == fb);
+            if (lane == first) atomicAdd(&s_h[fb], (uint32_t)__popcll(same));
+            if (bin == fb) bin = -4;
+            todo &= ~same;
+        }
+        if (bin >= 0) atomicAdd(&s_h[bin], 1u);
+    }
+    passing = wave_sum(passing); below = wave_sum(below); above = wave_sum(above); nan = wave_sum(nan);
+    if (lane == 0) {
+        if (passing) atomicAdd(&s_t[0], passing);
+        if (below) atomicAdd(&s_t[1], below);
+        if (above) atomicAdd(&s_t[2], above);
+        if (nan) atomicAdd(&s_t[3], nan);
+    }
+    __syncthreads();
+    for (uint32_t b = threadIdx.x; b < nbins; b += GS_BLOCK) { const uint32_t c = s_h[b]; if (c) atomicAdd(&out[b], c); }
+    if (threadIdx.x < 4 && s_t[threadIdx.x]) atomicAdd(&out[nbins + threadIdx.x], s_t[threadIdx.x]);
+}
+
 uint32_t stream_grid(size_t n)
 {
     const uint32_t g = gs_div_up(n ? n : 1, GS_BLOCK);
@@ -279,6 +396,73 @@ int gs_edit_select_sphere(gs_ctx *ctx, const float centre[3], float radius, uint
     hipLaunchKernelGGL(k_edit_select_sphere, dim3(stream_grid(ctx->n)), dim3(GS_BLOCK), 0, ctx->stream, (const uint4 *)ctx->splat, (uint32_t)ctx->n,
                        (double)centre[0], (double)centre[1], (double)centre[2], r2, ctx->edit_state, (uint32_t)set, (uint32_t)clear, invert ? 1u : 0u, ctx->edit_cnt);
     return read_counter(ctx, hit);
+}
+
+int gs_edit_select_range(gs_ctx *ctx, int prop, double lo, double hi, uint8_t set, uint8_t clear, bool invert, size_t *hit)
+{
+    int rc = counters(ctx);
+    if (rc != GS_OK) return rc;
+    gs_flag(gsm::prop_reads_cc(prop), [&](auto CC) {
+        hipLaunchKernelGGL((k_prop_select<decltype(CC)::value>), dim3(stream_grid(ctx->n)), dim3(GS_BLOCK), 0, ctx->stream, (const uint4 *)ctx->splat,
+                           (uint32_t)ctx->n, prop, lo, hi, ctx->edit_state, (uint32_t)set, (uint32_t)clear, invert ? 1u : 0u, ctx->edit_cnt);
+    });
+    return read_counter(ctx, hit);
+}
+
+// the reading passes' stream and device words (made once), the words cleared on that stream
+static int prop_begin(gs_ctx *ctx, size_t clear_bytes)
+{
+    GS_HIP(hipSetDevice(ctx->device));
+    if (!ctx->prop_stream) GS_HIP(hipStreamCreateWithFlags(&ctx->prop_stream, hipStreamNonBlocking));
+    if (!ctx->prop_buf) GS_HIP(hipMalloc(&ctx->prop_buf, GS_PROP_BUF_BYTES));
+    if (clear_bytes) GS_HIP(hipMemsetAsync(ctx->prop_buf, 0, clear_bytes, ctx->prop_stream));
+    return GS_OK;
+}
+// the state store as the filter sees it: no rows when the mask is 0 (every state passes or none does: nothing to load) or the store is empty
+static uint32_t prop_rows(const gs_ctx *ctx, uint8_t mask) { return (mask && ctx->edit_state) ? (uint32_t)ctx->edit_n : 0u; }
+
+int gs_prop_run_range(gs_ctx *ctx, int prop, uint8_t mask, uint8_t value, double *mn, double *mx, size_t *n)
+{
+    const uint32_t grid = stream_grid(ctx->n);                       // (grid x (16 + 4) bytes <= GS_PROP_BUF_BYTES)
+    static_assert(GS_EDIT_GRID * (sizeof(double2) + sizeof(uint32_t)) <= GS_PROP_BUF_BYTES, "the partials fit the buffer");
+    int rc = prop_begin(ctx, 0);
+    if (rc != GS_OK) return rc;
+    double2 *part = reinterpret_cast<double2 *>(ctx->prop_buf);
+    uint32_t *cnt = reinterpret_cast<uint32_t *>(part + GS_EDIT_GRID);
+    gs_flag(gsm::prop_reads_cc(prop), [&](auto CC) {
+        hipLaunchKernelGGL((k_prop_range<decltype(CC)::value>), dim3(grid), dim3(GS_BLOCK), 0, ctx->prop_stream, (const uint4 *)ctx->splat, (uint32_t)ctx->n, prop,
+                           (const uint8_t *)ctx->edit_state, prop_rows(ctx, mask), (uint32_t)mask, (uint32_t)value, part, cnt);
+    });
+    GS_HIP(hipGetLastError());
+    std::vector<double2> hp(grid);
+    std::vector<uint32_t> hc(grid);
+    GS_HIP(hipMemcpyAsync(hp.data(), part, grid * sizeof(double2), hipMemcpyDeviceToHost, ctx->prop_stream));
+    GS_HIP(hipMemcpyAsync(hc.data(), cnt, grid * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->prop_stream));
+    GS_HIP(hipStreamSynchronize(ctx->prop_stream));
+    double lo = INFINITY, hi = -INFINITY;
+    size_t c = 0;
+    for (uint32_t b = 0; b < grid; b++) { if (hp[b].x < lo) lo = hp[b].x; if (hp[b].y > hi) hi = hp[b].y; c += hc[b]; }
+    *mn = lo; *mx = hi; *n = c;
+    return GS_OK;
+}
+
+int gs_prop_run_histogram(gs_ctx *ctx, int prop, double lo, double hi, double scale, uint32_t nbins, uint8_t mask, uint8_t value, uint32_t *counts, uint64_t tally[4])
+{
+    static_assert((GS_HIST_MAX_BINS + 4) * sizeof(uint32_t) <= GS_PROP_BUF_BYTES, "the counts fit the buffer");
+    int rc = prop_begin(ctx, ((size_t)nbins + 4) * sizeof(uint32_t));
+    if (rc != GS_OK) return rc;
+    uint32_t *out = reinterpret_cast<uint32_t *>(ctx->prop_buf);
+    gs_flag(gsm::prop_reads_cc(prop), [&](auto CC) {
+        hipLaunchKernelGGL((k_prop_hist<decltype(CC)::value>), dim3(stream_grid(ctx->n)), dim3(GS_BLOCK), 0, ctx->prop_stream, (const uint4 *)ctx->splat,
+                           (uint32_t)ctx->n, prop, lo, hi, scale, nbins, (const uint8_t *)ctx->edit_state, prop_rows(ctx, mask), (uint32_t)mask, (uint32_t)value, out);
+    });
+    GS_HIP(hipGetLastError());
+    uint32_t t[4];
+    GS_HIP(hipMemcpyAsync(counts, out, (size_t)nbins * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->prop_stream));
+    GS_HIP(hipMemcpyAsync(t, out + nbins, sizeof t, hipMemcpyDeviceToHost, ctx->prop_stream));
+    GS_HIP(hipStreamSynchronize(ctx->prop_stream));
+    for (int k = 0; k < 4; k++) tally[k] = t[k];
+    return GS_OK;
 }
 
 int gs_edit_select_rect(gs_ctx *ctx, gs_ctx *L, const GsFrameUniforms &f, const int32_t rect[4], uint8_t set, uint8_t clear, bool invert, size_t *hit)
@@ -478,6 +662,53 @@ GS_API int gs_select_sphere(gs_ctx *ctx, const float centre[3], float radius, ui
     if (out_hit) *out_hit = 0;
     if (!ctx->n) return GS_OK;
     return edit_apply(ctx, ctx->n, [&] { return gs_edit_select_sphere(ctx, centre, radius, set_bits, clear_bits, (flags & GS_SELECT_INVERT) != 0, out_hit); });
+}
+
+// what the three property calls refuse alike
+static int prop_check(gs_ctx *ctx, int prop, const char *name)
+{
+    if (!gsm::prop_valid(prop)) FAIL(GS_E_BADARG, "%s: unknown property %d", name, prop);
+    if (!ctx->renderable && ctx->n) FAIL(GS_E_STATE, "context was fed worker matrices only (gs_push_matrices): it holds no packed records");
+    return GS_OK;
+}
+
+GS_API int gs_select_range(gs_ctx *ctx, int prop, double lo, double hi, uint8_t set_bits, uint8_t clear_bits, uint32_t flags, size_t *out_hit)
+{
+    CHECK_CTX(ctx);
+    if (lo != lo || hi != hi) FAIL(GS_E_BADARG, "gs_select_range: a bound is NaN");
+    if (flags & ~GS_SELECT_INVERT) FAIL(GS_E_BADARG, "gs_select_range: unknown flags %#x", flags);
+    TRY(prop_check(ctx, prop, "gs_select_range"));
+    if (out_hit) *out_hit = 0;
+    if (!ctx->n) return GS_OK;
+    return edit_apply(ctx, ctx->n, [&] { return gs_edit_select_range(ctx, prop, lo, hi, set_bits, clear_bits, (flags & GS_SELECT_INVERT) != 0, out_hit); });
+}
+
+GS_API int gs_prop_range(gs_ctx *ctx, int prop, uint8_t state_mask, uint8_t state_value, double *out_min, double *out_max, size_t *out_n)
+{
+    CHECK_CTX(ctx);
+    if (!out_min && !out_max && !out_n) FAIL(GS_E_BADARG, "gs_prop_range: no output");
+    TRY(prop_check(ctx, prop, "gs_prop_range"));
+    double mn = INFINITY, mx = -INFINITY;
+    size_t n = 0;
+    if (ctx->n) TRY(gs_prop_run_range(ctx, prop, state_mask, state_value, &mn, &mx, &n));
+    if (out_min) *out_min = mn;
+    if (out_max) *out_max = mx;
+    if (out_n) *out_n = n;
+    return GS_OK;
+}
+
+GS_API int gs_histogram(gs_ctx *ctx, int prop, double lo, double hi, uint32_t nbins, uint8_t state_mask, uint8_t state_value, uint32_t *counts, uint64_t tally[4])
+{
+    CHECK_CTX(ctx);
+    int32_t bin;
+    if (!counts) FAIL(GS_E_BADARG, "gs_histogram: counts is NULL");
+    if (gs_hist_bin(lo, lo, hi, nbins, &bin) != GS_OK) FAIL(GS_E_BADARG, "gs_histogram: lo < hi, both finite, and 1 .. %d bins expected", GS_HIST_MAX_BINS);
+    TRY(prop_check(ctx, prop, "gs_histogram"));
+    uint64_t t[4] = { 0, 0, 0, 0 };
+    memset(counts, 0, (size_t)nbins * sizeof(uint32_t));
+    if (ctx->n) TRY(gs_prop_run_histogram(ctx, prop, lo, hi, (double)nbins / (hi - lo), nbins, state_mask, state_value, counts, t));
+    if (tally) memcpy(tally, t, sizeof t);
+    return GS_OK;
 }
 
 GS_API int gs_select_rect(gs_ctx *ctx, const gs_render_params *p, const int32_t rect[4], uint8_t set_bits, uint8_t clear_bits, uint32_t flags, size_t *out_hit)

@@ -354,6 +354,21 @@ GS_API int gs_highlight_word(uint32_t rgba, uint32_t option_value, uint32_t *out
     return GS_OK;
 }
 
+GS_API int gs_prop_eval(const float cs[4], const uint32_t cc[4], int prop, double *out)
+{
+    if (!cs || !cc || !out || !gsm::prop_valid(prop)) return GS_E_BADARG;
+    *out = gsm::prop_value(cs, cc, prop);
+    return GS_OK;
+}
+
+GS_API int gs_hist_bin(double v, double lo, double hi, uint32_t nbins, int32_t *out_bin)
+{
+    if (!out_bin || !(lo < hi) || !(fabs(lo) <= 1.7976931348623157e308) || !(fabs(hi) <= 1.7976931348623157e308) || nbins < 1 || nbins > GS_HIST_MAX_BINS)
+        return GS_E_BADARG;
+    *out_bin = gsm::hist_bin(v, lo, hi, (double)nbins / (hi - lo), nbins);
+    return GS_OK;
+}
+
 // even-odd fill, pixel centres, f64; the crossing test's operations in the header's order (un-fused: -ffp-contract=off)
 GS_API int gs_mask_polygon(const float *xy, size_t npoints, int fb_width, int fb_height, uint8_t *mask_out, size_t stride)
 {

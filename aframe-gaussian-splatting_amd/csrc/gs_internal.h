@@ -219,6 +219,9 @@ struct gs_ctx {
     uint32_t hl_opt;               // GS_OPT_HIGHLIGHT (owner; taken per frame by gs_fill_uniforms)
     uint32_t hl_frame;             // lane: 1 if the lane's last frame was projected by an HL instantiation (gs_highlight_info; kept out of gs_stats)
     uint8_t *mask_buf; size_t mask_cap_bytes;   // owner: gs_select_mask's mask and depth plane on the device (grow-only scratch)
+    // owner: what gs_prop_range / gs_histogram run on -- a stream of their own (they read the resident arrays only and wait for no
+    // frame) and GS_PROP_BUF_BYTES of device memory for their counts and partials; both made by the first call
+    hipStream_t prop_stream; void *prop_buf;
 
     // sort scratch (sized by cap)
     float *depth;                  // stored f32 depth or +inf for culled
@@ -453,6 +456,13 @@ int gs_edit_select_rect(gs_ctx *ctx, gs_ctx *L, const GsFrameUniforms &u, const 
 // ... against a mask image in device memory (tight rows of u.W bytes, row 0 = top) and an optional plane of window depths (tight, may be null)
 int gs_edit_select_mask(gs_ctx *ctx, gs_ctx *L, const GsFrameUniforms &u, const uint8_t *mask_dev, const float *depth_dev, uint8_t set, uint8_t clear,
                         bool invert, size_t *hit);
+// ... by value: lo <= gsm::prop_value(record, prop) <= hi
+int gs_edit_select_range(gs_ctx *ctx, int prop, double lo, double hi, uint8_t set, uint8_t clear, bool invert, size_t *hit);
+// the two reading passes over the owner's records, on ctx->prop_stream (they wait for their own kernel only).  A splat takes part iff
+// (state & mask) == value, its state 0 beyond the store; counts: nbins words on the host, tally: { passing, below, above, NaN }
+#define GS_PROP_BUF_BYTES (64u << 10)
+int gs_prop_run_range(gs_ctx *ctx, int prop, uint8_t mask, uint8_t value, double *mn, double *mx, size_t *n);
+int gs_prop_run_histogram(gs_ctx *ctx, int prop, double lo, double hi, double scale, uint32_t nbins, uint8_t mask, uint8_t value, uint32_t *counts, uint64_t tally[4]);
 // stable compaction of the owner's resident arrays into `to` (allocated by the caller for ctx->cap splats; sh may be null); *kept = splats written
 struct GsCompactTo { uint4 *splat; float4 *sort_rows; float *bound_r; uint8_t *state; float *sh; uint32_t *old_index; };
 int gs_edit_compact(gs_ctx *ctx, const GsCompactTo &to, size_t *kept);

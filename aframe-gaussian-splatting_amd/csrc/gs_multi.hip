@@ -245,6 +245,26 @@ GS_API int gs_multi_select_sphere(gs_multi *m, const float centre[3], float radi
     return run_all(m, [=](gs_ctx *c, int i) { return gs_select_sphere(c, centre, radius, set_bits, clear_bits, flags, i == 0 ? out_hit : nullptr); });
 }
 
+GS_API int gs_multi_select_range(gs_multi *m, int prop, double lo, double hi, uint8_t set_bits, uint8_t clear_bits, uint32_t flags, size_t *out_hit)
+{
+    if (!m) return GS_E_BADARG;
+    m->have_sort = false;
+    return run_all(m, [=](gs_ctx *c, int i) { return gs_select_range(c, prop, lo, hi, set_bits, clear_bits, flags, i == 0 ? out_hit : nullptr); });
+}
+
+// (the reading calls: device 0 alone -- every device holds the same splats and states; behind whatever its feeder still has queued)
+GS_API int gs_multi_prop_range(gs_multi *m, int prop, uint8_t state_mask, uint8_t state_value, double *out_min, double *out_max, size_t *out_n)
+{
+    if (!m) return GS_E_BADARG;
+    return run_all(m, [=](gs_ctx *c, int i) { return i == 0 ? gs_prop_range(c, prop, state_mask, state_value, out_min, out_max, out_n) : GS_OK; });
+}
+
+GS_API int gs_multi_histogram(gs_multi *m, int prop, double lo, double hi, uint32_t nbins, uint8_t state_mask, uint8_t state_value, uint32_t *counts, uint64_t tally[4])
+{
+    if (!m) return GS_E_BADARG;
+    return run_all(m, [=](gs_ctx *c, int i) { return i == 0 ? gs_histogram(c, prop, lo, hi, nbins, state_mask, state_value, counts, tally) : GS_OK; });
+}
+
 GS_API int gs_multi_select_rect(gs_multi *m, const gs_render_params *p, const int32_t rect[4], uint8_t set_bits, uint8_t clear_bits, uint32_t flags, size_t *out_hit)
 {
     if (!m) return GS_E_BADARG;

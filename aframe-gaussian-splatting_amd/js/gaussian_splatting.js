@@ -30,7 +30,15 @@ const OPT_ANTIALIAS = 20;
 const OPT_HIGHLIGHT = 23;
 const ROW_LENGTH = 3 * 4 + 3 * 4 + 4 + 4;          // index.js:227
 
+const PROP_NAMES = ['x', 'y', 'z', 'red', 'green', 'blue', 'alpha', 'size2'];   // GS_PROP_*
+const PROP_FILTERS = { all: [0, 0], visible: [1, 0], selected: [3, 2] };        // (stateMask, stateValue); 1 = hidden, 2 = selected
+
 function elementsOf(m) { return m && m.elements ? m.elements : m; }
+function propId(name) {
+  const p = PROP_NAMES.indexOf(name);
+  if (p < 0) throw new RangeError('unknown property ' + name + ' (one of ' + PROP_NAMES.join(' ') + ')');
+  return p;
+}
 
 class GaussianSplatting {
   constructor(data, options) {
@@ -290,6 +298,28 @@ class GaussianSplatting {
     native.setOption(this.handle, OPT_HIGHLIGHT, ((c[0] & 255) | (c[1] & 255) << 8 | (c[2] & 255) << 16) + (w & 255) * 16777216);
   }
   highlightInfo() { return native.highlightInfo(this.handle); }
+  // The data panel: a histogram of one per-splat property -- 'x' 'y' 'z' (the rows' space, as pick().position), 'red' 'green' 'blue' 'alpha'
+  // (bytes) or 'size2' (the sum of the three squared axis lengths, object units^2) -- over opts.of = 'all' (default) | 'visible' |
+  // 'selected' (the visible selection), in opts.bins (default 256) bins over [opts.lo, opts.hi]; a bound left out is the property's own
+  // minimum / maximum among those splats (propRange first).  -> {counts: Uint32Array, lo, hi, passing, below, above, nan}; an empty or
+  // one-valued range is widened so that the call always has lo < hi.  Reads only: no tick, order or frame is disturbed.
+  histogram(prop, opts) {
+    const o = opts || {}, p = propId(prop), f = PROP_FILTERS[o.of || 'all'];
+    if (!f) throw new RangeError("histogram: of must be 'all', 'visible' or 'selected'");
+    let lo = o.lo, hi = o.hi;
+    if (lo === undefined || hi === undefined) {
+      const r = native.propRange(this.handle, p, f[0], f[1]);
+      if (lo === undefined) lo = Number.isFinite(r.min) ? r.min : 0;
+      if (hi === undefined) hi = Number.isFinite(r.max) ? r.max : lo;
+      if (!(lo < hi)) hi = lo + (Math.abs(lo) > 1 ? Math.abs(lo) : 1);
+    }
+    return Object.assign(native.histogram(this.handle, p, lo, hi, o.bins === undefined ? 256 : o.bins, f[0], f[1]), { lo, hi });
+  }
+  // select (opts.hide: hide) the splats whose property lies in [lo, hi] (opts.invert: the others) -> how many
+  selectRange(prop, lo, hi, opts) {
+    const o = opts || {};
+    return native.selectRange(this.handle, propId(prop), lo, hi, o.hide ? 1 : 2, 0, o.invert ? 1 : 0);
+  }
   // real deletion of the hidden splats (the GPU holds the cloud twice for the duration of the call) -> Uint32Array: the old index of
   // every splat that stays
   deleteHidden() {

@@ -589,6 +589,75 @@ static napi_value fn_select_sphere(napi_env env, napi_callback_info info)
     return make_count(env, hit);
 }
 
+/* ---- properties of the resident records (gs_splat.h: GS_PROP_*; prop 0..7 = x y z red green blue alpha size2).  A splat takes part in
+ * the two reading calls iff (state & stateMask) == stateValue. */
+/* propRange(h, prop, stateMask, stateValue) -> { min, max, count } */
+static napi_value fn_prop_range(napi_env env, napi_callback_info info)
+{
+    napi_value argv[4];
+    if (!get_args(env, info, 4, argv, NULL)) return NULL;
+    gs_ctx *ctx = get_ctx(env, argv[0]); if (!ctx) return NULL;
+    int32_t prop = 0; uint32_t mask = 0, value = 0;
+    if (napi_get_value_int32(env, argv[1], &prop) != napi_ok || !get_u32(env, argv[2], &mask) || !get_u32(env, argv[3], &value)) {
+        napi_throw_type_error(env, NULL, "propRange: (handle, prop, stateMask, stateValue)");
+        return NULL;
+    }
+    double mn = 0, mx = 0; size_t n = 0;
+    int rc = gs_prop_range(ctx, prop, (uint8_t)mask, (uint8_t)value, &mn, &mx, &n);
+    if (rc != GS_OK) return throw_gs(env, ctx, rc);
+    napi_value o, v;
+    NAPI_OK(napi_create_object(env, &o));
+    NAPI_OK(napi_create_double(env, mn, &v)); NAPI_OK(napi_set_named_property(env, o, "min", v));
+    NAPI_OK(napi_create_double(env, mx, &v)); NAPI_OK(napi_set_named_property(env, o, "max", v));
+    NAPI_OK(napi_create_double(env, (double)n, &v)); NAPI_OK(napi_set_named_property(env, o, "count", v));
+    return o;
+}
+
+/* histogram(h, prop, lo, hi, bins, stateMask, stateValue) -> { counts: Uint32Array(bins), passing, below, above, nan } */
+static napi_value fn_histogram(napi_env env, napi_callback_info info)
+{
+    napi_value argv[7];
+    if (!get_args(env, info, 7, argv, NULL)) return NULL;
+    gs_ctx *ctx = get_ctx(env, argv[0]); if (!ctx) return NULL;
+    int32_t prop = 0; uint32_t bins = 0, mask = 0, value = 0; double lo = 0, hi = 0;
+    if (napi_get_value_int32(env, argv[1], &prop) != napi_ok || napi_get_value_double(env, argv[2], &lo) != napi_ok ||
+        napi_get_value_double(env, argv[3], &hi) != napi_ok || napi_get_value_uint32(env, argv[4], &bins) != napi_ok || !get_u32(env, argv[5], &mask) ||
+        !get_u32(env, argv[6], &value)) {
+        napi_throw_type_error(env, NULL, "histogram: (handle, prop, lo, hi, bins, stateMask, stateValue)");
+        return NULL;
+    }
+    if (bins < 1 || bins > GS_HIST_MAX_BINS) { napi_throw_range_error(env, NULL, "histogram: 1 .. 4096 bins"); return NULL; }
+    napi_value ab, ta, o, v; void *data = NULL;
+    NAPI_OK(napi_create_arraybuffer(env, (size_t)bins * 4, &data, &ab));
+    uint64_t tally[4] = { 0, 0, 0, 0 };
+    int rc = gs_histogram(ctx, prop, lo, hi, bins, (uint8_t)mask, (uint8_t)value, (uint32_t *)data, tally);
+    if (rc != GS_OK) return throw_gs(env, ctx, rc);
+    NAPI_OK(napi_create_typedarray(env, napi_uint32_array, bins, ab, 0, &ta));
+    NAPI_OK(napi_create_object(env, &o));
+    NAPI_OK(napi_set_named_property(env, o, "counts", ta));
+    static const char *const names[4] = { "passing", "below", "above", "nan" };
+    for (int k = 0; k < 4; k++) { NAPI_OK(napi_create_double(env, (double)tally[k], &v)); NAPI_OK(napi_set_named_property(env, o, names[k], v)); }
+    return o;
+}
+
+/* selectRange(h, prop, lo, hi, setBits, clearBits, flags) -> splats hit */
+static napi_value fn_select_range(napi_env env, napi_callback_info info)
+{
+    napi_value argv[7];
+    if (!get_args(env, info, 7, argv, NULL)) return NULL;
+    gs_ctx *ctx = get_ctx(env, argv[0]); if (!ctx) return NULL;
+    int32_t prop = 0; uint32_t set = 0, clear = 0, flags = 0; double lo = 0, hi = 0;
+    if (napi_get_value_int32(env, argv[1], &prop) != napi_ok || napi_get_value_double(env, argv[2], &lo) != napi_ok ||
+        napi_get_value_double(env, argv[3], &hi) != napi_ok || !get_u32(env, argv[4], &set) || !get_u32(env, argv[5], &clear) || !get_u32(env, argv[6], &flags)) {
+        napi_throw_type_error(env, NULL, "selectRange: (handle, prop, lo, hi, setBits, clearBits, flags)");
+        return NULL;
+    }
+    size_t hit = 0;
+    int rc = gs_select_range(ctx, prop, lo, hi, (uint8_t)set, (uint8_t)clear, flags, &hit);
+    if (rc != GS_OK) return throw_gs(env, ctx, rc);
+    return make_count(env, hit);
+}
+
 /* selectRect(h, params, [x0, y0, x1, y1], setBits, clearBits, flags) -> positions of the order hit */
 static napi_value fn_select_rect(napi_env env, napi_callback_info info)
 {
@@ -1342,6 +1411,7 @@ static napi_value init(napi_env env, napi_value exports)
         { "scaledSize", fn_scaled_size },
         { "setState", fn_set_state }, { "setStateIds", fn_set_state_ids }, { "selectBox", fn_select_box }, { "selectSphere", fn_select_sphere },
         { "selectRect", fn_select_rect }, { "compact", fn_compact },
+        { "propRange", fn_prop_range }, { "histogram", fn_histogram }, { "selectRange", fn_select_range },
         { "selectMask", fn_select_mask }, { "maskPolygon", fn_mask_polygon }, { "highlightInfo", fn_highlight_info },
         { "createMulti", fn_create_multi }, { "multiDestroy", fn_multi_destroy }, { "multiPushSplat", fn_multi_push_splat },
         { "multiLoadPly", fn_multi_load_ply }, { "multiClear", fn_multi_clear }, { "multiCount", fn_multi_count },

@@ -718,6 +718,54 @@ GS_API int gs_sort_inspect(gs_ctx *ctx, gs_sort_info *info, uint32_t *out_idx, s
 #define GS_BUF_STATE 9        /* rows u8     the state store (gs_state_count: rows)                                                      */
 GS_API int gs_download(gs_ctx *ctx, int which, void *out, size_t nbytes);
 
+/* ---- per-splat properties: histograms and selection by value over the resident cloud (no reference counterpart; part of "editing
+ * the resident cloud" above) -----------------------------------------------------------------------------------------------------
+ * A property is a function of a splat's packed record (cs[4], cc[4], as GS_BUF_CENTER_SCALE and GS_BUF_COV_COLOR return them) to an
+ * f64; every operation is f64 and un-fused, and the kernels and gs_prop_eval call ONE function:
+ *   GS_PROP_X, _Y, _Z    (double)cs[0], (double)cs[1], -(double)cs[2]: the rows' object space, as gs_select_sphere reads it
+ *   GS_PROP_RED ... _ALPHA   bytes 0..3 of cc[3] as a double, 0..255
+ *   GS_PROP_SIZE2        the trace of the dequantised covariance in object units^2 -- the sum of the three squared axis lengths, the same
+ *                        under every rotation: ((double)q11 + (double)q22 + (double)q33) * (double)cs[3] with q11 = (int16)(cc[0] & 0xFFFF),
+ *                        q22 = (int16)(cc[1] >> 16), q33 = (int16)(cc[2] >> 16).  No square root anywhere: a caller who thinks in radii
+ *                        squares the bounds.
+ * Any other id: GS_E_BADARG.
+ * A splat PASSES THE FILTER (state_mask, state_value) iff (state & state_mask) == state_value, where a splat beyond the store's length
+ * has state 0: (0, 0) is every splat, (GS_STATE_HIDDEN, 0) what is drawn, (3, GS_STATE_SELECTED) the visible selection.
+ * gs_prop_range and gs_histogram only read: one streaming kernel each on a stream of their own, no drain, no order dropped, no option
+ * or statistic changed -- a frame drawn after one is the frame drawn without it.  gs_select_range is a region call like gs_select_sphere
+ * (it drains, drops the lanes' orders and counts the hidden splats again).  All three: a context fed with gs_push_matrices only is
+ * GS_E_STATE; with nothing resident the counts are zero, the range is empty, the hit count is 0 and the result is GS_OK. */
+#define GS_PROP_X 0
+#define GS_PROP_Y 1
+#define GS_PROP_Z 2
+#define GS_PROP_RED 3
+#define GS_PROP_GREEN 4
+#define GS_PROP_BLUE 5
+#define GS_PROP_ALPHA 6
+#define GS_PROP_SIZE2 7
+#define GS_HIST_MAX_BINS 4096
+/* one record's property on the host, by the kernels' own function (no context, no GPU).  NULL pointers, an unknown prop: GS_E_BADARG. */
+GS_API int gs_prop_eval(const float cs[4], const uint32_t cc[4], int prop, double *out);
+/* The binning rule (no context, no GPU): scale = (double)nbins / (hi - lo); *out_bin = min((int64)floor((v - lo) * scale), nbins - 1),
+ * so v == hi lands in the last bin; -1 for v < lo, -2 for v > hi, -3 for a NaN v.  Valid: lo < hi, both finite, 1 <= nbins <=
+ * GS_HIST_MAX_BINS; anything else, or out_bin NULL: GS_E_BADARG.  The kernel is handed lo, hi and this scale and evaluates exactly this. */
+GS_API int gs_hist_bin(double v, double lo, double hi, uint32_t nbins, int32_t *out_bin);
+/* minimum and maximum of the non-NaN values among the splats that pass (+-inf take part; none: *out_min = +inf, *out_max = -inf) and
+ * *out_n = the splats that pass, NaN ones included.  Each output is optional, but not all three: GS_E_BADARG. */
+GS_API int gs_prop_range(gs_ctx *ctx, int prop, uint8_t state_mask, uint8_t state_value, double *out_min, double *out_max, size_t *out_n);
+/* counts[b] (nbins words, required) = the passing splats whose gs_hist_bin(v, lo, hi, nbins) is b; tally (optional) = { passing, below lo,
+ * above hi, NaN }: sum(counts) + below + above + NaN == passing.  Arguments as gs_hist_bin. */
+GS_API int gs_histogram(gs_ctx *ctx, int prop, double lo, double hi, uint32_t nbins, uint8_t state_mask, uint8_t state_value, uint32_t *counts,
+                        uint64_t tally[4]);
+/* state = (state & ~clear_bits) | set_bits for every splat with lo <= v && v <= hi (a NaN v is outside); GS_SELECT_INVERT and *out_hit as
+ * in gs_select_sphere.  lo == hi is allowed, lo > hi selects nothing (with INVERT: everything); a NaN bound: GS_E_BADARG. */
+GS_API int gs_select_range(gs_ctx *ctx, int prop, double lo, double hi, uint8_t set_bits, uint8_t clear_bits, uint32_t flags, size_t *out_hit);
+/* gs_select_range on every device (the hit count of devices[0]); the two reading calls on devices[0] only: every device holds the same splats */
+GS_API int gs_multi_select_range(gs_multi *m, int prop, double lo, double hi, uint8_t set_bits, uint8_t clear_bits, uint32_t flags, size_t *out_hit);
+GS_API int gs_multi_prop_range(gs_multi *m, int prop, uint8_t state_mask, uint8_t state_value, double *out_min, double *out_max, size_t *out_n);
+GS_API int gs_multi_histogram(gs_multi *m, int prop, double lo, double hi, uint32_t nbins, uint8_t state_mask, uint8_t state_value, uint32_t *counts,
+                              uint64_t tally[4]);
+
 #ifdef __cplusplus
 }
 #endif
