@@ -36,9 +36,11 @@ COMM_ID_BYTES = 128
 BUF_CENTER_SCALE, BUF_COV_COLOR, BUF_SORT_ROWS, BUF_SORTED, BUF_PROJECTED, BUF_TILE_COUNT, BUF_TILE_STATS, BUF_UNSAT_MASK = 0, 1, 2, 3, 4, 5, 6, 7
 BUF_SH = 8
 BUF_STATE = 9
+BUF_CONTRIB = 10
 STATE_HIDDEN, STATE_SELECTED = 1, 2
 SELECT_INVERT = 1
 PROP_X, PROP_Y, PROP_Z, PROP_RED, PROP_GREEN, PROP_BLUE, PROP_ALPHA, PROP_SIZE2 = range(8)
+PROP_SEEN = 16                     # the contribution store in pixels (render_contrib); no function of the record: prop_eval refuses it
 HIST_MAX_BINS = 4096
 
 EXPORTS = [
@@ -61,6 +63,7 @@ EXPORTS = [
     "gs_select_mask", "gs_multi_select_mask", "gs_mask_polygon", "gs_highlight_info", "gs_highlight_word",
     "gs_prop_eval", "gs_hist_bin", "gs_prop_range", "gs_histogram", "gs_select_range",
     "gs_multi_prop_range", "gs_multi_histogram", "gs_multi_select_range",
+    "gs_render_contrib", "gs_render_contrib_device", "gs_contrib_clear", "gs_contrib_info",
 ]
 SURFACE_NONE = 0xFFFFFFFF          # gs_surface.id / gs_hit.id where the transmittance never falls below one half
 
@@ -247,6 +250,11 @@ def load(build_if_missing=True):
             getattr(L, pre + "prop_range").argtypes = [vp, i32, u8, u8, C.POINTER(f64), C.POINTER(f64), szp]
             getattr(L, pre + "histogram").argtypes = [vp, i32, f64, f64, C.c_uint32, u8, u8, vp, vp]
             getattr(L, pre + "select_range").argtypes = [vp, i32, f64, f64, u8, u8, C.c_uint32, szp]
+    if hasattr(L, "gs_render_contrib"):                        # (an older build loaded through GS_SPLAT_LIB for an A/B run has none)
+        L.gs_render_contrib.argtypes = [vp, C.POINTER(RenderParams), vp, sz]
+        L.gs_render_contrib_device.argtypes = [vp, C.POINTER(RenderParams), vp]
+        L.gs_contrib_clear.argtypes = [vp]
+        L.gs_contrib_info.argtypes = [vp, C.POINTER(sz), C.POINTER(C.c_uint64)]
     L.gs_download.argtypes = [vp, i32, vp, sz]
     if hasattr(L, "gs_sort_inspect"):
         L.gs_sort_inspect.argtypes = [vp, C.POINTER(SortInfo), vp, sz]
@@ -770,6 +778,34 @@ class Context:
     def render_surface_device(self, params, device_rgba=None, id_ptr=None, depth_ptr=None, alpha_ptr=None):
         s = Surface(id_ptr or None, depth_ptr or None, alpha_ptr or None)
         self._ck(self._L.gs_render_surface_device(self._h, C.byref(params), C.c_void_p(device_rgba) if device_rgba else None, C.byref(s)))
+
+    # per-splat contribution: the blend weights a splat's fragments had in the frames drawn by render_contrib
+    def render_contrib(self, params, want_rgba=True):
+        """gs_render_contrib -> rgba | None: the frame gs_render draws on the tile lists; every applied fragment adds its weight
+        alpha * exp(-q) * T, as 16.16 fixed point, to its splat's word of the contribution store (download_contrib, PROP_SEEN)"""
+        h, sw = max(params.fb_height, 0), max(params.x1 - params.x0, 0)
+        out = np.zeros((h, sw, 4), np.uint8) if want_rgba else None
+        self._ck(self._L.gs_render_contrib(self._h, C.byref(params), _p(out) if want_rgba and out.size else None, 0))
+        return out
+
+    def render_contrib_device(self, params, device_rgba=None):
+        self._ck(self._L.gs_render_contrib_device(self._h, C.byref(params), C.c_void_p(device_rgba) if device_rgba else None))
+
+    def contrib_clear(self):
+        self._ck(self._L.gs_contrib_clear(self._h))
+
+    def contrib_info(self):
+        """(rows in the contribution store, contribution frames that drew since it was last emptied)"""
+        rows, frames = C.c_size_t(0), C.c_uint64(0)
+        self._ck(self._L.gs_contrib_info(self._h, C.byref(rows), C.byref(frames)))
+        return rows.value, frames.value
+
+    def download_contrib(self):
+        """the contribution store: uint64[rows], each the sum of its splat's weights * 65536"""
+        rows = self.contrib_info()[0]
+        if not rows:
+            return np.zeros(0, np.uint64)
+        return self.download(BUF_CONTRIB, rows, np.uint64, 1).reshape(-1)
 
     def pick(self, params, points):
         """gs_pick: points = (n, 2) int (column, row; row 0 = top) -> structured array (id, depth, alpha, pos[3]) of what the full

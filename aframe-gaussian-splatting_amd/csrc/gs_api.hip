@@ -72,7 +72,7 @@ GS_API int gs_destroy(gs_ctx *ctx)
     dev_free(ctx->splat); dev_free(ctx->sort_rows); dev_free(ctx->bound_r); dev_free(ctx->pow10tab); dev_free(ctx->sh);
     dev_free(ctx->edit_state); dev_free(ctx->edit_cnt); dev_free(ctx->mask_buf);
     dev_free(ctx->scene_depth); dev_free(ctx->scene_rgba);
-    dev_free(ctx->prop_buf);
+    dev_free(ctx->prop_buf); dev_free(ctx->contrib);
     if (ctx->prop_stream) (void)hipStreamDestroy(ctx->prop_stream);
     if (ctx->ev_sort) (void)hipEventDestroy(ctx->ev_sort);
     delete ctx;
@@ -86,6 +86,7 @@ GS_API int gs_clear(gs_ctx *ctx)
     TRY(drain_all(ctx));
     if (ctx->edit_state && ctx->edit_n) GS_HIP(hipMemset(ctx->edit_state, 0, ctx->edit_n));   // (the allocation stays, all zero: a store grows zero-filled)
     ctx->edit_n = 0; ctx->edit_hidden = 0;
+    TRY(gs_contrib_clear(ctx));                                  // (the contribution store empties with the cloud)
     ctx->n = 0; ctx->sh_n = 0; ctx->sh_deg = 0; ctx->renderable = true;
     reset_cloud_measurements(ctx);
     for (int i = 0; i < GS_MAX_LANES; i++) {
@@ -470,6 +471,11 @@ GS_API int gs_download(gs_ctx *ctx, int which, void *out, size_t nbytes)
     if (which == GS_BUF_STATE) {
         if (nbytes > ctx->edit_n) FAIL(GS_E_BADARG, "buffer %d holds %zu bytes, %zu requested", which, ctx->edit_n, nbytes);
         if (nbytes) GS_HIP(hipMemcpy(out, ctx->edit_state, nbytes, hipMemcpyDeviceToHost));
+        return GS_OK;
+    }
+    if (which == GS_BUF_CONTRIB) {
+        if (nbytes > ctx->contrib_n * 8 || nbytes % 8) FAIL(GS_E_BADARG, "buffer %d holds %zu bytes, %zu requested", which, ctx->contrib_n * 8, nbytes);
+        if (nbytes) GS_HIP(hipMemcpy(out, ctx->contrib, nbytes, hipMemcpyDeviceToHost));
         return GS_OK;
     }
     if (which == GS_BUF_SH) {                                    // tight rows out of the padded store

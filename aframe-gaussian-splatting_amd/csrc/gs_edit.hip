@@ -217,6 +217,16 @@ __global__ __launch_bounds__(GS_BLOCK) void k_compact_sh(const uint4 *__restrict
     }
 }
 
+// ... and their words of the contribution store, by the same rule
+__global__ __launch_bounds__(GS_BLOCK) void k_compact_contrib(const unsigned long long *__restrict__ store, const uint32_t *__restrict__ old, uint32_t kept, uint32_t rows,
+                                                              unsigned long long *__restrict__ o_store)
+{
+    for (uint32_t k = blockIdx.x * GS_BLOCK + threadIdx.x; k < kept; k += gridDim.x * GS_BLOCK) {
+        const uint32_t i = old[k];
+        if (i < rows) o_store[k] = store[i];
+    }
+}
+
 // ---- per-splat properties (gs_splat.h: gs_prop_range / gs_histogram / gs_select_range).  One streaming pass each, grid-strided in whole
 // workgroup steps (every lane of a wave stays in the loop until the workgroup leaves it: the wave-wide votes below see all 64 lanes).
 // CC: the property reads the second half of the record (colour bytes, SIZE2); the position properties cost one 16-byte load per splat.
@@ -229,6 +239,16 @@ template <bool CC> __device__ __forceinline__ double prop_load(const uint4 *__re
     const uint32_t cc[4] = { cc4.x, cc4.y, cc4.z, cc4.w };
     return gsm::prop_value(cs, cc, prop);
 }
+// GS_PROP_SEEN is no function of the record: the splat's word of the contribution store (gs_frame.hip) in pixels, 0 beyond the store's
+// length -- exact below 2^53.  SEEN instantiations of the three kernels below take the store and its length and load nothing else; the
+// <false> and <true> kernels are what they were.  (No new ordering: the store is written by synchronous contribution frames only, which
+// have returned before a property call is made -- on prop_stream or the owner's.)
+typedef const unsigned long long *__restrict__ SeenStore;
+template <bool CC, bool SEEN> __device__ __forceinline__ double prop_load_any(const uint4 *__restrict__ splat, uint32_t i, int prop, SeenStore seen, uint32_t seen_n)
+{
+    if (SEEN) return i < seen_n ? (double)seen[i] / 65536.0 : 0.0;
+    return prop_load<CC>(splat, i, prop);
+}
 // the filter: rows = 0 when the mask is 0 or the store is empty (no byte is loaded then: a store that was never allocated is never read)
 __device__ __forceinline__ bool prop_passes(const uint8_t *__restrict__ state, uint32_t rows, uint32_t i, uint32_t mask, uint32_t value)
 {
@@ -236,24 +256,35 @@ __device__ __forceinline__ bool prop_passes(const uint8_t *__restrict__ state, u
     return (st & mask) == value;
 }
 
-template <bool CC>
-__global__ __launch_bounds__(GS_BLOCK) void k_prop_select(const uint4 *__restrict__ splat, uint32_t n, int prop, double lo, double hi, uint8_t *__restrict__ state,
-                                                          uint32_t set, uint32_t clear, uint32_t invert, uint32_t *__restrict__ hit)
+template <bool CC, bool SEEN>
+__device__ __forceinline__ void prop_select_body(const uint4 *__restrict__ splat, uint32_t n, int prop, double lo, double hi, uint8_t *__restrict__ state,
+                                                 uint32_t set, uint32_t clear, uint32_t invert, uint32_t *__restrict__ hit, SeenStore seen, uint32_t seen_n)
 {
     uint32_t c = 0;
     for (uint32_t i = blockIdx.x * GS_BLOCK + threadIdx.x; i < n; i += gridDim.x * GS_BLOCK) {
-        const double v = prop_load<CC>(splat, i, prop);
+        const double v = prop_load_any<CC, SEEN>(splat, i, prop, seen, seen_n);
         const bool inside = lo <= v && v <= hi;                      // (NaN: outside)
         if (inside != (invert != 0u)) { state[i] = (uint8_t)((state[i] & ~clear) | set); c++; }
     }
     block_count(c, hit);
 }
+template <bool CC>
+__global__ __launch_bounds__(GS_BLOCK) void k_prop_select(const uint4 *__restrict__ splat, uint32_t n, int prop, double lo, double hi, uint8_t *__restrict__ state,
+                                                          uint32_t set, uint32_t clear, uint32_t invert, uint32_t *__restrict__ hit)
+{
+    prop_select_body<CC, false>(splat, n, prop, lo, hi, state, set, clear, invert, hit, nullptr, 0u);
+}
+__global__ __launch_bounds__(GS_BLOCK) void k_prop_select_seen(SeenStore seen, uint32_t seen_n, uint32_t n, double lo, double hi, uint8_t *__restrict__ state,
+                                                               uint32_t set, uint32_t clear, uint32_t invert, uint32_t *__restrict__ hit)
+{
+    prop_select_body<false, true>(nullptr, n, GS_PROP_SEEN, lo, hi, state, set, clear, invert, hit, seen, seen_n);
+}
 
 // Per-workgroup partials, reduced on the host (as the depth pass' range: no f64 atomics on one address): part[blockIdx.x] = { min, max }
 // of the non-NaN values of the workgroup's passing splats (+inf, -inf where it saw none), cnt[blockIdx.x] = its passing splats.
-template <bool CC>
-__global__ __launch_bounds__(GS_BLOCK) void k_prop_range(const uint4 *__restrict__ splat, uint32_t n, int prop, const uint8_t *__restrict__ state, uint32_t rows,
-                                                         uint32_t mask, uint32_t value, double2 *__restrict__ part, uint32_t *__restrict__ cnt)
+template <bool CC, bool SEEN>
+__device__ __forceinline__ void prop_range_body(const uint4 *__restrict__ splat, uint32_t n, int prop, const uint8_t *__restrict__ state, uint32_t rows,
+                                                uint32_t mask, uint32_t value, double2 *__restrict__ part, uint32_t *__restrict__ cnt, SeenStore seen, uint32_t seen_n)
 {
     __shared__ double s_mn[GS_BLOCK / 64], s_mx[GS_BLOCK / 64];
     __shared__ uint32_t s_c[GS_BLOCK / 64];
@@ -261,7 +292,7 @@ __global__ __launch_bounds__(GS_BLOCK) void k_prop_range(const uint4 *__restrict
     uint32_t c = 0;
     for (uint32_t i = blockIdx.x * GS_BLOCK + threadIdx.x; i < n; i += gridDim.x * GS_BLOCK) {
         if (!prop_passes(state, rows, i, mask, value)) continue;
-        const double v = prop_load<CC>(splat, i, prop);
+        const double v = prop_load_any<CC, SEEN>(splat, i, prop, seen, seen_n);
         c++;
         if (v < mn) mn = v;                                          // (a NaN compares false twice)
         if (v > mx) mx = v;
@@ -281,6 +312,17 @@ __global__ __launch_bounds__(GS_BLOCK) void k_prop_range(const uint4 *__restrict
         cnt[blockIdx.x] = c;
     }
 }
+template <bool CC>
+__global__ __launch_bounds__(GS_BLOCK) void k_prop_range(const uint4 *__restrict__ splat, uint32_t n, int prop, const uint8_t *__restrict__ state, uint32_t rows,
+                                                         uint32_t mask, uint32_t value, double2 *__restrict__ part, uint32_t *__restrict__ cnt)
+{
+    prop_range_body<CC, false>(splat, n, prop, state, rows, mask, value, part, cnt, nullptr, 0u);
+}
+__global__ __launch_bounds__(GS_BLOCK) void k_prop_range_seen(SeenStore seen, uint32_t seen_n, uint32_t n, const uint8_t *__restrict__ state, uint32_t rows,
+                                                              uint32_t mask, uint32_t value, double2 *__restrict__ part, uint32_t *__restrict__ cnt)
+{
+    prop_range_body<false, true>(nullptr, n, GS_PROP_SEEN, state, rows, mask, value, part, cnt, seen, seen_n);
+}
 
 // The histogram: ONE table of nbins words in LDS per workgroup, cleared at the start and added to global memory at the end with one
 // atomic per non-empty bin, and equal bins of a wave COMBINED BEFORE they touch LDS.  Of the two ways to survive a pile-up (most alpha
@@ -292,9 +334,10 @@ __global__ __launch_bounds__(GS_BLOCK) void k_prop_range(const uint4 *__restrict
 // the rounds cost a few scalar instructions each and the lanes left over add 1 each, to words that are then mostly different.
 // out: nbins counts, then { passing, below, above, NaN }.
 #define GS_HIST_PEEL 4
-template <bool CC>
-__global__ __launch_bounds__(GS_BLOCK) void k_prop_hist(const uint4 *__restrict__ splat, uint32_t n, int prop, double lo, double hi, double scale, uint32_t nbins,
-                                                        const uint8_t *__restrict__ state, uint32_t rows, uint32_t mask, uint32_t value, uint32_t *__restrict__ out)
+template <bool CC, bool SEEN>
+__device__ __forceinline__ void prop_hist_body(const uint4 *__restrict__ splat, uint32_t n, int prop, double lo, double hi, double scale, uint32_t nbins,
+                                               const uint8_t *__restrict__ state, uint32_t rows, uint32_t mask, uint32_t value, uint32_t *__restrict__ out,
+                                               SeenStore seen, uint32_t seen_n)
 {
     __shared__ uint32_t s_h[GS_HIST_MAX_BINS];
     __shared__ uint32_t s_t[4];
@@ -307,7 +350,7 @@ __global__ __launch_bounds__(GS_BLOCK) void k_prop_hist(const uint4 *__restrict_
         const uint64_t i64 = base + threadIdx.x;
         const uint32_t i = (uint32_t)(i64 < n ? i64 : n);            // (i == n: no splat)
         int32_t bin = -4;                                            // not a passing splat
-        if (i < n && prop_passes(state, rows, i, mask, value)) bin = gsm::hist_bin(prop_load<CC>(splat, i, prop), lo, hi, scale, nbins);
+        if (i < n && prop_passes(state, rows, i, mask, value)) bin = gsm::hist_bin(prop_load_any<CC, SEEN>(splat, i, prop, seen, seen_n), lo, hi, scale, nbins);
         passing += bin != -4; below += bin == -1; above += bin == -2; nan += bin == -3;
         unsigned long long todo = __ballot(bin >= 0);
         for (int r = 0; r < GS_HIST_PEEL && todo; r++) {
@@ -330,6 +373,17 @@ __global__ __launch_bounds__(GS_BLOCK) void k_prop_hist(const uint4 *__restrict_
     __syncthreads();
     for (uint32_t b = threadIdx.x; b < nbins; b += GS_BLOCK) { const uint32_t c = s_h[b]; if (c) atomicAdd(&out[b], c); }
     if (threadIdx.x < 4 && s_t[threadIdx.x]) atomicAdd(&out[nbins + threadIdx.x], s_t[threadIdx.x]);
+}
+template <bool CC>
+__global__ __launch_bounds__(GS_BLOCK) void k_prop_hist(const uint4 *__restrict__ splat, uint32_t n, int prop, double lo, double hi, double scale, uint32_t nbins,
+                                                        const uint8_t *__restrict__ state, uint32_t rows, uint32_t mask, uint32_t value, uint32_t *__restrict__ out)
+{
+    prop_hist_body<CC, false>(splat, n, prop, lo, hi, scale, nbins, state, rows, mask, value, out, nullptr, 0u);
+}
+__global__ __launch_bounds__(GS_BLOCK) void k_prop_hist_seen(SeenStore seen, uint32_t seen_n, uint32_t n, double lo, double hi, double scale, uint32_t nbins,
+                                                             const uint8_t *__restrict__ state, uint32_t rows, uint32_t mask, uint32_t value, uint32_t *__restrict__ out)
+{
+    prop_hist_body<false, true>(nullptr, n, GS_PROP_SEEN, lo, hi, scale, nbins, state, rows, mask, value, out, seen, seen_n);
 }
 
 uint32_t stream_grid(size_t n)
@@ -402,7 +456,10 @@ int gs_edit_select_range(gs_ctx *ctx, int prop, double lo, double hi, uint8_t se
 {
     int rc = counters(ctx);
     if (rc != GS_OK) return rc;
-    gs_flag(gsm::prop_reads_cc(prop), [&](auto CC) {
+    if (prop == GS_PROP_SEEN)
+        hipLaunchKernelGGL(k_prop_select_seen, dim3(stream_grid(ctx->n)), dim3(GS_BLOCK), 0, ctx->stream, (const unsigned long long *)ctx->contrib, (uint32_t)ctx->contrib_n,
+                           (uint32_t)ctx->n, lo, hi, ctx->edit_state, (uint32_t)set, (uint32_t)clear, invert ? 1u : 0u, ctx->edit_cnt);
+    else gs_flag(gsm::prop_reads_cc(prop), [&](auto CC) {
         hipLaunchKernelGGL((k_prop_select<decltype(CC)::value>), dim3(stream_grid(ctx->n)), dim3(GS_BLOCK), 0, ctx->stream, (const uint4 *)ctx->splat,
                            (uint32_t)ctx->n, prop, lo, hi, ctx->edit_state, (uint32_t)set, (uint32_t)clear, invert ? 1u : 0u, ctx->edit_cnt);
     });
@@ -429,7 +486,10 @@ int gs_prop_run_range(gs_ctx *ctx, int prop, uint8_t mask, uint8_t value, double
     if (rc != GS_OK) return rc;
     double2 *part = reinterpret_cast<double2 *>(ctx->prop_buf);
     uint32_t *cnt = reinterpret_cast<uint32_t *>(part + GS_EDIT_GRID);
-    gs_flag(gsm::prop_reads_cc(prop), [&](auto CC) {
+    if (prop == GS_PROP_SEEN)
+        hipLaunchKernelGGL(k_prop_range_seen, dim3(grid), dim3(GS_BLOCK), 0, ctx->prop_stream, (const unsigned long long *)ctx->contrib, (uint32_t)ctx->contrib_n, (uint32_t)ctx->n,
+                           (const uint8_t *)ctx->edit_state, prop_rows(ctx, mask), (uint32_t)mask, (uint32_t)value, part, cnt);
+    else gs_flag(gsm::prop_reads_cc(prop), [&](auto CC) {
         hipLaunchKernelGGL((k_prop_range<decltype(CC)::value>), dim3(grid), dim3(GS_BLOCK), 0, ctx->prop_stream, (const uint4 *)ctx->splat, (uint32_t)ctx->n, prop,
                            (const uint8_t *)ctx->edit_state, prop_rows(ctx, mask), (uint32_t)mask, (uint32_t)value, part, cnt);
     });
@@ -452,7 +512,10 @@ int gs_prop_run_histogram(gs_ctx *ctx, int prop, double lo, double hi, double sc
     int rc = prop_begin(ctx, ((size_t)nbins + 4) * sizeof(uint32_t));
     if (rc != GS_OK) return rc;
     uint32_t *out = reinterpret_cast<uint32_t *>(ctx->prop_buf);
-    gs_flag(gsm::prop_reads_cc(prop), [&](auto CC) {
+    if (prop == GS_PROP_SEEN)
+        hipLaunchKernelGGL(k_prop_hist_seen, dim3(stream_grid(ctx->n)), dim3(GS_BLOCK), 0, ctx->prop_stream, (const unsigned long long *)ctx->contrib, (uint32_t)ctx->contrib_n,
+                           (uint32_t)ctx->n, lo, hi, scale, nbins, (const uint8_t *)ctx->edit_state, prop_rows(ctx, mask), (uint32_t)mask, (uint32_t)value, out);
+    else gs_flag(gsm::prop_reads_cc(prop), [&](auto CC) {
         hipLaunchKernelGGL((k_prop_hist<decltype(CC)::value>), dim3(stream_grid(ctx->n)), dim3(GS_BLOCK), 0, ctx->prop_stream, (const uint4 *)ctx->splat,
                            (uint32_t)ctx->n, prop, lo, hi, scale, nbins, (const uint8_t *)ctx->edit_state, prop_rows(ctx, mask), (uint32_t)mask, (uint32_t)value, out);
     });
@@ -521,6 +584,17 @@ int gs_edit_compact(gs_ctx *ctx, const GsCompactTo &to, size_t *kept)
     (void)hipFree(blk);
     if (e != hipSuccess) { snprintf(GS_ERRBUF(ctx), GS_ERRLEN, "gs_compact failed: %s", hipGetErrorString(e)); return GS_E_HIP; }
     *kept = total;
+    return GS_OK;
+}
+
+// ... and the contribution store's words of the kept splats among those that have one: new word k < kept = old word to.old_index[k]
+int gs_edit_compact_contrib(gs_ctx *ctx, const uint32_t *old_index, size_t kept, unsigned long long *to)
+{
+    if (!kept) return GS_OK;
+    hipLaunchKernelGGL(k_compact_contrib, dim3(stream_grid(kept)), dim3(GS_BLOCK), 0, ctx->stream, (const unsigned long long *)ctx->contrib, old_index, (uint32_t)kept,
+                       (uint32_t)ctx->contrib_n, to);
+    GS_HIP(hipGetLastError());
+    GS_HIP(hipStreamSynchronize(ctx->stream));
     return GS_OK;
 }
 
@@ -667,7 +741,7 @@ GS_API int gs_select_sphere(gs_ctx *ctx, const float centre[3], float radius, ui
 // what the three property calls refuse alike
 static int prop_check(gs_ctx *ctx, int prop, const char *name)
 {
-    if (!gsm::prop_valid(prop)) FAIL(GS_E_BADARG, "%s: unknown property %d", name, prop);
+    if (prop != GS_PROP_SEEN && !gsm::prop_valid(prop)) FAIL(GS_E_BADARG, "%s: unknown property %d", name, prop);   // (SEEN: the contribution store, no function of the record)
     if (!ctx->renderable && ctx->n) FAIL(GS_E_STATE, "context was fed worker matrices only (gs_push_matrices): it holds no packed records");
     return GS_OK;
 }
@@ -776,21 +850,27 @@ GS_API int gs_compact(gs_ctx *ctx, uint32_t *out_old_index, size_t *out_n)
     if (rc == GS_OK && sh_q) rc = dev_alloc(ctx, &to.sh, ctx->sh_cap * sh_q * 4);
     if (rc == GS_OK && hipMemset(to.state, 0, ctx->edit_cap) != hipSuccess) { snprintf(GS_ERRBUF(ctx), GS_ERRLEN, "gs_compact: clearing the new state store failed"); rc = GS_E_HIP; }
     // how many of the splats that have an SH row are hidden (the store ends at or before gs_count(): bytes beyond it are state 0)
-    size_t sh_hidden = 0, kept = 0;
+    size_t sh_hidden = 0, kept = 0, seen_hidden = 0;
+    unsigned long long *to_seen = nullptr;                       // the contribution store moves along like the states (both halves of its allocation: gs_frame.hip)
+    if (rc == GS_OK && ctx->contrib_n) rc = dev_alloc(ctx, &to_seen, 2 * ctx->contrib_cap);
+    if (rc == GS_OK && to_seen && hipMemset(to_seen, 0, ctx->contrib_cap * sizeof(unsigned long long)) != hipSuccess) { snprintf(GS_ERRBUF(ctx), GS_ERRLEN, "gs_compact: clearing the new contribution store failed"); rc = GS_E_HIP; }
+    if (rc == GS_OK && to_seen) rc = gs_edit_count_hidden(ctx, ctx->edit_state, ctx->contrib_n < ctx->edit_n ? ctx->contrib_n : ctx->edit_n, &seen_hidden);
     if (rc == GS_OK && sh_q) rc = gs_edit_count_hidden(ctx, ctx->edit_state, ctx->sh_n < ctx->edit_n ? ctx->sh_n : ctx->edit_n, &sh_hidden);
     if (rc == GS_OK) rc = gs_edit_compact(ctx, to, &kept);
     if (rc == GS_OK && sh_q) rc = gs_edit_compact_sh(ctx, to, sh_q, ctx->sh_n - sh_hidden);
+    if (rc == GS_OK && to_seen) rc = gs_edit_compact_contrib(ctx, to.old_index, ctx->contrib_n - seen_hidden, to_seen);
     if (rc == GS_OK && kept != ctx->n - ctx->edit_hidden) { snprintf(GS_ERRBUF(ctx), GS_ERRLEN, "gs_compact: kept %zu splats, expected %zu", kept, ctx->n - ctx->edit_hidden); rc = GS_E_HIP; }
     if (rc == GS_OK && out_old_index && kept && hipMemcpy(out_old_index, to.old_index, kept * sizeof(uint32_t), hipMemcpyDeviceToHost) != hipSuccess) {
         snprintf(GS_ERRBUF(ctx), GS_ERRLEN, "gs_compact: download of the index map failed"); rc = GS_E_HIP;
     }
     if (rc != GS_OK) {
-        dev_free(to.splat); dev_free(to.sort_rows); dev_free(to.bound_r); dev_free(to.state); dev_free(to.old_index); dev_free(to.sh);
+        dev_free(to.splat); dev_free(to.sort_rows); dev_free(to.bound_r); dev_free(to.state); dev_free(to.old_index); dev_free(to.sh); dev_free(to_seen);
         return rc;
     }
     dev_free(ctx->splat); dev_free(ctx->sort_rows); dev_free(ctx->bound_r); dev_free(ctx->edit_state); dev_free(to.old_index);
     ctx->splat = to.splat; ctx->sort_rows = to.sort_rows; ctx->bound_r = to.bound_r; ctx->edit_state = to.state;
     if (sh_q) { dev_free(ctx->sh); ctx->sh = to.sh; ctx->sh_n -= sh_hidden; }
+    if (to_seen) { dev_free(ctx->contrib); ctx->contrib = to_seen; ctx->contrib_n -= seen_hidden; }
     ctx->edit_n -= ctx->edit_hidden; ctx->edit_hidden = 0;       // (every hidden splat lay inside the store; stable order: a prefix stays a prefix)
     ctx->n = kept; ctx->stats.n_splats = kept;
     if (!kept) { ctx->renderable = true; ctx->sh_n = 0; ctx->sh_deg = 0; }   // (an empty context, as after gs_clear)

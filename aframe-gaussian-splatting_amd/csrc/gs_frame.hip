@@ -502,6 +502,7 @@ int gs_fill_uniforms(gs_ctx *ctx /* owner: options, adaptive share, scene */, co
         if (!regular) FAIL(GS_E_BADARG, "model_view is singular: no camera position to evaluate the spherical harmonics for");
     }
     u.surf_id = nullptr; u.surf_depth = nullptr; u.surf_alpha = nullptr; u.surface = 0;   // (gs_render_surface sets them)
+    u.contrib = nullptr; u.contrib_rows = 0; u.contribute = 0;      // (gs_render_contrib sets them)
     u.antialias = ctx->aa_opt ? 1u : 0u;                            // compensated opacity (GS_OPT_ANTIALIAS), per frame like the SH degree
     // highlighted selection (GS_OPT_HIGHLIGHT), per frame too: only with a weight AND a store -- a context that never edits keeps its kernels
     const bool hl = (ctx->hl_opt >> 24) != 0u && ctx->edit_n != 0 && ctx->edit_state;
@@ -532,6 +533,14 @@ static int render_sync_on_lane(gs_ctx *ctx, const GsFrameUniforms &u, void *devi
         return GS_OK;
     };
     for (int attempt = 0;; attempt++) {
+        // (a contribution frame that is drawn again must not count twice: the store is copied behind itself in front of the frame's kernels,
+        // on their stream -- no wait --, and comes back from there in front of a second attempt)
+        if (u.contribute) {
+            gs_ctx *P = gs_root(ctx);
+            unsigned long long *store = P->contrib, *copy = P->contrib + P->contrib_cap;
+            if (P->contrib_n) GS_HIP(hipMemcpyAsync(attempt ? store : copy, attempt ? copy : store, P->contrib_n * sizeof(unsigned long long), hipMemcpyDeviceToDevice, ctx->stream));
+            P->contrib_copied = true;
+        }
         TRY(gs_run_render(ctx, u, (uint8_t *)device_rgba));
         TRY(lane_read_control(ctx, false));
         TRY(queue_copy());
@@ -751,6 +760,88 @@ GS_API int gs_render_surface(gs_ctx *ctx, const gs_render_params *p, uint8_t *rg
     if (host_out->id) GS_HIP(hipMemcpy(host_out->id, dev.id, sw * h * 4, hipMemcpyDeviceToHost));
     if (host_out->depth) GS_HIP(hipMemcpy(host_out->depth, dev.depth, sw * h * 4, hipMemcpyDeviceToHost));
     if (host_out->alpha) GS_HIP(hipMemcpy(host_out->alpha, dev.alpha, sw * h * 4, hipMemcpyDeviceToHost));
+    return GS_OK;
+}
+
+// ---- contribution frames: every splat's blend weights, summed over the frames drawn (include/gs_splat.h: "per-splat contribution")
+// The store is the owner's, parallel to the splats like the SH rows and the states, made by the first contribution frame: one 64-bit sum of
+// 16.16 weights per splat, the words behind contrib_n zero (whoever shortens the store clears what it gives up).  A contribution frame is a
+// synchronous frame on the tile lists, as a surface frame is, whose blend (k_blend_contrib) adds to the store; a copy of the store, queued
+// on the frame's stream in front of its kernels, lies behind it in the same allocation, for the frame that has to be drawn again -- an
+// incomplete order, pair buffers that overflowed: any frame can meet the latter -- or fails (render_sync_on_lane).
+// The property calls that read the store (gs_edit.hip: GS_PROP_SEEN) come after such a frame has returned: nothing is left to order.
+static int contrib_ensure(gs_ctx *ctx)
+{
+    GS_HIP(hipSetDevice(ctx->device));
+    const size_t want = ctx->n;
+    if (want > ctx->contrib_cap) {
+        size_t cap = ctx->contrib_cap ? ctx->contrib_cap : (size_t)1 << 16;
+        while (cap < want) cap *= 2;
+        unsigned long long *nw = nullptr;
+        TRY(dev_alloc(ctx, &nw, 2 * cap));
+        hipError_t e = hipMemsetAsync(nw, 0, cap * sizeof(unsigned long long), ctx->stream);
+        if (e == hipSuccess && ctx->contrib_n) e = hipMemcpyAsync(nw, ctx->contrib, ctx->contrib_n * sizeof(unsigned long long), hipMemcpyDeviceToDevice, ctx->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+        if (e != hipSuccess) { dev_free(nw); FAIL(GS_E_HIP, "growing the contribution store failed: %s", hipGetErrorString(e)); }
+        dev_free(ctx->contrib);
+        ctx->contrib = nw; ctx->contrib_cap = cap;
+    }
+    if (want > ctx->contrib_n) ctx->contrib_n = want;             // (zero-filled: the words behind the old length are zero)
+    return GS_OK;
+}
+
+static int contrib_common(gs_ctx *ctx, const gs_render_params *p, void *device_rgba, uint8_t *host_rgba, size_t stride)
+{
+    if (p && (p->flags & GS_RENDER_COUNT_FRAGS)) FAIL(GS_E_BADARG, "a contribution frame cannot count fragments (GS_RENDER_COUNT_FRAGS)");
+    GsFrameUniforms u;
+    TRY(gs_fill_uniforms(ctx, p, u));
+    if (!ctx->renderable && ctx->n) FAIL(GS_E_STATE, "context was fed worker matrices only (gs_push_matrices): it can sort but not render");
+    TRY(contrib_ensure(ctx));
+    u.flags &= ~(uint32_t)GS_RENDER_ASYNC;
+    u.subtile = 0; u.row_walk = 0; u.split_min = 0;
+    u.contribute = 1; u.contrib = ctx->contrib; u.contrib_rows = (uint32_t)ctx->contrib_n;
+    ctx->contrib_copied = false;                                   // (render_sync_on_lane: set once this frame's copy of the store is queued)
+    const int rc = gs_render_uniforms(ctx, u, device_rgba, host_rgba, stride);
+    const gs_ctx *L = ctx->lanes[ctx->cur];
+    if (rc != GS_OK) {
+        // (whatever the frame added before it failed is taken back; the failure is the frame's)
+        if (ctx->contrib_copied && ctx->contrib_n && hipStreamSynchronize(L->stream) == hipSuccess)
+            (void)hipMemcpy(ctx->contrib, ctx->contrib + ctx->contrib_cap, ctx->contrib_n * sizeof(unsigned long long), hipMemcpyDeviceToDevice);
+        return rc;
+    }
+    if (L->n && L->have_sort) ctx->contrib_frames++;              // (gs_run_render: without a completed order the frame is the background)
+    return GS_OK;
+}
+
+GS_API int gs_render_contrib(gs_ctx *ctx, const gs_render_params *p, uint8_t *rgba_out, size_t stride)
+{
+    CHECK_CTX(ctx);
+    return contrib_common(ctx, p, nullptr, rgba_out, stride);
+}
+
+GS_API int gs_render_contrib_device(gs_ctx *ctx, const gs_render_params *p, void *device_rgba)
+{
+    CHECK_CTX(ctx);
+    return contrib_common(ctx, p, device_rgba, nullptr, 0);
+}
+
+GS_API int gs_contrib_clear(gs_ctx *ctx)
+{
+    CHECK_CTX(ctx);
+    if (ctx->contrib && ctx->contrib_n) {
+        GS_HIP(hipSetDevice(ctx->device));
+        GS_HIP(hipMemsetAsync(ctx->contrib, 0, ctx->contrib_n * sizeof(unsigned long long), ctx->stream));
+        GS_HIP(hipStreamSynchronize(ctx->stream));
+    }
+    ctx->contrib_n = 0; ctx->contrib_frames = 0;
+    return GS_OK;
+}
+
+GS_API int gs_contrib_info(const gs_ctx *ctx, size_t *rows, uint64_t *frames)
+{
+    if (!ctx) return GS_E_BADARG;
+    if (rows) *rows = ctx->contrib_n;
+    if (frames) *frames = ctx->contrib_frames;
     return GS_OK;
 }
 

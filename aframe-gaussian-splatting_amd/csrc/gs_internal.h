@@ -163,6 +163,10 @@ struct GsFrameUniforms {           // per-render constants, passed by value to k
     uint32_t highlight;            // R | G << 8 | B << 16 | W << 24; 0 unless the option's W > 0 AND the state store is non-empty
     uint32_t hl_rows;              // the state store's length: splats beyond it have state 0
     const uint8_t *hl_state;       // the store (the owner's edit_state)
+    // contribution frames (gs_render_contrib; behind everything else).  Read by k_blend_contrib only; the host picks it iff contribute != 0
+    unsigned long long *contrib;   // the owner's contribution store: one 64-bit sum of 16.16 blend weights per splat
+    uint32_t contrib_rows;         // its length (gs_count() when the frame was drawn)
+    uint32_t contribute;           // != 0: a contribution frame -- tile lists, k_blend_contrib
 };
 
 struct GsLaneWorker;
@@ -222,6 +226,12 @@ struct gs_ctx {
     // owner: what gs_prop_range / gs_histogram run on -- a stream of their own (they read the resident arrays only and wait for no
     // frame) and GS_PROP_BUF_BYTES of device memory for their counts and partials; both made by the first call
     hipStream_t prop_stream; void *prop_buf;
+    // the contribution store (owner only; gs_render_contrib, gs_frame.hip): one 64-bit word per splat, parallel to the splats, allocated by the first
+    // contribution frame.  The first contrib_n words are the store; the allocation holds contrib_cap words and, behind them, as many again: the copy
+    // of the store a contribution frame is drawn from again if it turns out incomplete (a frame drawn twice must not count twice)
+    unsigned long long *contrib; size_t contrib_n, contrib_cap;
+    uint64_t contrib_frames;       // contribution frames that drew since the store was last emptied
+    bool contrib_copied;           // the contribution frame under way has queued its copy of the store (what a failed frame is undone from)
 
     // sort scratch (sized by cap)
     float *depth;                  // stored f32 depth or +inf for culled
@@ -468,6 +478,8 @@ struct GsCompactTo { uint4 *splat; float4 *sort_rows; float *bound_r; uint8_t *s
 int gs_edit_compact(gs_ctx *ctx, const GsCompactTo &to, size_t *kept);
 // ... and then the SH rows of the kept splats: new row k < sh_kept = old row to.old_index[k], sh_words 16-byte words each
 int gs_edit_compact_sh(gs_ctx *ctx, const GsCompactTo &to, size_t sh_words, size_t sh_kept);
+// ... and the contribution store's words: to[k] = store[old_index[k]] for k < kept (old_index in device memory)
+int gs_edit_compact_contrib(gs_ctx *ctx, const uint32_t *old_index, size_t kept, unsigned long long *to);
 // ---- gs_render.hip
 int gs_run_render(gs_ctx *ctx, const GsFrameUniforms &u, uint8_t *device_out);
 int gs_run_round1(gs_ctx *ctx, const GsFrameUniforms &u, uint8_t *device_out);

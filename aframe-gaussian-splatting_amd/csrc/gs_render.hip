@@ -1206,7 +1206,14 @@ __device__ __forceinline__ f2 fma2_hi0(f2 a, f2 b, f2 c)
 // the state they share anyway.  Per entry the four T are compared with 0.5 and the entry's slot is latched (the smallest slot: the
 // first crossing); the slot's sorted position and depth are kept at staging (s_j) and read back when the batch ends.  Lists only
 // (span lists or pair records), the compare/select step; pixels outside the strip start at T = 0: never a crossing, never written.
-template <bool COUNT, int ROUND, bool SCENE, bool SUB, bool WALK = false, bool SURF = false>
+// CONTRIB: a contribution frame (gs_render_contrib): every fragment the step really applies -- it passes the discard (and depth) test and
+// its lane is still in the list -- adds its blend weight alpha * e, the very e the colours are multiplied by, to its splat's word of
+// the contribution store, as a 16.16 fixed-point integer rounded per fragment: integer sums do not depend on the order in which the
+// atomics arrive, so two frames with the same transmittance chains leave the same store.  Only the strip's own pixels count (in0..in3,
+// as the fragment count).  Across the wave the weights of a batch are summed in LDS first (the words behind the staged positions in
+// s_j, cleared at staging; at most 256 pixels x 65536 = 2^24 per entry and batch) and the lane that staged an entry adds its sum to
+// global memory once, with one 64-bit atomic, when the batch has been walked.  Lists only, the compare/select step, like SURF.
+template <bool COUNT, int ROUND, bool SCENE, bool SUB, bool WALK = false, bool SURF = false, bool CONTRIB = false>
 __device__ __forceinline__ void k_blend_body(const uint2 *__restrict__ tile_range, const void *__restrict__ pairs,
                                              const gsm::Projected *__restrict__ proj, const GsFrameUniforms &u,
                                              uint8_t *__restrict__ out, float4 *__restrict__ state, uint32_t *__restrict__ mask,
@@ -1219,9 +1226,11 @@ __device__ __forceinline__ void k_blend_body(const uint2 *__restrict__ tile_rang
     __shared__ float4 s_ent[3 * (GS_BLEND_BATCH + 1)];
     __shared__ float s_z[GS_BLEND_BATCH + 2];                    // their window depths (SCENE only)
     __shared__ __attribute__((aligned(16))) uint8_t s_list[SUB ? GS_SUBTILE_GROUPS * GS_SUBTILE_STRIDE : 16];   // GS_OPT_SUBTILE: per 4x4-pixel block, the batch's entries (slots) that can reach it
-    __shared__ uint32_t s_j[SURF ? 2 * GS_BLEND_BATCH : WALK ? GS_BLEND_BATCH : 1];   // WALK: the batch's runs (their indices), by slot; SURF: those, and the window depths behind them
+    __shared__ uint32_t s_j[(SURF || CONTRIB) ? 2 * GS_BLEND_BATCH : WALK ? GS_BLEND_BATCH : 1];   // WALK: the batch's runs (their indices), by slot; SURF: those, and the window depths behind them
+                                                                 // CONTRIB: the entries' sorted positions, and the batch's weight sums behind them
     static_assert(!WALK || (!COUNT && ROUND == 0 && !SUB), "the row walk serves round 0 of plain frames");
     static_assert(!SURF || (!COUNT && !SUB && !WALK), "a surface frame takes the tile lists");
+    static_assert(!CONTRIB || (!COUNT && !SUB && !WALK && !SURF), "a contribution frame takes the tile lists");
     const int lane = threadIdx.x;
     // (a round whose records did not fit bins nothing and this kernel draws the background: the completion word says so)
     if (blockIdx.x == 0 && lane == 0 && u.status && ctl->pair_overflow) atomicOr(u.status, 2u);
@@ -1252,7 +1261,8 @@ __device__ __forceinline__ void k_blend_body(const uint2 *__restrict__ tile_rang
     const f2 qmA = { (row_in && xb < u.x1b) ? 4.0f : -1.0f, (row_in && xb + 1 < u.x1b) ? 4.0f : -1.0f };
     const f2 qmB = { (row_in && xb + 2 < u.x1b) ? 4.0f : -1.0f, (row_in && xb + 3 < u.x1b) ? 4.0f : -1.0f };
     // (GS_RENDER_COUNT_FRAGS counts the strip's own pixels only: the up to three blended beyond x1 are no fragments of a reference that draws [x0, x1))
-    const uint32_t in0 = (COUNT && xb < u.x1) ? 1u : 0u, in1 = (COUNT && xb + 1 < u.x1) ? 1u : 0u, in2 = (COUNT && xb + 2 < u.x1) ? 1u : 0u, in3 = (COUNT && xb + 3 < u.x1) ? 1u : 0u;
+    // (a contribution frame adds the weights of the same pixels only)
+    const uint32_t in0 = ((COUNT || CONTRIB) && xb < u.x1) ? 1u : 0u, in1 = ((COUNT || CONTRIB) && xb + 1 < u.x1) ? 1u : 0u, in2 = ((COUNT || CONTRIB) && xb + 2 < u.x1) ? 1u : 0u, in3 = ((COUNT || CONTRIB) && xb + 3 < u.x1) ? 1u : 0u;
     f2 TA = { qmA.x > 0.0f ? 1.0f : 0.0f, qmA.y > 0.0f ? 1.0f : 0.0f }, TB = { qmB.x > 0.0f ? 1.0f : 0.0f, qmB.y > 0.0f ? 1.0f : 0.0f };
     // (GS_BLEND_FACTOR 2: the constant that stands for qm in the factor form of the step; qm itself then lives only where the step compares)
     const f2 cwA = { qmA.x > 0.0f ? GS_BLEND_W_C_IN : GS_BLEND_W_C_OUT, qmA.y > 0.0f ? GS_BLEND_W_C_IN : GS_BLEND_W_C_OUT };
@@ -1282,7 +1292,7 @@ __device__ __forceinline__ void k_blend_body(const uint2 *__restrict__ tile_rang
     // [0, T]: k_project's records are finite, so q is finite or +inf, exp(A) in [0, 1] -- so there is nothing left to write by hand)
 #define GS_LANE_LIVE() (fmaxf(fmaxf(TA.x, TA.y), fmaxf(TB.x, TB.y)) >= t_eps)
     f2 kbig = { GS_BLEND_W_K, GS_BLEND_W_K }, kone = { 1.0f, 1.0f };   // (GS_BLEND_APPLY_W; the empty asm keeps them in registers: as literals the
-    if (GS_BLEND_FACTOR == 2 && !COUNT && !SCENE && !SURF) {       // compiler builds each pair again in front of every use, 2 moves per entry)
+    if (GS_BLEND_FACTOR == 2 && !COUNT && !SCENE && !SURF && !CONTRIB) {   // compiler builds each pair again in front of every use, 2 moves per entry)
         kbig = -kbig;                                              // form 2 multiplies by -K and needs no 1; the kernels that compare keep
         asm volatile("" : "+v"(kbig));                             // the statement they had, and with it their code
     } else asm volatile("" : "+v"(kbig), "+v"(kone));
@@ -1362,6 +1372,7 @@ __device__ __forceinline__ void k_blend_body(const uint2 *__restrict__ tile_rang
                 s_ent[3 * slot + 2] = make_float4(-rb.w, (float)(rgba & 0xFF) * a255, (float)((rgba >> 8) & 0xFF) * a255, (float)((rgba >> 16) & 0xFF) * a255);
                 if (SCENE) s_z[slot] = u.has_depth ? zwin[j] : 0.0f;
                 if (SURF) { s_j[slot] = j; s_j[GS_BLEND_BATCH + slot] = __float_as_uint(zwin[j]); }
+                if (CONTRIB) { s_j[slot] = j; s_j[GS_BLEND_BATCH + slot] = 0u; }
             }
         }
         if (lane == 0 && (nb & 1)) {
@@ -1431,6 +1442,14 @@ __device__ __forceinline__ void k_blend_body(const uint2 *__restrict__ tile_rang
                         const f2 chv_ = { ch_.x, ch_.y };                                                              \
                         cbA = fma2_hi0(chv_, eA, cbA); cbB = fma2_hi0(chv_, eB, cbB);                                  \
                         if (COUNT) nfr += ((uint32_t)p0 & in0) + ((uint32_t)p1 & in1) + ((uint32_t)p2 & in2) + ((uint32_t)p3 & in3); \
+                        if (CONTRIB) {                               /* alpha * e per pixel, 16.16, the strip's applied fragments only */ \
+                            const f2 wA_ = (f2)(-nalpha) * eA, wB_ = (f2)(-nalpha) * eB;                               \
+                            const uint32_t wq_ = (((uint32_t)p0 & in0) ? (uint32_t)(wA_.x * 65536.0f + 0.5f) : 0u) +   \
+                                                 (((uint32_t)p1 & in1) ? (uint32_t)(wA_.y * 65536.0f + 0.5f) : 0u) +   \
+                                                 (((uint32_t)p2 & in2) ? (uint32_t)(wB_.x * 65536.0f + 0.5f) : 0u) +   \
+                                                 (((uint32_t)p3 & in3) ? (uint32_t)(wB_.y * 65536.0f + 0.5f) : 0u);    \
+                            if (wq_) atomicAdd(&s_j[GS_BLEND_BATCH + (ss)], wq_);                                      \
+                        }                                                                                              \
                         if (SURF) {                                  /* the first slot behind which T < 0.5 */         \
                             const uint32_t s_ = (ss);                                                                  \
                             sfc0 = TA.x < 0.5f ? min(sfc0, s_) : sfc0; sfc1 = TA.y < 0.5f ? min(sfc1, s_) : sfc1;      \
@@ -1507,7 +1526,7 @@ __device__ __forceinline__ void k_blend_body(const uint2 *__restrict__ tile_rang
                 GS_BLEND_Q(1, eb + 48, qA1, qB1)                      // slot nb holds an inert record when nb is odd
                 const uint32_t s = SCENE ? vo / 48u : 0u;               // (the entry's index: only the scene's depth test needs it)
                 const float z0 = SCENE ? s_z[s] : 0.0f;
-                if (GS_BLEND_FACTOR && !COUNT && !SCENE && !SURF) {
+                if (GS_BLEND_FACTOR && !COUNT && !SCENE && !SURF && !CONTRIB) {
                     GS_BLEND_APPLY_W(qA0, qB0, eb)
                     GS_BLEND_APPLY_W(qA1, qB1, eb + 48)
                 } else {
@@ -1534,6 +1553,19 @@ __device__ __forceinline__ void k_blend_body(const uint2 *__restrict__ tile_rang
         }
         end -= nb;
         __syncthreads();                                           // s_ent is rewritten by the next batch
+        if (CONTRIB) {
+            // the batch's sums -> the store: the lane that staged entry `lane` adds what the wave collected for it (its own words of s_j: the
+            // next staging clears them behind this read).  The splat's index as the sort numbers it: what k_project read at this position
+            // (a position behind a near-only sort's records is the reference's zero tail: k_project drew splat 0 there, as it does from the
+            // zeros a whole order holds at those positions, so splat 0 is what the colours received and what is credited -- in both forms alike)
+            const uint32_t wsum = (uint32_t)lane < nb ? s_j[GS_BLEND_BATCH + lane] : 0u;
+            if (wsum) {
+                const uint32_t jc = s_j[lane];
+                const uint32_t near_sorted = ctl->near_sorted, n_rec = ctl->n_sorted, j_base = near_sorted ? ctl->n_valid - n_rec : 0u;
+                const uint32_t ic = !near_sorted ? sorted[jc] : (jc - j_base < n_rec ? sorted[jc - j_base] : 0u);
+                if (ic < u.contrib_rows) atomicAdd(u.contrib + ic, (unsigned long long)wsum);
+            }
+        }
         if (__all(!live)) break;
     }
     if (!COUNT && GS_BLEND_BATCH == 64 && !(u.flags & GS_RENDER_NO_EARLY_OUT)) {
@@ -1684,6 +1716,17 @@ __global__ __launch_bounds__(64) void k_blend_surf(const uint2 *__restrict__ til
                                                    const uint32_t *__restrict__ scene_rgba, GsControl *ctl, const uint32_t *__restrict__ sorted)
 {
     k_blend_body<false, ROUND, SCENE, false, false, true>(tile_range, pairs, proj, u, out, state, mask, zwin, scene_depth, scene_rgba, ctl, sorted);
+}
+
+// ... of a contribution frame (its own name too)
+template <int ROUND, bool SCENE>
+__global__ __launch_bounds__(64) void k_blend_contrib(const uint2 *__restrict__ tile_range, const void *__restrict__ pairs,
+                                                      const gsm::Projected *__restrict__ proj, GsFrameUniforms u,
+                                                      uint8_t *__restrict__ out, float4 *__restrict__ state, uint32_t *__restrict__ mask,
+                                                      const float *__restrict__ zwin, const float *__restrict__ scene_depth,
+                                                      const uint32_t *__restrict__ scene_rgba, GsControl *ctl, const uint32_t *__restrict__ sorted)
+{
+    k_blend_body<false, ROUND, SCENE, false, false, false, true>(tile_range, pairs, proj, u, out, state, mask, zwin, scene_depth, scene_rgba, ctl, sorted);
 }
 
 // GS_OPT_BLEND_SPLIT: the tiles with LONG lists, four wavefronts per tile, ONE pixel per lane (wave w: tile rows 4w .. 4w+3).
@@ -1913,6 +1956,7 @@ template <int ROUND, bool SCENE> GS_BODY(F_blend_px, (k_blend_px<ROUND, SCENE>),
 // single-frame only (gs_frames_batchable keeps such frames out of pairs; launch_blend<.., 2> refuses them): there is no twin kernel of these
 template <int ROUND, bool SCENE, bool SUB> GS_BODY(F_blend_count, (k_blend<true, ROUND, SCENE, SUB>), (k_blend_body<true, ROUND, SCENE, SUB>));
 template <int ROUND, bool SCENE> GS_BODY(F_blend_surf, (k_blend_surf<ROUND, SCENE>), (k_blend_body<false, ROUND, SCENE, false, false, true>));
+template <int ROUND, bool SCENE> GS_BODY(F_blend_contrib, (k_blend_contrib<ROUND, SCENE>), (k_blend_body<false, ROUND, SCENE, false, false, false, true>));
 
 // The sequences below draw NF frames that take the same path, every kernel launched once: S[k] is frame k's lane (sibling lanes on ONE
 // stream -- S[0]'s --, each with its own scratch, control block and output), U[k] its uniforms, out[k] its image.  Whatever decides the PATH
@@ -1930,7 +1974,7 @@ int launch_blend(gs_ctx *const S[], const GsFrameUniforms V[], uint8_t *const ou
     const uint32_t gb = ROUND == 1 ? (ntiles < 1024 ? ntiles : 1024) : ntiles;
     const bool scene = u.has_depth || u.has_scene_rgba;
     const bool count = (u.flags & GS_RENDER_COUNT_FRAGS) != 0;
-    if (NF != 1 && (count || u.record_staged || u.surface)) { snprintf(GS_ERRBUF(ctx), GS_ERRLEN, "paired blend: a measurement or surface frame"); return GS_E_STATE; }
+    if (NF != 1 && (count || u.record_staged || u.surface || u.contribute)) { snprintf(GS_ERRBUF(ctx), GS_ERRLEN, "paired blend: a measurement, surface or contribution frame"); return GS_E_STATE; }
     GsFrameUniforms W[NF];
     for (int k = 0; k < NF; k++) W[k] = V[k];
     if (count || u.record_staged) W[0].split_min = 0;             // measurement renders: every tile by k_blend
@@ -1940,13 +1984,14 @@ int launch_blend(gs_ctx *const S[], const GsFrameUniforms V[], uint8_t *const ou
                             S[k]->state, S[k]->unsat_mask, (const float *)S[k]->zwin, (const float *)S[k]->scene_depth, (const uint32_t *)S[k]->scene_rgba, S[k]->ctl);
     };
     if constexpr (NF == 1) {
-        if (u.surface) {
-            // a surface frame: tile lists, one wavefront per tile (gs_render_surface switches the other paths off for the frame)
+        if (u.surface || u.contribute) {
+            // a surface or contribution frame: tile lists, one wavefront per tile (gs_render_surface / gs_render_contrib switch the other paths off for the frame)
             const auto sargs = [&](int) {
                 return gs_pack_make((const uint2 *)ctx->tile_range, lists[0], (const gsm::Projected *)ctx->proj, W[0], out[0], ctx->state, ctx->unsat_mask, (const float *)ctx->zwin,
                                     (const float *)ctx->scene_depth, (const uint32_t *)ctx->scene_rgba, ctx->ctl, (const uint32_t *)ctx->sorted);
             };
-            gs_flag(scene, [&](auto SC) { gs_launch<1, F_blend_surf<ROUND, decltype(SC)::value>, 64>(gb, st, 0, sargs); });
+            if (u.surface) gs_flag(scene, [&](auto SC) { gs_launch<1, F_blend_surf<ROUND, decltype(SC)::value>, 64>(gb, st, 0, sargs); });
+            else gs_flag(scene, [&](auto SC) { gs_launch<1, F_blend_contrib<ROUND, decltype(SC)::value>, 64>(gb, st, 0, sargs); });
             GS_HIP(hipGetLastError());
             return GS_OK;
         }
@@ -2172,7 +2217,7 @@ bool gs_frames_batchable(const GsFrameUniforms &a, const GsFrameUniforms &b)
     return a.near_count == b.near_count && a.skip_round1 == b.skip_round1 && a.W == b.W && a.H == b.H && a.x0 == b.x0 && a.x1 == b.x1 &&
            a.flags == b.flags && !(a.flags & (GS_RENDER_COUNT_FRAGS | GS_RENDER_COUNT_EVALUATED)) && !a.record_staged && !b.record_staged &&
            a.split_min == b.split_min && a.subtile == b.subtile && a.row_walk == b.row_walk && a.has_depth == b.has_depth && a.has_scene_rgba == b.has_scene_rgba && a.t_eps == b.t_eps &&
-           a.sh_degree == b.sh_degree && a.antialias == b.antialias && a.highlight == b.highlight && !a.surface && !b.surface;
+           a.sh_degree == b.sh_degree && a.antialias == b.antialias && a.highlight == b.highlight && !a.surface && !b.surface && !a.contribute && !b.contribute;
 }
 
 int gs_run_render2(gs_ctx *const S[2], const GsFrameUniforms U[2], uint8_t *const device_out[2])

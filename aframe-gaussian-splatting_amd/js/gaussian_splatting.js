@@ -34,9 +34,11 @@ const PROP_NAMES = ['x', 'y', 'z', 'red', 'green', 'blue', 'alpha', 'size2'];   
 const PROP_FILTERS = { all: [0, 0], visible: [1, 0], selected: [3, 2] };        // (stateMask, stateValue); 1 = hidden, 2 = selected
 
 function elementsOf(m) { return m && m.elements ? m.elements : m; }
+const PROP_SEEN = 16;                              // GS_PROP_SEEN: 'seen', the contribution store in pixels (accumulateSeen)
 function propId(name) {
+  if (name === 'seen') return PROP_SEEN;
   const p = PROP_NAMES.indexOf(name);
-  if (p < 0) throw new RangeError('unknown property ' + name + ' (one of ' + PROP_NAMES.join(' ') + ')');
+  if (p < 0) throw new RangeError('unknown property ' + name + ' (one of ' + PROP_NAMES.join(' ') + ' seen)');
   return p;
 }
 
@@ -230,6 +232,18 @@ class GaussianSplatting {
     return native.renderSurface(this.handle, this._renderParams(camera, viewport, options));
   }
 
+  // Per-splat contribution (beyond the reference): one contribution frame with the component's current camera -- the camera, viewport
+  // and options of the last render / frame / renderSurface call -- adds every splat's blend weights in that view to the 'seen' store,
+  // in pixels.  Draw a few views, then histogram('seen'), selectRange('seen', 0, bound, {hide: true}) and deleteHidden() remove what
+  // no view shows.  -> {rows, frames}: the store's length and the views accumulated so far.  clearSeen() starts over.
+  accumulateSeen() {
+    const v = this._lastView;
+    if (!v) throw new Error('accumulateSeen: no frame has been drawn yet');
+    native.renderContrib(this.handle, this._renderParams(v.camera, v.viewport, v.options), false);
+    return native.contribInfo(this.handle);
+  }
+  clearSeen() { native.contribClear(this.handle); }
+
   // What a cursor, laser-controls or raycaster hit needs: the splat under pixel (x, y) of the CURRENT frame's drawing buffer (the
   // camera, viewport and options of the last render / frame / renderSurface call; column, row, row 0 = top), or null where nothing
   // is opaque enough (the transmittance never falls below one half).  -> {index, depth, alpha, position, worldPosition}:
@@ -299,7 +313,7 @@ class GaussianSplatting {
   }
   highlightInfo() { return native.highlightInfo(this.handle); }
   // The data panel: a histogram of one per-splat property -- 'x' 'y' 'z' (the rows' space, as pick().position), 'red' 'green' 'blue' 'alpha'
-  // (bytes) or 'size2' (the sum of the three squared axis lengths, object units^2) -- over opts.of = 'all' (default) | 'visible' |
+  // (bytes), 'size2' (the sum of the three squared axis lengths, object units^2) or 'seen' (accumulateSeen, pixels) -- over opts.of = 'all' (default) | 'visible' |
   // 'selected' (the visible selection), in opts.bins (default 256) bins over [opts.lo, opts.hi]; a bound left out is the property's own
   // minimum / maximum among those splats (propRange first).  -> {counts: Uint32Array, lo, hi, passing, below, above, nan}; an empty or
   // one-valued range is widened so that the call always has lo < hi.  Reads only: no tick, order or frame is disturbed.

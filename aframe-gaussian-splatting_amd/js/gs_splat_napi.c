@@ -460,6 +460,57 @@ static napi_value fn_render_surface(napi_env env, napi_callback_info info)
     return o;
 }
 
+/* ---- per-splat contribution (gs_splat.h: gs_render_contrib).  renderContrib(h, params, wantRgba) -> Uint8Array RGBA | null: the frame
+ * gs_render draws on the tile lists; every applied fragment adds its blend weight to its splat's word of the contribution store */
+static napi_value fn_render_contrib(napi_env env, napi_callback_info info)
+{
+    napi_value argv[3];
+    if (!get_args(env, info, 3, argv, NULL)) return NULL;
+    gs_ctx *ctx = get_ctx(env, argv[0]); if (!ctx) return NULL;
+    gs_render_params p;
+    bool want = true;
+    if (!fill_params(env, argv[1], &p) || napi_get_value_bool(env, argv[2], &want) != napi_ok) {
+        napi_throw_type_error(env, NULL, "renderContrib: (handle, params, wantRgba)");
+        return NULL;
+    }
+    if (p.x1 <= p.x0 || p.fb_height <= 0) { napi_throw_range_error(env, NULL, "renderContrib: empty strip"); return NULL; }
+    const size_t bytes = (size_t)(p.x1 - p.x0) * (size_t)p.fb_height * 4;
+    napi_value ab, ta; void *out = NULL;
+    if (want) NAPI_OK(napi_create_arraybuffer(env, bytes, &out, &ab));
+    int rc = gs_render_contrib(ctx, &p, (uint8_t *)out, 0);
+    if (rc != GS_OK) return throw_gs(env, ctx, rc);
+    if (!want) { NAPI_OK(napi_get_null(env, &ta)); return ta; }
+    NAPI_OK(napi_create_typedarray(env, napi_uint8_array, bytes, ab, 0, &ta));
+    return ta;
+}
+
+/* contribClear(h): the store to length 0, the frame count to 0 */
+static napi_value fn_contrib_clear(napi_env env, napi_callback_info info)
+{
+    napi_value argv[1], u;
+    if (!get_args(env, info, 1, argv, NULL)) return NULL;
+    gs_ctx *ctx = get_ctx(env, argv[0]); if (!ctx) return NULL;
+    int rc = gs_contrib_clear(ctx);
+    if (rc != GS_OK) return throw_gs(env, ctx, rc);
+    NAPI_OK(napi_get_undefined(env, &u));
+    return u;
+}
+
+/* contribInfo(h) -> { rows, frames } */
+static napi_value fn_contrib_info(napi_env env, napi_callback_info info)
+{
+    napi_value argv[1], o, v;
+    if (!get_args(env, info, 1, argv, NULL)) return NULL;
+    gs_ctx *ctx = get_ctx(env, argv[0]); if (!ctx) return NULL;
+    size_t rows = 0; uint64_t frames = 0;
+    int rc = gs_contrib_info(ctx, &rows, &frames);
+    if (rc != GS_OK) return throw_gs(env, ctx, rc);
+    NAPI_OK(napi_create_object(env, &o));
+    NAPI_OK(napi_create_double(env, (double)rows, &v)); NAPI_OK(napi_set_named_property(env, o, "rows", v));
+    NAPI_OK(napi_create_double(env, (double)frames, &v)); NAPI_OK(napi_set_named_property(env, o, "frames", v));
+    return o;
+}
+
 /* pick(h, params, Int32Array [x0, y0, x1, y1, ...]) -> [{index, depth, alpha, position}]: what the full frame's planes hold at those
  * pixels (column, row; row 0 = top) and the hit splat's position as its .splat row stores it (gs_pick); index -1 and position null
  * where there is no surface */
@@ -589,7 +640,7 @@ static napi_value fn_select_sphere(napi_env env, napi_callback_info info)
     return make_count(env, hit);
 }
 
-/* ---- properties of the resident records (gs_splat.h: GS_PROP_*; prop 0..7 = x y z red green blue alpha size2).  A splat takes part in
+/* ---- properties of the resident records (gs_splat.h: GS_PROP_*; prop 0..7 = x y z red green blue alpha size2, 16 = seen: the contribution store).  A splat takes part in
  * the two reading calls iff (state & stateMask) == stateValue. */
 /* propRange(h, prop, stateMask, stateValue) -> { min, max, count } */
 static napi_value fn_prop_range(napi_env env, napi_callback_info info)
@@ -1411,6 +1462,7 @@ static napi_value init(napi_env env, napi_value exports)
         { "scaledSize", fn_scaled_size },
         { "setState", fn_set_state }, { "setStateIds", fn_set_state_ids }, { "selectBox", fn_select_box }, { "selectSphere", fn_select_sphere },
         { "selectRect", fn_select_rect }, { "compact", fn_compact },
+        { "renderContrib", fn_render_contrib }, { "contribClear", fn_contrib_clear }, { "contribInfo", fn_contrib_info },
         { "propRange", fn_prop_range }, { "histogram", fn_histogram }, { "selectRange", fn_select_range },
         { "selectMask", fn_select_mask }, { "maskPolygon", fn_mask_polygon }, { "highlightInfo", fn_highlight_info },
         { "createMulti", fn_create_multi }, { "multiDestroy", fn_multi_destroy }, { "multiPushSplat", fn_multi_push_splat },

@@ -716,6 +716,7 @@ GS_API int gs_sort_inspect(gs_ctx *ctx, gs_sort_info *info, uint32_t *out_idx, s
                                  unsaturated (measurement aid)                                                         */
 #define GS_BUF_SH 8           /* rows x 3 (D+1)^2 f32  the SH store, tight rows as pushed (gs_sh_count: rows and D)                   */
 #define GS_BUF_STATE 9        /* rows u8     the state store (gs_state_count: rows)                                                      */
+#define GS_BUF_CONTRIB 10     /* rows u64    the contribution store (gs_contrib_info: rows); whole words only                            */
 GS_API int gs_download(gs_ctx *ctx, int which, void *out, size_t nbytes);
 
 /* ---- per-splat properties: histograms and selection by value over the resident cloud (no reference counterpart; part of "editing
@@ -765,6 +766,40 @@ GS_API int gs_multi_select_range(gs_multi *m, int prop, double lo, double hi, ui
 GS_API int gs_multi_prop_range(gs_multi *m, int prop, uint8_t state_mask, uint8_t state_value, double *out_min, double *out_max, size_t *out_n);
 GS_API int gs_multi_histogram(gs_multi *m, int prop, double lo, double hi, uint32_t nbins, uint8_t state_mask, uint8_t state_value, uint32_t *counts,
                               uint64_t tally[4]);
+
+/* ---- per-splat contribution: what a splat adds to the pictures (no reference counterpart; part of "editing the resident cloud") ------
+ * The contribution store holds one uint64_t per splat, parallel to the splats like the SH rows and the states and owned by the context:
+ * the sum, over the contribution frames drawn so far, of the blend weights of the splat's fragments.  Splats beyond the store's length
+ * have contribution 0; gs_clear and gs_contrib_clear empty it; a context that never calls gs_render_contrib allocates nothing and
+ * launches exactly the kernels it launches without this section.  (Device memory: 16 bytes per splat of capacity -- the store and the
+ * copy of it a frame takes, on its own stream, so that a frame the library has to draw again counts once.)
+ * gs_render_contrib draws a frame as gs_render_surface does -- synchronous (GS_RENDER_ASYNC is cleared), always on the tile lists (the
+ * row walk, sub-tile lists, the split blend and paired launches are off for that frame only; the options stay as set), either binning,
+ * one round or two, the scene's depth and colour honoured -- and its colour is bit-identical to gs_render's on the lists with the same
+ * GS_OPT_NEAR_PERMILLE.  rgba_out / device_rgba may be NULL.  The store first grows, zero-filled, to gs_count().
+ * GS_RENDER_COUNT_FRAGS: GS_E_BADARG; GS_RENDER_NO_EARLY_OUT is allowed; a matrices-only context: GS_E_STATE; with no completed order
+ * the frame is the background and adds nothing.  A contribution frame is a collected frame like any other: what the adaptive options
+ * go by afterwards (the measured share, GS_OPT_SUBTILE / GS_OPT_ROW_WALK = 1) is what gs_render of the same frame would have left; with
+ * those options pinned, a later plain frame and its gs_stats are what they are without the call.
+ * WHAT IS ADDED: store[sorted[j]] receives every fragment the blend really applies -- it passes the discard test (q <= 4), the LEQUAL
+ * test where a scene depth is set, and is evaluated before its lane (4 pixels of one row) has left the list: early termination is
+ * honoured, and a pixel below the threshold whose lane is still live still counts, exactly as the colour accumulators received it --
+ * and that belongs to a pixel of the strip [x0, x1) itself.  Per fragment, with e = exp(-q) * T_before (the factor its colour is
+ * multiplied by) and alpha the record's opacity:  w = alpha * e (one f32 multiplication),  wq = (uint32_t)(w * 65536.0f + 0.5f).
+ * Integer sums do not depend on the order of the additions: frames whose transmittance chains are bit-identical leave identical stores
+ * (one round or two, span lists or pair records, a frame or its strips with x0 % 4 == 0 added up, a run repeated).  Hidden and culled
+ * splats receive nothing.  Frames gathered from several ranks or devices (gs_comm, gs_multi) and gs_render_stereo never accumulate.
+ * The store survives sorts, pushes (new splats start at 0), state and option changes; gs_compact carries it along in stable order for
+ * the kept splats among those that have a word.
+ * GS_PROP_SEEN is the store as a property for gs_prop_range, gs_histogram, gs_select_range and their gs_multi_ forms (each device's
+ * own store): (double)store[i] / 65536.0, in pixels, exact below 2^53, 0 beyond the store.  It is no function of the record:
+ * gs_prop_eval refuses it, and ids 8..15 stay unknown. */
+GS_API int gs_render_contrib(gs_ctx *ctx, const gs_render_params *p, uint8_t *rgba_out, size_t stride);   /* rgba_out may be NULL */
+GS_API int gs_render_contrib_device(gs_ctx *ctx, const gs_render_params *p, void *device_rgba);           /* may be NULL */
+GS_API int gs_contrib_clear(gs_ctx *ctx);                                 /* store -> length 0, frames -> 0 */
+/* rows: the store's length; frames: contribution frames that drew since the store was last emptied.  Either may be NULL. */
+GS_API int gs_contrib_info(const gs_ctx *ctx, size_t *rows, uint64_t *frames);
+#define GS_PROP_SEEN 16
 
 #ifdef __cplusplus
 }
