@@ -64,6 +64,7 @@ EXPORTS = [
     "gs_prop_eval", "gs_hist_bin", "gs_prop_range", "gs_histogram", "gs_select_range",
     "gs_multi_prop_range", "gs_multi_histogram", "gs_multi_select_range",
     "gs_render_contrib", "gs_render_contrib_device", "gs_contrib_clear", "gs_contrib_info",
+    "gs_export_row", "gs_export_splat", "gs_export_sh", "gs_splat_to_ply", "gs_export_ply", "gs_multi_export_splat", "gs_multi_export_ply",
 ]
 SURFACE_NONE = 0xFFFFFFFF          # gs_surface.id / gs_hit.id where the transmittance never falls below one half
 
@@ -255,6 +256,14 @@ def load(build_if_missing=True):
         L.gs_render_contrib_device.argtypes = [vp, C.POINTER(RenderParams), vp]
         L.gs_contrib_clear.argtypes = [vp]
         L.gs_contrib_info.argtypes = [vp, C.POINTER(sz), C.POINTER(C.c_uint64)]
+    if hasattr(L, "gs_export_splat"):                          # (an older build loaded through GS_SPLAT_LIB for an A/B run has none)
+        u8, szp = C.c_uint8, C.POINTER(sz)
+        L.gs_export_row.argtypes = [vp, vp, vp, vp]
+        L.gs_splat_to_ply.argtypes = [vp, vp, vp, sz, i32, sz, vp, szp]
+        L.gs_export_sh.argtypes = [vp, u8, u8, vp, szp, C.POINTER(i32)]
+        for pre in ("gs_", "gs_multi_"):
+            getattr(L, pre + "export_splat").argtypes = [vp, u8, u8, vp, vp, vp, szp]
+            getattr(L, pre + "export_ply").argtypes = [vp, u8, u8, i32, vp, szp]
     L.gs_download.argtypes = [vp, i32, vp, sz]
     if hasattr(L, "gs_sort_inspect"):
         L.gs_sort_inspect.argtypes = [vp, C.POINTER(SortInfo), vp, sz]
@@ -495,6 +504,82 @@ def hist_bin(v, lo, hi, nbins):
     return res.reshape(vals.shape) if vals.ndim else res[0]
 
 
+def export_row(cs, cc, want_wide=False):
+    """gs_export_row: packed records -- cs = float32[..., 4], cc = uint32[..., 4], as BUF_CENTER_SCALE and BUF_COV_COLOR hold them -- back to
+    32-byte .splat rows by the export kernel's own function -> uint8[n, 32] (want_wide: and float32[n, 7], the scales and the stored
+    quaternion before the byte rounding)"""
+    a = np.ascontiguousarray(cs, np.float32)
+    b = np.ascontiguousarray(cc, np.uint32)
+    if a.shape[-1:] != (4,) or a.shape != b.shape:
+        raise ValueError("cs and cc: records of four words each, the same number of them")
+    ra, rb = a.reshape(-1, 4), b.reshape(-1, 4)
+    rows = np.zeros((len(ra), 32), np.uint8)
+    wide = np.zeros((len(ra), 7), np.float32)
+    f, pa, pb, pr, pw = load().gs_export_row, ra.ctypes.data, rb.ctypes.data, rows.ctypes.data, wide.ctypes.data
+    for i in range(len(ra)):
+        rc = f(pa + 16 * i, pb + 16 * i, pr + 32 * i, pw + 28 * i if want_wide else None)
+        if rc != GS_OK:
+            raise GsError(rc, "gs_export_row: bad argument")
+    return (rows, wide) if want_wide else rows
+
+
+def splat_to_ply(rows, wide=None, sh=None, degree=0):
+    """gs_splat_to_ply: .splat rows (+ the wide parts of export_splat, + SH rows of `degree` for the first len(sh) of them) -> the bytes
+    of a binary little-endian INRIA .ply (uint8 array) that ply_to_splat / load_ply / ply_sh read back"""
+    r = np.ascontiguousarray(np.asarray(rows).view(np.uint8).reshape(-1))
+    if r.size % 32:
+        raise ValueError("rows must be a multiple of 32 bytes")
+    n = r.size // 32
+    w = None
+    if wide is not None:
+        w = np.ascontiguousarray(wide, np.float32).reshape(-1)
+        if w.size != 7 * n:
+            raise ValueError("wide: seven floats per row")
+    s, ns = None, 0
+    if sh is not None:
+        s, ns = _sh_rows(sh, degree)
+    nb = C.c_size_t(0)
+    rc = load().gs_splat_to_ply(_p(r), _p(w), _p(s), ns, int(degree), n, None, C.byref(nb))
+    if rc != GS_OK:
+        raise GsError(rc, "gs_splat_to_ply: bad argument")
+    out = np.zeros(nb.value, np.uint8)
+    rc = load().gs_splat_to_ply(_p(r), _p(w), _p(s), ns, int(degree), n, _p(out), C.byref(nb))
+    if rc != GS_OK:
+        raise GsError(rc, "gs_splat_to_ply: bad argument")
+    return out
+
+
+OF_FILTERS = {"all": (0, 0), "visible": (STATE_HIDDEN, 0), "selected": (STATE_HIDDEN | STATE_SELECTED, STATE_SELECTED)}
+
+
+def _of(of):
+    """a state filter: 'all' | 'visible' | 'selected', or (state_mask, state_value)"""
+    m, v = OF_FILTERS[of] if isinstance(of, str) else of
+    return int(m), int(v)
+
+
+def _export_splat(L, fn, h, ck, of, want_wide, want_index):
+    m, v = _of(of)
+    n = C.c_size_t(0)
+    ck(fn(h, m, v, None, None, None, C.byref(n)))
+    rows = np.zeros((n.value, 32), np.uint8)
+    wide = np.zeros((n.value, 7), np.float32) if want_wide else None
+    index = np.zeros(n.value, np.uint32) if want_index else None
+    if n.value:
+        ck(fn(h, m, v, _p(rows), _p(wide), _p(index), C.byref(n)))
+    out = (rows,) + ((wide,) if want_wide else ()) + ((index,) if want_index else ())
+    return out if len(out) > 1 else rows
+
+
+def _export_ply(fn, h, ck, of, sh_degree):
+    m, v = _of(of)
+    nb = C.c_size_t(0)
+    ck(fn(h, m, v, int(sh_degree), None, C.byref(nb)))
+    out = np.zeros(nb.value, np.uint8)
+    ck(fn(h, m, v, int(sh_degree), _p(out), C.byref(nb)))
+    return out[:nb.value]
+
+
 def mask_polygon(points, width, height, out=None):
     """gs_mask_polygon: even-odd fill of the closed polygon `points` (n x (x, y), pixels, row 0 = top) -> uint8[height, width] of 0 / 1.
     out: a C-contiguous uint8 array of `height` rows to fill instead (its row length is the stride; bytes beyond `width` stay)."""
@@ -687,6 +772,25 @@ class Context:
         n = C.c_size_t(0)
         self._ck(self._L.gs_compact(self._h, _p(old), C.byref(n)))
         return old[:n.value].copy()
+
+    # export: the resident cloud back to the host.  of: 'all' | 'visible' | 'selected' or (state_mask, state_value); reading calls
+    def export_splat(self, of="all", want_wide=False, want_index=False):
+        """gs_export_splat: the passing splats as .splat rows in ascending old index -> uint8[n, 32] (, float32[n, 7]) (, uint32[n])"""
+        return _export_splat(self._L, self._L.gs_export_splat, self._h, self._ck, of, want_wide, want_index)
+
+    def export_sh(self, of="all"):
+        """gs_export_sh: the SH rows of the exported splats that have one (the first rows of export_splat) -> (float32[n, 3 (D+1)^2], D)"""
+        m, v = _of(of)
+        n, d = C.c_size_t(0), C.c_int(0)
+        self._ck(self._L.gs_export_sh(self._h, m, v, None, C.byref(n), C.byref(d)))
+        out = np.zeros((n.value, 3 * (d.value + 1) ** 2), np.float32)
+        if n.value:
+            self._ck(self._L.gs_export_sh(self._h, m, v, _p(out), C.byref(n), C.byref(d)))
+        return out, d.value
+
+    def export_ply(self, of="all", sh_degree=3):
+        """gs_export_ply: the passing splats as the bytes of an INRIA .ply (uint8 array) with min(sh_degree, stored degree) SH bands"""
+        return _export_ply(self._L.gs_export_ply, self._h, self._ck, of, sh_degree)
 
     def state_count(self):
         """(rows in the state store, hidden splats among them)"""
@@ -1067,6 +1171,13 @@ class Multi:
         n = C.c_size_t(0)
         self._ck(self._L.gs_multi_compact(self._h, _p(old), C.byref(n)))
         return old[:n.value].copy()
+
+    def export_splat(self, of="all", want_wide=False, want_index=False):
+        """gs_multi_export_splat: Context.export_splat on devices[0] (every device holds the same splats)"""
+        return _export_splat(self._L, self._L.gs_multi_export_splat, self._h, self._ck, of, want_wide, want_index)
+
+    def export_ply(self, of="all", sh_degree=3):
+        return _export_ply(self._L.gs_multi_export_ply, self._h, self._ck, of, sh_degree)
 
     def set_option(self, opt, value):
         self._ck(self._L.gs_multi_set_option(self._h, int(opt), int(value)))

@@ -1,0 +1,275 @@
+// gs_export.hip -- the resident cloud back to the host as .splat rows and as a .ply (include/gs_splat.h: gs_export_splat,
+// gs_export_sh, gs_export_ply): the splats that pass a state filter, compacted in stable order, each packed record turned into a
+// row again by gsm::export_row (gs_export.h: a symmetric 3x3 eigen-decomposition per splat, f64).
+//
+// The compaction is gs_compact's scheme (gs_edit.hip) with the property calls' filter as its predicate: a workgroup owns
+// GS_EXPORT_CHUNK consecutive splats, a thread GS_EXPORT_IPT consecutive ones; count -> offsets -> scatter.  The three kernels are
+// this file's own -- gs_compact launches what it launched before -- and a context that never exports launches none of them.
+// Like gs_prop_range and gs_histogram the calls only read the resident arrays: they run on the owner's prop_stream, wait for
+// their own kernels and copies alone, drain no lane, drop no order and touch no option or statistic.
+//
+// Launch shape of the scatter: 256 threads, a thread's eight splats walked by a rolled loop, the sweep loop rolled too (one copy of
+// the three rotations: the instruction cache).  The eigen-solver keeps the matrix (6 f64) and the vectors (9 f64) in registers, a
+// rotation's temporaries die with it: the compiler reports 58 vector registers, no private memory, 8 waves per SIMD -- far below the
+// spill line, so no register budget is set.  The kernel is bound by f64 divisions and square roots (two of each per rotation, 24
+// rotations per splat), not by memory (32 bytes in and 32 + 28 + 4 out per splat): many waves per SIMD to hide their latency is
+// what helps, and the skipped rotations (an entry that is exactly 0) only diverge within a wave.
+#include "gs_lanes.h"
+#include "gs_sh.h"
+#include "gs_export.h"
+
+namespace {
+
+#define GS_EXPORT_IPT 8u                                         // GS_EDIT_IPT, GS_EDIT_CHUNK of gs_edit.hip
+#define GS_EXPORT_CHUNK (GS_EXPORT_IPT * GS_BLOCK)
+
+__device__ __forceinline__ uint32_t wave_sum(uint32_t v)
+{
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
+    return v;
+}
+// exclusive scan of one value per thread over the workgroup (256 threads), in thread order; total: the sum (every thread calls it)
+__device__ __forceinline__ uint32_t block_excl_scan(uint32_t v, uint32_t *s_w /* [GS_BLOCK / 64] */, uint32_t &total)
+{
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    uint32_t inc = v;
+    for (int d = 1; d < 64; d <<= 1) { const uint32_t t = __shfl_up(inc, d, 64); if (lane >= d) inc += t; }
+    __syncthreads();                                               // (s_w may still be read from the previous call)
+    if (lane == 63) s_w[w] = inc;
+    __syncthreads();
+    uint32_t base = 0;
+    for (int k = 0; k < w; k++) base += s_w[k];
+    total = s_w[0] + s_w[1] + s_w[2] + s_w[3];
+    return base + inc - v;
+}
+
+// the property calls' filter (gs_edit.hip: prop_passes): rows = 0 when the mask is 0 or the store is empty -- no byte is loaded then
+__device__ __forceinline__ bool export_passes(const uint8_t *__restrict__ state, uint32_t rows, uint32_t i, uint32_t n, uint32_t mask, uint32_t value)
+{
+    if (i >= n) return false;
+    const uint32_t st = i < rows ? (uint32_t)state[i] : 0u;
+    return (st & mask) == value;
+}
+
+__global__ __launch_bounds__(GS_BLOCK) void k_export_count(const uint8_t *__restrict__ state, uint32_t rows, uint32_t n, uint32_t mask, uint32_t value,
+                                                           uint32_t *__restrict__ blk)
+{
+    __shared__ uint32_t s_c;
+    if (threadIdx.x == 0) s_c = 0;
+    __syncthreads();
+    uint32_t c = 0;
+    const uint32_t i0 = blockIdx.x * GS_EXPORT_CHUNK + threadIdx.x * GS_EXPORT_IPT;
+    for (uint32_t j = 0; j < GS_EXPORT_IPT; j++) c += export_passes(state, rows, i0 + j, n, mask, value) ? 1u : 0u;
+    c = wave_sum(c);
+    if ((threadIdx.x & 63) == 0 && c) atomicAdd(&s_c, c);
+    __syncthreads();
+    if (threadIdx.x == 0) blk[blockIdx.x] = s_c;
+}
+// one workgroup: blk[0, nblk) -> their exclusive sums in place, blk[nblk] = the total
+__global__ __launch_bounds__(GS_BLOCK) void k_export_offsets(uint32_t *__restrict__ blk, uint32_t nblk)
+{
+    __shared__ uint32_t s_w[GS_BLOCK / 64];
+    uint32_t carry = 0;
+    for (uint32_t b0 = 0; b0 < nblk; b0 += GS_BLOCK) {
+        const uint32_t b = b0 + threadIdx.x;
+        const uint32_t v = b < nblk ? blk[b] : 0u;
+        uint32_t total;
+        const uint32_t ex = block_excl_scan(v, s_w, total);
+        if (b < nblk) blk[b] = carry + ex;
+        carry += total;
+    }
+    if (threadIdx.x == 0) blk[nblk] = carry;
+}
+// the new index of this thread's first passing splat, and which of its splats pass (bit j: splat i0 + j)
+__device__ __forceinline__ uint32_t export_slot(const uint8_t *__restrict__ state, uint32_t rows, uint32_t n, uint32_t mask, uint32_t value,
+                                                const uint32_t *__restrict__ blk, uint32_t i0, uint32_t &take)
+{
+    __shared__ uint32_t s_w[GS_BLOCK / 64];
+    take = 0;
+#pragma unroll
+    for (uint32_t j = 0; j < GS_EXPORT_IPT; j++) take |= export_passes(state, rows, i0 + j, n, mask, value) ? (1u << j) : 0u;
+    uint32_t total;
+    return blk[blockIdx.x] + block_excl_scan((uint32_t)__popc(take), s_w, total);   // (k + passing <= blk[nblk]: what the outputs hold)
+}
+// o_rows: 2 x 16 bytes per row; o_wide (may be null): 7 f32 per row; o_index (may be null): the old index
+__global__ __launch_bounds__(GS_BLOCK) void k_export_scatter(const uint8_t *__restrict__ state, uint32_t rows, uint32_t n, uint32_t mask, uint32_t value,
+                                                                const uint32_t *__restrict__ blk, const uint4 *__restrict__ splat, uint4 *__restrict__ o_rows,
+                                                                float *__restrict__ o_wide, uint32_t *__restrict__ o_index)
+{
+    const uint32_t i0 = blockIdx.x * GS_EXPORT_CHUNK + threadIdx.x * GS_EXPORT_IPT;
+    uint32_t take;
+    uint32_t k = export_slot(state, rows, n, mask, value, blk, i0, take);
+#pragma unroll 1
+    for (uint32_t j = 0; j < GS_EXPORT_IPT; j++) {
+        if (!((take >> j) & 1u)) continue;
+        const uint32_t i = i0 + j;
+        const uint4 cs4 = splat[2 * (size_t)i], cc4 = splat[2 * (size_t)i + 1];
+        const float cs[4] = { __uint_as_float(cs4.x), __uint_as_float(cs4.y), __uint_as_float(cs4.z), __uint_as_float(cs4.w) };
+        const uint32_t cc[4] = { cc4.x, cc4.y, cc4.z, cc4.w };
+        uint32_t w[8];
+        float wide[7];
+        gsm::export_row(cs, cc, w, wide);
+        o_rows[2 * (size_t)k] = make_uint4(w[0], w[1], w[2], w[3]);
+        o_rows[2 * (size_t)k + 1] = make_uint4(w[4], w[5], w[6], w[7]);
+        if (o_wide) {
+#pragma unroll
+            for (int q = 0; q < 7; q++) o_wide[7 * (size_t)k + q] = wide[q];
+        }
+        if (o_index) o_index[k] = i;
+        k++;
+    }
+}
+// the SH rows of the passing splats among the first n (= those that have a row): padded store rows -> padded rows, in stable order
+__global__ __launch_bounds__(GS_BLOCK) void k_export_sh(const uint8_t *__restrict__ state, uint32_t rows, uint32_t n, uint32_t mask, uint32_t value,
+                                                        const uint32_t *__restrict__ blk, const uint4 *__restrict__ sh, uint32_t row_q, uint4 *__restrict__ o_sh)
+{
+    const uint32_t i0 = blockIdx.x * GS_EXPORT_CHUNK + threadIdx.x * GS_EXPORT_IPT;
+    uint32_t take;
+    uint32_t k = export_slot(state, rows, n, mask, value, blk, i0, take);
+#pragma unroll 1
+    for (uint32_t j = 0; j < GS_EXPORT_IPT; j++) {
+        if (!((take >> j) & 1u)) continue;
+        for (uint32_t q = 0; q < row_q; q++) o_sh[(size_t)k * row_q + q] = sh[(size_t)(i0 + j) * row_q + q];
+        k++;
+    }
+}
+
+// everything a call holds on the device for its duration
+struct ExportScratch {
+    uint32_t *blk = nullptr, *index = nullptr;
+    uint4 *rows = nullptr, *sh = nullptr;
+    float *wide = nullptr;
+    ~ExportScratch() { dev_free(blk); dev_free(index); dev_free(rows); dev_free(sh); dev_free(wide); }
+};
+
+// the reading passes' stream (gs_edit.hip: prop_begin makes the same one), and the filter's view of the state store
+int export_begin(gs_ctx *ctx, const char *name)
+{
+    if (!ctx->renderable && ctx->n) FAIL(GS_E_STATE, "%s: context was fed worker matrices only (gs_push_matrices): it holds no packed records", name);
+    if (!ctx->n) return GS_OK;
+    GS_HIP(hipSetDevice(ctx->device));
+    if (!ctx->prop_stream) GS_HIP(hipStreamCreateWithFlags(&ctx->prop_stream, hipStreamNonBlocking));
+    return GS_OK;
+}
+uint32_t filter_rows(const gs_ctx *ctx, uint8_t mask) { return (mask && ctx->edit_state) ? (uint32_t)ctx->edit_n : 0u; }
+
+// count and offsets over the first n splats: S.blk[0, nblk) = where each workgroup's rows begin, *total = the passing splats
+int export_offsets(gs_ctx *ctx, ExportScratch &S, uint32_t n, uint8_t mask, uint8_t value, size_t *total)
+{
+    const uint32_t nblk = gs_div_up(n, GS_EXPORT_CHUNK);
+    TRY(dev_alloc(ctx, &S.blk, (size_t)nblk + 1));
+    hipStream_t st = ctx->prop_stream;
+    hipLaunchKernelGGL(k_export_count, dim3(nblk), dim3(GS_BLOCK), 0, st, (const uint8_t *)ctx->edit_state, filter_rows(ctx, mask), n, (uint32_t)mask, (uint32_t)value, S.blk);
+    hipLaunchKernelGGL(k_export_offsets, dim3(1), dim3(GS_BLOCK), 0, st, S.blk, nblk);
+    GS_HIP(hipGetLastError());
+    uint32_t t = 0;
+    GS_HIP(hipMemcpyAsync(&t, S.blk + nblk, sizeof t, hipMemcpyDeviceToHost, st));
+    GS_HIP(hipStreamSynchronize(st));
+    *total = t;
+    return GS_OK;
+}
+
+// gs_export_sh: the same count and offsets over the splats that have an SH row, then their rows (the store's degree)
+int export_sh_rows(gs_ctx *ctx, uint8_t mask, uint8_t value, float *out_sh, size_t *out_nrows, int *out_degree)
+{
+    *out_nrows = 0;
+    if (out_degree) *out_degree = 0;
+    TRY(export_begin(ctx, "gs_export_sh"));
+    const size_t n = ctx->sh_n < ctx->n ? ctx->sh_n : ctx->n;
+    if (!n) return GS_OK;
+    if (out_degree) *out_degree = ctx->sh_deg;
+    ExportScratch S;
+    size_t total = 0;
+    TRY(export_offsets(ctx, S, (uint32_t)n, mask, value, &total));
+    *out_nrows = total;
+    if (!out_sh || !total) return GS_OK;
+    const size_t K = (size_t)gsm::sh_coefs(ctx->sh_deg), KS = (size_t)gsm::sh_channel_stride(ctx->sh_deg);
+    const uint32_t row_q = (uint32_t)(3 * KS / 4);
+    TRY(dev_alloc(ctx, &S.sh, total * row_q));
+    hipStream_t st = ctx->prop_stream;
+    hipLaunchKernelGGL(k_export_sh, dim3(gs_div_up(n, GS_EXPORT_CHUNK)), dim3(GS_BLOCK), 0, st, (const uint8_t *)ctx->edit_state, filter_rows(ctx, mask), (uint32_t)n,
+                       (uint32_t)mask, (uint32_t)value, (const uint32_t *)S.blk, (const uint4 *)ctx->sh, row_q, S.sh);
+    GS_HIP(hipGetLastError());
+    GS_HIP(hipMemcpy2DAsync(out_sh, K * 4, S.sh, KS * 4, K * 4, total * 3, hipMemcpyDeviceToHost, st));   // tight rows out of the padded ones
+    GS_HIP(hipStreamSynchronize(st));
+    return GS_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+GS_API int gs_export_splat(gs_ctx *ctx, uint8_t state_mask, uint8_t state_value, void *out_rows, float *out_wide, uint32_t *out_index, size_t *out_nrows)
+{
+    CHECK_CTX(ctx);
+    if (!out_nrows) FAIL(GS_E_BADARG, "gs_export_splat: out_nrows is NULL");
+    *out_nrows = 0;
+    TRY(export_begin(ctx, "gs_export_splat"));
+    if (!ctx->n) return GS_OK;
+    const uint32_t n = (uint32_t)ctx->n;
+    ExportScratch S;
+    size_t total = 0;
+    TRY(export_offsets(ctx, S, n, state_mask, state_value, &total));
+    *out_nrows = total;
+    if (!out_rows || !total) return GS_OK;                       // the size query, or nothing passes
+    TRY(dev_alloc(ctx, &S.rows, total * 2));
+    if (out_wide) TRY(dev_alloc(ctx, &S.wide, total * 7));
+    if (out_index) TRY(dev_alloc(ctx, &S.index, total));
+    hipStream_t st = ctx->prop_stream;
+    hipLaunchKernelGGL(k_export_scatter, dim3(gs_div_up(n, GS_EXPORT_CHUNK)), dim3(GS_BLOCK), 0, st, (const uint8_t *)ctx->edit_state, filter_rows(ctx, state_mask), n,
+                       (uint32_t)state_mask, (uint32_t)state_value, (const uint32_t *)S.blk, (const uint4 *)ctx->splat, S.rows, S.wide, S.index);
+    GS_HIP(hipGetLastError());
+    GS_HIP(hipMemcpyAsync(out_rows, S.rows, total * 32, hipMemcpyDeviceToHost, st));
+    if (out_wide) GS_HIP(hipMemcpyAsync(out_wide, S.wide, total * 7 * sizeof(float), hipMemcpyDeviceToHost, st));
+    if (out_index) GS_HIP(hipMemcpyAsync(out_index, S.index, total * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    GS_HIP(hipStreamSynchronize(st));
+    return GS_OK;
+}
+
+GS_API int gs_export_sh(gs_ctx *ctx, uint8_t state_mask, uint8_t state_value, float *out_sh, size_t *out_nrows, int *out_degree)
+{
+    CHECK_CTX(ctx);
+    if (!out_nrows) FAIL(GS_E_BADARG, "gs_export_sh: out_nrows is NULL");
+    return export_sh_rows(ctx, state_mask, state_value, out_sh, out_nrows, out_degree);
+}
+
+GS_API int gs_export_ply(gs_ctx *ctx, uint8_t state_mask, uint8_t state_value, int sh_degree, void *out_bytes, size_t *out_nbytes)
+{
+    CHECK_CTX(ctx);
+    if (!out_nbytes) FAIL(GS_E_BADARG, "gs_export_ply: out_nbytes is NULL");
+    *out_nbytes = 0;
+    if (sh_degree < 0 || sh_degree > GS_SH_MAX_DEGREE) FAIL(GS_E_BADARG, "gs_export_ply: sh_degree must be 0..3");
+    TRY(export_begin(ctx, "gs_export_ply"));
+    // the degree written: what is asked for, at most what is stored
+    const int stored = (ctx->sh_n && ctx->n) ? ctx->sh_deg : 0, D = sh_degree < stored ? sh_degree : stored;
+    size_t n = 0;
+    TRY(gs_export_splat(ctx, state_mask, state_value, nullptr, nullptr, nullptr, &n));
+    if (!out_bytes) {
+        if (gs_splat_to_ply(nullptr, nullptr, nullptr, 0, D, n, nullptr, out_nbytes) != GS_OK) FAIL(GS_E_BADARG, "gs_export_ply: size query failed");
+        return GS_OK;
+    }
+    std::vector<uint8_t> rows;
+    std::vector<float> wide, sh, cut;
+    size_t sh_rows = 0;
+    int sh_deg = 0;
+    try {
+        rows.resize(n * 32 + 1); wide.resize(n * 7 + 1);
+        if (n) TRY(gs_export_splat(ctx, state_mask, state_value, rows.data(), wide.data(), nullptr, &n));
+        if (stored) {
+            TRY(export_sh_rows(ctx, state_mask, state_value, nullptr, &sh_rows, &sh_deg));
+            const size_t Ks = (size_t)gsm::sh_coefs(stored), Kd = (size_t)gsm::sh_coefs(D);
+            sh.resize(sh_rows * 3 * Ks + 1);
+            if (sh_rows) TRY(export_sh_rows(ctx, state_mask, state_value, sh.data(), &sh_rows, &sh_deg));
+            // the leading bands of every channel: rows of degree `stored` -> rows of degree D
+            cut.resize(sh_rows * 3 * Kd + 1);
+            for (size_t i = 0; i < sh_rows; i++)
+                for (size_t c = 0; c < 3; c++) memcpy(&cut[(i * 3 + c) * Kd], &sh[(i * 3 + c) * Ks], Kd * sizeof(float));
+        }
+    } catch (...) { FAIL(GS_E_OOM, "gs_export_ply: out of host memory for %zu rows", n); }
+    const int rc = gs_splat_to_ply(rows.data(), wide.data(), sh_rows ? cut.data() : nullptr, sh_rows, D, n, out_bytes, out_nbytes);
+    if (rc != GS_OK) FAIL(rc, "gs_export_ply: writing the file failed");
+    return GS_OK;
+}
+
+}  // extern "C"

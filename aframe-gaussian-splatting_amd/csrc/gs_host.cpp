@@ -15,6 +15,7 @@
 #include "gs_ply.h"
 #include "gs_sh.h"
 #include "gs_device_math.h"
+#include "gs_export.h"
 
 namespace {
 
@@ -388,6 +389,67 @@ GS_API int gs_mask_polygon(const float *xy, size_t npoints, int fb_width, int fb
         }
     }
     return GS_OK;
+}
+
+GS_API int gs_export_row(const float cs[4], const uint32_t cc[4], void *row32, float wide[7])
+{
+    if (!cs || !cc || !row32) return GS_E_BADARG;
+    uint32_t w[8];
+    gsm::export_row(cs, cc, w, wide);
+    memcpy(row32, w, 32);
+    return GS_OK;
+}
+
+// The INRIA header for n vertices whose rows carry K coefficients per channel; the text only
+static std::string ply_header(size_t n, int K)
+{
+    std::string h = "ply\nformat binary_little_endian 1.0\nelement vertex " + std::to_string(n) + "\n";
+    for (const char *p : { "x", "y", "z", "nx", "ny", "nz", "f_dc_0", "f_dc_1", "f_dc_2" }) h += std::string("property float ") + p + "\n";
+    for (int k = 0; k < 3 * (K - 1); k++) h += "property float f_rest_" + std::to_string(k) + "\n";
+    for (const char *p : { "opacity", "scale_0", "scale_1", "scale_2", "rot_0", "rot_1", "rot_2", "rot_3" }) h += std::string("property float ") + p + "\n";
+    return h + "end_header\n";
+}
+
+static int splat_to_ply(const void *rows, const float *wide, const float *sh, size_t sh_rows, int degree, size_t nrows, void *out_bytes, size_t *out_nbytes)
+{
+    if (!out_nbytes || degree < 0 || degree > GS_SH_MAX_DEGREE) return GS_E_BADARG;
+    if (sh_rows > nrows || (sh_rows && !sh)) return GS_E_BADARG;
+    const int K = gsm::sh_coefs(degree);
+    const size_t floats = 17 + 3 * (size_t)(K - 1);
+    const std::string head = ply_header(nrows, K);
+    *out_nbytes = head.size() + nrows * floats * sizeof(float);
+    if (!out_bytes) return GS_OK;
+    if (nrows && !rows) return GS_E_BADARG;
+    uint8_t *out = (uint8_t *)out_bytes;
+    memcpy(out, head.data(), head.size());
+    out += head.size();
+    const double SH_C0 = 0.28209479177387814;
+    std::vector<float> f(floats);
+    for (size_t i = 0; i < nrows; i++) {
+        const uint8_t *r = (const uint8_t *)rows + 32 * i;
+        float pos_scale[6];
+        memcpy(pos_scale, r, 24);
+        size_t at = 0;
+        f[at++] = pos_scale[0]; f[at++] = pos_scale[1]; f[at++] = pos_scale[2];
+        f[at++] = 0.0f; f[at++] = 0.0f; f[at++] = 0.0f;                              // normals: unused by every loader of the format
+        const float *row_sh = i < sh_rows ? sh + i * 3 * (size_t)K : nullptr;
+        for (int c = 0; c < 3; c++) f[at++] = row_sh ? row_sh[c * K] : (float)(((double)r[24 + c] / 255.0 - 0.5) / SH_C0);
+        for (int c = 0; c < 3; c++) for (int k = 1; k < K; k++) f[at++] = row_sh ? row_sh[c * K + k] : 0.0f;   // channel-major, as gs_ply_sh reads it
+        // the logit of alpha / 255, alpha kept inside [0.25, 254.75]: 0 and 255 come back as 0 and 255 through clamped_u8(sigmoid * 255)
+        double a = (double)r[27];
+        a = a < 0.25 ? 0.25 : a > 254.75 ? 254.75 : a;
+        f[at++] = (float)log(a / (255.0 - a));
+        for (int k = 0; k < 3; k++) f[at++] = (float)log((double)pos_scale[3 + k]);
+        for (int k = 0; k < 4; k++) f[at++] = wide ? wide[7 * i + 3 + k] : (float)(((double)r[28 + k] - 128.0) / 128.0);
+        memcpy(out + i * floats * sizeof(float), f.data(), floats * sizeof(float));
+    }
+    return GS_OK;
+}
+
+GS_API int gs_splat_to_ply(const void *rows, const float *wide, const float *sh, size_t sh_rows, int degree, size_t nrows, void *out_bytes, size_t *out_nbytes)
+{
+    try { return splat_to_ply(rows, wide, sh, sh_rows, degree, nrows, out_bytes, out_nbytes); }
+    catch (...) { return GS_E_OOM; }
 }
 
 GS_API int gs_camera_in_object(const float model_view[16], double out[3])

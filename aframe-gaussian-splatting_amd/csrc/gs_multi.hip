@@ -265,6 +265,19 @@ GS_API int gs_multi_histogram(gs_multi *m, int prop, double lo, double hi, uint3
     return run_all(m, [=](gs_ctx *c, int i) { return i == 0 ? gs_histogram(c, prop, lo, hi, nbins, state_mask, state_value, counts, tally) : GS_OK; });
 }
 
+// (the exports: reading calls too)
+GS_API int gs_multi_export_splat(gs_multi *m, uint8_t state_mask, uint8_t state_value, void *out_rows, float *out_wide, uint32_t *out_index, size_t *out_nrows)
+{
+    if (!m) return GS_E_BADARG;
+    return run_all(m, [=](gs_ctx *c, int i) { return i == 0 ? gs_export_splat(c, state_mask, state_value, out_rows, out_wide, out_index, out_nrows) : GS_OK; });
+}
+
+GS_API int gs_multi_export_ply(gs_multi *m, uint8_t state_mask, uint8_t state_value, int sh_degree, void *out_bytes, size_t *out_nbytes)
+{
+    if (!m) return GS_E_BADARG;
+    return run_all(m, [=](gs_ctx *c, int i) { return i == 0 ? gs_export_ply(c, state_mask, state_value, sh_degree, out_bytes, out_nbytes) : GS_OK; });
+}
+
 GS_API int gs_multi_select_rect(gs_multi *m, const gs_render_params *p, const int32_t rect[4], uint8_t set_bits, uint8_t clear_bits, uint32_t flags, size_t *out_hit)
 {
     if (!m) return GS_E_BADARG;

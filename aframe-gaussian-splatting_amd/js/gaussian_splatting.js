@@ -334,6 +334,20 @@ class GaussianSplatting {
     const o = opts || {};
     return native.selectRange(this.handle, propId(prop), lo, hi, o.hide ? 1 : 2, 0, o.invert ? 1 : 0);
   }
+  // Save the edited cloud: the splats of opts.of = 'all' (default) | 'visible' | 'selected' (as in histogram) as an ArrayBuffer of
+  // 32-byte .splat rows, or as a binary .ply with up to opts.shDegree (default 3) spherical-harmonics bands where the cloud was loaded
+  // with them -- what this component and the reference's loaders read.  Scale and rotation are recovered from the packed covariance
+  // (gs_splat.h: gs_export_row).  Reads only; the caller owns the bytes (a download link, fs.writeFileSync).
+  exportSplat(opts) {
+    const f = PROP_FILTERS[(opts || {}).of || 'all'];
+    if (!f) throw new RangeError("exportSplat: of must be 'all', 'visible' or 'selected'");
+    return native.exportSplat(this.handle, f[0], f[1]);
+  }
+  exportPly(opts) {
+    const o = opts || {}, f = PROP_FILTERS[o.of || 'all'];
+    if (!f) throw new RangeError("exportPly: of must be 'all', 'visible' or 'selected'");
+    return native.exportPly(this.handle, f[0], f[1], o.shDegree === undefined ? 3 : o.shDegree);
+  }
   // real deletion of the hidden splats (the GPU holds the cloud twice for the duration of the call) -> Uint32Array: the old index of
   // every splat that stays
   deleteHidden() {

@@ -691,6 +691,51 @@ static napi_value fn_histogram(napi_env env, napi_callback_info info)
     return o;
 }
 
+/* ---- export (gs_splat.h: gs_export_splat / gs_export_ply): the splats with (state & stateMask) == stateValue back to the host */
+/* exportSplat(h, stateMask, stateValue) -> ArrayBuffer of 32-byte .splat rows, ascending index */
+static napi_value fn_export_splat(napi_env env, napi_callback_info info)
+{
+    napi_value argv[3];
+    if (!get_args(env, info, 3, argv, NULL)) return NULL;
+    gs_ctx *ctx = get_ctx(env, argv[0]); if (!ctx) return NULL;
+    uint32_t mask = 0, value = 0;
+    if (!get_u32(env, argv[1], &mask) || !get_u32(env, argv[2], &value)) {
+        napi_throw_type_error(env, NULL, "exportSplat: (handle, stateMask, stateValue)");
+        return NULL;
+    }
+    size_t n = 0;
+    int rc = gs_export_splat(ctx, (uint8_t)mask, (uint8_t)value, NULL, NULL, NULL, &n);
+    if (rc != GS_OK) return throw_gs(env, ctx, rc);
+    napi_value ab; void *data = NULL;
+    NAPI_OK(napi_create_arraybuffer(env, n * 32, &data, &ab));
+    if (n) {
+        rc = gs_export_splat(ctx, (uint8_t)mask, (uint8_t)value, data, NULL, NULL, &n);
+        if (rc != GS_OK) return throw_gs(env, ctx, rc);
+    }
+    return ab;
+}
+
+/* exportPly(h, stateMask, stateValue, shDegree) -> ArrayBuffer: a binary little-endian INRIA .ply */
+static napi_value fn_export_ply(napi_env env, napi_callback_info info)
+{
+    napi_value argv[4];
+    if (!get_args(env, info, 4, argv, NULL)) return NULL;
+    gs_ctx *ctx = get_ctx(env, argv[0]); if (!ctx) return NULL;
+    uint32_t mask = 0, value = 0; int32_t degree = 0;
+    if (!get_u32(env, argv[1], &mask) || !get_u32(env, argv[2], &value) || napi_get_value_int32(env, argv[3], &degree) != napi_ok) {
+        napi_throw_type_error(env, NULL, "exportPly: (handle, stateMask, stateValue, shDegree)");
+        return NULL;
+    }
+    size_t nb = 0;
+    int rc = gs_export_ply(ctx, (uint8_t)mask, (uint8_t)value, degree, NULL, &nb);
+    if (rc != GS_OK) return throw_gs(env, ctx, rc);
+    napi_value ab; void *data = NULL;
+    NAPI_OK(napi_create_arraybuffer(env, nb, &data, &ab));
+    rc = gs_export_ply(ctx, (uint8_t)mask, (uint8_t)value, degree, data, &nb);
+    if (rc != GS_OK) return throw_gs(env, ctx, rc);
+    return ab;
+}
+
 /* selectRange(h, prop, lo, hi, setBits, clearBits, flags) -> splats hit */
 static napi_value fn_select_range(napi_env env, napi_callback_info info)
 {
@@ -1464,6 +1509,7 @@ static napi_value init(napi_env env, napi_value exports)
         { "selectRect", fn_select_rect }, { "compact", fn_compact },
         { "renderContrib", fn_render_contrib }, { "contribClear", fn_contrib_clear }, { "contribInfo", fn_contrib_info },
         { "propRange", fn_prop_range }, { "histogram", fn_histogram }, { "selectRange", fn_select_range },
+        { "exportSplat", fn_export_splat }, { "exportPly", fn_export_ply },
         { "selectMask", fn_select_mask }, { "maskPolygon", fn_mask_polygon }, { "highlightInfo", fn_highlight_info },
         { "createMulti", fn_create_multi }, { "multiDestroy", fn_multi_destroy }, { "multiPushSplat", fn_multi_push_splat },
         { "multiLoadPly", fn_multi_load_ply }, { "multiClear", fn_multi_clear }, { "multiCount", fn_multi_count },

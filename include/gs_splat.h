@@ -801,6 +801,73 @@ GS_API int gs_contrib_clear(gs_ctx *ctx);                                 /* sto
 GS_API int gs_contrib_info(const gs_ctx *ctx, size_t *rows, uint64_t *frames);
 #define GS_PROP_SEEN 16
 
+/* ---- export: the resident cloud back to the host as .splat rows and as a .ply (no reference counterpart: the reference's README
+ * describes scan -> .ply -> .splat, and processPlyBuffer / gs_ply_to_splat is that converter; nothing there leaves a page again.  Part of
+ * "editing the resident cloud": what remains after hiding, selecting and gs_compact is saved with these calls) ------------------------
+ * gs_download returns the packed records only; pushDataBuffer (index.js:343-402) has folded scale and rotation into six int16 covariance
+ * entries times cs[3] and kept neither.  THE RULE that makes a 32-byte row of a record (cs[4], cc[4]) again -- one function,
+ * csrc/gs_export.h: gsm::export_row, called by the kernel and by gs_export_row -- is, every operation IEEE f64, un-fused, built from
+ * + - * / sqrt and comparisons only, in this order:
+ *   position   f32 (cs[0], cs[1], -cs[2]): the exact inverse of index.js:350-354.   colour   cc[3], unchanged.
+ *   matrix     s = (double)cs[3]; with q(h) the int16 in a 16-bit half:  a00 = q(cc[0] lo) * s, a01 = q(cc[0] hi) * s, a02 = q(cc[1] lo) * s,
+ *              a11 = q(cc[1] hi) * s, a12 = q(cc[2] lo) * s, a22 = q(cc[2] hi) * s -- the covariance in the packed (z-mirrored) space,
+ *              R^T diag(scale^2) R for the matrix R pack builds from the quaternion bytes.   V = identity (v[row][column]).
+ *   Jacobi     8 sweeps, each the pairs (p, q) = (0, 1), (0, 2), (1, 2) in that order, r the third index.  A pair whose apq is exactly 0 is
+ *              skipped; else  theta = (aqq - app) / (apq + apq);  root = sqrt(theta * theta + 1);
+ *              t = theta >= 0 ? 1 / (theta + root) : -1 / (root - theta);  c = 1 / sqrt(t * t + 1);  s = t * c;  h = t * apq;
+ *              app -= h;  aqq += h;  apq = 0;  (arp, arq) = (c * arp - s * arq, s * arp + c * arq)  from the old pair;  and for each row i
+ *              of V  (vip, viq) = (c * vip - s * viq, s * vip + c * viq).
+ *   scales     l_k = akk > 0 ? akk : 0;  ordered descending together with V's columns by three exchanges of neighbours on strict
+ *              comparisons -- if l0 < l1 swap (0, 1); if l1 < l2 swap (1, 2); if l0 < l1 swap (0, 1) -- so ties keep the Jacobi order;
+ *              det = (v00 * (v11 * v22 - v12 * v21) - v01 * (v10 * v22 - v12 * v20)) + v02 * (v10 * v21 - v11 * v20); det < 0: column 2 of V
+ *              is negated.  scale_k = (float)sqrt(l_k).
+ *   quaternion r[k][i] = v[i][k] (row k of R is eigenvector k), three.js' makeRotationFromQuaternion convention;  tr = (r00 + r11) + r22;
+ *              the first of tr, r00, r11, r22 that is >= the ones after it and (for tr) >= all three diagonals picks the branch:
+ *                tr:   S = sqrt(tr + 1) * 2;                  w = S / 4;           x = (r21 - r12) / S;  y = (r02 - r20) / S;  z = (r10 - r01) / S
+ *                r00:  S = sqrt(((1 + r00) - r11) - r22) * 2;  w = (r21 - r12) / S;  x = S / 4;            y = (r01 + r10) / S;  z = (r02 + r20) / S
+ *                r11:  S = sqrt(((1 + r11) - r00) - r22) * 2;  w = (r02 - r20) / S;  x = (r01 + r10) / S;  y = S / 4;            z = (r12 + r21) / S
+ *                r22:  S = sqrt(((1 + r22) - r00) - r11) * 2;  w = (r10 - r01) / S;  x = (r02 + r20) / S;  y = (r12 + r21) / S;  z = S / 4
+ *              all four negated if w < 0, or w == 0 and the first non-zero of x, y, z is negative.  Stored: (w, x, y, -z), index.js:344-349;
+ *              byte = clamped_u8(v * 128 + 128): clamp to [0, 255], round to nearest, ties to even (Uint8ClampedArray, index.js:704-707).
+ *   wide       (optional) the three scales and the stored quaternion (w, x, y, -z) as f32, before the byte rounding: what a .ply keeps.
+ *   degenerate cs[3] not finite (decided on its bits): the three scales are cs[3], the quaternion (1, 0, 0, 0) -> bytes (255, 128, 128, 128).
+ *              cs[3] == +-0, or all six entries 0: scales 0 and the same quaternion.  No NaN reaches a comparison.
+ * Re-packing an exported row gives back cs[0..2], cc[3] and the sort row's position exactly; the covariance comes back within what the
+ * format itself loses (8-bit quaternion bytes, int16 entries): docs/LAB_NOTES.md 9n.
+ * gs_export_splat, gs_export_sh and gs_export_ply ONLY READ, like gs_prop_range and gs_histogram: three kernels of their own (count,
+ * offsets, scatter: gs_compact's scheme with the filter (state & state_mask) == state_value as the predicate, a splat beyond the store
+ * has state 0) on the same stream of their own, no drain, no order dropped, no option or statistic changed -- a frame drawn after an
+ * export is the frame drawn without it, and a context that never exports launches exactly the kernels it launched before (the export
+ * kernels are launched by these calls alone; gs_compact and every frame path are untouched).  The rows are staged in device memory for
+ * the call (32 + 28 + 4 bytes per exported splat) and released before it returns.
+ * Matrices-only context: GS_E_STATE.  Nothing resident or nothing passing: 0 rows, GS_OK. */
+/* host, no GPU: one record by the rule above; row32: 32 bytes; wide may be NULL.  NULL cs, cc or row32: GS_E_BADARG. */
+GS_API int gs_export_row(const float cs[4], const uint32_t cc[4], void *row32, float wide[7]);
+/* The passing splats in ascending old index: out_rows[k] (32 bytes each), out_wide[k] (7 f32, optional), out_index[k] = the old index of
+ * row k (optional); *out_nrows = their number (required: NULL is GS_E_BADARG).  out_rows == NULL: size query (counts only; at most
+ * gs_count() rows).  With (GS_STATE_HIDDEN, 0) the rows and the index map are those gs_compact followed by a (0, 0) export gives. */
+GS_API int gs_export_splat(gs_ctx *ctx, uint8_t state_mask, uint8_t state_value, void *out_rows, float *out_wide, uint32_t *out_index, size_t *out_nrows);
+/* The SH rows (tight, 3 (D+1)^2 f32, D = the store's degree -> *out_degree, optional) of the exported splats that have one: the SH store is
+ * a prefix of the splats and the order is stable, so they belong to the FIRST *out_nrows exported rows (gs_compact treats them the same
+ * way).  out_sh == NULL: size query.  An empty store: 0 rows, degree 0. */
+GS_API int gs_export_sh(gs_ctx *ctx, uint8_t state_mask, uint8_t state_value, float *out_sh, size_t *out_nrows, int *out_degree);
+/* host, no context: rows (+ optional wide parts, + optional SH rows of `degree` 0..3 for the first sh_rows <= nrows of them, tight) -> a
+ * binary little-endian INRIA .ply of f32 properties  x y z nx ny nz f_dc_0..2 [f_rest_0 .. 3 ((degree+1)^2 - 1) - 1] opacity scale_0..2
+ * rot_0..3  that gs_ply_to_splat / gs_load_ply / gs_ply_sh read back:
+ *   nx ny nz  0.   scale_k = (float)log((double)scale_k).   rot = the wide quaternion, or (byte - 128) / 128 when wide is NULL.
+ *   f_dc_c    the stored sh[c][0] where the splat has an SH row, else (float)((byte / 255 - 0.5) / SH_C0): the byte comes back exactly.
+ *   f_rest    channel-major (f_rest_(c * per + k - 1) = sh[c][k], per = (degree+1)^2 - 1); zeros for the splats without an SH row.
+ *   opacity   (float)log(a / (255 - a)), a = the alpha byte kept inside [0.25, 254.75]: every byte 0..255 comes back exactly.
+ * *out_nbytes = the file's length (required).  out_bytes == NULL: size query (rows may be NULL then).  nrows = 0: the header alone, with
+ * `element vertex 0`.  A degree outside 0..3, sh_rows > nrows, sh_rows > 0 with sh NULL, nrows > 0 with rows NULL: GS_E_BADARG. */
+GS_API int gs_splat_to_ply(const void *rows, const float *wide, const float *sh, size_t sh_rows, int degree, size_t nrows, void *out_bytes, size_t *out_nbytes);
+/* gs_export_splat (with the wide parts) + gs_export_sh + gs_splat_to_ply: the file carries min(sh_degree, the store's degree) bands, the
+ * leading ones of every stored channel.  out_bytes == NULL: size query.  sh_degree outside 0..3, NULL out_nbytes: GS_E_BADARG. */
+GS_API int gs_export_ply(gs_ctx *ctx, uint8_t state_mask, uint8_t state_value, int sh_degree, void *out_bytes, size_t *out_nbytes);
+/* on devices[0]: every device holds the same splats and states */
+GS_API int gs_multi_export_splat(gs_multi *m, uint8_t state_mask, uint8_t state_value, void *out_rows, float *out_wide, uint32_t *out_index, size_t *out_nrows);
+GS_API int gs_multi_export_ply(gs_multi *m, uint8_t state_mask, uint8_t state_value, int sh_degree, void *out_bytes, size_t *out_nbytes);
+
 #ifdef __cplusplus
 }
 #endif
