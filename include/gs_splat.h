@@ -314,7 +314,18 @@ GS_API int gs_compact(gs_ctx *ctx, uint32_t *out_old_index, size_t *out_n);
  * (GL convention: 0 = near plane, 1 = far plane; a fragment survives iff its depth zndc*0.5+0.5 <= the buffer, LEQUAL)
  * and an optional RGBA8 colour image that replaces the constant background.  Both fb_width x fb_height, tightly packed,
  * row 0 = top, host memory (copied); NULL for either = not used; gs_set_scene(ctx, NULL, NULL, 0, 0) clears.
- * Renders whose fb_width/fb_height differ from the scene's fail with GS_E_BADARG. */
+ * Renders whose fb_width/fb_height differ from the scene's fail with GS_E_BADARG (gs_render, gs_render_surface, gs_render_contrib,
+ * gs_render_stereo alike; after gs_set_scene(ctx, NULL, NULL, 0, 0) the context draws as before).
+ * Pinned by tests/test_scene_edges_gpu.py on every blend path:
+ *   - the test is zwin <= depth in f32, zwin = zndc * 0.5f + 0.5f: EQUALITY SURVIVES (a host that passes the depth plane of
+ *     gs_render_surface back in keeps the surface splat), one ulp below rejects.  A NaN depth (either sign, any payload) rejects every fragment of the
+ *     pixel.  Depth values are compared as they are, not clamped: zwin lies in [0, 1], so negatives and -inf reject all, +inf and
+ *     anything >= 1 accept all, and 0, -0 and denormals reject every splat behind the near plane.
+ *   - the scene's alpha byte takes part as dst.a: out.a = a + dst.a * (1 - a), dst.a = byte / 255; where nothing is drawn all four
+ *     bytes of the scene come back exactly.  With rgba set the background is not used; with depth alone it is the destination.
+ *   - GS_RENDER_FLIP_Y flips the output, not the scene: depth and rgba are read at the image row (row 0 = top), the pixel is
+ *     written at the flipped row -- the flipped frame is the plain frame upside down.
+ *   - a strip reads the depth plane under the pixels it blends, up to its right edge rounded up to four pixels inside the frame. */
 GS_API int gs_set_scene(gs_ctx *ctx, const float *depth, const uint8_t *rgba, int fb_width, int fb_height);
 
 /* Page-locked host memory for framebuffers (gs_render copies into it at PCIe speed, no staging copy; the N-API addon hands
@@ -577,7 +588,9 @@ typedef struct gs_stats {
                                    4th frame of a lane (an event pair costs ~5 % of the pipelined frame rate); 0: off */
 #define GS_OPT_TERMINATION 2    /* value = 1/eps: a pixel stops blending once its transmittance T < eps (default 1024, SURVEY.md 8a row 9:
                                    what lies behind then weighs < eps = 0.25 LSB of RGBA8 in total; the image stays within 1 LSB of the
-                                   back-to-front result for any eps < 1/256.  4096 was the round-1 default: 9 % fewer frames/s) */
+                                   back-to-front result for any eps < 1/256 -- held by tests/test_scene_edges_gpu.py::test_termination_bound
+                                   on every blend path, with and without a scene, for 256, 257, 1024, 4096 and 2^24 against the
+                                   GS_RENDER_NO_EARLY_OUT frame.  4096 was the round-1 default: 9 % fewer frames/s) */
 #define GS_OPT_NEAR_PERMILLE 3  /* occlusion-aware binning: 0 = adapt (default), 1..999 = bin that share of the nearest
                                    splats first and the rest only against unsaturated tiles, 1000 = single round      */
 #define GS_OPT_RECORD_STAGED 4  /* value != 0: each render overwrites the tile-range table with (list entries staged,
