@@ -1635,7 +1635,8 @@ __device__ __forceinline__ void k_blend_body(const uint2 *__restrict__ tile_rang
                     ((uint32_t)(fminf(fmaxf(o3, 0.0f), 1.0f) * 255.0f + 0.5f) << 24);
         }
         uint32_t *dst = reinterpret_cast<uint32_t *>(out) + (size_t)orow * sw + (xb - u.x0);
-        if (xb + 3 < u.x1 && (sw & 3) == 0) *reinterpret_cast<uint4 *>(dst) = make_uint4(px[0], px[1], px[2], px[3]);
+        // (16-byte stores need a 16-byte aligned strip: the caller's device pointer is only promised to hold RGBA8 words)
+        if (xb + 3 < u.x1 && (sw & 3) == 0 && !((uintptr_t)out & 15u)) *reinterpret_cast<uint4 *>(dst) = make_uint4(px[0], px[1], px[2], px[3]);
         else {
 #pragma unroll
             for (int k = 0; k < 4; k++) if (xb + k < u.x1) dst[k] = px[k];

@@ -189,7 +189,8 @@ GS_API int gs_render(gs_ctx *ctx, const gs_render_params *p, uint8_t *rgba_out, 
  * corresponding columns of the full frame bit for bit; other strips within 1 LSB (early termination works on groups of 4
  * pixels counted from x0). */
 /* Same, but the strip stays on the GPU: device_rgba is a device pointer (e.g. a torch tensor's
- * data_ptr, tight rows) or NULL to render into the context's own framebuffer only. */
+ * data_ptr, tight rows) or NULL to render into the context's own framebuffer only.  device_rgba needs 4-byte alignment;
+ * 16-byte-aligned strips whose width is a multiple of 4 are stored four pixels at a time. */
 GS_API int gs_render_device(gs_ctx *ctx, const gs_render_params *p, void *device_rgba);
 /* gs_sort for ONE column strip of a frame that is then drawn with exactly these parameters (strip->x0, x1; NULL = gs_sort):
  * splats whose quad cannot reach the strip are left out by a conservative bound (4 min(sqrt(2 lambda1), 1024) + 2 pixels
@@ -223,7 +224,8 @@ GS_API int gs_render_stereo(gs_ctx *ctx, const gs_render_params eyes[2], uint8_t
 typedef struct gs_surface { uint32_t *id; float *depth; float *alpha; } gs_surface;   /* any may be NULL: that plane is not written */
 /* host planes; rgba_out may be NULL (no colour wanted) */
 GS_API int gs_render_surface(gs_ctx *ctx, const gs_render_params *p, uint8_t *rgba_out, size_t stride, const gs_surface *host_out);
-/* device planes (tight; 16-byte aligned planes are stored four pixels at a time); device_rgba may be NULL */
+/* device planes (tight; 16-byte aligned planes are stored four pixels at a time); device_rgba may be NULL.  device_rgba needs 4-byte
+ * alignment; 16-byte-aligned strips whose width is a multiple of 4 are stored four pixels at a time. */
 GS_API int gs_render_surface_device(gs_ctx *ctx, const gs_render_params *p, void *device_rgba, const gs_surface *device_out);
 /* What the full-frame planes of `p` (its x0 / x1 are ignored) hold at npoints pixels xy = (column, row; row 0 = top) -- exactly -- and
  * the hit splat's centre in the rows' object space, as a .splat row stores it (NaN where id is none).  Draws one 16-pixel column
@@ -808,6 +810,7 @@ GS_API int gs_multi_histogram(gs_multi *m, int prop, double lo, double hi, uint3
  * own store): (double)store[i] / 65536.0, in pixels, exact below 2^53, 0 beyond the store.  It is no function of the record:
  * gs_prop_eval refuses it, and ids 8..15 stay unknown. */
 GS_API int gs_render_contrib(gs_ctx *ctx, const gs_render_params *p, uint8_t *rgba_out, size_t stride);   /* rgba_out may be NULL */
+/* device_rgba needs 4-byte alignment; 16-byte-aligned strips whose width is a multiple of 4 are stored four pixels at a time. */
 GS_API int gs_render_contrib_device(gs_ctx *ctx, const gs_render_params *p, void *device_rgba);           /* may be NULL */
 GS_API int gs_contrib_clear(gs_ctx *ctx);                                 /* store -> length 0, frames -> 0 */
 /* rows: the store's length; frames: contribution frames that drew since the store was last emptied.  Either may be NULL. */
