@@ -65,6 +65,8 @@ EXPORTS = [
     "gs_multi_prop_range", "gs_multi_histogram", "gs_multi_select_range",
     "gs_render_contrib", "gs_render_contrib_device", "gs_contrib_clear", "gs_contrib_info",
     "gs_export_row", "gs_export_splat", "gs_export_sh", "gs_splat_to_ply", "gs_export_ply", "gs_multi_export_splat", "gs_multi_export_ply",
+    "gs_adjust_colour", "gs_adjust_word", "gs_adjust_sh_row", "gs_replace_splat", "gs_replace_sh",
+    "gs_multi_adjust_colour", "gs_multi_replace_splat", "gs_multi_replace_sh",
 ]
 SURFACE_NONE = 0xFFFFFFFF          # gs_surface.id / gs_hit.id where the transmittance never falls below one half
 
@@ -109,6 +111,20 @@ class Surface(C.Structure):
 
 class Hit(C.Structure):
     _fields_ = [("id", C.c_uint32), ("depth", C.c_float), ("alpha", C.c_float), ("pos", C.c_float * 3)]
+
+
+class ColourAdjust(C.Structure):
+    """gs_colour_adjust: colour' = m (row-major 3x3) colour + offset (byte units), alpha' = alpha_scale * alpha + alpha_offset"""
+    _fields_ = [("m", C.c_float * 9), ("offset", C.c_float * 3), ("alpha_scale", C.c_float), ("alpha_offset", C.c_float)]
+
+
+def colour_adjust(m=None, offset=(0.0, 0.0, 0.0), alpha_scale=1.0, alpha_offset=0.0):
+    """A ColourAdjust; the defaults are the identity.  m: 9 values, row-major (out channel c reads m[3c .. 3c+2])"""
+    a = ColourAdjust()
+    a.m[:] = [float(v) for v in np.asarray(np.eye(3) if m is None else m, np.float32).reshape(9)]
+    a.offset[:] = [float(v) for v in np.asarray(offset, np.float32).reshape(3)]
+    a.alpha_scale, a.alpha_offset = float(np.float32(alpha_scale)), float(np.float32(alpha_offset))
+    return a
 
 
 HIT_DTYPE = np.dtype([("id", np.uint32), ("depth", np.float32), ("alpha", np.float32), ("pos", np.float32, 3)])
@@ -264,6 +280,13 @@ def load(build_if_missing=True):
         for pre in ("gs_", "gs_multi_"):
             getattr(L, pre + "export_splat").argtypes = [vp, u8, u8, vp, vp, vp, szp]
             getattr(L, pre + "export_ply").argtypes = [vp, u8, u8, i32, vp, szp]
+    if hasattr(L, "gs_adjust_colour"):                         # (likewise)
+        L.gs_adjust_word.argtypes = [C.c_uint32, C.POINTER(ColourAdjust), u32p]
+        L.gs_adjust_sh_row.argtypes = [vp, i32, C.POINTER(ColourAdjust), vp]
+        for pre in ("gs_", "gs_multi_"):
+            getattr(L, pre + "adjust_colour").argtypes = [vp, C.POINTER(ColourAdjust), u8, u8, szp]
+            getattr(L, pre + "replace_splat").argtypes = [vp, sz, vp, sz]
+            getattr(L, pre + "replace_sh").argtypes = [vp, sz, vp, sz, i32]
     L.gs_download.argtypes = [vp, i32, vp, sz]
     if hasattr(L, "gs_sort_inspect"):
         L.gs_sort_inspect.argtypes = [vp, C.POINTER(SortInfo), vp, sz]
@@ -521,6 +544,51 @@ def export_row(cs, cc, want_wide=False):
         if rc != GS_OK:
             raise GsError(rc, "gs_export_row: bad argument")
     return (rows, wide) if want_wide else rows
+
+
+def adjust_word(rgba, adjust):
+    """gs_adjust_word: the colour word(s) R | G << 8 | B << 16 | A << 24 under the ColourAdjust, by the kernel's own function (one value,
+    or an array of them)"""
+    w = np.ascontiguousarray(rgba, np.uint32)
+    flat, out = w.reshape(-1), C.c_uint32(0)
+    res = np.zeros(flat.size, np.uint32)
+    f, pa, po = load().gs_adjust_word, C.byref(adjust), C.byref(out)
+    for i, v in enumerate(flat.tolist()):
+        rc = f(v, pa, po)
+        if rc != GS_OK:
+            raise GsError(rc, "gs_adjust_word: bad argument")
+        res[i] = out.value
+    return res.reshape(w.shape) if w.ndim else res[0]
+
+
+def adjust_sh_rows(sh_rows, degree, adjust, in_place=False):
+    """gs_adjust_sh_row over rows of 3 (degree+1)^2 f32 each -> float32[n, 3 (degree+1)^2] (in_place: sh_rows itself, a C-contiguous
+    float32 array, is rewritten and returned)"""
+    k = 3 * (int(degree) + 1) ** 2
+    src = sh_rows if in_place else np.ascontiguousarray(sh_rows, np.float32).reshape(-1, k)
+    if in_place and (src.dtype != np.float32 or not src.flags.c_contiguous or src.size % k):
+        raise ValueError("in_place: a C-contiguous float32 array of whole rows expected")
+    out = src if in_place else np.zeros_like(src)
+    f, pa = load().gs_adjust_sh_row, C.byref(adjust)
+    for i in range(src.size // k):
+        rc = f(src.ctypes.data + 4 * k * i, int(degree), pa, out.ctypes.data + 4 * k * i)
+        if rc != GS_OK:
+            raise GsError(rc, "gs_adjust_sh_row: bad argument")
+    return out
+
+
+def _adjust_colour(fn, h, ck, adjust, of):
+    m, v = _of(of)
+    hit = C.c_size_t(0)
+    ck(fn(h, C.byref(adjust), m, v, C.byref(hit)))
+    return hit.value
+
+
+def _replace_splat(fn, h, ck, first, rows):
+    rows = np.ascontiguousarray(np.asarray(rows).view(np.uint8).reshape(-1))
+    if rows.size % 32:
+        raise ValueError("rows must be a multiple of 32 bytes")
+    ck(fn(h, int(first), _p(rows), rows.size // 32))
 
 
 def splat_to_ply(rows, wide=None, sh=None, degree=0):
@@ -791,6 +859,19 @@ class Context:
     def export_ply(self, of="all", sh_degree=3):
         """gs_export_ply: the passing splats as the bytes of an INRIA .ply (uint8 array) with min(sh_degree, stored degree) SH bands"""
         return _export_ply(self._L.gs_export_ply, self._h, self._ck, of, sh_degree)
+
+    # in-place changes: colour and opacity of the splats that pass `of` on the GPU; rows and SH rows written over resident ones
+    def adjust_colour(self, adjust, of="all"):
+        """gs_adjust_colour: the ColourAdjust on the colour word and SH row of every passing splat -> how many pass"""
+        return _adjust_colour(self._L.gs_adjust_colour, self._h, self._ck, adjust, of)
+
+    def replace_splat(self, first, rows):
+        """gs_replace_splat: .splat rows over splats [first, first + len(rows)); every order is dropped, as by a push"""
+        _replace_splat(self._L.gs_replace_splat, self._h, self._ck, first, rows)
+
+    def replace_sh(self, first, sh_rows, degree):
+        rows, n = _sh_rows(sh_rows, degree)
+        self._ck(self._L.gs_replace_sh(self._h, int(first), _p(rows), n, int(degree)))
 
     def state_count(self):
         """(rows in the state store, hidden splats among them)"""
@@ -1178,6 +1259,19 @@ class Multi:
 
     def export_ply(self, of="all", sh_degree=3):
         return _export_ply(self._L.gs_multi_export_ply, self._h, self._ck, of, sh_degree)
+
+    # in-place changes: colour and opacity of the splats that pass `of` on the GPU; rows and SH rows written over resident ones
+    def adjust_colour(self, adjust, of="all"):
+        """gs_adjust_colour: the ColourAdjust on the colour word and SH row of every passing splat -> how many pass"""
+        return _adjust_colour(self._L.gs_multi_adjust_colour, self._h, self._ck, adjust, of)
+
+    def replace_splat(self, first, rows):
+        """gs_replace_splat: .splat rows over splats [first, first + len(rows)); every order is dropped, as by a push"""
+        _replace_splat(self._L.gs_multi_replace_splat, self._h, self._ck, first, rows)
+
+    def replace_sh(self, first, sh_rows, degree):
+        rows, n = _sh_rows(sh_rows, degree)
+        self._ck(self._L.gs_multi_replace_sh(self._h, int(first), _p(rows), n, int(degree)))
 
     def set_option(self, opt, value):
         self._ck(self._L.gs_multi_set_option(self._h, int(opt), int(value)))

@@ -16,6 +16,7 @@
 #include "gs_sh.h"
 #include "gs_device_math.h"
 #include "gs_export.h"
+#include "gs_adjust.h"
 
 namespace {
 
@@ -397,6 +398,30 @@ GS_API int gs_export_row(const float cs[4], const uint32_t cc[4], void *row32, f
     uint32_t w[8];
     gsm::export_row(cs, cc, w, wide);
     memcpy(row32, w, 32);
+    return GS_OK;
+}
+
+// the colour adjustment by the kernels' own functions (gs_adjust.h)
+GS_API int gs_adjust_word(uint32_t rgba, const gs_colour_adjust *adjust, uint32_t *out)
+{
+    gsm::AdjustParams p;
+    if (!adjust || !out || !gsm::adjust_widen(adjust->m, adjust->offset, adjust->alpha_scale, adjust->alpha_offset, p)) return GS_E_BADARG;
+    *out = gsm::adjust_word(rgba, p);
+    return GS_OK;
+}
+
+GS_API int gs_adjust_sh_row(const float *sh_row, int degree, const gs_colour_adjust *adjust, float *out_row)
+{
+    gsm::AdjustParams p;
+    if (!sh_row || !out_row || !adjust || degree < 0 || degree > GS_SH_MAX_DEGREE) return GS_E_BADARG;
+    if (!gsm::adjust_widen(adjust->m, adjust->offset, adjust->alpha_scale, adjust->alpha_offset, p)) return GS_E_BADARG;
+    const int K = gsm::sh_coefs(degree);
+    for (int k = 0; k < K; k++) {                                // (the three old values are read before the three new ones are written: out_row may be sh_row)
+        const float in[3] = { sh_row[k], sh_row[K + k], sh_row[2 * K + k] };
+        float o[3];
+        gsm::adjust_sh_coef(in, k, p, o);
+        out_row[k] = o[0]; out_row[K + k] = o[1]; out_row[2 * K + k] = o[2];
+    }
     return GS_OK;
 }
 

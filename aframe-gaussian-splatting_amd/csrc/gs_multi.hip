@@ -300,6 +300,26 @@ GS_API int gs_multi_compact(gs_multi *m, uint32_t *out_old_index, size_t *out_n)
     return run_all(m, [=](gs_ctx *c, int i) { return gs_compact(c, i == 0 ? out_old_index : nullptr, i == 0 ? out_n : nullptr); });
 }
 
+// (in-place changes: the colour adjustment drops no order, so the gathered sort stays good; replaced rows are a push)
+GS_API int gs_multi_adjust_colour(gs_multi *m, const gs_colour_adjust *adjust, uint8_t state_mask, uint8_t state_value, size_t *out_hit)
+{
+    if (!m) return GS_E_BADARG;
+    return run_all(m, [=](gs_ctx *c, int i) { return gs_adjust_colour(c, adjust, state_mask, state_value, i == 0 ? out_hit : nullptr); });
+}
+
+GS_API int gs_multi_replace_splat(gs_multi *m, size_t first, const void *rows, size_t nrows)
+{
+    if (!m) return GS_E_BADARG;
+    m->have_sort = false;
+    return run_all(m, [=](gs_ctx *c, int) { return gs_replace_splat(c, first, rows, nrows); });
+}
+
+GS_API int gs_multi_replace_sh(gs_multi *m, size_t first, const float *sh_rows, size_t nrows, int degree)
+{
+    if (!m) return GS_E_BADARG;
+    return run_all(m, [=](gs_ctx *c, int) { return gs_replace_sh(c, first, sh_rows, nrows, degree); });
+}
+
 GS_API size_t gs_multi_count(const gs_multi *m) { return (m && !m->f.empty()) ? gs_count(m->f[0]->ctx) : 0; }
 
 GS_API int gs_multi_set_option(gs_multi *m, int option, int64_t value)

@@ -348,6 +348,20 @@ class GaussianSplatting {
     if (!f) throw new RangeError("exportPly: of must be 'all', 'visible' or 'selected'");
     return native.exportPly(this.handle, f[0], f[1], o.shDegree === undefined ? 3 : o.shDegree);
   }
+  // Change resident splats in place.  adjustColour: colour' = matrix (9 numbers, row-major; default the identity) x colour + offset (3, in
+  // byte units), alpha' = alphaScale x alpha + alphaOffset, for the splats of opts.of (as in histogram), on the GPU, bytes and
+  // spherical-harmonics rows alike (gs_splat.h: gs_adjust_colour) -> how many were adjusted.  The order stays good: the next render shows it.
+  adjustColour(opts) {
+    const o = opts || {}, f = PROP_FILTERS[o.of || 'all'];
+    if (!f) throw new RangeError("adjustColour: of must be 'all', 'visible' or 'selected'");
+    return native.adjustColour(this.handle, o.matrix || [1, 0, 0, 0, 1, 0, 0, 0, 1], o.offset || [0, 0, 0],
+      o.alphaScale === undefined ? 1 : o.alphaScale, o.alphaOffset === undefined ? 0 : o.alphaOffset, f[0], f[1]);
+  }
+  // replaceSplat / replaceSh: 32-byte .splat rows (spherical-harmonics rows of `degree`) over the resident ones from index `first` on --
+  // with exportSplat the way to move part of the cloud: export, transform on the host, write back.  Replaced rows drop the order like a
+  // push: the draws show the background until the next tick.
+  replaceSplat(first, rows) { return native.replaceSplat(this.handle, first, rows); }
+  replaceSh(first, rows, degree) { return native.replaceSh(this.handle, first, rows, degree); }
   // real deletion of the hidden splats (the GPU holds the cloud twice for the duration of the call) -> Uint32Array: the old index of
   // every splat that stays
   deleteHidden() {

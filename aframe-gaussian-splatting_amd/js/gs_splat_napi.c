@@ -736,6 +736,67 @@ static napi_value fn_export_ply(napi_env env, napi_callback_info info)
     return ab;
 }
 
+/* ---- in-place changes (gs_splat.h: gs_adjust_colour / gs_replace_splat / gs_replace_sh) */
+/* adjustColour(h, m9, offset3, alphaScale, alphaOffset, stateMask, stateValue) -> splats adjusted */
+static napi_value fn_adjust_colour(napi_env env, napi_callback_info info)
+{
+    napi_value argv[7];
+    if (!get_args(env, info, 7, argv, NULL)) return NULL;
+    gs_ctx *ctx = get_ctx(env, argv[0]); if (!ctx) return NULL;
+    gs_colour_adjust a;
+    double as = 1, ao = 0;
+    uint32_t mask = 0, value = 0;
+    if (!get_floats(env, argv[1], a.m, 9) || !get_floats(env, argv[2], a.offset, 3) || napi_get_value_double(env, argv[3], &as) != napi_ok ||
+        napi_get_value_double(env, argv[4], &ao) != napi_ok || !get_u32(env, argv[5], &mask) || !get_u32(env, argv[6], &value)) {
+        napi_throw_type_error(env, NULL, "adjustColour: (handle, m9, offset3, alphaScale, alphaOffset, stateMask, stateValue)");
+        return NULL;
+    }
+    a.alpha_scale = (float)as; a.alpha_offset = (float)ao;
+    size_t hit = 0;
+    int rc = gs_adjust_colour(ctx, &a, (uint8_t)mask, (uint8_t)value, &hit);
+    if (rc != GS_OK) return throw_gs(env, ctx, rc);
+    return make_count(env, hit);
+}
+
+/* replaceSplat(h, first, rows) -> rows written: 32-byte .splat rows over splats [first, first + rows) */
+static napi_value fn_replace_splat(napi_env env, napi_callback_info info)
+{
+    napi_value argv[3];
+    if (!get_args(env, info, 3, argv, NULL)) return NULL;
+    gs_ctx *ctx = get_ctx(env, argv[0]); if (!ctx) return NULL;
+    double first = 0;
+    void *data; size_t len;
+    if (napi_get_value_double(env, argv[1], &first) != napi_ok || first < 0 || !get_bytes(env, argv[2], &data, &len) || len % 32) {
+        napi_throw_type_error(env, NULL, "replaceSplat: (handle, first, ArrayBuffer or TypedArray of 32-byte rows)");
+        return NULL;
+    }
+    int rc = gs_replace_splat(ctx, (size_t)first, data, len / 32);
+    if (rc != GS_OK) return throw_gs(env, ctx, rc);
+    return make_count(env, len / 32);
+}
+
+/* replaceSh(h, first, rows, degree) -> rows written: tight SH rows of 3 (degree+1)^2 f32 over rows [first, first + rows) of the store */
+static napi_value fn_replace_sh(napi_env env, napi_callback_info info)
+{
+    napi_value argv[4];
+    if (!get_args(env, info, 4, argv, NULL)) return NULL;
+    gs_ctx *ctx = get_ctx(env, argv[0]); if (!ctx) return NULL;
+    double first = 0;
+    void *data; size_t len;
+    int32_t degree = 0;
+    if (napi_get_value_double(env, argv[1], &first) != napi_ok || first < 0 || !get_bytes(env, argv[2], &data, &len) ||
+        napi_get_value_int32(env, argv[3], &degree) != napi_ok) {
+        napi_throw_type_error(env, NULL, "replaceSh: (handle, first, Float32Array, degree)");
+        return NULL;
+    }
+    if (degree < 1 || degree > 3) { napi_throw_range_error(env, NULL, "replaceSh: degree must be 1..3"); return NULL; }
+    const size_t row = 12 * (size_t)((degree + 1) * (degree + 1));
+    if (len % row) { napi_throw_range_error(env, NULL, "replaceSh: whole rows of 3 (degree+1)^2 floats expected"); return NULL; }
+    int rc = gs_replace_sh(ctx, (size_t)first, (const float *)data, len / row, degree);
+    if (rc != GS_OK) return throw_gs(env, ctx, rc);
+    return make_count(env, len / row);
+}
+
 /* selectRange(h, prop, lo, hi, setBits, clearBits, flags) -> splats hit */
 static napi_value fn_select_range(napi_env env, napi_callback_info info)
 {
@@ -1510,6 +1571,7 @@ static napi_value init(napi_env env, napi_value exports)
         { "renderContrib", fn_render_contrib }, { "contribClear", fn_contrib_clear }, { "contribInfo", fn_contrib_info },
         { "propRange", fn_prop_range }, { "histogram", fn_histogram }, { "selectRange", fn_select_range },
         { "exportSplat", fn_export_splat }, { "exportPly", fn_export_ply },
+        { "adjustColour", fn_adjust_colour }, { "replaceSplat", fn_replace_splat }, { "replaceSh", fn_replace_sh },
         { "selectMask", fn_select_mask }, { "maskPolygon", fn_mask_polygon }, { "highlightInfo", fn_highlight_info },
         { "createMulti", fn_create_multi }, { "multiDestroy", fn_multi_destroy }, { "multiPushSplat", fn_multi_push_splat },
         { "multiLoadPly", fn_multi_load_ply }, { "multiClear", fn_multi_clear }, { "multiCount", fn_multi_count },

@@ -250,7 +250,8 @@ GS_API int gs_pick(gs_ctx *ctx, const gs_render_params *p, const int32_t *xy, si
  *     render before the next sort draws the background only, as after a push), and gs_sync() does not draw frames of before the change again by itself.
  *     A state change takes effect at the NEXT sort: a draw uses the last completed order (index.js:201-207).
  *   - gs_stats.n_hidden: the hidden splats the last collected sort skipped.
- * Out of scope: in-place edits of a splat's position or colour, undo. */
+ * Out of scope: in-place edits of a splat's position, rotation or scale ON THE DEVICE (rigid motion: gs_replace_splat takes rows that
+ * were transformed on the host), undo. */
 #define GS_STATE_HIDDEN 1u
 #define GS_STATE_SELECTED 2u
 #define GS_SELECT_INVERT 1u      /* region calls: apply the rule to the splats NOT in the region */
@@ -310,6 +311,48 @@ GS_API int gs_highlight_word(uint32_t rgba, uint32_t option_value, uint32_t *out
  * again over the kept splats when gs_sort_poll collects it (nothing kept: its reply is the empty context's [0]).  Nothing hidden:
  * nothing happens (*out_n = gs_count()). */
 GS_API int gs_compact(gs_ctx *ctx, uint32_t *out_old_index, size_t *out_n);
+/* Changing resident splats in place.
+ * COLOUR AND OPACITY, on the GPU: an affine map of the colour and a linear one of alpha for the splats with (state & state_mask) ==
+ * state_value.  THE RULE -- one function, csrc/gs_adjust.h, called by the kernels and by the two host evaluators below -- is, every
+ * operation IEEE f64, un-fused, on the parameters widened from f32, in this order:
+ *   word   of R | G << 8 | B << 16 | A << 24:  v_c = ((m[3c] * R + m[3c+1] * G) + m[3c+2] * B) + offset[c];  byte c = clamped_u8(v_c);
+ *          A' = clamped_u8(alpha_scale * A + alpha_offset);  clamped_u8: clamp to [0, 255], round to nearest, ties to even, NaN -> 0.
+ *   SH row of degree D, K = (D+1)^2 coefficients per channel (the colour before the clamp is affine in them, so the same map applies):
+ *          sh'[c][k] = (float)((m[3c] * sh[0][k] + m[3c+1] * sh[1][k]) + m[3c+2] * sh[2][k])  for k >= 1, and for k = 0 the same sum
+ *          + ((0.5 * ((m[3c] + m[3c+1]) + m[3c+2]) + offset[c] / 255) - 0.5) / SH_C0, SH_C0 = 0.28209479177387814, before the f32
+ *          rounding.  The three new values of a k come from the three old ones.  Alpha has no SH part.
+ * The identity (unit matrix, zero offsets, alpha 1 and 0) gives back every word, and every finite SH row (its constant is exactly 0; a
+ * coefficient -0 may come back +0).  The byte and the SH row of one splat are adjusted INDEPENDENTLY: bytes clamp, coefficients do
+ * not, so afterwards the degree-0 evaluation of a row need not equal the byte any more.  A parameter that is not finite: GS_E_BADARG. */
+typedef struct gs_colour_adjust {
+    float m[9];          /* row-major 3x3: out channel c reads m[3c+0..2] */
+    float offset[3];     /* in units of one colour byte */
+    float alpha_scale, alpha_offset;   /* alpha' from the alpha byte, byte units */
+} gs_colour_adjust;
+/* The colour word of every passing splat (a splat beyond the state store has state 0) is rewritten in place -- a 4-byte read-modify-write;
+ * nothing else of the record is touched -- and, where the splat has an SH row, that row too.  *out_hit (optional): the passing splats.
+ * Frames in flight read both arrays, so every lane is drained first; the depth sort never reads colour, so NO order is dropped: the
+ * next render of the last completed order shows the change.  gs_sync() does not draw frames of before the change again by itself.
+ * ONE thing the sort does hold of the alpha byte: the sort row's fourth word, (largest scale) x alpha / 255 as packed at push time, on which
+ * the sort culls splats smaller than 0.0001 |depth| (index.js:397, 548).  The sort rows are left alone, so that cull keeps judging by the
+ * alpha of the push: a splat faded to alpha 0 stays in the order (and draws with weight 0), one that was culled stays culled.  A host that
+ * wants the cull to follow writes the rows back with gs_replace_splat, which packs them again.  The
+ * state store is neither grown nor changed; the hidden count and the contribution store stay.  Two streaming kernels of their own on
+ * the context's stream; the call waits for them.  Matrices-only context: GS_E_STATE.  Nothing resident: hit 0, GS_OK. */
+GS_API int gs_adjust_colour(gs_ctx *ctx, const gs_colour_adjust *adjust, uint8_t state_mask, uint8_t state_value, size_t *out_hit);
+/* host, no context, no GPU: one word, and one SH row (tight, as gs_push_sh takes it; degree 0..3; out_row may be sh_row), by the rule
+ * above.  NULL pointers, a parameter that is not finite, a degree out of range: GS_E_BADARG. */
+GS_API int gs_adjust_word(uint32_t rgba, const gs_colour_adjust *adjust, uint32_t *out);
+GS_API int gs_adjust_sh_row(const float *sh_row, int degree, const gs_colour_adjust *adjust, float *out_row);
+/* ROWS: splats [first, first + nrows) are overwritten with .splat rows packed by the pack kernel of gs_push_splat: both records, the sort
+ * row and the strip bound.  States, SH rows, contribution words and gs_count() stay.  Otherwise like a push: lanes drained, every
+ * lane's order dropped, a sort posted with gs_sort_begin is run again when it is collected.  With gs_export_splat (and its wide parts)
+ * this is how a host moves, rotates or scales part of the cloud: export, transform on the host, write back the rows it touched.
+ * first + nrows > gs_count(): GS_E_BADARG, nothing changed.  Matrices-only context: GS_E_STATE.  nrows == 0: GS_OK. */
+GS_API int gs_replace_splat(gs_ctx *ctx, size_t first, const void *rows, size_t nrows);
+/* SH rows [first, first + nrows) of the store are overwritten (tight rows in, padded as by gs_push_sh).  Lanes drained, no order dropped.
+ * A degree other than the store's, or a range beyond gs_sh_count(): GS_E_BADARG. */
+GS_API int gs_replace_sh(gs_ctx *ctx, size_t first, const float *sh_rows, size_t nrows, int degree);
 
 /* Scene compositing inputs (reference: the splat mesh is drawn in three.js' transparent pass with depthTest: true,
  * depthWrite: false over the opaque scene, index.js:177-181): an optional window-space depth buffer of that scene
@@ -445,6 +488,10 @@ GS_API int gs_multi_select_rect(gs_multi *m, const gs_render_params *p, const in
 GS_API int gs_multi_select_mask(gs_multi *m, const gs_render_params *p, const uint8_t *mask, size_t mask_stride, const float *depth_max, uint8_t set_bits,
                                 uint8_t clear_bits, uint32_t flags, size_t *out_hit);
 GS_API int gs_multi_compact(gs_multi *m, uint32_t *out_old_index, size_t *out_n);
+/* the in-place changes on every device; the hit count is devices[0]'s */
+GS_API int gs_multi_adjust_colour(gs_multi *m, const gs_colour_adjust *adjust, uint8_t state_mask, uint8_t state_value, size_t *out_hit);
+GS_API int gs_multi_replace_splat(gs_multi *m, size_t first, const void *rows, size_t nrows);
+GS_API int gs_multi_replace_sh(gs_multi *m, size_t first, const float *sh_rows, size_t nrows, int degree);
 GS_API size_t gs_multi_count(const gs_multi *m);
 GS_API int gs_multi_set_option(gs_multi *m, int option, int64_t value);              /* gs_set_option on every device     */
 /* tick + worker sort for the frame `views` describe (one view, or the two XR eyes with the head camera's view row, index.js:441):
