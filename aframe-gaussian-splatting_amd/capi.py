@@ -14,6 +14,7 @@ from . import build as _build
 GS_OK = 0
 E_BADARG, E_PLY_HEADER, E_PLY_PROP, E_HIP, E_OOM, E_NODEVICE, E_STATE, E_PLY_DATA, E_RETRY = -1, -2, -3, -4, -5, -6, -7, -8, -9
 RENDER_FLIP_Y, RENDER_COUNT_FRAGS, RENDER_NO_EARLY_OUT, RENDER_ASYNC, RENDER_COUNT_EVALUATED = 1, 2, 4, 8, 16
+RENDER_PARALLEL = 32               # a parallel-projection camera (gs_splat.h: "Parallel-projection cameras")
 OPT_PROFILE, OPT_TERMINATION, OPT_NEAR_PERMILLE, OPT_RECORD_STAGED, OPT_PIPELINE_DEPTH, OPT_WIDE_PAIRS, OPT_ENQUEUE_THREADS = 1, 2, 3, 4, 5, 6, 7
 OPT_COMM_SELF_COPY = 8
 OPT_BLEND_SPLIT = 9
@@ -67,6 +68,7 @@ EXPORTS = [
     "gs_export_row", "gs_export_splat", "gs_export_sh", "gs_splat_to_ply", "gs_export_ply", "gs_multi_export_splat", "gs_multi_export_ply",
     "gs_adjust_colour", "gs_adjust_word", "gs_adjust_sh_row", "gs_replace_splat", "gs_replace_sh",
     "gs_multi_adjust_colour", "gs_multi_replace_splat", "gs_multi_replace_sh",
+    "gs_project_record", "gs_ortho_matrix", "gs_projection_info",
 ]
 SURFACE_NONE = 0xFFFFFFFF          # gs_surface.id / gs_hit.id where the transmittance never falls below one half
 
@@ -259,6 +261,10 @@ def load(build_if_missing=True):
         L.gs_mask_polygon.argtypes = [vp, sz, i32, i32, vp, sz]
         L.gs_highlight_info.argtypes = [vp, u32p, u32p]
         L.gs_highlight_word.argtypes = [C.c_uint32, C.c_uint32, u32p]
+    if hasattr(L, "gs_project_record"):                        # (an older build loaded through GS_SPLAT_LIB for an A/B run has none)
+        L.gs_project_record.argtypes = [vp, vp, C.POINTER(RenderParams), vp, C.POINTER(C.c_float), C.POINTER(C.c_int)]
+        L.gs_ortho_matrix.argtypes = [C.c_double] * 6 + [vp]
+        L.gs_projection_info.argtypes = [vp, u32p]
     if hasattr(L, "gs_histogram"):                             # (an older build loaded through GS_SPLAT_LIB for an A/B run has none)
         u8, szp, f64 = C.c_uint8, C.POINTER(sz), C.c_double
         L.gs_prop_eval.argtypes = [vp, vp, i32, vp]
@@ -369,6 +375,36 @@ def projection_matrix(proj):
     a = np.ascontiguousarray(proj, np.float64); o = np.zeros(16, np.float64)
     load().gs_projection_matrix(_p(a), _p(o))
     return o
+
+
+def ortho_matrix(left, right, top, bottom, near, far):
+    """gs_ortho_matrix: three.js Matrix4.makeOrthographic (WebGL convention), column-major f64; feed it through projection_matrix and draw
+    with RENDER_PARALLEL"""
+    o = np.zeros(16, np.float64)
+    rc = load().gs_ortho_matrix(float(left), float(right), float(top), float(bottom), float(near), float(far), _p(o))
+    if rc != GS_OK:
+        raise GsError(rc, "gs_ortho_matrix: bad argument")
+    return o
+
+
+def project_record(cs, cc, params):
+    """gs_project_record: packed records -- cs = float32[n, 4], cc = uint32[n, 4] -- through the kernels' own projection with `params`
+    (RENDER_PARALLEL in its flags or not) -> (records uint32[n, 8] as BUF_PROJECTED holds them, zwin float32[n], visible bool[n])"""
+    a = np.ascontiguousarray(cs, np.float32).reshape(-1, 4)
+    b = np.ascontiguousarray(cc, np.uint32).reshape(-1, 4)
+    if len(a) != len(b):
+        raise ValueError("cs and cc: the same number of records")
+    n = len(a)
+    rec = np.zeros((n, 8), np.float32)
+    zwin, vis = np.zeros(n, np.float32), np.zeros(n, bool)
+    f, z, v = load().gs_project_record, C.c_float(0), C.c_int(0)
+    pa, pb, pr = a.ctypes.data, b.ctypes.data, rec.ctypes.data
+    for i in range(n):
+        rc = f(pa + 16 * i, pb + 16 * i, C.byref(params), pr + 32 * i, C.byref(z), C.byref(v))
+        if rc != GS_OK:
+            raise GsError(rc, "gs_project_record: bad argument")
+        zwin[i], vis[i] = z.value, bool(v.value)
+    return rec.view(np.uint32), zwin, vis
 
 
 def tick_uniforms(cam_world, obj_world, cutout_world=None):
@@ -812,6 +848,12 @@ class Context:
         self._ck(self._L.gs_highlight_info(self._h, C.byref(v), C.byref(last)))
         return v.value, last.value
 
+    def projection_info(self):
+        """1 if the last frame was projected by the parallel kernels (RENDER_PARALLEL), else 0"""
+        last = C.c_uint32(0)
+        self._ck(self._L.gs_projection_info(self._h, C.byref(last)))
+        return last.value
+
     # properties of the resident records (PROP_*): their range, a histogram, selection by value.  A splat takes part in the first two iff
     # (state & state_mask) == state_value
     def prop_range(self, prop, state_mask=0, state_value=0):
@@ -1167,6 +1209,15 @@ class Multi:
         if rc != GS_OK:
             raise GsError(rc, self._L.gs_last_error(h).decode())
         return v.value, last.value
+
+    def ctx_projection_info(self, i):
+        """gs_projection_info of the context on devices[i] (call sync() first)"""
+        last = C.c_uint32(0)
+        h = self._L.gs_multi_ctx(self._h, int(i))
+        rc = self._L.gs_projection_info(h, C.byref(last))
+        if rc != GS_OK:
+            raise GsError(rc, self._L.gs_last_error(h).decode())
+        return last.value
 
     def clear(self):
         self._ck(self._L.gs_multi_clear(self._h))

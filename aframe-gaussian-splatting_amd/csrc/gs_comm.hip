@@ -623,7 +623,8 @@ GS_API int gs_render_gathered(gs_ctx *ctx, const gs_render_params *views, int nv
         if (pcs[i].owner != rank) continue;
         gs_render_params p = views[pcs[i].view];
         p.x0 = pcs[i].x0; p.x1 = pcs[i].x1;
-        p.flags = (flags & ~(uint32_t)GS_RENDER_ASYNC) | (async ? GS_RENDER_ASYNC : 0u);
+        // (the camera model is the view's own: GS_RENDER_PARALLEL of views[v].flags or of `flags`)
+        p.flags = (flags & ~(uint32_t)GS_RENDER_ASYNC) | (async ? GS_RENDER_ASYNC : 0u) | (views[pcs[i].view].flags & GS_RENDER_PARALLEL);
         GsFrameUniforms u;
         first = gs_fill_uniforms(ctx, &p, u);
         uint8_t *slot = L->gstage + (self ? L->gstage_cap / 2 : 0) + j.off[i];
@@ -641,6 +642,9 @@ GS_API int gs_sort_gathered(gs_ctx *ctx, const float view[4], const float *cutou
 {
     if (!ctx || !views) return GS_E_BADARG;
     if (nviews < 1 || nviews > 2) FAILC(GS_E_BADARG, "gs_sort_gathered: %d views (1 or 2)", nviews);
+    for (int v = 0; v < nviews; v++)
+        if ((views[v].flags & GS_RENDER_PARALLEL) && !gsm::parallel_matrix_ok(views[v].projection))
+            FAILC(GS_E_BADARG, "gs_sort_gathered: GS_RENDER_PARALLEL: the bottom row of view %d's projection is not (0, 0, 0, 1)", v);
     GsComm *c = ctx->comm;
     const int world = c && c->comm ? c->world : 1, rank = c && c->comm ? c->rank : 0;
     int widths[2] = { views[0].fb_width, nviews > 1 ? views[1].fb_width : 0 };

@@ -278,10 +278,35 @@ GS_HD void dilated_eigenvalues(float cov00, float cov01, float cov11, float &l1,
     l2 = fmaxf(mid - radius, 0.1f);
 }
 
+// Parallel projection (GS_RENDER_PARALLEL): the 2x3 matrix M that takes an object-space offset to a pixel offset, M[0..2] = row 0 (x),
+// M[3..5] = row 1 (y).  With P's bottom row (0, 0, 0, 1) and an affine mv, pw is 1 and the centre project_splat computes is
+// ((px * 0.5 + 0.5) * vw, (py * 0.5 + 0.5) * vh): M is the exact derivative of that centre -- the same for every splat of the frame, no
+// division, `focal` plays no part.  Every operation f32, in this order, un-fused.  The one place the rule is written: project_splat<true>
+// (kernels and gs_project_record alike) calls it.
+GS_HD void parallel_jacobian(const float *mv, const float *P, float vw, float vh, float M[6])
+{
+    const float hx = 0.5f * vw, hy = 0.5f * vh;
+    const float j00 = hx * P[0], j01 = hx * P[4], j02 = hx * P[8];
+    const float j10 = hy * P[1], j11 = hy * P[5], j12 = hy * P[9];
+    for (int k = 0; k < 3; k++) {
+        M[k] = (j00 * mv[4 * k] + j01 * mv[4 * k + 1]) + j02 * mv[4 * k + 2];
+        M[3 + k] = (j10 * mv[4 * k] + j11 * mv[4 * k + 1]) + j12 * mv[4 * k + 2];
+    }
+}
+// what GS_RENDER_PARALLEL asks of a projection matrix: bottom row (0, 0, 0, 1), compared as f32 (a -0 passes)
+GS_HD bool parallel_matrix_ok(const float *P) { return P[3] == 0.0f && P[7] == 0.0f && P[11] == 0.0f && P[15] == 1.0f; }
+
 // Returns false when the vertex shader would emit nothing for this splat (frustum cull index.js:110-115,
 // far-plane clip, or NaN axes).  mv/P are the f32 uniforms, column-major.
-GS_HD bool project_splat(const float cs[4], const uint32_t cc[4], const float *mv, const float *P, float focal,
-                         float vw, float vh, Projected &o, ProjExtra &x)
+// PAR (GS_RENDER_PARALLEL): the Jacobian lines are parallel_jacobian's instead of the reference's focal / camz; everything before
+// and after them is the same text.
+#if defined(__HIPCC__)
+template <bool PAR = false> __host__ __device__ __forceinline__
+#else
+template <bool PAR = false> static inline
+#endif
+bool project_splat(const float cs[4], const uint32_t cc[4], const float *mv, const float *P, float focal,
+                   float vw, float vh, Projected &o, ProjExtra &x)
 {
     const float cx = cs[0], cy = cs[1], cz = cs[2], scl = cs[3];
     const float camx = ((mv[0] * cx + mv[4] * cy) + mv[8] * cz) + mv[12];
@@ -300,10 +325,17 @@ GS_HD bool project_splat(const float cs[4], const uint32_t cc[4], const float *m
     const float m13 = (float)(int16_t)(cc[1] & 0xFFFF) * scl, m22 = (float)(int16_t)(cc[1] >> 16) * scl;
     const float m23 = (float)(int16_t)(cc[2] & 0xFFFF) * scl, m33 = (float)(int16_t)(cc[2] >> 16) * scl;
 
-    const float j00 = focal / camz, j02 = -(focal * camx) / (camz * camz);
-    const float j11 = -focal / camz, j12 = (focal * camy) / (camz * camz);
-    const float M00 = j00 * mv[0] + j02 * mv[2], M01 = j00 * mv[4] + j02 * mv[6], M02 = j00 * mv[8] + j02 * mv[10];
-    const float M10 = j11 * mv[1] + j12 * mv[2], M11 = j11 * mv[5] + j12 * mv[6], M12 = j11 * mv[9] + j12 * mv[10];
+    float M00, M01, M02, M10, M11, M12;
+    if constexpr (PAR) {
+        float M[6];
+        parallel_jacobian(mv, P, vw, vh, M);
+        M00 = M[0]; M01 = M[1]; M02 = M[2]; M10 = M[3]; M11 = M[4]; M12 = M[5];
+    } else {
+        const float j00 = focal / camz, j02 = -(focal * camx) / (camz * camz);
+        const float j11 = -focal / camz, j12 = (focal * camy) / (camz * camz);
+        M00 = j00 * mv[0] + j02 * mv[2]; M01 = j00 * mv[4] + j02 * mv[6]; M02 = j00 * mv[8] + j02 * mv[10];
+        M10 = j11 * mv[1] + j12 * mv[2]; M11 = j11 * mv[5] + j12 * mv[6]; M12 = j11 * mv[9] + j12 * mv[10];
+    }
     const float t0 = (m11 * M00 + m12 * M01) + m13 * M02;
     const float t1 = (m12 * M00 + m22 * M01) + m23 * M02;
     const float t2 = (m13 * M00 + m23 * M01) + m33 * M02;

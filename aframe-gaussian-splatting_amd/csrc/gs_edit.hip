@@ -92,6 +92,7 @@ __global__ __launch_bounds__(GS_BLOCK) void k_edit_select_sphere(const uint4 *__
 }
 
 struct RectUniforms { float mv[16], proj[16]; float focal, vw, vh; float x0, y0, x1, y1, hm1; };   // the rectangle clipped to the frame; hm1 = fb_height - 1
+template <bool PAR>
 __global__ __launch_bounds__(GS_BLOCK) void k_edit_select_rect(const uint32_t *__restrict__ sorted, const GsControl *__restrict__ ctl, uint32_t n,
                                                                const uint4 *__restrict__ splat, RectUniforms u, uint8_t *__restrict__ state,
                                                                uint32_t set, uint32_t clear, uint32_t invert, uint32_t *__restrict__ hit)
@@ -106,7 +107,7 @@ __global__ __launch_bounds__(GS_BLOCK) void k_edit_select_rect(const uint32_t *_
         const uint32_t cc[4] = { cc4.x, cc4.y, cc4.z, cc4.w };
         gsm::Projected p; gsm::ProjExtra x;
         bool inside = false;
-        if (gsm::project_splat(cs, cc, u.mv, u.proj, u.focal, u.vw, u.vh, p, x)) {   // what k_project calls, with the frame's uniforms
+        if (gsm::project_splat<PAR>(cs, cc, u.mv, u.proj, u.focal, u.vw, u.vh, p, x)) {   // what k_project<.., PAR> calls, with the frame's uniforms
             const float px = floorf(p.cx), py = u.hm1 - floorf(p.cy);   // GL rows (y up) -> image rows (top-down); NaN compares false
             inside = px >= u.x0 && px < u.x1 && py >= u.y0 && py < u.y1;
         }
@@ -119,6 +120,7 @@ __global__ __launch_bounds__(GS_BLOCK) void k_edit_select_rect(const uint32_t *_
 // depths, tight too: a position is taken iff its centre's pixel lies in the frame, the mask is set there and -- with a plane -- the depth
 // k_project writes to zwin is <= the plane's value there (a NaN on either side: not taken)
 struct MaskUniforms { float mv[16], proj[16]; float focal, vw, vh; int32_t W, H; };
+template <bool PAR>
 __global__ __launch_bounds__(GS_BLOCK) void k_edit_select_mask(const uint32_t *__restrict__ sorted, const GsControl *__restrict__ ctl, uint32_t n,
                                                                const uint4 *__restrict__ splat, MaskUniforms u, const uint8_t *__restrict__ mask,
                                                                const float *__restrict__ depth_max, uint8_t *__restrict__ state,
@@ -134,7 +136,7 @@ __global__ __launch_bounds__(GS_BLOCK) void k_edit_select_mask(const uint32_t *_
         const uint32_t cc[4] = { cc4.x, cc4.y, cc4.z, cc4.w };
         gsm::Projected p; gsm::ProjExtra x;
         bool inside = false;
-        if (gsm::project_splat(cs, cc, u.mv, u.proj, u.focal, u.vw, u.vh, p, x)) {   // what k_project calls, with the frame's uniforms
+        if (gsm::project_splat<PAR>(cs, cc, u.mv, u.proj, u.focal, u.vw, u.vh, p, x)) {   // what k_project<.., PAR> calls, with the frame's uniforms
             const float fx = floorf(p.cx), fy = floorf(p.cy);
             if (fx >= 0.0f && fx < (float)u.W && fy >= 0.0f && fy < (float)u.H) {     // (NaN compares false; inside the frame: exact integers)
                 const size_t px = (size_t)(u.H - 1 - (int32_t)fy) * (size_t)u.W + (size_t)(int32_t)fx;   // GL rows (y up) -> image rows (top-down)
@@ -540,8 +542,10 @@ int gs_edit_select_rect(gs_ctx *ctx, gs_ctx *L, const GsFrameUniforms &f, const 
     u.x0 = (float)x0; u.y0 = (float)y0; u.x1 = (float)x1; u.y1 = (float)y1; u.hm1 = (float)(f.H - 1);
     // (the lane's stream holds the order; the owner's stream is idle and the lanes were drained: one stream suffices)
     GS_HIP(hipStreamSynchronize(ctx->stream));
-    hipLaunchKernelGGL(k_edit_select_rect, dim3(stream_grid(ctx->n)), dim3(GS_BLOCK), 0, L->stream, (const uint32_t *)L->sorted, (const GsControl *)L->ctl,
-                       (uint32_t)ctx->n, (const uint4 *)ctx->splat, u, ctx->edit_state, (uint32_t)set, (uint32_t)clear, invert ? 1u : 0u, ctx->edit_cnt);
+    gs_flag((f.flags & GS_RENDER_PARALLEL) != 0, [&](auto PAR) {   // (the camera model of the frame, as launch_project picks k_project's)
+        hipLaunchKernelGGL(k_edit_select_rect<decltype(PAR)::value>, dim3(stream_grid(ctx->n)), dim3(GS_BLOCK), 0, L->stream, (const uint32_t *)L->sorted, (const GsControl *)L->ctl,
+                           (uint32_t)ctx->n, (const uint4 *)ctx->splat, u, ctx->edit_state, (uint32_t)set, (uint32_t)clear, invert ? 1u : 0u, ctx->edit_cnt);
+    });
     GS_HIP(hipGetLastError());
     GS_HIP(hipStreamSynchronize(L->stream));
     return read_counter(ctx, hit);
@@ -557,9 +561,11 @@ int gs_edit_select_mask(gs_ctx *ctx, gs_ctx *L, const GsFrameUniforms &f, const 
     u.focal = f.focal; u.vw = f.vw; u.vh = f.vh; u.W = f.W; u.H = f.H;
     // (the uploads and the counters went to the owner's stream; the lane's stream holds the order: as gs_edit_select_rect)
     GS_HIP(hipStreamSynchronize(ctx->stream));
-    hipLaunchKernelGGL(k_edit_select_mask, dim3(stream_grid(ctx->n)), dim3(GS_BLOCK), 0, L->stream, (const uint32_t *)L->sorted, (const GsControl *)L->ctl,
-                       (uint32_t)ctx->n, (const uint4 *)ctx->splat, u, mask_dev, depth_dev, ctx->edit_state, (uint32_t)set, (uint32_t)clear, invert ? 1u : 0u,
-                       ctx->edit_cnt);
+    gs_flag((f.flags & GS_RENDER_PARALLEL) != 0, [&](auto PAR) {
+        hipLaunchKernelGGL(k_edit_select_mask<decltype(PAR)::value>, dim3(stream_grid(ctx->n)), dim3(GS_BLOCK), 0, L->stream, (const uint32_t *)L->sorted, (const GsControl *)L->ctl,
+                           (uint32_t)ctx->n, (const uint4 *)ctx->splat, u, mask_dev, depth_dev, ctx->edit_state, (uint32_t)set, (uint32_t)clear, invert ? 1u : 0u,
+                           ctx->edit_cnt);
+    });
     GS_HIP(hipGetLastError());
     GS_HIP(hipStreamSynchronize(L->stream));
     return read_counter(ctx, hit);
@@ -825,6 +831,17 @@ GS_API int gs_highlight_info(const gs_ctx *ctx, uint32_t *option_value, uint32_t
         gs_ctx *c = const_cast<gs_ctx *>(ctx);
         for (int i = 0; i < GS_MAX_LANES; i++) if (c->lanes[i]) (void)lane_drain(c->lanes[i]);   // (as gs_get_stats: what the workers were handed is settled)
         *last_frame = c->lanes[c->cur]->hl_frame;
+    }
+    return GS_OK;
+}
+
+GS_API int gs_projection_info(const gs_ctx *ctx, uint32_t *last_frame_parallel)
+{
+    if (!ctx) return GS_E_BADARG;
+    if (last_frame_parallel) {
+        gs_ctx *c = const_cast<gs_ctx *>(ctx);
+        for (int i = 0; i < GS_MAX_LANES; i++) if (c->lanes[i]) (void)lane_drain(c->lanes[i]);   // (as gs_highlight_info)
+        *last_frame_parallel = c->lanes[c->cur]->par_frame;
     }
     return GS_OK;
 }

@@ -269,7 +269,11 @@ GS_API int gs_sort_for(gs_ctx *ctx, const float view[4], const float *cutout16, 
     // a perspective projection whose w does not depend on x or y (three.js PerspectiveCamera, WebXR eye frusta); anything else
     // is sorted whole
     const float *P = strip->projection;
-    const bool persp = P[3] == 0.0f && P[7] == 0.0f && P[15] == 0.0f && P[11] != 0.0f;
+    const bool parallel = (strip->flags & GS_RENDER_PARALLEL) != 0;
+    if (parallel && !gsm::parallel_matrix_ok(P))
+        FAIL(GS_E_BADARG, "gs_sort_for: GS_RENDER_PARALLEL: the projection's bottom row is (%g, %g, %g, %g), not (0, 0, 0, 1)", (double)P[3], (double)P[7], (double)P[11], (double)P[15]);
+    // (a parallel camera: the reach test's bound is the perspective Jacobian's, so such a strip keeps every splat -- the order is gs_sort's)
+    const bool persp = !parallel && P[3] == 0.0f && P[7] == 0.0f && P[15] == 0.0f && P[11] != 0.0f;
     return sort_common(ctx, view, cutout16, persp ? &st : nullptr, out_idx, out_n);
 }
 
@@ -451,6 +455,11 @@ int gs_fill_uniforms(gs_ctx *ctx /* owner: options, adaptive share, scene */, co
     if (p->fb_width <= 0 || p->fb_height <= 0 || p->fb_width > 65535 * GS_TILE || p->fb_height > 65535 * GS_TILE)
         FAIL(GS_E_BADARG, "bad framebuffer size %dx%d", p->fb_width, p->fb_height);
     if (p->x0 < 0 || p->x1 > p->fb_width || p->x0 >= p->x1) FAIL(GS_E_BADARG, "bad strip [%d,%d) for width %d", p->x0, p->x1, p->fb_width);
+    // a parallel camera (GS_RENDER_PARALLEL): w must not depend on the position -- checked here, the one door every frame, strip, eye, pick
+    // and screen-space selection goes through
+    if ((p->flags & GS_RENDER_PARALLEL) && !gsm::parallel_matrix_ok(p->projection))
+        FAIL(GS_E_BADARG, "GS_RENDER_PARALLEL: the projection's bottom row is (%g, %g, %g, %g), not (0, 0, 0, 1)", (double)p->projection[3], (double)p->projection[7],
+             (double)p->projection[11], (double)p->projection[15]);
     memcpy(u.mv, p->model_view, sizeof u.mv); memcpy(u.proj, p->projection, sizeof u.proj);
     u.W = p->fb_width; u.H = p->fb_height; u.x0 = p->x0; u.x1 = p->x1;
     u.out_pitch = p->x1 - p->x0;
@@ -639,6 +648,7 @@ int gs_render_uniforms(gs_ctx *ctx, const GsFrameUniforms &u_in, void *device_rg
     L->stats.surface = u.surface ? 1u : 0u;
     L->stats.antialias = u.antialias ? 1u : 0u;
     L->hl_frame = u.highlight ? 1u : 0u;
+    L->par_frame = (u.flags & GS_RENDER_PARALLEL) ? 1u : 0u;
     u.need_seed = L->share_lane.need_seed_pending; L->share_lane.need_seed_pending = 0;  // (a seed for the lane's need words travels with its next frame)
     bool async = (u.flags & GS_RENDER_ASYNC) && !(u.flags & GS_RENDER_COUNT_FRAGS);
     // A context that has not MEASURED its share yet (fresh, cleared, the share un-pinned) draws its first two-round frame synchronously

@@ -349,6 +349,43 @@ GS_API int gs_antialias_factor(const float cov[3], float *out_c)
     return GS_OK;
 }
 
+// one packed record through the kernels' own projection (gsm::project_splat<PAR>), with gs_render's focal rule (gs_fill_uniforms)
+GS_API int gs_project_record(const float cs[4], const uint32_t cc[4], const gs_render_params *p, float record[8], float *zwin, int *visible)
+{
+    if (!cs || !cc || !p || !record || !zwin || !visible) return GS_E_BADARG;
+    if (p->fb_width <= 0 || p->fb_height <= 0) return GS_E_BADARG;
+    const bool par = (p->flags & GS_RENDER_PARALLEL) != 0;
+    if (par && !gsm::parallel_matrix_ok(p->projection)) return GS_E_BADARG;
+    const float focal = p->focal > 0 ? p->focal : (float)(((double)p->fb_height / 2.0) * fabs((double)p->projection[5]));
+    const float vw = (float)p->fb_width, vh = (float)p->fb_height;
+    gsm::Projected o; gsm::ProjExtra x;
+    memset(&o, 0, sizeof o); memset(&x, 0, sizeof x);
+    const bool vis = par ? gsm::project_splat<true>(cs, cc, p->model_view, p->projection, focal, vw, vh, o, x)
+                         : gsm::project_splat<false>(cs, cc, p->model_view, p->projection, focal, vw, vh, o, x);
+    *visible = vis ? 1 : 0;
+    memset(record, 0, 8 * sizeof(float));
+    *zwin = 0.0f;
+    if (vis) {
+        memcpy(record, &o, 8 * sizeof(float));                       // (Projected is the record: cx, cy, ax, ay, bx, by, the colour word, alpha)
+        *zwin = x.zndc * 0.5f + 0.5f;
+    }
+    return GS_OK;
+}
+
+// three.js Matrix4.makeOrthographic, WebGL coordinate system (z in [-1, 1]), in its operation order
+GS_API int gs_ortho_matrix(double left, double right, double top, double bottom, double near_, double far_, double out[16])
+{
+    if (!out) return GS_E_BADARG;
+    const double w = 1.0 / (right - left), h = 1.0 / (top - bottom), pp = 1.0 / (far_ - near_);
+    const double x = (right + left) * w, y = (top + bottom) * h;
+    const double z = (far_ + near_) * pp, zinv = -2.0 * pp;
+    out[0] = 2.0 * w; out[4] = 0.0;     out[8] = 0.0;   out[12] = -x;
+    out[1] = 0.0;     out[5] = 2.0 * h; out[9] = 0.0;   out[13] = -y;
+    out[2] = 0.0;     out[6] = 0.0;     out[10] = zinv; out[14] = -z;
+    out[3] = 0.0;     out[7] = 0.0;     out[11] = 0.0;  out[15] = 1.0;
+    return GS_OK;
+}
+
 GS_API int gs_highlight_word(uint32_t rgba, uint32_t option_value, uint32_t *out)
 {
     if (!out) return GS_E_BADARG;

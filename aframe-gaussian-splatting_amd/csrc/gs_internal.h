@@ -222,6 +222,7 @@ struct gs_ctx {
     int aa_opt;                    // GS_OPT_ANTIALIAS (owner; taken per frame by gs_fill_uniforms)
     uint32_t hl_opt;               // GS_OPT_HIGHLIGHT (owner; taken per frame by gs_fill_uniforms)
     uint32_t hl_frame;             // lane: 1 if the lane's last frame was projected by an HL instantiation (gs_highlight_info; kept out of gs_stats)
+    uint32_t par_frame;            // lane: 1 if the lane's last frame was projected by a PAR instantiation (gs_projection_info; kept out of gs_stats too)
     uint8_t *mask_buf; size_t mask_cap_bytes;   // owner: gs_select_mask's mask and depth plane on the device (grow-only scratch)
     // owner: what gs_prop_range / gs_histogram run on -- a stream of their own (they read the resident arrays only and wait for no
     // frame) and GS_PROP_BUF_BYTES of device memory for their counts and partials; both made by the first call

@@ -112,6 +112,12 @@ int run_all(gs_multi *m, const std::function<int(gs_ctx *, int)> &fn) { const in
 int check_views(gs_multi *m, const gs_render_params *views, int nviews)
 {
     if (!views || nviews < 1 || nviews > 2) { snprintf(m->err, sizeof m->err, "1 or 2 views"); return GS_E_BADARG; }
+    // (a parallel camera's matrix is refused here, on the caller's thread: the contexts would only report it at gs_multi_sync)
+    for (int v = 0; v < nviews; v++)
+        if ((views[v].flags & GS_RENDER_PARALLEL) && !gsm::parallel_matrix_ok(views[v].projection)) {
+            snprintf(m->err, sizeof m->err, "GS_RENDER_PARALLEL: the bottom row of view %d's projection is not (0, 0, 0, 1)", v);
+            return GS_E_BADARG;
+        }
     return GS_OK;
 }
 
@@ -363,7 +369,7 @@ static int render_once(gs_multi *m, const gs_render_params *views, int nviews, u
         int rc = pieces_of(rank, a.world, a.views, a.nviews, mine, &n);
         for (int i = 0; rc == GS_OK && i < n; i++) {
             gs_render_params p = a.views[mine[i].view];
-            p.x0 = mine[i].x0; p.x1 = mine[i].x1; p.flags = a.flags;
+            p.x0 = mine[i].x0; p.x1 = mine[i].x1; p.flags = a.flags | (p.flags & GS_RENDER_PARALLEL);   // (the camera model is the view's own)
             const size_t st = a.stride ? a.stride : (size_t)p.fb_width * 4;
             rc = gs_render(c, &p, a.host[mine[i].view] + (size_t)p.x0 * 4, st);      // the strip lands in its columns of the caller's frame
         }

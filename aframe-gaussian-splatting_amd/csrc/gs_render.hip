@@ -141,7 +141,10 @@ __device__ __forceinline__ uint32_t sh_colour_word(const GsFrameUniforms &u, uin
 // splat is written, counted and binned whatever the factor (0 included), so geometry, coverage and every count stay what they are.
 // HL (highlighted selection, GS_OPT_HIGHLIGHT): a splat that writes its record and whose state byte has GS_STATE_SELECTED blends the RGB
 // bytes of its colour word -- after SH -- towards the frame's highlight colour (gsm::highlight_word); one byte load per record written.
-template <int ROUND, bool RUNS, bool SH, bool AA, bool HL>
+// PAR (parallel projection, GS_RENDER_PARALLEL): the splat's Jacobian is gsm::parallel_jacobian of the frame's matrices -- formed per thread
+// from the uniforms the kernel already holds in scalar registers (18 multiplications and 12 additions, fewer instructions than the four
+// IEEE divisions of focal / camz they stand in for), so the frame uniforms keep their layout; the record, binning and blend are the same.
+template <int ROUND, bool RUNS, bool SH, bool AA, bool HL, bool PAR>
 __device__ __forceinline__ void k_project_body(const uint32_t *__restrict__ sorted, const uint4 *__restrict__ splat,
                                                const GsFrameUniforms &u, gsm::Projected *__restrict__ proj, uint2 *__restrict__ rect,
                                                uint32_t *__restrict__ tile_count, uint32_t *__restrict__ spine,
@@ -177,7 +180,7 @@ __device__ __forceinline__ void k_project_body(const uint32_t *__restrict__ sort
             const float cs[4] = { __uint_as_float(cs4.x), __uint_as_float(cs4.y), __uint_as_float(cs4.z), __uint_as_float(cs4.w) };
             const uint32_t cc[4] = { cc4.x, cc4.y, cc4.z, cc4.w };
             gsm::Projected p; gsm::ProjExtra x;
-            if (gsm::project_splat(cs, cc, u.mv, u.proj, u.focal, u.vw, u.vh, p, x)) {
+            if (gsm::project_splat<PAR>(cs, cc, u.mv, u.proj, u.focal, u.vw, u.vh, p, x)) {
                 float xmin, xmax, ymin, ymax;
                 gsm::splat_pixel_bounds(p, x, xmin, xmax, ymin, ymax);
                 // clamp in float (bounds can be far outside the int range), then to the strip / screen
@@ -276,15 +279,15 @@ __device__ __forceinline__ void k_project_body(const uint32_t *__restrict__ sort
     if (threadIdx.x == 0) part_vis[blockIdx.x] = s_vis;
 }
 
-// plain, with view-dependent colour (SH), with compensated opacity (AA), with the selection highlighted (HL), or any of them together
-template <int ROUND, bool RUNS, bool SH, bool AA, bool HL>
+// plain, with view-dependent colour (SH), with compensated opacity (AA), with the selection highlighted (HL), for a parallel camera (PAR), or any of them together
+template <int ROUND, bool RUNS, bool SH, bool AA, bool HL, bool PAR>
 __global__ __launch_bounds__(GS_BLOCK) void k_project(const uint32_t *__restrict__ sorted, const uint4 *__restrict__ splat,
                                                       GsFrameUniforms u, gsm::Projected *__restrict__ proj, uint2 *__restrict__ rect,
                                                       uint32_t *__restrict__ tile_count, uint32_t *__restrict__ spine,
                                                       uint32_t *__restrict__ part_vis, const uint32_t *__restrict__ mask,
                                                       float *__restrict__ zwin, GsControl *ctl)
 {
-    k_project_body<ROUND, RUNS, SH, AA, HL>(sorted, splat, u, proj, rect, tile_count, spine, part_vis, mask, zwin, ctl);
+    k_project_body<ROUND, RUNS, SH, AA, HL, PAR>(sorted, splat, u, proj, rect, tile_count, spine, part_vis, mask, zwin, ctl);
 }
 
 // One workgroup: exclusive scan of the per-chunk totals (spine) -> chunk base offsets, I = grand total (refused and
@@ -1944,7 +1947,7 @@ int bits_for(uint32_t n) { int b = 1; while (b < 32 && (1u << b) < n) b++; retur
 // The kernels of a round as body functors (gs_internal.h: GS_BODY), each with its plain kernel: what gs_launch<NF, F, ...> launches for one frame
 // (the plain kernel) and for a pair (k_twin<F, ...>).  A NEW KERNEL gets its body, its thin __global__ wrapper, one line here and one gs_launch
 // in the sequence below -- once, for both frame counts.
-template <int ROUND, bool RUNS, bool SH, bool AA, bool HL> GS_BODY(F_project, (k_project<ROUND, RUNS, SH, AA, HL>), (k_project_body<ROUND, RUNS, SH, AA, HL>));
+template <int ROUND, bool RUNS, bool SH, bool AA, bool HL, bool PAR> GS_BODY(F_project, (k_project<ROUND, RUNS, SH, AA, HL, PAR>), (k_project_body<ROUND, RUNS, SH, AA, HL, PAR>));
 template <int ROUND> GS_BODY(F_row_scan, (k_row_scan<ROUND>), (k_row_scan_body<ROUND>));
 template <int ROUND, bool W16> GS_BODY(F_emit_runs, (k_emit_runs<ROUND, W16>), (k_emit_runs_body<ROUND, W16>));
 template <int ROUND> GS_BODY(F_seg_count, (k_seg_count<ROUND>), (k_seg_count_body<ROUND>));
@@ -2061,7 +2064,7 @@ bool row_walk_round(const GsFrameUniforms &u)
 }
 
 // the projection of a round: plain, with view-dependent colour (GS_OPT_SH_DEGREE), with compensated opacity (GS_OPT_ANTIALIAS), with the selection highlighted
-// (GS_OPT_HIGHLIGHT and a non-empty state store), or any of them together.
+// (GS_OPT_HIGHLIGHT and a non-empty state store), for a parallel camera (GS_RENDER_PARALLEL), or any of them together.
 // RUNS: a span-list round (row counts per 256-splat chunk) / the pair records (tiles touched per chunk: the spine).  F[k]: the frame as
 // the kernel sees it
 template <int ROUND, bool RUNS, int NF>
@@ -2073,8 +2076,9 @@ void launch_project(gs_ctx *const S[], const GsFrameUniforms F[], uint32_t g)
                             S[k]->part_vis, (const uint32_t *)S[k]->unsat_mask, S[k]->zwin, S[k]->ctl);
     };
     gs_flag(F[0].sh_degree != 0, [&](auto SH) { gs_flag(F[0].antialias != 0, [&](auto AA) { gs_flag(F[0].highlight != 0, [&](auto HL) {
-        gs_launch<NF, F_project<ROUND, RUNS, decltype(SH)::value, decltype(AA)::value, decltype(HL)::value>, GS_BLOCK>(g, st, 0, args);
-    }); }); });
+        gs_flag((F[0].flags & GS_RENDER_PARALLEL) != 0, [&](auto PAR) {
+            gs_launch<NF, F_project<ROUND, RUNS, decltype(SH)::value, decltype(AA)::value, decltype(HL)::value, decltype(PAR)::value>, GS_BLOCK>(g, st, 0, args);
+        }); }); }); });
 }
 
 // one round with span lists: project (+ row counts) -> row scan -> runs -> lists -> blend (row walk: no lists)

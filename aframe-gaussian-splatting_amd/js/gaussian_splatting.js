@@ -28,6 +28,10 @@ const schema = {                                   // index.js:2-7
 const OPT_SH_DEGREE = 19;
 const OPT_ANTIALIAS = 20;
 const OPT_HIGHLIGHT = 23;
+// beyond the reference: GS_RENDER_PARALLEL, for params.flags -- pass { flags: RENDER_PARALLEL } as the `options` of render / frame / renderSurface /
+// pick / selectRect / selectMask when `camera` is a THREE.OrthographicCamera (its projectionMatrix has the bottom row 0, 0, 0, 1): the splats are
+// then projected by that camera's constant Jacobian instead of the reference's perspective focal / z (index.js:127-131)
+const RENDER_PARALLEL = 32;
 const ROW_LENGTH = 3 * 4 + 3 * 4 + 4 + 4;          // index.js:227
 
 const PROP_NAMES = ['x', 'y', 'z', 'red', 'green', 'blue', 'alpha', 'size2'];   // GS_PROP_*
@@ -490,4 +494,4 @@ function register(AFRAME) {
   });
 }
 
-module.exports = { schema, GaussianSplatting, register, native };
+module.exports = { schema, GaussianSplatting, register, native, RENDER_PARALLEL };

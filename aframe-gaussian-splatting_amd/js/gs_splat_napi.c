@@ -1588,6 +1588,8 @@ static napi_value init(napi_env env, napi_value exports)
     }
     napi_value v;
     if (napi_create_uint32(env, gs_version(), &v) == napi_ok) napi_set_named_property(env, exports, "version", v);
+    /* params.flags of a parallel-projection camera (an OrthographicCamera's projectionMatrix): every call that takes params honours it */
+    if (napi_create_uint32(env, GS_RENDER_PARALLEL, &v) == napi_ok) napi_set_named_property(env, exports, "RENDER_PARALLEL", v);
     return exports;
 }
 

@@ -171,6 +171,9 @@ GS_API int gs_sort_poll(gs_ctx *ctx, int wait, uint32_t *out_idx, uint32_t *out_
                                     stay valid and unread until gs_sync(), one buffer per frame in flight, and should be
                                     page-locked (gs_host_alloc) for the copy to overlap the following frames.           */
 
+#define GS_RENDER_PARALLEL 32u   /* a PARALLEL-PROJECTION camera (orthographic, sheared or not): "Parallel-projection cameras" below.  (Bit 5 was free:
+                                    the library keeps no internal flags in gs_render_params.flags or in its frame uniforms.)               */
+
 typedef struct gs_render_params {
     float model_view[16]; /* gsModelViewMatrix, column-major (getModelViewMatrix, index.js:467-487)      */
     float projection[16]; /* gsProjectionMatrix, column-major (getProjectionMatrix, index.js:456-466)    */
@@ -205,6 +208,44 @@ GS_API int gs_sort_for(gs_ctx *ctx, const float view[4], const float *cutout16, 
 
 /* XR: two eyes share one sort order from the head camera (index.js:441) -- two params, two images. */
 GS_API int gs_render_stereo(gs_ctx *ctx, const gs_render_params eyes[2], uint8_t *rgba_out[2], size_t stride);
+
+/* ---- Parallel-projection cameras (no reference counterpart: the vertex shader's Jacobian is the perspective focal / camz, index.js:127-131) ----
+ * Axis-aligned top, front and side views of an editing host: a rectangle or lasso selects a prism, not a frustum, and sizes compare across
+ * depth.  Params whose flags carry GS_RENDER_PARALLEL are projected by the rule below -- a frame, a strip, each eye of gs_render_stereo, a
+ * surface or contribution frame, gs_pick, gs_select_rect / gs_select_mask, gathered and gs_multi frames (there the camera model is the
+ * VIEW's own: the bit is taken from views[v].flags, or from the call's `flags` for all views).  Without the flag nothing changes: such a
+ * frame launches the kernels it launched before (the rule sits behind a template flag of k_project and of the two selection kernels).
+ *   - projection must have P[3] == 0, P[7] == 0, P[11] == 0 and P[15] == 1, compared as f32 (a -0 passes); otherwise the call -- any entry
+ *     point that takes params, gs_sort_for / gs_sort_gathered / gs_multi_sort included -- returns GS_E_BADARG with a message.  Rows 0..2 are
+ *     free: sheared (oblique) parallel projections work.  gs_ortho_matrix + gs_projection_matrix give the usual box.  `focal` is ignored.
+ *   - THE RULE (csrc/gs_device_math.h: gsm::parallel_jacobian, called by the kernels and by gs_project_record), f32, un-fused, in this order:
+ *       hx = 0.5f * vw;  hy = 0.5f * vh;
+ *       j00 = hx * P[0]; j01 = hx * P[4]; j02 = hx * P[8];     j10 = hy * P[1]; j11 = hy * P[5]; j12 = hy * P[9];
+ *       M0k = (j00 * mv[4k] + j01 * mv[4k+1]) + j02 * mv[4k+2];   M1k = (j10 * mv[4k] + j11 * mv[4k+1]) + j12 * mv[4k+2];   k = 0, 1, 2
+ *     M replaces the reference's M = J * mat3(modelView) (index.js:127-133); it is the exact derivative of the centre the projection already
+ *     computes, the same for every splat of the frame.  Everything else is the perspective text: the clip-space position, the 1.2 bounds
+ *     and near-plane culls (pw is camw: 1 for an affine model_view), the covariance, the 0.3 px^2 dilation, the eigenvalues and axes, the
+ *     zndc > 1 cull, the record, and the factor of GS_OPT_ANTIALIAS.  Binning, every blend path and write-out see the record only.
+ *   - THE DEPTH SORT is untouched: along the view row it is already the right order for a parallel camera, and both of its culls stay --
+ *     splats behind the camera plane are dropped, and so are splats smaller than 0.0001 |depth| (index.js:548).  Depth influences nothing
+ *     else in such a frame, so a host should PARK A PARALLEL CAMERA JUST OUTSIDE THE CLOUD, not far away: at a large distance the size cull
+ *     removes small splats that the frame would draw at full size.
+ *   - gs_sort_for / gs_sort_gathered with the flag keep every splat (the strip's reach bound is the perspective Jacobian's): the returned
+ *     order is gs_sort's and the pixels are bit-identical.  A parallel reach bound in the strip depth kernels is out of scope.
+ *   - GS_OPT_SH_DEGREE frames keep evaluating the colour from the point gs_camera_in_object gives (the camera's position, not a constant
+ *     view direction: out of scope).  GS_OPT_ANTIALIAS and GS_OPT_HIGHLIGHT combine unchanged.
+ *   - GS_OPT_FRAME_BATCH: two queued frames that both carry the flag pair up; a frame with it and one without go out alone, as frames
+ *     with different flags always have.
+ * Out of scope: a parallel reach bound for strip sorts, a constant SH direction, fisheye or other camera models. */
+/* One packed record (cs = the centre/scale texel, cc = the covariance/colour texel: gs_download(GS_BUF_SPLAT) rows) through the kernels' own
+ * projection function, with or without GS_RENDER_PARALLEL in p->flags; host only, no context.  The `focal` rule is gs_render's.  record:
+ * the eight words GS_BUF_PROJECTED holds (cx, cy, ax, ay, bx, by, the colour word, alpha -- NOT compensated by GS_OPT_ANTIALIAS);
+ * *zwin = zndc * 0.5f + 0.5f; *visible = 0 where the projection emits nothing (record and *zwin are then zero).  NULL pointers, a
+ * non-positive frame size, or the flag with a matrix that fails the check above: GS_E_BADARG. */
+GS_API int gs_project_record(const float cs[4], const uint32_t cc[4], const gs_render_params *p, float record[8], float *zwin, int *visible);
+/* Whether the last frame of the current frame's lane was projected by the parallel kernels (1 / 0), as gs_highlight_info reports the
+ * highlight.  The pointer may be NULL. */
+GS_API int gs_projection_info(const gs_ctx *ctx, uint32_t *last_frame_parallel);
 
 /* ---- surface output (no reference counterpart: the material has depthWrite: false, index.js:177-181, so nothing tells a host what
  * lies under a pixel) ------------------------------------------------------------------------------------------------------
@@ -570,6 +611,10 @@ GS_API int gs_multi_sync(gs_multi *m);
 GS_API void gs_model_view_matrix(const double cam_world[16], const double obj_world[16], double out[16]);
 /* getProjectionMatrix: camera.projectionMatrix -> gsProjectionMatrix */
 GS_API void gs_projection_matrix(const double proj[16], double out[16]);
+/* three.js Matrix4.makeOrthographic(left, right, top, bottom, near, far), WebGL convention (z to [-1, 1]), column-major f64, in three.js'
+ * operation order: an OrthographicCamera's projectionMatrix.  Feed it through gs_projection_matrix like any camera.projectionMatrix and
+ * draw with GS_RENDER_PARALLEL.  out NULL: GS_E_BADARG. */
+GS_API int gs_ortho_matrix(double left, double right, double top, double bottom, double near_plane, double far_plane, double out[16]);
 /* tick: the two messages posted to the worker: view[4] and (if cutout_world != NULL) cutout[16] */
 GS_API void gs_tick_uniforms(const double cam_world[16], const double obj_world[16], const double *cutout_world,
                              float view[4], float cutout[16]);
