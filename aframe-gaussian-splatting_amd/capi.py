@@ -69,7 +69,10 @@ EXPORTS = [
     "gs_adjust_colour", "gs_adjust_word", "gs_adjust_sh_row", "gs_replace_splat", "gs_replace_sh",
     "gs_multi_adjust_colour", "gs_multi_replace_splat", "gs_multi_replace_sh",
     "gs_project_record", "gs_ortho_matrix", "gs_projection_info",
+    "gs_cply_info", "gs_cply_to_splat", "gs_cply_sh_host", "gs_splat_to_cply", "gs_log_fixed", "gs_load_cply", "gs_cply_to_splat_gpu", "gs_export_cply",
+    "gs_multi_load_cply", "gs_multi_export_cply",
 ]
+CPLY_MORTON = 1                    # gs_splat_to_cply / gs_export_cply flags: rows in stable Morton order
 SURFACE_NONE = 0xFFFFFFFF          # gs_surface.id / gs_hit.id where the transmittance never falls below one half
 
 
@@ -286,6 +289,17 @@ def load(build_if_missing=True):
         for pre in ("gs_", "gs_multi_"):
             getattr(L, pre + "export_splat").argtypes = [vp, u8, u8, vp, vp, vp, szp]
             getattr(L, pre + "export_ply").argtypes = [vp, u8, u8, i32, vp, szp]
+    if hasattr(L, "gs_load_cply"):                             # (likewise)
+        u8, szp = C.c_uint8, C.POINTER(sz)
+        L.gs_cply_info.argtypes = [vp, sz, szp, szp, C.POINTER(i32), C.POINTER(i32), C.c_char_p, sz]
+        L.gs_cply_to_splat.argtypes = [vp, sz, vp, vp, szp, C.c_char_p, sz]
+        L.gs_cply_sh_host.argtypes = [vp, sz, i32, vp, szp, C.POINTER(i32), C.c_char_p, sz]
+        L.gs_splat_to_cply.argtypes = [vp, vp, vp, sz, i32, sz, C.c_uint32, vp, vp, szp]
+        L.gs_log_fixed.argtypes = [C.c_double, C.POINTER(C.c_double)]
+        L.gs_cply_to_splat_gpu.argtypes = [vp, vp, sz, vp, vp, szp]
+        for pre in ("gs_", "gs_multi_"):
+            getattr(L, pre + "load_cply").argtypes = [vp, vp, sz]
+            getattr(L, pre + "export_cply").argtypes = [vp, u8, u8, i32, C.c_uint32, vp, vp, szp]
     if hasattr(L, "gs_adjust_colour"):                         # (likewise)
         L.gs_adjust_word.argtypes = [C.c_uint32, C.POINTER(ColourAdjust), u32p]
         L.gs_adjust_sh_row.argtypes = [vp, i32, C.POINTER(ColourAdjust), vp]
@@ -653,6 +667,101 @@ def splat_to_ply(rows, wide=None, sh=None, degree=0):
     return out
 
 
+def cply_info(ply_bytes):
+    """gs_cply_info: the header of a compressed .ply -> dict(splats, chunks, sh_degree, chunk_floats); GsError (GS_E_PLY_HEADER) for anything
+    else, an INRIA .ply included: that is the sniff"""
+    buf = np.frombuffer(bytes(ply_bytes), np.uint8)
+    n, c = C.c_size_t(0), C.c_size_t(0); d, cf = C.c_int(0), C.c_int(0); err = C.create_string_buffer(256)
+    rc = load().gs_cply_info(_p(buf), buf.size, C.byref(n), C.byref(c), C.byref(d), C.byref(cf), err, 256)
+    if rc != GS_OK:
+        raise GsError(rc, err.value.decode())
+    return {"splats": n.value, "chunks": c.value, "sh_degree": d.value, "chunk_floats": cf.value}
+
+
+def _cply_rows(call, ck, buf, want_wide):
+    n = C.c_size_t(0)
+    ck(call(_p(buf), buf.size, None, None, C.byref(n)))
+    rows = np.zeros((n.value, 32), np.uint8)
+    wide = np.zeros((n.value, 7), np.float32) if want_wide else None
+    if n.value:
+        ck(call(_p(buf), buf.size, _p(rows), _p(wide), C.byref(n)))
+    return (rows, wide) if want_wide else rows
+
+
+def cply_to_splat(ply_bytes, want_wide=False):
+    """gs_cply_to_splat: a compressed .ply -> its rows in file order (uint8[n, 32]) [, their wide parts (float32[n, 7])]"""
+    buf = np.frombuffer(bytes(ply_bytes), np.uint8)
+    err = C.create_string_buffer(256)
+
+    def ck(rc):
+        if rc != GS_OK:
+            raise GsError(rc, err.value.decode())
+    return _cply_rows(lambda *a: load().gs_cply_to_splat(*a, err, 256), ck, buf, want_wide)
+
+
+def cply_sh(ply_bytes, degree=3):
+    """gs_cply_sh_host: the SH rows of a compressed .ply in file order -> (float32[n, 3 (D+1)^2], D), D = min(degree, the file's)"""
+    buf = np.frombuffer(bytes(ply_bytes), np.uint8)
+    n = C.c_size_t(0); d = C.c_int(-1); err = C.create_string_buffer(256)
+    rc = load().gs_cply_sh_host(_p(buf), buf.size, int(degree), None, C.byref(n), C.byref(d), err, 256)
+    if rc != GS_OK:
+        raise GsError(rc, err.value.decode())
+    out = np.zeros((n.value, 3 * (d.value + 1) ** 2), np.float32)
+    if n.value:
+        rc = load().gs_cply_sh_host(_p(buf), buf.size, int(degree), _p(out), C.byref(n), C.byref(d), err, 256)
+        if rc != GS_OK:
+            raise GsError(rc, err.value.decode())
+    return out, d.value
+
+
+def splat_to_cply(rows, wide=None, sh=None, degree=0, morton=False, want_index=False):
+    """gs_splat_to_cply: splat_to_ply's inputs -> the bytes of a compressed .ply (uint8 array) [, the input row of every output row]"""
+    r = np.ascontiguousarray(np.asarray(rows).view(np.uint8).reshape(-1))
+    if r.size % 32:
+        raise ValueError("rows must be a multiple of 32 bytes")
+    n = r.size // 32
+    w = None
+    if wide is not None:
+        w = np.ascontiguousarray(wide, np.float32).reshape(-1)
+        if w.size != 7 * n:
+            raise ValueError("wide: seven floats per row")
+    s, ns = None, 0
+    if sh is not None:
+        s, ns = _sh_rows(sh, degree)
+    flags = CPLY_MORTON if morton else 0
+    nb = C.c_size_t(0)
+    rc = load().gs_splat_to_cply(_p(r), _p(w), _p(s), ns, int(degree), n, flags, None, None, C.byref(nb))
+    if rc != GS_OK:
+        raise GsError(rc, "gs_splat_to_cply: bad argument")
+    out = np.zeros(nb.value, np.uint8)
+    index = np.zeros(n, np.uint32) if want_index else None
+    rc = load().gs_splat_to_cply(_p(r), _p(w), _p(s), ns, int(degree), n, flags, _p(index), _p(out), C.byref(nb))
+    if rc != GS_OK:
+        raise GsError(rc, "gs_splat_to_cply: bad argument")
+    return (out, index) if want_index else out
+
+
+def log_fixed(x):
+    """gs_log_fixed: the encoder's logarithm (the same bits on the host and on the device)"""
+    out = C.c_double(0.0)
+    load().gs_log_fixed(float(x), C.byref(out))
+    return out.value
+
+
+def _export_cply(fn, count_fn, h, ck, of, sh_degree, morton, want_index):
+    m, v = _of(of)
+    flags = CPLY_MORTON if morton else 0
+    nb, n = C.c_size_t(0), C.c_size_t(0)
+    ck(fn(h, m, v, int(sh_degree), flags, None, None, C.byref(nb)))
+    out = np.zeros(nb.value, np.uint8)
+    index = None
+    if want_index:
+        ck(count_fn(h, m, v, None, None, None, C.byref(n)))
+        index = np.zeros(n.value, np.uint32)
+    ck(fn(h, m, v, int(sh_degree), flags, _p(index), _p(out), C.byref(nb)))
+    return (out[:nb.value], index) if want_index else out[:nb.value]
+
+
 OF_FILTERS = {"all": (0, 0), "visible": (STATE_HIDDEN, 0), "selected": (STATE_HIDDEN | STATE_SELECTED, STATE_SELECTED)}
 
 
@@ -901,6 +1010,20 @@ class Context:
     def export_ply(self, of="all", sh_degree=3):
         """gs_export_ply: the passing splats as the bytes of an INRIA .ply (uint8 array) with min(sh_degree, stored degree) SH bands"""
         return _export_ply(self._L.gs_export_ply, self._h, self._ck, of, sh_degree)
+
+    def load_cply(self, ply_bytes):
+        """gs_load_cply: decode a compressed .ply on the GPU and append its rows in file order (and its SH rows under load_ply's rule)"""
+        buf = np.frombuffer(bytes(ply_bytes), np.uint8)
+        self._ck(self._L.gs_load_cply(self._h, _p(buf), buf.size))
+
+    def cply_to_splat_gpu(self, ply_bytes, want_wide=False):
+        """gs_cply_to_splat_gpu: cply_to_splat by the decode kernel"""
+        buf = np.frombuffer(bytes(ply_bytes), np.uint8)
+        return _cply_rows(lambda *a: self._L.gs_cply_to_splat_gpu(self._h, *a), self._ck, buf, want_wide)
+
+    def export_cply(self, of="all", sh_degree=3, morton=True, want_index=False):
+        """gs_export_cply: the passing splats as the bytes of a compressed .ply (uint8 array) [, the resident index of every output row]"""
+        return _export_cply(self._L.gs_export_cply, self._L.gs_export_splat, self._h, self._ck, of, sh_degree, morton, want_index)
 
     # in-place changes: colour and opacity of the splats that pass `of` on the GPU; rows and SH rows written over resident ones
     def adjust_colour(self, adjust, of="all"):
@@ -1310,6 +1433,13 @@ class Multi:
 
     def export_ply(self, of="all", sh_degree=3):
         return _export_ply(self._L.gs_multi_export_ply, self._h, self._ck, of, sh_degree)
+
+    def load_cply(self, ply_bytes):
+        buf = np.frombuffer(bytes(ply_bytes), np.uint8)
+        self._ck(self._L.gs_multi_load_cply(self._h, _p(buf), buf.size))
+
+    def export_cply(self, of="all", sh_degree=3, morton=True, want_index=False):
+        return _export_cply(self._L.gs_multi_export_cply, self._L.gs_multi_export_splat, self._h, self._ck, of, sh_degree, morton, want_index)
 
     # in-place changes: colour and opacity of the splats that pass `of` on the GPU; rows and SH rows written over resident ones
     def adjust_colour(self, adjust, of="all"):

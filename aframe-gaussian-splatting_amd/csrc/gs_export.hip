@@ -17,6 +17,7 @@
 #include "gs_lanes.h"
 #include "gs_sh.h"
 #include "gs_export.h"
+#include "gs_export_stage.h"
 
 namespace {
 
@@ -197,6 +198,41 @@ int export_sh_rows(gs_ctx *ctx, uint8_t mask, uint8_t value, float *out_sh, size
 }
 
 }  // namespace
+
+// the passing splats staged for a writer that stays on the device (gs_export_stage.h): gs_export_splat's and gs_export_sh's launches without the copies
+int gs_export_stage(gs_ctx *ctx, const char *name, uint8_t mask, uint8_t value, bool with_rows, GsExportStage *out)
+{
+    *out = GsExportStage();
+    TRY(export_begin(ctx, name));
+    if (!ctx->n) return GS_OK;
+    const uint32_t n = (uint32_t)ctx->n;
+    hipStream_t st = ctx->prop_stream;
+    {
+        ExportScratch S;
+        TRY(export_offsets(ctx, S, n, mask, value, &out->total));
+        if (with_rows && out->total) {
+            TRY(dev_alloc(ctx, &out->rows, out->total * 2)); TRY(dev_alloc(ctx, &out->wide, out->total * 7)); TRY(dev_alloc(ctx, &out->index, out->total));
+            hipLaunchKernelGGL(k_export_scatter, dim3(gs_div_up(n, GS_EXPORT_CHUNK)), dim3(GS_BLOCK), 0, st, (const uint8_t *)ctx->edit_state, filter_rows(ctx, mask), n,
+                               (uint32_t)mask, (uint32_t)value, (const uint32_t *)S.blk, (const uint4 *)ctx->splat, out->rows, out->wide, out->index);
+            GS_HIP(hipGetLastError());
+            GS_HIP(hipStreamSynchronize(st));                    // (S.blk is released with this block)
+        }
+    }
+    const size_t ns = ctx->sh_n < ctx->n ? ctx->sh_n : ctx->n;
+    if (!ns) return GS_OK;
+    out->sh_deg = ctx->sh_deg;
+    out->sh_row_q = (uint32_t)(3 * (size_t)gsm::sh_channel_stride(ctx->sh_deg) / 4);
+    ExportScratch S;
+    TRY(export_offsets(ctx, S, (uint32_t)ns, mask, value, &out->sh_total));
+    if (!with_rows || !out->sh_total) return GS_OK;
+    TRY(dev_alloc(ctx, &out->sh, out->sh_total * out->sh_row_q));
+    hipLaunchKernelGGL(k_export_sh, dim3(gs_div_up(ns, GS_EXPORT_CHUNK)), dim3(GS_BLOCK), 0, st, (const uint8_t *)ctx->edit_state, filter_rows(ctx, mask), (uint32_t)ns,
+                       (uint32_t)mask, (uint32_t)value, (const uint32_t *)S.blk, (const uint4 *)ctx->sh, out->sh_row_q, out->sh);
+    GS_HIP(hipGetLastError());
+    GS_HIP(hipStreamSynchronize(st));
+    return GS_OK;
+}
+void gs_export_stage_free(GsExportStage *s) { dev_free(s->rows); dev_free(s->wide); dev_free(s->index); dev_free(s->sh); *s = GsExportStage(); }
 
 extern "C" {
 

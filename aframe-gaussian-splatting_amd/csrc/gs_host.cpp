@@ -3,7 +3,10 @@
 //     f64 operations per frame, in three.js' operation order so the f32 uniforms match the reference's;
 //   * processPlyBuffer (index.js:600-745): the one-time .ply -> .splat row conversion;
 //   * view-dependent colour (gs_sh.h): the SH rows of a .ply in the converter's order, one colour on the host, and the
-//     camera position the projection kernel evaluates them for.
+//     camera position the projection kernel evaluates them for;
+//   * the chunked compressed .ply (include/gs_splat.h: "Compressed .ply"; at the end of this file): the strict header reader both
+//     directions share (gs_cply_plan), the host evaluators of the decode and of the writer (gs_cply_to_splat, gs_cply_sh_host,
+//     gs_splat_to_cply) and gs_log_fixed.  The per-splat arithmetic is gs_cply.h's, the functions the kernels call (gs_cply.hip).
 #include <math.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -17,6 +20,7 @@
 #include "gs_device_math.h"
 #include "gs_export.h"
 #include "gs_adjust.h"
+#include "gs_cply.h"
 
 namespace {
 
@@ -518,6 +522,281 @@ GS_API int gs_camera_in_object(const float model_view[16], double out[3])
 {
     if (!model_view || !out) return GS_E_BADARG;
     return gsm::camera_in_object(model_view, out) ? GS_OK : GS_E_BADARG;
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------- compressed .ply
+
+namespace {
+
+const char *const kChunkProps[18] = { "min_x", "min_y", "min_z", "max_x", "max_y", "max_z",
+                                      "min_scale_x", "min_scale_y", "min_scale_z", "max_scale_x", "max_scale_y", "max_scale_z",
+                                      "min_r", "min_g", "min_b", "max_r", "max_g", "max_b" };
+const char *const kVertexProps[4] = { "packed_position", "packed_rotation", "packed_scale", "packed_color" };
+
+// "element <name> <count>" with a plain decimal count
+bool element_line(const std::string &line, const char *name, size_t *count)
+{
+    const std::string head = std::string("element ") + name + " ";
+    if (line.compare(0, head.size(), head) != 0 || line.size() == head.size() || line.size() > head.size() + 18) return false;
+    size_t v = 0;
+    for (size_t j = head.size(); j < line.size(); j++) {
+        if (line[j] < '0' || line[j] > '9') return false;
+        v = v * 10 + (size_t)(line[j] - '0');
+    }
+    *count = v;
+    return true;
+}
+
+int cply_plan(const void *bytes, size_t nbytes, gsm::CplyInfo *info, char *err, size_t errlen)
+{
+    memset(info, 0, sizeof *info);
+    if (!bytes) return fail(err, errlen, GS_E_BADARG, "compressed .ply: bytes is NULL");
+    const size_t hl = std::min<size_t>(nbytes, 65536);
+    const std::string head((const char *)bytes, hl);
+    // the end of the header: the first line that is exactly "end_header"
+    size_t end = std::string::npos;
+    if (head.compare(0, 11, "end_header\n") == 0) end = 0;
+    else { const size_t at = head.find("\nend_header\n"); if (at != std::string::npos) end = at + 1; }
+    if (end == std::string::npos) return fail(err, errlen, GS_E_PLY_HEADER, "compressed .ply: no end_header line");
+    std::vector<std::string> lines;
+    for (size_t ls = 0; ls < end;) {
+        const size_t le = head.find('\n', ls);
+        const std::string line = head.substr(ls, le - ls);
+        if (!(line.compare(0, 8, "comment ") == 0 || line == "comment")) lines.push_back(line);
+        ls = le + 1;
+    }
+    size_t at = 0;
+    auto next = [&]() -> const std::string & { static const std::string none; return at < lines.size() ? lines[at++] : none; };
+    if (next() != "ply") return fail(err, errlen, GS_E_PLY_HEADER, "compressed .ply: the file does not begin with \"ply\"");
+    if (next() != "format binary_little_endian 1.0") return fail(err, errlen, GS_E_PLY_HEADER, "compressed .ply: format is not binary_little_endian 1.0");
+    size_t C = 0, N = 0, NS = 0;
+    if (!element_line(next(), "chunk", &C)) return fail(err, errlen, GS_E_PLY_HEADER, "compressed .ply: \"element chunk\" expected first (not a compressed file)");
+    int cf = 0;
+    while (cf < 18 && at < lines.size() && lines[at] == std::string("property float ") + kChunkProps[cf]) { cf++; at++; }
+    if (cf != 12 && cf != 18) return fail(err, errlen, GS_E_PLY_HEADER, "compressed .ply: element chunk: property float %s expected", kChunkProps[cf < 18 ? cf : 17]);
+    if (!element_line(next(), "vertex", &N)) return fail(err, errlen, GS_E_PLY_HEADER, "compressed .ply: \"element vertex\" expected after the 12 or 18 chunk properties");
+    for (int k = 0; k < 4; k++)
+        if (next() != std::string("property uint ") + kVertexProps[k]) return fail(err, errlen, GS_E_PLY_HEADER, "compressed .ply: element vertex: property uint %s expected", kVertexProps[k]);
+    int per = 0;
+    if (at < lines.size()) {
+        if (!element_line(next(), "sh", &NS)) return fail(err, errlen, GS_E_PLY_HEADER, "compressed .ply: \"element sh\" or end_header expected after the vertex properties");
+        while (at < lines.size()) {
+            if (lines[at] != "property uchar f_rest_" + std::to_string(per)) return fail(err, errlen, GS_E_PLY_HEADER, "compressed .ply: element sh: property uchar f_rest_<k> in ascending k expected, found \"%s\"", lines[at].c_str());
+            per++; at++;
+        }
+        if (per != 9 && per != 24 && per != 45) return fail(err, errlen, GS_E_PLY_HEADER, "compressed .ply: element sh: 9, 24 or 45 f_rest_* properties expected");
+        if (NS != N) return fail(err, errlen, GS_E_PLY_HEADER, "compressed .ply: element sh and element vertex differ in count");
+        per /= 3;
+    }
+    if (N > 0x7FFFFFF0ull) return fail(err, errlen, GS_E_PLY_HEADER, "compressed .ply: more than 2^31 splats");
+    if (C != (N + GS_CPLY_CHUNK - 1) / GS_CPLY_CHUNK) return fail(err, errlen, GS_E_PLY_HEADER, "compressed .ply: element chunk count is not ceil(vertices / 256)");
+    info->n = N; info->chunks = C; info->chunk_floats = cf; info->per = per;
+    info->degree = per == 3 ? 1 : per == 8 ? 2 : per == 15 ? 3 : 0;
+    info->data_start = end + 11;
+    const size_t body = C * (size_t)cf * 4 + N * 16 + N * 3 * (size_t)per;
+    if (body > nbytes - info->data_start) return fail(err, errlen, GS_E_PLY_DATA, "compressed .ply: the body is shorter than the header promises");
+    return GS_OK;
+}
+
+// where the three arrays of the body begin
+struct Body { const uint8_t *chunks, *verts, *sh; };
+Body body_of(const void *bytes, const gsm::CplyInfo &I)
+{
+    Body b;
+    b.chunks = (const uint8_t *)bytes + I.data_start;
+    b.verts = b.chunks + I.chunks * (size_t)I.chunk_floats * 4;
+    b.sh = b.verts + I.n * 16;
+    return b;
+}
+
+int cply_to_splat(const void *bytes, size_t nbytes, void *out_rows, float *out_wide, size_t *out_nrows, char *err, size_t errlen)
+{
+    if (!bytes || !out_nrows) return fail(err, errlen, GS_E_BADARG, "gs_cply_to_splat: NULL argument");
+    *out_nrows = 0;
+    gsm::CplyInfo I;
+    const int rc = cply_plan(bytes, nbytes, &I, err, errlen);
+    if (rc != GS_OK) return rc;
+    *out_nrows = I.n;
+    if (!out_rows) return GS_OK;
+    const Body B = body_of(bytes, I);
+    for (size_t i = 0; i < I.n; i++) {
+        float chunk[18]; uint32_t packed[4], row[8];
+        memcpy(chunk, B.chunks + (i >> 8) * (size_t)I.chunk_floats * 4, (size_t)I.chunk_floats * 4);
+        memcpy(packed, B.verts + i * 16, 16);
+        gsm::cply_decode(chunk, I.chunk_floats, packed, row, out_wide ? out_wide + 7 * i : nullptr, nullptr);
+        memcpy((uint8_t *)out_rows + 32 * i, row, 32);
+    }
+    return GS_OK;
+}
+
+int cply_sh(const void *bytes, size_t nbytes, int degree, float *out_sh, size_t *out_nrows, int *out_degree, char *err, size_t errlen)
+{
+    if (!bytes || !out_nrows || !out_degree) return fail(err, errlen, GS_E_BADARG, "gs_cply_sh_host: NULL argument");
+    if (degree < 0 || degree > GS_SH_MAX_DEGREE) return fail(err, errlen, GS_E_BADARG, "gs_cply_sh_host: degree must be 0..3");
+    *out_nrows = 0; *out_degree = -1;
+    gsm::CplyInfo I;
+    const int rc = cply_plan(bytes, nbytes, &I, err, errlen);
+    if (rc != GS_OK) return rc;
+    const int D = degree < I.degree ? degree : I.degree, K = gsm::sh_coefs(D);
+    *out_degree = D; *out_nrows = I.n;
+    if (!out_sh) return GS_OK;
+    const Body B = body_of(bytes, I);
+    for (size_t i = 0; i < I.n; i++) {
+        float chunk[18]; uint32_t packed[4], row[8]; double colour[3];
+        memcpy(chunk, B.chunks + (i >> 8) * (size_t)I.chunk_floats * 4, (size_t)I.chunk_floats * 4);
+        memcpy(packed, B.verts + i * 16, 16);
+        gsm::cply_decode(chunk, I.chunk_floats, packed, row, nullptr, colour);
+        float *o = out_sh + i * 3 * (size_t)K;
+        const uint8_t *s = B.sh + i * 3 * (size_t)I.per;
+        for (int c = 0; c < 3; c++) {
+            o[c * K] = gsm::cply_sh_dc(colour[c]);
+            for (int k = 1; k < K; k++) o[c * K + k] = gsm::cply_sh_rest(s[c * I.per + (k - 1)]);
+        }
+    }
+    return GS_OK;
+}
+
+std::string cply_header(size_t n, int per)
+{
+    std::string h = "ply\nformat binary_little_endian 1.0\nelement chunk " + std::to_string((n + GS_CPLY_CHUNK - 1) / GS_CPLY_CHUNK) + "\n";
+    for (const char *p : kChunkProps) h += std::string("property float ") + p + "\n";
+    h += "element vertex " + std::to_string(n) + "\n";
+    for (const char *p : kVertexProps) h += std::string("property uint ") + p + "\n";
+    if (per) {
+        h += "element sh " + std::to_string(n) + "\n";
+        for (int k = 0; k < 3 * per; k++) h += "property uchar f_rest_" + std::to_string(k) + "\n";
+    }
+    return h + "end_header\n";
+}
+
+int splat_to_cply(const void *rows, const float *wide, const float *sh, size_t sh_rows, int degree, size_t nrows, uint32_t flags, uint32_t *out_index,
+                  void *out_bytes, size_t *out_nbytes)
+{
+    if (!out_nbytes || degree < 0 || degree > GS_SH_MAX_DEGREE || (flags & ~GS_CPLY_MORTON)) return GS_E_BADARG;
+    if (sh_rows > nrows || (sh_rows && !sh) || nrows > 0x7FFFFFF0ull) return GS_E_BADARG;
+    const int K = gsm::sh_coefs(degree), per = K - 1;
+    const std::string head = cply_header(nrows, per);
+    const size_t C = (nrows + GS_CPLY_CHUNK - 1) / GS_CPLY_CHUNK;
+    *out_nbytes = head.size() + C * 72 + nrows * 16 + nrows * 3 * (size_t)per;
+    if (!out_bytes) return GS_OK;
+    if (nrows && !rows) return GS_E_BADARG;
+    uint8_t *out = (uint8_t *)out_bytes;
+    memcpy(out, head.data(), head.size());
+    uint8_t *o_chunks = out + head.size(), *o_verts = o_chunks + C * 72, *o_sh = o_verts + nrows * 16;
+    // the nine values of every row
+    std::vector<float> val(nrows * 9 + 1);
+    for (size_t i = 0; i < nrows; i++) {
+        uint32_t row[8];
+        memcpy(row, (const uint8_t *)rows + 32 * i, 32);
+        gsm::cply_values(row, wide ? wide + 7 * i : nullptr, i < sh_rows ? sh + i * 3 * (size_t)K : nullptr, K, &val[9 * i]);
+    }
+    std::vector<uint32_t> order(nrows);
+    for (size_t i = 0; i < nrows; i++) order[i] = (uint32_t)i;
+    if (flags & GS_CPLY_MORTON) {
+        uint32_t kmin[3] = { GS_CPLY_KEY_MIN_ID, GS_CPLY_KEY_MIN_ID, GS_CPLY_KEY_MIN_ID }, kmax[3] = { GS_CPLY_KEY_MAX_ID, GS_CPLY_KEY_MAX_ID, GS_CPLY_KEY_MAX_ID };
+        for (size_t i = 0; i < nrows; i++)
+            for (int a = 0; a < 3; a++) {
+                const float v = val[9 * i + a];
+                if (!gsm::cply_finite(v)) continue;
+                const uint32_t k = gsm::cply_key(v);
+                kmin[a] = std::min(kmin[a], k); kmax[a] = std::max(kmax[a], k);
+            }
+        float box[6];
+        for (int a = 0; a < 3; a++) gsm::cply_bounds_of(kmin[a], kmax[a], box[a], box[3 + a]);
+        std::vector<uint32_t> code(nrows);
+        for (size_t i = 0; i < nrows; i++) code[i] = gsm::cply_morton(&val[9 * i], box);
+        std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return code[a] < code[b]; });
+    }
+    for (size_t ch = 0; ch < C; ch++) {
+        const size_t j0 = ch * GS_CPLY_CHUNK, j1 = std::min(nrows, j0 + GS_CPLY_CHUNK);
+        uint32_t kmin[9], kmax[9];
+        for (int q = 0; q < 9; q++) { kmin[q] = GS_CPLY_KEY_MIN_ID; kmax[q] = GS_CPLY_KEY_MAX_ID; }
+        for (size_t j = j0; j < j1; j++)
+            for (int q = 0; q < 9; q++) {
+                const float v = val[9 * (size_t)order[j] + q];
+                if (!gsm::cply_finite(v)) continue;
+                const uint32_t k = gsm::cply_key(v);
+                kmin[q] = std::min(kmin[q], k); kmax[q] = std::max(kmax[q], k);
+            }
+        // the record's layout: min xyz, max xyz | min scale, max scale | min rgb, max rgb
+        float bounds[18];
+        for (int g = 0; g < 3; g++)
+            for (int a = 0; a < 3; a++) gsm::cply_bounds_of(kmin[3 * g + a], kmax[3 * g + a], bounds[6 * g + a], bounds[6 * g + 3 + a]);
+        memcpy(o_chunks + ch * 72, bounds, 72);
+        for (size_t j = j0; j < j1; j++) {
+            const size_t i = order[j];
+            uint32_t row[8], w[4];
+            memcpy(row, (const uint8_t *)rows + 32 * i, 32);
+            gsm::cply_encode(&val[9 * i], bounds, row, wide ? wide + 7 * i : nullptr, w);
+            memcpy(o_verts + 16 * j, w, 16);
+            for (int c = 0; c < 3; c++)
+                for (int k = 1; k < K; k++) o_sh[j * 3 * (size_t)per + c * per + (k - 1)] = i < sh_rows ? gsm::cply_sh_byte(sh[(i * 3 + c) * K + k]) : (uint8_t)128;
+            if (out_index) out_index[j] = (uint32_t)i;
+        }
+    }
+    return GS_OK;
+}
+
+}  // namespace
+
+// shared with gs_cply.hip; no C++ exception crosses it
+extern "C" int gs_cply_plan(const void *bytes, size_t nbytes, gsm::CplyInfo *info, char *err, size_t errlen)
+{
+    try { return cply_plan(bytes, nbytes, info, err, errlen); }
+    catch (...) { return fail(err, errlen, GS_E_OOM, "out of host memory while reading the compressed .ply header"); }
+}
+
+// the header text of a file of n splats with `degree` bands (out == NULL: its length alone)
+extern "C" int gs_cply_write_header(size_t n, int degree, void *out, size_t *len)
+{
+    try {
+        const std::string h = cply_header(n, gsm::sh_coefs(degree) - 1);
+        *len = h.size();
+        if (out) memcpy(out, h.data(), h.size());
+        return GS_OK;
+    } catch (...) { return GS_E_OOM; }
+}
+
+extern "C" {
+
+GS_API int gs_cply_info(const void *bytes, size_t nbytes, size_t *out_nsplats, size_t *out_nchunks, int *out_sh_degree, int *out_chunk_floats, char *err, size_t errlen)
+{
+    gsm::CplyInfo I;
+    const int rc = gs_cply_plan(bytes, nbytes, &I, err, errlen);
+    if (rc != GS_OK && rc != GS_E_PLY_DATA) return rc;           // (a short body: the header's figures are still reported)
+    if (out_nsplats) *out_nsplats = I.n;
+    if (out_nchunks) *out_nchunks = I.chunks;
+    if (out_sh_degree) *out_sh_degree = I.degree;
+    if (out_chunk_floats) *out_chunk_floats = I.chunk_floats;
+    return rc;
+}
+
+GS_API int gs_cply_to_splat(const void *bytes, size_t nbytes, void *out_rows, float *out_wide, size_t *out_nrows, char *err, size_t errlen)
+{
+    try { return cply_to_splat(bytes, nbytes, out_rows, out_wide, out_nrows, err, errlen); }
+    catch (...) { return fail(err, errlen, GS_E_OOM, "out of host memory while decoding the compressed .ply"); }
+}
+
+GS_API int gs_cply_sh_host(const void *bytes, size_t nbytes, int degree, float *out_sh, size_t *out_nrows, int *out_degree, char *err, size_t errlen)
+{
+    try { return cply_sh(bytes, nbytes, degree, out_sh, out_nrows, out_degree, err, errlen); }
+    catch (...) { return fail(err, errlen, GS_E_OOM, "out of host memory while reading the compressed .ply coefficients"); }
+}
+
+GS_API int gs_splat_to_cply(const void *rows, const float *wide, const float *sh, size_t sh_rows, int degree, size_t nrows, uint32_t flags, uint32_t *out_index,
+                            void *out_bytes, size_t *out_nbytes)
+{
+    try { return splat_to_cply(rows, wide, sh, sh_rows, degree, nrows, flags, out_index, out_bytes, out_nbytes); }
+    catch (...) { return GS_E_OOM; }
+}
+
+GS_API int gs_log_fixed(double x, double *out)
+{
+    if (!out) return GS_E_BADARG;
+    *out = gsm::log_fixed(x);
+    return GS_OK;
 }
 
 }  // extern "C"

@@ -284,6 +284,19 @@ GS_API int gs_multi_export_ply(gs_multi *m, uint8_t state_mask, uint8_t state_va
     return run_all(m, [=](gs_ctx *c, int i) { return i == 0 ? gs_export_ply(c, state_mask, state_value, sh_degree, out_bytes, out_nbytes) : GS_OK; });
 }
 
+GS_API int gs_multi_load_cply(gs_multi *m, const void *bytes, size_t nbytes)
+{
+    if (!m) return GS_E_BADARG;
+    m->have_sort = false;
+    return run_all(m, [bytes, nbytes](gs_ctx *c, int) { return gs_load_cply(c, bytes, nbytes); });
+}
+
+GS_API int gs_multi_export_cply(gs_multi *m, uint8_t state_mask, uint8_t state_value, int sh_degree, uint32_t flags, uint32_t *out_index, void *out_bytes, size_t *out_nbytes)
+{
+    if (!m) return GS_E_BADARG;
+    return run_all(m, [=](gs_ctx *c, int i) { return i == 0 ? gs_export_cply(c, state_mask, state_value, sh_degree, flags, out_index, out_bytes, out_nbytes) : GS_OK; });
+}
+
 GS_API int gs_multi_select_rect(gs_multi *m, const gs_render_params *p, const int32_t rect[4], uint8_t set_bits, uint8_t clear_bits, uint32_t flags, size_t *out_hit)
 {
     if (!m) return GS_E_BADARG;

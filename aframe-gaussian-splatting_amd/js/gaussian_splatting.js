@@ -105,6 +105,11 @@ class GaussianSplatting {
       if (isPly) {
         const all = Buffer.alloc(total); fs.readSync(fd, all, 0, total, 0);
         const input = all.buffer.slice(all.byteOffset, all.byteOffset + total);
+        if (native.cplyInfo(input)) {                // a chunked compressed .ply: decoded on the GPU, file order, SH rows under the option
+          this.loadedVertexCount = native.loadCply(this.handle, input);
+          this.sortReady = true;
+          return this.loadedVertexCount;
+        }
         const rows = this.processPlyBuffer(input);
         this.pushDataBuffer(rows, Math.floor(rows.byteLength / this.rowLength));
         if (this.shDegree > 0) {                     // the coefficients processPlyBuffer drops, in its row order
@@ -351,6 +356,13 @@ class GaussianSplatting {
     const o = opts || {}, f = PROP_FILTERS[o.of || 'all'];
     if (!f) throw new RangeError("exportPly: of must be 'all', 'visible' or 'selected'");
     return native.exportPly(this.handle, f[0], f[1], o.shDegree === undefined ? 3 : o.shDegree);
+  }
+  // ... or as a chunked compressed .ply (16 bytes per splat + one bounds record per 256; gs_splat.h: "Compressed .ply"), encoded on the
+  // GPU; opts.morton (default true): rows in Morton order, so that a chunk's bounds are tight
+  exportCply(opts) {
+    const o = opts || {}, f = PROP_FILTERS[o.of || 'all'];
+    if (!f) throw new RangeError("exportCply: of must be 'all', 'visible' or 'selected'");
+    return native.exportCply(this.handle, f[0], f[1], o.shDegree === undefined ? 3 : o.shDegree, o.morton === undefined ? true : !!o.morton);
   }
   // Change resident splats in place.  adjustColour: colour' = matrix (9 numbers, row-major; default the identity) x colour + offset (3, in
   // byte units), alpha' = alphaScale x alpha + alphaOffset, for the splats of opts.of (as in histogram), on the GPU, bytes and

@@ -736,6 +736,65 @@ static napi_value fn_export_ply(napi_env env, napi_callback_info info)
     return ab;
 }
 
+/* ---- compressed .ply (gs_splat.h: "Compressed .ply") */
+/* cplyInfo(bytes) -> { splats, chunks, shDegree, chunkFloats }, or null where the header is not a compressed file's (the sniff) */
+static napi_value fn_cply_info(napi_env env, napi_callback_info info)
+{
+    napi_value argv[1];
+    if (!get_args(env, info, 1, argv, NULL)) return NULL;
+    void *data; size_t len;
+    if (!get_bytes(env, argv[0], &data, &len)) { napi_throw_type_error(env, NULL, "expected an ArrayBuffer or TypedArray"); return NULL; }
+    size_t n = 0, c = 0; int degree = 0, floats = 0;
+    char err[256];
+    napi_value o, v;
+    const int rc = gs_cply_info(data, len, &n, &c, &degree, &floats, err, sizeof err);
+    if (rc != GS_OK && rc != GS_E_PLY_DATA) { NAPI_OK(napi_get_null(env, &o)); return o; }
+    NAPI_OK(napi_create_object(env, &o));
+    NAPI_OK(napi_create_double(env, (double)n, &v)); NAPI_OK(napi_set_named_property(env, o, "splats", v));
+    NAPI_OK(napi_create_double(env, (double)c, &v)); NAPI_OK(napi_set_named_property(env, o, "chunks", v));
+    NAPI_OK(napi_create_int32(env, degree, &v)); NAPI_OK(napi_set_named_property(env, o, "shDegree", v));
+    NAPI_OK(napi_create_int32(env, floats, &v)); NAPI_OK(napi_set_named_property(env, o, "chunkFloats", v));
+    return o;
+}
+
+/* loadCply(h, bytes) -> the splats resident afterwards */
+static napi_value fn_load_cply(napi_env env, napi_callback_info info)
+{
+    napi_value argv[2];
+    if (!get_args(env, info, 2, argv, NULL)) return NULL;
+    gs_ctx *ctx = get_ctx(env, argv[0]); if (!ctx) return NULL;
+    void *data; size_t len;
+    if (!get_bytes(env, argv[1], &data, &len)) { napi_throw_type_error(env, NULL, "expected an ArrayBuffer or TypedArray"); return NULL; }
+    const int rc = gs_load_cply(ctx, data, len);
+    if (rc != GS_OK) return throw_gs(env, ctx, rc);
+    napi_value r;
+    NAPI_OK(napi_create_double(env, (double)gs_count(ctx), &r));
+    return r;
+}
+
+/* exportCply(h, stateMask, stateValue, shDegree, morton) -> ArrayBuffer: a chunked compressed .ply */
+static napi_value fn_export_cply(napi_env env, napi_callback_info info)
+{
+    napi_value argv[5];
+    if (!get_args(env, info, 5, argv, NULL)) return NULL;
+    gs_ctx *ctx = get_ctx(env, argv[0]); if (!ctx) return NULL;
+    uint32_t mask = 0, value = 0; int32_t degree = 0; bool morton = false;
+    if (!get_u32(env, argv[1], &mask) || !get_u32(env, argv[2], &value) || napi_get_value_int32(env, argv[3], &degree) != napi_ok ||
+        napi_get_value_bool(env, argv[4], &morton) != napi_ok) {
+        napi_throw_type_error(env, NULL, "exportCply: (handle, stateMask, stateValue, shDegree, morton)");
+        return NULL;
+    }
+    const uint32_t flags = morton ? GS_CPLY_MORTON : 0u;
+    size_t nb = 0;
+    int rc = gs_export_cply(ctx, (uint8_t)mask, (uint8_t)value, degree, flags, NULL, NULL, &nb);
+    if (rc != GS_OK) return throw_gs(env, ctx, rc);
+    napi_value ab; void *data = NULL;
+    NAPI_OK(napi_create_arraybuffer(env, nb, &data, &ab));
+    rc = gs_export_cply(ctx, (uint8_t)mask, (uint8_t)value, degree, flags, NULL, data, &nb);
+    if (rc != GS_OK) return throw_gs(env, ctx, rc);
+    return ab;
+}
+
 /* ---- in-place changes (gs_splat.h: gs_adjust_colour / gs_replace_splat / gs_replace_sh) */
 /* adjustColour(h, m9, offset3, alphaScale, alphaOffset, stateMask, stateValue) -> splats adjusted */
 static napi_value fn_adjust_colour(napi_env env, napi_callback_info info)
@@ -1570,7 +1629,7 @@ static napi_value init(napi_env env, napi_value exports)
         { "selectRect", fn_select_rect }, { "compact", fn_compact },
         { "renderContrib", fn_render_contrib }, { "contribClear", fn_contrib_clear }, { "contribInfo", fn_contrib_info },
         { "propRange", fn_prop_range }, { "histogram", fn_histogram }, { "selectRange", fn_select_range },
-        { "exportSplat", fn_export_splat }, { "exportPly", fn_export_ply },
+        { "exportSplat", fn_export_splat }, { "exportPly", fn_export_ply }, { "cplyInfo", fn_cply_info }, { "loadCply", fn_load_cply }, { "exportCply", fn_export_cply },
         { "adjustColour", fn_adjust_colour }, { "replaceSplat", fn_replace_splat }, { "replaceSh", fn_replace_sh },
         { "selectMask", fn_select_mask }, { "maskPolygon", fn_mask_polygon }, { "highlightInfo", fn_highlight_info },
         { "createMulti", fn_create_multi }, { "multiDestroy", fn_multi_destroy }, { "multiPushSplat", fn_multi_push_splat },

@@ -976,6 +976,84 @@ GS_API int gs_export_ply(gs_ctx *ctx, uint8_t state_mask, uint8_t state_value, i
 GS_API int gs_multi_export_splat(gs_multi *m, uint8_t state_mask, uint8_t state_value, void *out_rows, float *out_wide, uint32_t *out_index, size_t *out_nrows);
 GS_API int gs_multi_export_ply(gs_multi *m, uint8_t state_mask, uint8_t state_value, int sh_degree, void *out_bytes, size_t *out_nbytes);
 
+/* ---- Compressed .ply: the chunked 16-byte splat format (16 bytes per splat + one bounds record per 256 splats + optional SH bytes).
+ * The rules below are restated from memory of the published format (PlayCanvas / SuperSplat).  No file written by those tools was at
+ * hand: INTEROPERABILITY WITH THEIR FILES IS SUPPOSED, NOT VERIFIED (docs/LAB_NOTES.md 9s).  What is verified: the host and the GPU
+ * forms below agree byte for byte, and a written file reads back within the format's own quantisation.
+ *
+ * Header   ASCII, lines end in \n: "ply", "format binary_little_endian 1.0", then EXACTLY these elements in this order (`comment` lines
+ *          are allowed anywhere before end_header):
+ *            element chunk C     12 or 18 `property float`: min_x min_y min_z max_x max_y max_z, min_scale_x min_scale_y min_scale_z
+ *                                max_scale_x max_scale_y max_scale_z and, in the 18 form, min_r min_g min_b max_r max_g max_b
+ *            element vertex N    `property uint` packed_position, packed_rotation, packed_scale, packed_color
+ *            element sh N        (optional) `property uchar` f_rest_0 .. f_rest_(3 * per - 1), per = 3, 8 or 15 (degree 1, 2, 3), channel-major
+ *                                as in INRIA files: f_rest_(c * per + k - 1) = sh[c][k]
+ *          C must be ceil(N / 256).  Any other name, type, order or count, a wrong C, an sh count != N: GS_E_PLY_HEADER with a message
+ *          (a valid INRIA .ply is therefore GS_E_PLY_HEADER here: that is the sniff).  A body shorter than promised: GS_E_PLY_DATA.
+ * Decode   (gsm::cply_decode, csrc/gs_cply.h: ONE function, called by the kernel and by the host evaluator; IEEE f64, un-fused, in this
+ *          order.)  Splat i uses chunk i >> 8.  u(v, b) = (double)(v & (2^b - 1)) / (2^b - 1).  The chunk's floats are widened first.
+ *            position  t = (u(p >> 21, 11), u(p >> 11, 10), u(p, 11)): 11 + 10 + 11 bits tile the word;  x = (float)(min_x + (max_x - min_x) * t_x), likewise y, z
+ *            scale     the same split of packed_scale against min_scale / max_scale gives the log scale l;  scale = (float)js_exp(l)
+ *                      (csrc/gs_ply.h: Math.exp as the .ply converter evaluates it)
+ *            rotation  w = packed_rotation, k = w >> 30;  a = (u(w >> 20, 10) - 0.5) * sqrt(2), b from w >> 10, c from w;
+ *                      m = sqrt(max(0, 1 - ((a * a + b * b) + c * c)));  the quaternion (rot_0 .. rot_3) = (w, x, y, z) as a .ply stores it
+ *                      has m at index k and a, b, c at the other three indices in ascending order.  Bytes as the .ply converter makes
+ *                      them: q / sqrt(((q0 * q0 + q1 * q1) + q2 * q2) + q3 * q3), then clamped_u8(q * 128 + 128).  Wide part (optional,
+ *                      7 f32 per row: the three scales, then the quaternion): the normalised quaternion before the byte rounding.
+ *            colour    t = (u(c >> 24, 8), u(c >> 16, 8), u(c >> 8, 8)), alpha u(c, 8);  18-float chunks: v_c = min_c + (max_c - min_c) * t_c,
+ *                      12-float chunks: v_c = t_c;  byte = clamped_u8(v_c * 255), alpha byte = clamped_u8(alpha * 255)
+ *            SH row    (files with `element sh`)  sh[c][0] = (float)((v_c - 0.5) / SH_C0),  sh[c][k] = (float)(byte * (8.0 / 255.0) - 4.0), k >= 1
+ * Encode   (gsm::cply_encode + the bounds rule; the inputs of gs_splat_to_ply.)  Where wide is NULL the scales come from the row and the
+ *          quaternion from (byte - 128) / 128.
+ *            code(t, b)  t is NaN or t <= 0 ? 0 : min(2^b - 1, (uint32)floor(t * (2^b - 1) + 0.5));  against bounds (lo, hi):
+ *                        t = hi > lo ? (v - lo) / (hi - lo) : 0
+ *            values      position: the row's f32;  log scale: (float)clamp(log_fixed((double)scale), -20, 20), -20 for a scale <= 0 or NaN;
+ *                        colour: (float)(0.5 + SH_C0 * sh[c][0]) where the splat has an SH row, else (float)(byte / 255.0);  alpha code: the byte
+ *            log_fixed   x = m * 2^e, m in [sqrt(1/2), sqrt(2)), s = (m - 1) / (m + 1), z = s * s,
+ *                        log = e * ln2 + 2 * (s + s * (z * (1/3 + z * (1/5 + ... + z * (1/21))))): + - * / and the exponent field only, so the
+ *                        host's and the device's bits are the same.  Denormals are scaled by 2^54 first.  0: -inf; negative, NaN: NaN.
+ *            bounds      per chunk and per value the smallest and the largest, as f32, over the chunk's splats whose value is finite (-0
+ *                        orders below +0); the last chunk is partial: real splats only.  No finite value: lo = hi = 0.  Always 18 floats.
+ *            rotation    normalise; a zero or non-finite quaternion becomes (1, 0, 0, 0);  k = the first index of the largest |q_i|;  all four
+ *                        negated if q_k < 0;  the three others are code(q_i / sqrt(2) + 0.5, 10)
+ *            SH          byte = clamped_u8((v + 4) * (255.0 / 8.0));  splats without an SH row take zeros (byte 128)
+ *            order       GS_CPLY_MORTON: rows in ascending 30-bit Morton code, STABLE (ties keep ascending input index); else input order.
+ *                        (lo, hi) per axis = the smallest and largest finite position over all rows;  i_axis = t is NaN or t < 0 ? 0 :
+ *                        min(1023, (uint32)floor(t * 1024));  code = spread(ix) | spread(iy) << 1 | spread(iz) << 2.  The resident
+ *                        cloud is in importance order, which is spatially incoherent: without the flag every chunk's box is the scene's.
+ * The GPU forms: gs_load_cply and gs_cply_to_splat_gpu decode with one kernel (k_cply_decode) on lane 0's stream after draining the lanes,
+ * like gs_load_ply.  gs_export_cply ONLY READS, like gs_export_ply: the passing splats are staged by the export scheme, then ordered
+ * (k_cply_bounds_pos, k_cply_keys, four stable radix passes with scratch of the call's own) and encoded (k_cply_encode: one workgroup per
+ * chunk) on the reading calls' stream: no drain, no order dropped, no option or statistic changed.  A context that never calls them
+ * launches exactly the kernels it launched before. */
+#define GS_CPLY_MORTON 1u
+/* host, no context: what the header says.  Every out pointer is optional.  GS_E_PLY_DATA still reports the header's figures. */
+GS_API int gs_cply_info(const void *bytes, size_t nbytes, size_t *out_nsplats, size_t *out_nchunks, int *out_sh_degree, int *out_chunk_floats, char *err, size_t errlen);
+/* host: the file's rows in file order (32 bytes each) and, optionally, their wide parts (7 f32 each).  out_rows == NULL: size query. */
+GS_API int gs_cply_to_splat(const void *bytes, size_t nbytes, void *out_rows, float *out_wide, size_t *out_nrows, char *err, size_t errlen);
+/* host: the SH rows (tight, 3 (D+1)^2 f32, D = min(degree, the file's) -> *out_degree) in file order; a file without `element sh` has
+ * degree 0: the DC terms alone.  out_sh == NULL: size query. */
+GS_API int gs_cply_sh_host(const void *bytes, size_t nbytes, int degree, float *out_sh, size_t *out_nrows, int *out_degree, char *err, size_t errlen);
+/* host: gs_splat_to_ply's inputs -> a compressed file.  flags: 0 or GS_CPLY_MORTON.  out_index (optional): the input row of output row j.
+ * out_bytes == NULL: size query.  Unknown flags and gs_splat_to_ply's bad arguments: GS_E_BADARG. */
+GS_API int gs_splat_to_cply(const void *rows, const float *wide, const float *sh, size_t sh_rows, int degree, size_t nrows, uint32_t flags, uint32_t *out_index,
+                            void *out_bytes, size_t *out_nbytes);
+/* host: gsm::log_fixed, the logarithm the encoder takes of a scale */
+GS_API int gs_log_fixed(double x, double *out);
+/* Decode on the GPU and append the rows IN FILE ORDER (no importance sort) straight from HBM through the pack kernel.  With GS_OPT_SH_DEGREE
+ * at 1..3 the file's SH rows (min(option, file) bands) are appended under gs_load_ply's rule: only while the store is parallel to the
+ * splats and the degrees agree. */
+GS_API int gs_load_cply(gs_ctx *ctx, const void *bytes, size_t nbytes);
+/* gs_cply_to_splat by the kernel; out_wide optional; out_rows == NULL: size query (header checks only). */
+GS_API int gs_cply_to_splat_gpu(gs_ctx *ctx, const void *bytes, size_t nbytes, void *out_rows, float *out_wide, size_t *out_nrows);
+/* The bytes gs_splat_to_cply makes of gs_export_splat (with the wide parts) + gs_export_sh of the same filter, the SH rows cut to
+ * min(sh_degree, the store's degree) bands -- encoded on the device.  out_index (optional): the resident index of output row j.
+ * out_bytes == NULL: size query. */
+GS_API int gs_export_cply(gs_ctx *ctx, uint8_t state_mask, uint8_t state_value, int sh_degree, uint32_t flags, uint32_t *out_index, void *out_bytes, size_t *out_nbytes);
+GS_API int gs_multi_load_cply(gs_multi *m, const void *bytes, size_t nbytes);
+/* on devices[0]: every device holds the same splats and states */
+GS_API int gs_multi_export_cply(gs_multi *m, uint8_t state_mask, uint8_t state_value, int sh_degree, uint32_t flags, uint32_t *out_index, void *out_bytes, size_t *out_nbytes);
+
 #ifdef __cplusplus
 }
 #endif
