@@ -12,27 +12,14 @@
 // Both are f64 like the property and export kernels; neither uses LDS beyond the four words of the count.
 #include "gs_lanes.h"
 #include "gs_sh.h"
+#include "gs_cloud_pass.h"
 #include "gs_adjust.h"
 
 namespace {
 
-#define GS_ADJUST_GRID 2048u                                     // workgroups at most (GS_EDIT_GRID of gs_edit.hip)
-
-__device__ __forceinline__ uint32_t wave_sum(uint32_t v)
-{
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
-    return v;
-}
-// one atomic per workgroup: every thread calls it (a barrier inside) -- gs_edit.hip: block_count
-__device__ __forceinline__ void block_count(uint32_t mine, uint32_t *__restrict__ out)
-{
-    __shared__ uint32_t s_w[GS_BLOCK / 64];
-    const uint32_t t = wave_sum(mine);
-    if ((threadIdx.x & 63) == 0) s_w[threadIdx.x >> 6] = t;
-    __syncthreads();
-    if (threadIdx.x == 0) { const uint32_t s = s_w[0] + s_w[1] + s_w[2] + s_w[3]; if (s) atomicAdd(out, s); }
-}
+// (earlier versions of the tests read this name out of this file; the kernels' cap is pass_grid's default, gs_cloud_pass.h's GS_EDIT_GRID)
+#define GS_ADJUST_GRID 2048u
+static_assert(GS_ADJUST_GRID == GS_EDIT_GRID, "the adjust kernels run under the editing kernels' cap");
 
 // words: the records as 32-bit words, eight per splat; rows = 0 when the mask is 0 or the store is empty (no state byte is loaded then)
 __global__ __launch_bounds__(GS_BLOCK) void k_adjust_colour(const uint8_t *__restrict__ state, uint32_t rows, uint32_t n, uint32_t mask, uint32_t value,
@@ -40,8 +27,7 @@ __global__ __launch_bounds__(GS_BLOCK) void k_adjust_colour(const uint8_t *__res
 {
     uint32_t c = 0;
     for (uint32_t i = blockIdx.x * GS_BLOCK + threadIdx.x; i < n; i += gridDim.x * GS_BLOCK) {
-        const uint32_t st = i < rows ? (uint32_t)state[i] : 0u;
-        if ((st & mask) != value) continue;
+        if (!state_passes(state, rows, i, mask, value)) continue;
         uint32_t *w = words + 8 * (size_t)i + 7;                 // splat[2 i + 1].w
         *w = gsm::adjust_word(*w, p);
         c++;
@@ -56,8 +42,7 @@ __global__ __launch_bounds__(GS_BLOCK) void k_adjust_sh(const uint8_t *__restric
     const uint64_t total = (uint64_t)n * K;
     for (uint64_t t = (uint64_t)blockIdx.x * GS_BLOCK + threadIdx.x; t < total; t += (uint64_t)gridDim.x * GS_BLOCK) {
         const uint32_t i = (uint32_t)(t / K), k = (uint32_t)(t % K);
-        const uint32_t st = i < rows ? (uint32_t)state[i] : 0u;
-        if ((st & mask) != value) continue;
+        if (!state_passes(state, rows, i, mask, value)) continue;
         float *r = sh + (size_t)i * 3 * KS + k;
         const float in[3] = { r[0], r[KS], r[2 * KS] };
         float out[3];
@@ -66,33 +51,21 @@ __global__ __launch_bounds__(GS_BLOCK) void k_adjust_sh(const uint8_t *__restric
     }
 }
 
-uint32_t adjust_grid(uint64_t items)
-{
-    const uint64_t g = (items + GS_BLOCK - 1) / GS_BLOCK;
-    return g > GS_ADJUST_GRID ? GS_ADJUST_GRID : (uint32_t)(g ? g : 1);
-}
-
 int adjust_run(gs_ctx *ctx, const gsm::AdjustParams &p, uint8_t mask, uint8_t value, size_t *hit)
 {
     GS_HIP(hipSetDevice(ctx->device));
     TRY(drain_all(ctx));                                         // frames in flight read both arrays
-    if (!ctx->edit_cnt) GS_HIP(hipMalloc((void **)&ctx->edit_cnt, 2 * sizeof(uint32_t)));   // (gs_edit.hip: counters)
-    GS_HIP(hipMemsetAsync(ctx->edit_cnt, 0, 2 * sizeof(uint32_t), ctx->stream));
-    const uint32_t n = (uint32_t)ctx->n, rows = (mask && ctx->edit_state) ? (uint32_t)ctx->edit_n : 0u;
-    hipLaunchKernelGGL(k_adjust_colour, dim3(adjust_grid(n)), dim3(GS_BLOCK), 0, ctx->stream, (const uint8_t *)ctx->edit_state, rows, n, (uint32_t)mask, (uint32_t)value,
+    TRY(counters(ctx));
+    const uint32_t n = (uint32_t)ctx->n, rows = filter_rows(ctx, mask);
+    hipLaunchKernelGGL(k_adjust_colour, dim3(pass_grid(n)), dim3(GS_BLOCK), 0, ctx->stream, (const uint8_t *)ctx->edit_state, rows, n, (uint32_t)mask, (uint32_t)value,
                        p, reinterpret_cast<uint32_t *>(ctx->splat), ctx->edit_cnt);
     const uint32_t sh_rows = (uint32_t)(ctx->sh_n < ctx->n ? ctx->sh_n : ctx->n);
     if (sh_rows) {
         const uint32_t K = (uint32_t)gsm::sh_coefs(ctx->sh_deg), KS = (uint32_t)gsm::sh_channel_stride(ctx->sh_deg);
-        hipLaunchKernelGGL(k_adjust_sh, dim3(adjust_grid((uint64_t)sh_rows * K)), dim3(GS_BLOCK), 0, ctx->stream, (const uint8_t *)ctx->edit_state, rows, sh_rows,
+        hipLaunchKernelGGL(k_adjust_sh, dim3(pass_grid((uint64_t)sh_rows * K)), dim3(GS_BLOCK), 0, ctx->stream, (const uint8_t *)ctx->edit_state, rows, sh_rows,
                            (uint32_t)mask, (uint32_t)value, p, ctx->sh, K, KS);
     }
-    GS_HIP(hipGetLastError());
-    uint32_t v = 0;
-    GS_HIP(hipMemcpyAsync(&v, ctx->edit_cnt, sizeof v, hipMemcpyDeviceToHost, ctx->stream));
-    GS_HIP(hipStreamSynchronize(ctx->stream));
-    if (hit) *hit = v;
-    return GS_OK;
+    return read_counter(ctx, hit);
 }
 
 }  // namespace
@@ -129,9 +102,7 @@ GS_API int gs_replace_splat(gs_ctx *ctx, size_t first, const void *rows, size_t 
     e = hipStreamSynchronize(ctx->stream);
     if (rc == GS_OK && e != hipSuccess) { snprintf(GS_ERRBUF(ctx), GS_ERRLEN, "pack failed: %s", hipGetErrorString(e)); rc = GS_E_HIP; }
     dev_free(stage);
-    // like a push: no lane's order survives, and a sort begun before the change is run again when it is collected
-    for (int i = 0; i < GS_MAX_LANES; i++) if (ctx->lanes[i]) ctx->lanes[i]->have_sort = false;
-    if (ctx->pend_lane > 0) ctx->pend_n = (size_t)-1;
+    drop_orders(ctx);
     return rc;
 }
 

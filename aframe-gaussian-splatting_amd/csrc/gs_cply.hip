@@ -18,6 +18,7 @@
 // Both are byte-shuffling and f64-ALU work on a one-time path; a context that never calls them launches none of these kernels.
 #include "gs_lanes.h"
 #include "gs_sh.h"
+#include "gs_cloud_pass.h"
 #include "gs_cply.h"
 #include "gs_export_stage.h"
 
@@ -26,18 +27,7 @@ extern "C" int gs_cply_write_header(size_t n, int degree, void *out, size_t *len
 
 namespace {
 
-__device__ __forceinline__ uint32_t wave_min(uint32_t v)
-{
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) { const uint32_t o = __shfl_xor(v, m, 64); v = o < v ? o : v; }
-    return v;
-}
-__device__ __forceinline__ uint32_t wave_max(uint32_t v)
-{
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) { const uint32_t o = __shfl_xor(v, m, 64); v = o > v ? o : v; }
-    return v;
-}
+#define GS_CPLY_GRID 16384u                                      // workgroups at most for the grid-strided kernels here
 
 // sh_out (may be null): rows of 3 x KS f32 (the store's padded layout, pad 0), K coefficients kept per channel
 __global__ __launch_bounds__(GS_BLOCK) void k_cply_decode(const float *__restrict__ chunks, int cf, const uint4 *__restrict__ verts,
@@ -167,8 +157,6 @@ __global__ __launch_bounds__(GS_BLOCK) void k_cply_encode(const uint4 *__restric
     if (o_index) o_index[j] = index[src];
 }
 
-uint32_t stream_grid(size_t n) { uint32_t g = gs_div_up(n, GS_BLOCK); return g > 16384 ? 16384u : g; }
-
 // everything the decoder holds on the device for a call
 struct DecodeScratch {
     float *chunks = nullptr; uint4 *verts = nullptr; uint8_t *shb = nullptr;
@@ -193,7 +181,7 @@ int decode_to_device(gs_ctx *ctx, const void *bytes, const gsm::CplyInfo &I, uin
         TRY(dev_alloc(ctx, &S.shb, sh_bytes));
         GS_HIP(hipMemcpyAsync(S.shb, body + chunk_bytes + vert_bytes, sh_bytes, hipMemcpyHostToDevice, st));
     }
-    hipLaunchKernelGGL(k_cply_decode, dim3(stream_grid(I.n)), dim3(GS_BLOCK), 0, st, (const float *)S.chunks, I.chunk_floats, (const uint4 *)S.verts,
+    hipLaunchKernelGGL(k_cply_decode, dim3(pass_grid(I.n, GS_CPLY_GRID)), dim3(GS_BLOCK), 0, st, (const float *)S.chunks, I.chunk_floats, (const uint4 *)S.verts,
                        (const uint8_t *)S.shb, I.per, (uint32_t)I.n, rows, wide, sh_out, gsm::sh_coefs(D), gsm::sh_channel_stride(D));
     GS_HIP(hipGetLastError());
     GS_HIP(hipStreamSynchronize(st));
@@ -333,8 +321,8 @@ GS_API int gs_export_cply(gs_ctx *ctx, uint8_t state_mask, uint8_t state_value, 
         // [0] = n for the radix kernels, [1..6] = the box's keys
         const uint32_t host_small[8] = { n32, GS_CPLY_KEY_MIN_ID, GS_CPLY_KEY_MIN_ID, GS_CPLY_KEY_MIN_ID, GS_CPLY_KEY_MAX_ID, GS_CPLY_KEY_MAX_ID, GS_CPLY_KEY_MAX_ID, 0u };
         GS_HIP(hipMemcpyAsync(S.small, host_small, sizeof host_small, hipMemcpyHostToDevice, st));
-        hipLaunchKernelGGL(k_cply_bounds_pos, dim3(stream_grid(n) > 1024 ? 1024 : stream_grid(n)), dim3(GS_BLOCK), 0, st, (const uint4 *)S.stage.rows, n32, S.small + 1);
-        hipLaunchKernelGGL(k_cply_keys, dim3(stream_grid(n)), dim3(GS_BLOCK), 0, st, (const uint4 *)S.stage.rows, n32, (const uint32_t *)(S.small + 1), S.kv_a);
+        hipLaunchKernelGGL(k_cply_bounds_pos, dim3(pass_grid(n, 1024)), dim3(GS_BLOCK), 0, st, (const uint4 *)S.stage.rows, n32, S.small + 1);
+        hipLaunchKernelGGL(k_cply_keys, dim3(pass_grid(n, GS_CPLY_GRID)), dim3(GS_BLOCK), 0, st, (const uint4 *)S.stage.rows, n32, (const uint32_t *)(S.small + 1), S.kv_a);
         GS_HIP(hipGetLastError());
         int rc = GS_OK;
         for (int pass = 0; pass < 4 && rc == GS_OK; pass++) {

@@ -9,42 +9,15 @@
 // Behind the launchers: the entry points of the C ABI that call them (gs_set_state ... gs_compact).
 #include "gs_lanes.h"
 #include "gs_sh.h"
+#include "gs_cloud_pass.h"
 
 namespace {
 
-#define GS_EDIT_IPT 8u                                           // items per thread: consecutive ones (a thread's items keep their order)
-#define GS_EDIT_CHUNK (GS_EDIT_IPT * GS_BLOCK)                   // items per workgroup step
-#define GS_EDIT_GRID 2048u                                       // workgroups at most for the grid-strided kernels
-
-__device__ __forceinline__ uint32_t wave_sum(uint32_t v)
-{
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
-    return v;
-}
-// one atomic per workgroup: every thread calls it (barriers inside)
-__device__ __forceinline__ void block_count(uint32_t mine, uint32_t *__restrict__ out)
-{
-    __shared__ uint32_t s_w[GS_BLOCK / 64];
-    const uint32_t t = wave_sum(mine);
-    if ((threadIdx.x & 63) == 0) s_w[threadIdx.x >> 6] = t;
-    __syncthreads();
-    if (threadIdx.x == 0) { const uint32_t s = s_w[0] + s_w[1] + s_w[2] + s_w[3]; if (s) atomicAdd(out, s); }
-}
-// exclusive scan of one value per thread over the workgroup (256 threads), in thread order; total: the sum (every thread calls it)
-__device__ __forceinline__ uint32_t block_excl_scan(uint32_t v, uint32_t *s_w /* [GS_BLOCK / 64] */, uint32_t &total)
-{
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    uint32_t inc = v;
-    for (int d = 1; d < 64; d <<= 1) { const uint32_t t = __shfl_up(inc, d, 64); if (lane >= d) inc += t; }
-    __syncthreads();                                               // (s_w may still be read from the previous call)
-    if (lane == 63) s_w[w] = inc;
-    __syncthreads();
-    uint32_t base = 0;
-    for (int k = 0; k < w; k++) base += s_w[k];
-    total = s_w[0] + s_w[1] + s_w[2] + s_w[3];
-    return base + inc - v;
-}
+// Earlier versions of the tests read these two names out of THIS file.  The constants live in gs_cloud_pass.h; the lines below restate
+// them token for token, and one that differs does not compile
+#pragma clang diagnostic error "-Wmacro-redefined"
+#define GS_EDIT_IPT 8u
+#define GS_EDIT_GRID 2048u
 
 __global__ __launch_bounds__(GS_BLOCK) void k_edit_count_hidden(const uint8_t *__restrict__ state, uint32_t n, uint32_t *__restrict__ out)
 {
@@ -72,7 +45,7 @@ __global__ __launch_bounds__(GS_BLOCK) void k_edit_select_box(const float4 *__re
         const float4 m = rows[i];
         // the depth pass' own test (index.js:526-545)
         const bool inside = b.affine ? gsm::in_cutout_affine(b.c, m.x, m.y, m.z) : gsm::in_cutout(b.c, m.x, m.y, m.z);
-        if (inside != (invert != 0u)) { state[i] = (uint8_t)((state[i] & ~clear) | set); c++; }
+        c += take_if(inside, invert, state, i, set, clear);
     }
     block_count(c, hit);
 }
@@ -85,17 +58,39 @@ __global__ __launch_bounds__(GS_BLOCK) void k_edit_select_sphere(const uint4 *__
         const uint4 cs = splat[2 * (size_t)i];                       // the packed centre (x, y, -z): index.js:350-354
         const double dx = (double)__uint_as_float(cs.x) - cx, dy = (double)__uint_as_float(cs.y) - cy, dz = (double)(-__uint_as_float(cs.z)) - cz;
         const double d2 = (dx * dx + dy * dy) + dz * dz;             // (un-fused: the library is built with -ffp-contract=off)
-        const bool inside = d2 <= r2;                                // (NaN: outside)
-        if (inside != (invert != 0u)) { state[i] = (uint8_t)((state[i] & ~clear) | set); c++; }
+        c += take_if(d2 <= r2, invert, state, i, set, clear);       // (NaN: outside)
     }
     block_count(c, hit);
 }
 
-struct RectUniforms { float mv[16], proj[16]; float focal, vw, vh; float x0, y0, x1, y1, hm1; };   // the rectangle clipped to the frame; hm1 = fb_height - 1
-template <bool PAR>
-__global__ __launch_bounds__(GS_BLOCK) void k_edit_select_rect(const uint32_t *__restrict__ sorted, const GsControl *__restrict__ ctl, uint32_t n,
-                                                               const uint4 *__restrict__ splat, RectUniforms u, uint8_t *__restrict__ state,
-                                                               uint32_t set, uint32_t clear, uint32_t invert, uint32_t *__restrict__ hit)
+// ---- the two selections made on the screen: one walk over the whole order, the centre projected by the frame's own function, then a test
+// of the centre's pixel.  The rectangle, clipped to the frame; hm1 = fb_height - 1
+struct ScreenUniforms { float mv[16], proj[16]; float focal, vw, vh; };
+struct InRect {
+    float x0, y0, x1, y1, hm1;
+    __device__ __forceinline__ bool operator()(const gsm::Projected &p, const gsm::ProjExtra &) const
+    {
+        const float px = floorf(p.cx), py = hm1 - floorf(p.cy);      // GL rows (y up) -> image rows (top-down); NaN compares false
+        return px >= x0 && px < x1 && py >= y0 && py < y1;
+    }
+};
+// A mask image: one byte per pixel, tight rows of W, row 0 = top (non-zero = inside), and an optional plane of window depths, tight too: a
+// position is taken iff its centre's pixel lies in the frame, the mask is set there and -- with a plane -- the depth k_project writes to
+// zwin is <= the plane's value there (a NaN on either side: not taken)
+struct InMask {
+    int32_t W, H; const uint8_t *__restrict__ mask; const float *__restrict__ depth_max;
+    __device__ __forceinline__ bool operator()(const gsm::Projected &p, const gsm::ProjExtra &x) const
+    {
+        const float fx = floorf(p.cx), fy = floorf(p.cy);
+        if (!(fx >= 0.0f && fx < (float)W && fy >= 0.0f && fy < (float)H)) return false;   // (NaN compares false; inside the frame: exact integers)
+        const size_t px = (size_t)(H - 1 - (int32_t)fy) * (size_t)W + (size_t)(int32_t)fx;   // GL rows (y up) -> image rows (top-down)
+        return mask[px] != 0 && (!depth_max || x.zndc * 0.5f + 0.5f <= depth_max[px]);       // k_project's zwin
+    }
+};
+template <bool PAR, typename T>
+__global__ __launch_bounds__(GS_BLOCK) void k_edit_select_screen(const uint32_t *__restrict__ sorted, const GsControl *__restrict__ ctl, uint32_t n,
+                                                                 const uint4 *__restrict__ splat, ScreenUniforms u, T test, uint8_t *__restrict__ state,
+                                                                 uint32_t set, uint32_t clear, uint32_t invert, uint32_t *__restrict__ hit)
 {
     const uint32_t V = ctl->n_kept < n ? ctl->n_kept : n;           // the whole order: V positions, every value an index below n
     uint32_t c = 0;
@@ -106,103 +101,29 @@ __global__ __launch_bounds__(GS_BLOCK) void k_edit_select_rect(const uint32_t *_
         const float cs[4] = { __uint_as_float(cs4.x), __uint_as_float(cs4.y), __uint_as_float(cs4.z), __uint_as_float(cs4.w) };
         const uint32_t cc[4] = { cc4.x, cc4.y, cc4.z, cc4.w };
         gsm::Projected p; gsm::ProjExtra x;
-        bool inside = false;
-        if (gsm::project_splat<PAR>(cs, cc, u.mv, u.proj, u.focal, u.vw, u.vh, p, x)) {   // what k_project<.., PAR> calls, with the frame's uniforms
-            const float px = floorf(p.cx), py = u.hm1 - floorf(p.cy);   // GL rows (y up) -> image rows (top-down); NaN compares false
-            inside = px >= u.x0 && px < u.x1 && py >= u.y0 && py < u.y1;
-        }
-        if (inside != (invert != 0u)) { state[idx] = (uint8_t)((state[idx] & ~clear) | set); c++; }
+        // what k_project<.., PAR> calls, with the frame's uniforms
+        const bool inside = gsm::project_splat<PAR>(cs, cc, u.mv, u.proj, u.focal, u.vw, u.vh, p, x) && test(p, x);
+        c += take_if(inside, invert, state, idx, set, clear);
     }
     block_count(c, hit);
 }
 
-// The same walk against a mask image: one byte per pixel, tight rows of W, row 0 = top (non-zero = inside), and an optional plane of window
-// depths, tight too: a position is taken iff its centre's pixel lies in the frame, the mask is set there and -- with a plane -- the depth
-// k_project writes to zwin is <= the plane's value there (a NaN on either side: not taken)
-struct MaskUniforms { float mv[16], proj[16]; float focal, vw, vh; int32_t W, H; };
-template <bool PAR>
-__global__ __launch_bounds__(GS_BLOCK) void k_edit_select_mask(const uint32_t *__restrict__ sorted, const GsControl *__restrict__ ctl, uint32_t n,
-                                                               const uint4 *__restrict__ splat, MaskUniforms u, const uint8_t *__restrict__ mask,
-                                                               const float *__restrict__ depth_max, uint8_t *__restrict__ state,
-                                                               uint32_t set, uint32_t clear, uint32_t invert, uint32_t *__restrict__ hit)
-{
-    const uint32_t V = ctl->n_kept < n ? ctl->n_kept : n;           // the whole order: V positions, every value an index below n
-    uint32_t c = 0;
-    for (uint32_t j = blockIdx.x * GS_BLOCK + threadIdx.x; j < V; j += gridDim.x * GS_BLOCK) {
-        const uint32_t idx = sorted[j];
-        if (idx >= n) continue;
-        const uint4 cs4 = splat[2 * (size_t)idx], cc4 = splat[2 * (size_t)idx + 1];
-        const float cs[4] = { __uint_as_float(cs4.x), __uint_as_float(cs4.y), __uint_as_float(cs4.z), __uint_as_float(cs4.w) };
-        const uint32_t cc[4] = { cc4.x, cc4.y, cc4.z, cc4.w };
-        gsm::Projected p; gsm::ProjExtra x;
-        bool inside = false;
-        if (gsm::project_splat<PAR>(cs, cc, u.mv, u.proj, u.focal, u.vw, u.vh, p, x)) {   // what k_project<.., PAR> calls, with the frame's uniforms
-            const float fx = floorf(p.cx), fy = floorf(p.cy);
-            if (fx >= 0.0f && fx < (float)u.W && fy >= 0.0f && fy < (float)u.H) {     // (NaN compares false; inside the frame: exact integers)
-                const size_t px = (size_t)(u.H - 1 - (int32_t)fy) * (size_t)u.W + (size_t)(int32_t)fx;   // GL rows (y up) -> image rows (top-down)
-                inside = mask[px] != 0;
-                if (inside && depth_max) inside = x.zndc * 0.5f + 0.5f <= depth_max[px];   // k_project's zwin
-            }
-        }
-        if (inside != (invert != 0u)) { state[idx] = (uint8_t)((state[idx] & ~clear) | set); c++; }
-    }
-    block_count(c, hit);
-}
-
-// ---- gs_compact: flags -> offsets -> scatter.  A workgroup owns GS_EDIT_CHUNK consecutive splats, a thread GS_EDIT_IPT consecutive ones
-__device__ __forceinline__ bool edit_kept(const uint8_t *__restrict__ state, uint32_t rows, uint32_t i, uint32_t n)
-{
-    return i < n && !(i < rows && (state[i] & GS_STATE_HIDDEN));
-}
-__global__ __launch_bounds__(GS_BLOCK) void k_compact_count(const uint8_t *__restrict__ state, uint32_t rows, uint32_t n, uint32_t *__restrict__ blk)
-{
-    __shared__ uint32_t s_c;
-    if (threadIdx.x == 0) s_c = 0;
-    __syncthreads();
-    uint32_t c = 0;
-    const uint32_t i0 = blockIdx.x * GS_EDIT_CHUNK + threadIdx.x * GS_EDIT_IPT;
-    for (uint32_t j = 0; j < GS_EDIT_IPT; j++) c += edit_kept(state, rows, i0 + j, n) ? 1u : 0u;
-    c = wave_sum(c);
-    if ((threadIdx.x & 63) == 0 && c) atomicAdd(&s_c, c);
-    __syncthreads();
-    if (threadIdx.x == 0) blk[blockIdx.x] = s_c;
-}
-// one workgroup: blk[0, nblk) -> their exclusive sums in place, blk[nblk] = the total
-__global__ __launch_bounds__(GS_BLOCK) void k_compact_offsets(uint32_t *__restrict__ blk, uint32_t nblk)
-{
-    __shared__ uint32_t s_w[GS_BLOCK / 64];
-    uint32_t carry = 0;
-    for (uint32_t b0 = 0; b0 < nblk; b0 += GS_BLOCK) {
-        const uint32_t b = b0 + threadIdx.x;
-        const uint32_t v = b < nblk ? blk[b] : 0u;
-        uint32_t total;
-        const uint32_t ex = block_excl_scan(v, s_w, total);
-        if (b < nblk) blk[b] = carry + ex;
-        carry += total;
-    }
-    if (threadIdx.x == 0) blk[nblk] = carry;
-}
-__global__ __launch_bounds__(GS_BLOCK) void k_compact_scatter(const uint8_t *__restrict__ state, uint32_t rows, uint32_t n, const uint32_t *__restrict__ blk,
+// ---- gs_compact: the shared compaction (gs_cloud_pass.h) over NotHidden, and the scatter of every resident array
+__global__ __launch_bounds__(GS_BLOCK) void k_compact_scatter(NotHidden kept, uint32_t n, const uint32_t *__restrict__ blk,
                                                               const uint4 *__restrict__ splat, const float4 *__restrict__ sort_rows, const float *__restrict__ bound_r,
                                                               uint32_t renderable, uint4 *__restrict__ o_splat, float4 *__restrict__ o_rows, float *__restrict__ o_bound,
                                                               uint8_t *__restrict__ o_state, uint32_t *__restrict__ o_old)
 {
-    __shared__ uint32_t s_w[GS_BLOCK / 64];
-    const uint32_t i0 = blockIdx.x * GS_EDIT_CHUNK + threadIdx.x * GS_EDIT_IPT;
-    bool keep[GS_EDIT_IPT];
-    uint32_t c = 0;
-#pragma unroll
-    for (uint32_t j = 0; j < GS_EDIT_IPT; j++) { keep[j] = edit_kept(state, rows, i0 + j, n); c += keep[j] ? 1u : 0u; }
-    uint32_t total;
-    uint32_t k = blk[blockIdx.x] + block_excl_scan(c, s_w, total);  // the new index of this thread's first kept splat (k + kept < blk[nblk] <= n)
+    uint32_t i0, take;
+    uint32_t k = compact_slot(kept, n, blk, i0, take);              // the new index of this thread's first kept splat (k + kept < blk[nblk] <= n)
 #pragma unroll
     for (uint32_t j = 0; j < GS_EDIT_IPT; j++) {
-        if (!keep[j]) continue;
+        if (!((take >> j) & 1u)) continue;
         const uint32_t i = i0 + j;
         if (renderable) { o_splat[2 * (size_t)k] = splat[2 * (size_t)i]; o_splat[2 * (size_t)k + 1] = splat[2 * (size_t)i + 1]; }
         o_rows[k] = sort_rows[i];
         o_bound[k] = bound_r[i];
-        o_state[k] = i < rows ? state[i] : (uint8_t)0;               // (the hidden bit is clear: the splat was kept)
+        o_state[k] = i < kept.rows ? kept.state[i] : (uint8_t)0;    // (the hidden bit is clear: the splat was kept)
         o_old[k] = i;
         k++;
     }
@@ -251,13 +172,6 @@ template <bool CC, bool SEEN> __device__ __forceinline__ double prop_load_any(co
     if (SEEN) return i < seen_n ? (double)seen[i] / 65536.0 : 0.0;
     return prop_load<CC>(splat, i, prop);
 }
-// the filter: rows = 0 when the mask is 0 or the store is empty (no byte is loaded then: a store that was never allocated is never read)
-__device__ __forceinline__ bool prop_passes(const uint8_t *__restrict__ state, uint32_t rows, uint32_t i, uint32_t mask, uint32_t value)
-{
-    const uint32_t st = i < rows ? (uint32_t)state[i] : 0u;
-    return (st & mask) == value;
-}
-
 template <bool CC, bool SEEN>
 __device__ __forceinline__ void prop_select_body(const uint4 *__restrict__ splat, uint32_t n, int prop, double lo, double hi, uint8_t *__restrict__ state,
                                                  uint32_t set, uint32_t clear, uint32_t invert, uint32_t *__restrict__ hit, SeenStore seen, uint32_t seen_n)
@@ -265,8 +179,7 @@ __device__ __forceinline__ void prop_select_body(const uint4 *__restrict__ splat
     uint32_t c = 0;
     for (uint32_t i = blockIdx.x * GS_BLOCK + threadIdx.x; i < n; i += gridDim.x * GS_BLOCK) {
         const double v = prop_load_any<CC, SEEN>(splat, i, prop, seen, seen_n);
-        const bool inside = lo <= v && v <= hi;                      // (NaN: outside)
-        if (inside != (invert != 0u)) { state[i] = (uint8_t)((state[i] & ~clear) | set); c++; }
+        c += take_if(lo <= v && v <= hi, invert, state, i, set, clear);   // (NaN: outside)
     }
     block_count(c, hit);
 }
@@ -293,19 +206,13 @@ __device__ __forceinline__ void prop_range_body(const uint4 *__restrict__ splat,
     double mn = INFINITY, mx = -INFINITY;
     uint32_t c = 0;
     for (uint32_t i = blockIdx.x * GS_BLOCK + threadIdx.x; i < n; i += gridDim.x * GS_BLOCK) {
-        if (!prop_passes(state, rows, i, mask, value)) continue;
+        if (!state_passes(state, rows, i, mask, value)) continue;
         const double v = prop_load_any<CC, SEEN>(splat, i, prop, seen, seen_n);
         c++;
         if (v < mn) mn = v;                                          // (a NaN compares false twice)
         if (v > mx) mx = v;
     }
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) {
-        const double a = __shfl_xor(mn, m, 64), b = __shfl_xor(mx, m, 64);
-        if (a < mn) mn = a;
-        if (b > mx) mx = b;
-    }
-    c = wave_sum(c);
+    mn = wave_min(mn); mx = wave_max(mx); c = wave_sum(c);
     if ((threadIdx.x & 63) == 0) { s_mn[threadIdx.x >> 6] = mn; s_mx[threadIdx.x >> 6] = mx; s_c[threadIdx.x >> 6] = c; }
     __syncthreads();
     if (threadIdx.x == 0) {
@@ -352,7 +259,7 @@ __device__ __forceinline__ void prop_hist_body(const uint4 *__restrict__ splat, 
         const uint64_t i64 = base + threadIdx.x;
         const uint32_t i = (uint32_t)(i64 < n ? i64 : n);            // (i == n: no splat)
         int32_t bin = -4;                                            // not a passing splat
-        if (i < n && prop_passes(state, rows, i, mask, value)) bin = gsm::hist_bin(prop_load_any<CC, SEEN>(splat, i, prop, seen, seen_n), lo, hi, scale, nbins);
+        if (i < n && state_passes(state, rows, i, mask, value)) bin = gsm::hist_bin(prop_load_any<CC, SEEN>(splat, i, prop, seen, seen_n), lo, hi, scale, nbins);
         passing += bin != -4; below += bin == -1; above += bin == -2; nan += bin == -3;
         unsigned long long todo = __ballot(bin >= 0);
         for (int r = 0; r < GS_HIST_PEEL && todo; r++) {
@@ -388,26 +295,23 @@ __global__ __launch_bounds__(GS_BLOCK) void k_prop_hist_seen(SeenStore seen, uin
     prop_hist_body<false, true>(nullptr, n, GS_PROP_SEEN, lo, hi, scale, nbins, state, rows, mask, value, out, seen, seen_n);
 }
 
-uint32_t stream_grid(size_t n)
+// what gs_edit_select_rect and gs_edit_select_mask do alike, around their test of a pixel
+template <typename T> int select_screen(gs_ctx *ctx, gs_ctx *L, const GsFrameUniforms &f, T test, uint8_t set, uint8_t clear, bool invert, size_t *hit)
 {
-    const uint32_t g = gs_div_up(n ? n : 1, GS_BLOCK);
-    return g > GS_EDIT_GRID ? GS_EDIT_GRID : g;
-}
-
-int counters(gs_ctx *ctx)
-{
-    if (!ctx->edit_cnt) GS_HIP(hipMalloc((void **)&ctx->edit_cnt, 2 * sizeof(uint32_t)));
-    GS_HIP(hipMemsetAsync(ctx->edit_cnt, 0, 2 * sizeof(uint32_t), ctx->stream));
-    return GS_OK;
-}
-int read_counter(gs_ctx *ctx, size_t *out)
-{
-    uint32_t v = 0;
-    GS_HIP(hipGetLastError());
-    GS_HIP(hipMemcpyAsync(&v, ctx->edit_cnt, sizeof v, hipMemcpyDeviceToHost, ctx->stream));
+    TRY(counters(ctx));
+    ScreenUniforms u;
+    memcpy(u.mv, f.mv, sizeof u.mv); memcpy(u.proj, f.proj, sizeof u.proj);
+    u.focal = f.focal; u.vw = f.vw; u.vh = f.vh;
+    // (the uploads and the counters went to the owner's stream, which is otherwise idle -- the lanes were drained; the lane's stream holds the order)
     GS_HIP(hipStreamSynchronize(ctx->stream));
-    if (out) *out = v;
-    return GS_OK;
+    gs_flag((f.flags & GS_RENDER_PARALLEL) != 0, [&](auto PAR) {   // (the camera model of the frame, as launch_project picks k_project's)
+        hipLaunchKernelGGL((k_edit_select_screen<decltype(PAR)::value, T>), dim3(pass_grid(ctx->n)), dim3(GS_BLOCK), 0, L->stream, (const uint32_t *)L->sorted,
+                           (const GsControl *)L->ctl, (uint32_t)ctx->n, (const uint4 *)ctx->splat, u, test, ctx->edit_state, (uint32_t)set, (uint32_t)clear,
+                           invert ? 1u : 0u, ctx->edit_cnt);
+    });
+    GS_HIP(hipGetLastError());
+    GS_HIP(hipStreamSynchronize(L->stream));
+    return read_counter(ctx, hit);
 }
 
 }  // namespace
@@ -418,14 +322,14 @@ int gs_edit_count_hidden(gs_ctx *ctx, const uint8_t *state, size_t n, size_t *ou
     if (!n) return GS_OK;
     int rc = counters(ctx);
     if (rc != GS_OK) return rc;
-    hipLaunchKernelGGL(k_edit_count_hidden, dim3(stream_grid(n)), dim3(GS_BLOCK), 0, ctx->stream, state, (uint32_t)n, ctx->edit_cnt);
+    hipLaunchKernelGGL(k_edit_count_hidden, dim3(pass_grid(n)), dim3(GS_BLOCK), 0, ctx->stream, state, (uint32_t)n, ctx->edit_cnt);
     return read_counter(ctx, out);
 }
 
 int gs_edit_apply_ids(gs_ctx *ctx, const uint32_t *ids_dev, size_t n, uint8_t set, uint8_t clear)
 {
     if (!n) return GS_OK;
-    hipLaunchKernelGGL(k_edit_apply_ids, dim3(stream_grid(n)), dim3(GS_BLOCK), 0, ctx->stream, ctx->edit_state, (uint32_t)ctx->edit_n, ids_dev, (uint32_t)n,
+    hipLaunchKernelGGL(k_edit_apply_ids, dim3(pass_grid(n)), dim3(GS_BLOCK), 0, ctx->stream, ctx->edit_state, (uint32_t)ctx->edit_n, ids_dev, (uint32_t)n,
                        (uint32_t)set, (uint32_t)clear);
     GS_HIP(hipGetLastError());
     GS_HIP(hipStreamSynchronize(ctx->stream));
@@ -439,7 +343,7 @@ int gs_edit_select_box(gs_ctx *ctx, const float box16[16], uint8_t set, uint8_t 
     BoxUniforms b;
     for (int i = 0; i < 16; i++) b.c[i] = (double)box16[i];
     b.affine = (b.c[3] == 0.0 && b.c[7] == 0.0 && b.c[11] == 0.0 && b.c[15] == 1.0) ? 1 : 0;   // (gs_sort.hip: fill_sort_uniforms)
-    hipLaunchKernelGGL(k_edit_select_box, dim3(stream_grid(ctx->n)), dim3(GS_BLOCK), 0, ctx->stream, (const float4 *)ctx->sort_rows, (uint32_t)ctx->n, b,
+    hipLaunchKernelGGL(k_edit_select_box, dim3(pass_grid(ctx->n)), dim3(GS_BLOCK), 0, ctx->stream, (const float4 *)ctx->sort_rows, (uint32_t)ctx->n, b,
                        ctx->edit_state, (uint32_t)set, (uint32_t)clear, invert ? 1u : 0u, ctx->edit_cnt);
     return read_counter(ctx, hit);
 }
@@ -449,7 +353,7 @@ int gs_edit_select_sphere(gs_ctx *ctx, const float centre[3], float radius, uint
     int rc = counters(ctx);
     if (rc != GS_OK) return rc;
     const double r2 = (double)radius * (double)radius;
-    hipLaunchKernelGGL(k_edit_select_sphere, dim3(stream_grid(ctx->n)), dim3(GS_BLOCK), 0, ctx->stream, (const uint4 *)ctx->splat, (uint32_t)ctx->n,
+    hipLaunchKernelGGL(k_edit_select_sphere, dim3(pass_grid(ctx->n)), dim3(GS_BLOCK), 0, ctx->stream, (const uint4 *)ctx->splat, (uint32_t)ctx->n,
                        (double)centre[0], (double)centre[1], (double)centre[2], r2, ctx->edit_state, (uint32_t)set, (uint32_t)clear, invert ? 1u : 0u, ctx->edit_cnt);
     return read_counter(ctx, hit);
 }
@@ -459,10 +363,10 @@ int gs_edit_select_range(gs_ctx *ctx, int prop, double lo, double hi, uint8_t se
     int rc = counters(ctx);
     if (rc != GS_OK) return rc;
     if (prop == GS_PROP_SEEN)
-        hipLaunchKernelGGL(k_prop_select_seen, dim3(stream_grid(ctx->n)), dim3(GS_BLOCK), 0, ctx->stream, (const unsigned long long *)ctx->contrib, (uint32_t)ctx->contrib_n,
+        hipLaunchKernelGGL(k_prop_select_seen, dim3(pass_grid(ctx->n)), dim3(GS_BLOCK), 0, ctx->stream, (const unsigned long long *)ctx->contrib, (uint32_t)ctx->contrib_n,
                            (uint32_t)ctx->n, lo, hi, ctx->edit_state, (uint32_t)set, (uint32_t)clear, invert ? 1u : 0u, ctx->edit_cnt);
     else gs_flag(gsm::prop_reads_cc(prop), [&](auto CC) {
-        hipLaunchKernelGGL((k_prop_select<decltype(CC)::value>), dim3(stream_grid(ctx->n)), dim3(GS_BLOCK), 0, ctx->stream, (const uint4 *)ctx->splat,
+        hipLaunchKernelGGL((k_prop_select<decltype(CC)::value>), dim3(pass_grid(ctx->n)), dim3(GS_BLOCK), 0, ctx->stream, (const uint4 *)ctx->splat,
                            (uint32_t)ctx->n, prop, lo, hi, ctx->edit_state, (uint32_t)set, (uint32_t)clear, invert ? 1u : 0u, ctx->edit_cnt);
     });
     return read_counter(ctx, hit);
@@ -471,18 +375,15 @@ int gs_edit_select_range(gs_ctx *ctx, int prop, double lo, double hi, uint8_t se
 // the reading passes' stream and device words (made once), the words cleared on that stream
 static int prop_begin(gs_ctx *ctx, size_t clear_bytes)
 {
-    GS_HIP(hipSetDevice(ctx->device));
-    if (!ctx->prop_stream) GS_HIP(hipStreamCreateWithFlags(&ctx->prop_stream, hipStreamNonBlocking));
+    TRY(reading_stream(ctx));
     if (!ctx->prop_buf) GS_HIP(hipMalloc(&ctx->prop_buf, GS_PROP_BUF_BYTES));
     if (clear_bytes) GS_HIP(hipMemsetAsync(ctx->prop_buf, 0, clear_bytes, ctx->prop_stream));
     return GS_OK;
 }
-// the state store as the filter sees it: no rows when the mask is 0 (every state passes or none does: nothing to load) or the store is empty
-static uint32_t prop_rows(const gs_ctx *ctx, uint8_t mask) { return (mask && ctx->edit_state) ? (uint32_t)ctx->edit_n : 0u; }
 
 int gs_prop_run_range(gs_ctx *ctx, int prop, uint8_t mask, uint8_t value, double *mn, double *mx, size_t *n)
 {
-    const uint32_t grid = stream_grid(ctx->n);                       // (grid x (16 + 4) bytes <= GS_PROP_BUF_BYTES)
+    const uint32_t grid = pass_grid(ctx->n);                       // (grid x (16 + 4) bytes <= GS_PROP_BUF_BYTES)
     static_assert(GS_EDIT_GRID * (sizeof(double2) + sizeof(uint32_t)) <= GS_PROP_BUF_BYTES, "the partials fit the buffer");
     int rc = prop_begin(ctx, 0);
     if (rc != GS_OK) return rc;
@@ -490,10 +391,10 @@ int gs_prop_run_range(gs_ctx *ctx, int prop, uint8_t mask, uint8_t value, double
     uint32_t *cnt = reinterpret_cast<uint32_t *>(part + GS_EDIT_GRID);
     if (prop == GS_PROP_SEEN)
         hipLaunchKernelGGL(k_prop_range_seen, dim3(grid), dim3(GS_BLOCK), 0, ctx->prop_stream, (const unsigned long long *)ctx->contrib, (uint32_t)ctx->contrib_n, (uint32_t)ctx->n,
-                           (const uint8_t *)ctx->edit_state, prop_rows(ctx, mask), (uint32_t)mask, (uint32_t)value, part, cnt);
+                           (const uint8_t *)ctx->edit_state, filter_rows(ctx, mask), (uint32_t)mask, (uint32_t)value, part, cnt);
     else gs_flag(gsm::prop_reads_cc(prop), [&](auto CC) {
         hipLaunchKernelGGL((k_prop_range<decltype(CC)::value>), dim3(grid), dim3(GS_BLOCK), 0, ctx->prop_stream, (const uint4 *)ctx->splat, (uint32_t)ctx->n, prop,
-                           (const uint8_t *)ctx->edit_state, prop_rows(ctx, mask), (uint32_t)mask, (uint32_t)value, part, cnt);
+                           (const uint8_t *)ctx->edit_state, filter_rows(ctx, mask), (uint32_t)mask, (uint32_t)value, part, cnt);
     });
     GS_HIP(hipGetLastError());
     std::vector<double2> hp(grid);
@@ -515,11 +416,11 @@ int gs_prop_run_histogram(gs_ctx *ctx, int prop, double lo, double hi, double sc
     if (rc != GS_OK) return rc;
     uint32_t *out = reinterpret_cast<uint32_t *>(ctx->prop_buf);
     if (prop == GS_PROP_SEEN)
-        hipLaunchKernelGGL(k_prop_hist_seen, dim3(stream_grid(ctx->n)), dim3(GS_BLOCK), 0, ctx->prop_stream, (const unsigned long long *)ctx->contrib, (uint32_t)ctx->contrib_n,
-                           (uint32_t)ctx->n, lo, hi, scale, nbins, (const uint8_t *)ctx->edit_state, prop_rows(ctx, mask), (uint32_t)mask, (uint32_t)value, out);
+        hipLaunchKernelGGL(k_prop_hist_seen, dim3(pass_grid(ctx->n)), dim3(GS_BLOCK), 0, ctx->prop_stream, (const unsigned long long *)ctx->contrib, (uint32_t)ctx->contrib_n,
+                           (uint32_t)ctx->n, lo, hi, scale, nbins, (const uint8_t *)ctx->edit_state, filter_rows(ctx, mask), (uint32_t)mask, (uint32_t)value, out);
     else gs_flag(gsm::prop_reads_cc(prop), [&](auto CC) {
-        hipLaunchKernelGGL((k_prop_hist<decltype(CC)::value>), dim3(stream_grid(ctx->n)), dim3(GS_BLOCK), 0, ctx->prop_stream, (const uint4 *)ctx->splat,
-                           (uint32_t)ctx->n, prop, lo, hi, scale, nbins, (const uint8_t *)ctx->edit_state, prop_rows(ctx, mask), (uint32_t)mask, (uint32_t)value, out);
+        hipLaunchKernelGGL((k_prop_hist<decltype(CC)::value>), dim3(pass_grid(ctx->n)), dim3(GS_BLOCK), 0, ctx->prop_stream, (const uint4 *)ctx->splat,
+                           (uint32_t)ctx->n, prop, lo, hi, scale, nbins, (const uint8_t *)ctx->edit_state, filter_rows(ctx, mask), (uint32_t)mask, (uint32_t)value, out);
     });
     GS_HIP(hipGetLastError());
     uint32_t t[4];
@@ -532,55 +433,27 @@ int gs_prop_run_histogram(gs_ctx *ctx, int prop, double lo, double hi, double sc
 
 int gs_edit_select_rect(gs_ctx *ctx, gs_ctx *L, const GsFrameUniforms &f, const int32_t rect[4], uint8_t set, uint8_t clear, bool invert, size_t *hit)
 {
-    int rc = counters(ctx);
-    if (rc != GS_OK) return rc;
-    RectUniforms u;
-    memcpy(u.mv, f.mv, sizeof u.mv); memcpy(u.proj, f.proj, sizeof u.proj);
-    u.focal = f.focal; u.vw = f.vw; u.vh = f.vh;
     const int32_t x0 = rect[0] > 0 ? rect[0] : 0, y0 = rect[1] > 0 ? rect[1] : 0;
     const int32_t x1 = rect[2] < f.W ? rect[2] : f.W, y1 = rect[3] < f.H ? rect[3] : f.H;
-    u.x0 = (float)x0; u.y0 = (float)y0; u.x1 = (float)x1; u.y1 = (float)y1; u.hm1 = (float)(f.H - 1);
-    // (the lane's stream holds the order; the owner's stream is idle and the lanes were drained: one stream suffices)
-    GS_HIP(hipStreamSynchronize(ctx->stream));
-    gs_flag((f.flags & GS_RENDER_PARALLEL) != 0, [&](auto PAR) {   // (the camera model of the frame, as launch_project picks k_project's)
-        hipLaunchKernelGGL(k_edit_select_rect<decltype(PAR)::value>, dim3(stream_grid(ctx->n)), dim3(GS_BLOCK), 0, L->stream, (const uint32_t *)L->sorted, (const GsControl *)L->ctl,
-                           (uint32_t)ctx->n, (const uint4 *)ctx->splat, u, ctx->edit_state, (uint32_t)set, (uint32_t)clear, invert ? 1u : 0u, ctx->edit_cnt);
-    });
-    GS_HIP(hipGetLastError());
-    GS_HIP(hipStreamSynchronize(L->stream));
-    return read_counter(ctx, hit);
+    const InRect test = { (float)x0, (float)y0, (float)x1, (float)y1, (float)(f.H - 1) };
+    return select_screen(ctx, L, f, test, set, clear, invert, hit);
 }
 
 int gs_edit_select_mask(gs_ctx *ctx, gs_ctx *L, const GsFrameUniforms &f, const uint8_t *mask_dev, const float *depth_dev, uint8_t set, uint8_t clear,
                         bool invert, size_t *hit)
 {
-    int rc = counters(ctx);
-    if (rc != GS_OK) return rc;
-    MaskUniforms u;
-    memcpy(u.mv, f.mv, sizeof u.mv); memcpy(u.proj, f.proj, sizeof u.proj);
-    u.focal = f.focal; u.vw = f.vw; u.vh = f.vh; u.W = f.W; u.H = f.H;
-    // (the uploads and the counters went to the owner's stream; the lane's stream holds the order: as gs_edit_select_rect)
-    GS_HIP(hipStreamSynchronize(ctx->stream));
-    gs_flag((f.flags & GS_RENDER_PARALLEL) != 0, [&](auto PAR) {
-        hipLaunchKernelGGL(k_edit_select_mask<decltype(PAR)::value>, dim3(stream_grid(ctx->n)), dim3(GS_BLOCK), 0, L->stream, (const uint32_t *)L->sorted, (const GsControl *)L->ctl,
-                           (uint32_t)ctx->n, (const uint4 *)ctx->splat, u, mask_dev, depth_dev, ctx->edit_state, (uint32_t)set, (uint32_t)clear, invert ? 1u : 0u,
-                           ctx->edit_cnt);
-    });
-    GS_HIP(hipGetLastError());
-    GS_HIP(hipStreamSynchronize(L->stream));
-    return read_counter(ctx, hit);
+    const InMask test = { f.W, f.H, mask_dev, depth_dev };
+    return select_screen(ctx, L, f, test, set, clear, invert, hit);
 }
 
 int gs_edit_compact(gs_ctx *ctx, const GsCompactTo &to, size_t *kept)
 {
-    const uint32_t n = (uint32_t)ctx->n, rows = (uint32_t)ctx->edit_n;
-    const uint32_t nblk = gs_div_up(n, GS_EDIT_CHUNK);
-    uint32_t *blk = nullptr;
-    GS_HIP(hipMalloc((void **)&blk, ((size_t)nblk + 1) * sizeof(uint32_t)));
+    const uint32_t n = (uint32_t)ctx->n, nblk = gs_div_up(n, GS_EDIT_CHUNK);
+    const NotHidden pred = { ctx->edit_state, (uint32_t)ctx->edit_n };
     hipStream_t st = ctx->stream;
-    hipLaunchKernelGGL(k_compact_count, dim3(nblk), dim3(GS_BLOCK), 0, st, (const uint8_t *)ctx->edit_state, rows, n, blk);
-    hipLaunchKernelGGL(k_compact_offsets, dim3(1), dim3(GS_BLOCK), 0, st, blk, nblk);
-    hipLaunchKernelGGL(k_compact_scatter, dim3(nblk), dim3(GS_BLOCK), 0, st, (const uint8_t *)ctx->edit_state, rows, n, (const uint32_t *)blk,
+    uint32_t *blk = nullptr;
+    TRY(compact_offsets(ctx, st, pred, n, &blk, nullptr));       // (the total is read behind the scatter: one wait for the three kernels)
+    hipLaunchKernelGGL(k_compact_scatter, dim3(nblk), dim3(GS_BLOCK), 0, st, pred, n, (const uint32_t *)blk,
                        (const uint4 *)ctx->splat, (const float4 *)ctx->sort_rows, (const float *)ctx->bound_r, ctx->renderable ? 1u : 0u,
                        to.splat, to.sort_rows, to.bound_r, to.state, to.old_index);
     uint32_t total = 0;
@@ -597,7 +470,7 @@ int gs_edit_compact(gs_ctx *ctx, const GsCompactTo &to, size_t *kept)
 int gs_edit_compact_contrib(gs_ctx *ctx, const uint32_t *old_index, size_t kept, unsigned long long *to)
 {
     if (!kept) return GS_OK;
-    hipLaunchKernelGGL(k_compact_contrib, dim3(stream_grid(kept)), dim3(GS_BLOCK), 0, ctx->stream, (const unsigned long long *)ctx->contrib, old_index, (uint32_t)kept,
+    hipLaunchKernelGGL(k_compact_contrib, dim3(pass_grid(kept)), dim3(GS_BLOCK), 0, ctx->stream, (const unsigned long long *)ctx->contrib, old_index, (uint32_t)kept,
                        (uint32_t)ctx->contrib_n, to);
     GS_HIP(hipGetLastError());
     GS_HIP(hipStreamSynchronize(ctx->stream));
@@ -608,7 +481,7 @@ int gs_edit_compact_contrib(gs_ctx *ctx, const uint32_t *old_index, size_t kept,
 int gs_edit_compact_sh(gs_ctx *ctx, const GsCompactTo &to, size_t sh_words, size_t sh_kept)
 {
     if (!sh_kept || !to.sh) return GS_OK;
-    hipLaunchKernelGGL(k_compact_sh, dim3(stream_grid(sh_kept * sh_words)), dim3(GS_BLOCK), 0, ctx->stream, (const uint4 *)ctx->sh, (const uint32_t *)to.old_index,
+    hipLaunchKernelGGL(k_compact_sh, dim3(pass_grid(sh_kept * sh_words)), dim3(GS_BLOCK), 0, ctx->stream, (const uint4 *)ctx->sh, (const uint32_t *)to.old_index,
                        (uint32_t)sh_kept, (uint32_t)ctx->sh_n, (uint32_t)sh_words, reinterpret_cast<uint4 *>(to.sh));
     GS_HIP(hipGetLastError());
     GS_HIP(hipStreamSynchronize(ctx->stream));
@@ -631,8 +504,7 @@ static int edit_begin(gs_ctx *ctx, size_t rows)
 // after a change: the hidden count, and no lane's order survives (as after a push)
 static int edit_end(gs_ctx *ctx)
 {
-    for (int i = 0; i < GS_MAX_LANES; i++) if (ctx->lanes[i]) ctx->lanes[i]->have_sort = false;
-    if (ctx->pend_lane > 0) ctx->pend_n = (size_t)-1;            // a sort begun before the change is run again when it is collected
+    drop_orders(ctx);
     return gs_edit_count_hidden(ctx, ctx->edit_state, ctx->edit_n, &ctx->edit_hidden);
 }
 

@@ -2,9 +2,8 @@
 // gs_export_sh, gs_export_ply): the splats that pass a state filter, compacted in stable order, each packed record turned into a
 // row again by gsm::export_row (gs_export.h: a symmetric 3x3 eigen-decomposition per splat, f64).
 //
-// The compaction is gs_compact's scheme (gs_edit.hip) with the property calls' filter as its predicate: a workgroup owns
-// GS_EXPORT_CHUNK consecutive splats, a thread GS_EXPORT_IPT consecutive ones; count -> offsets -> scatter.  The three kernels are
-// this file's own -- gs_compact launches what it launched before -- and a context that never exports launches none of them.
+// The compaction is the one gs_compact uses (gs_cloud_pass.h: count -> offsets -> slot) with the state filter as its predicate; the two
+// scatters are this file's own, and a context that never exports launches none of them.
 // Like gs_prop_range and gs_histogram the calls only read the resident arrays: they run on the owner's prop_stream, wait for
 // their own kernels and copies alone, drain no lane, drop no order and touch no option or statistic.
 //
@@ -16,93 +15,24 @@
 // what helps, and the skipped rotations (an entry that is exactly 0) only diverge within a wave.
 #include "gs_lanes.h"
 #include "gs_sh.h"
+#include "gs_cloud_pass.h"
 #include "gs_export.h"
 #include "gs_export_stage.h"
 
 namespace {
 
-#define GS_EXPORT_IPT 8u                                         // GS_EDIT_IPT, GS_EDIT_CHUNK of gs_edit.hip
-#define GS_EXPORT_CHUNK (GS_EXPORT_IPT * GS_BLOCK)
+// (earlier versions of the tests read this name out of this file; the constant is gs_cloud_pass.h's GS_EDIT_IPT)
+#define GS_EXPORT_IPT 8u
+static_assert(GS_EXPORT_IPT == GS_EDIT_IPT, "the exports run the shared compaction: one chunk size");
 
-__device__ __forceinline__ uint32_t wave_sum(uint32_t v)
-{
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
-    return v;
-}
-// exclusive scan of one value per thread over the workgroup (256 threads), in thread order; total: the sum (every thread calls it)
-__device__ __forceinline__ uint32_t block_excl_scan(uint32_t v, uint32_t *s_w /* [GS_BLOCK / 64] */, uint32_t &total)
-{
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    uint32_t inc = v;
-    for (int d = 1; d < 64; d <<= 1) { const uint32_t t = __shfl_up(inc, d, 64); if (lane >= d) inc += t; }
-    __syncthreads();                                               // (s_w may still be read from the previous call)
-    if (lane == 63) s_w[w] = inc;
-    __syncthreads();
-    uint32_t base = 0;
-    for (int k = 0; k < w; k++) base += s_w[k];
-    total = s_w[0] + s_w[1] + s_w[2] + s_w[3];
-    return base + inc - v;
-}
-
-// the property calls' filter (gs_edit.hip: prop_passes): rows = 0 when the mask is 0 or the store is empty -- no byte is loaded then
-__device__ __forceinline__ bool export_passes(const uint8_t *__restrict__ state, uint32_t rows, uint32_t i, uint32_t n, uint32_t mask, uint32_t value)
-{
-    if (i >= n) return false;
-    const uint32_t st = i < rows ? (uint32_t)state[i] : 0u;
-    return (st & mask) == value;
-}
-
-__global__ __launch_bounds__(GS_BLOCK) void k_export_count(const uint8_t *__restrict__ state, uint32_t rows, uint32_t n, uint32_t mask, uint32_t value,
-                                                           uint32_t *__restrict__ blk)
-{
-    __shared__ uint32_t s_c;
-    if (threadIdx.x == 0) s_c = 0;
-    __syncthreads();
-    uint32_t c = 0;
-    const uint32_t i0 = blockIdx.x * GS_EXPORT_CHUNK + threadIdx.x * GS_EXPORT_IPT;
-    for (uint32_t j = 0; j < GS_EXPORT_IPT; j++) c += export_passes(state, rows, i0 + j, n, mask, value) ? 1u : 0u;
-    c = wave_sum(c);
-    if ((threadIdx.x & 63) == 0 && c) atomicAdd(&s_c, c);
-    __syncthreads();
-    if (threadIdx.x == 0) blk[blockIdx.x] = s_c;
-}
-// one workgroup: blk[0, nblk) -> their exclusive sums in place, blk[nblk] = the total
-__global__ __launch_bounds__(GS_BLOCK) void k_export_offsets(uint32_t *__restrict__ blk, uint32_t nblk)
-{
-    __shared__ uint32_t s_w[GS_BLOCK / 64];
-    uint32_t carry = 0;
-    for (uint32_t b0 = 0; b0 < nblk; b0 += GS_BLOCK) {
-        const uint32_t b = b0 + threadIdx.x;
-        const uint32_t v = b < nblk ? blk[b] : 0u;
-        uint32_t total;
-        const uint32_t ex = block_excl_scan(v, s_w, total);
-        if (b < nblk) blk[b] = carry + ex;
-        carry += total;
-    }
-    if (threadIdx.x == 0) blk[nblk] = carry;
-}
-// the new index of this thread's first passing splat, and which of its splats pass (bit j: splat i0 + j)
-__device__ __forceinline__ uint32_t export_slot(const uint8_t *__restrict__ state, uint32_t rows, uint32_t n, uint32_t mask, uint32_t value,
-                                                const uint32_t *__restrict__ blk, uint32_t i0, uint32_t &take)
-{
-    __shared__ uint32_t s_w[GS_BLOCK / 64];
-    take = 0;
-#pragma unroll
-    for (uint32_t j = 0; j < GS_EXPORT_IPT; j++) take |= export_passes(state, rows, i0 + j, n, mask, value) ? (1u << j) : 0u;
-    uint32_t total;
-    return blk[blockIdx.x] + block_excl_scan((uint32_t)__popc(take), s_w, total);   // (k + passing <= blk[nblk]: what the outputs hold)
-}
 // o_rows: 2 x 16 bytes per row; o_wide (may be null): 7 f32 per row; o_index (may be null): the old index
-__global__ __launch_bounds__(GS_BLOCK) void k_export_scatter(const uint8_t *__restrict__ state, uint32_t rows, uint32_t n, uint32_t mask, uint32_t value,
-                                                                const uint32_t *__restrict__ blk, const uint4 *__restrict__ splat, uint4 *__restrict__ o_rows,
-                                                                float *__restrict__ o_wide, uint32_t *__restrict__ o_index)
+__global__ __launch_bounds__(GS_BLOCK) void k_export_scatter(StateFilter pass, uint32_t n, const uint32_t *__restrict__ blk, const uint4 *__restrict__ splat,
+                                                             uint4 *__restrict__ o_rows, float *__restrict__ o_wide, uint32_t *__restrict__ o_index)
 {
-    const uint32_t i0 = blockIdx.x * GS_EXPORT_CHUNK + threadIdx.x * GS_EXPORT_IPT;
-    uint32_t take;
-    uint32_t k = export_slot(state, rows, n, mask, value, blk, i0, take);
+    uint32_t i0, take;
+    uint32_t k = compact_slot(pass, n, blk, i0, take);
 #pragma unroll 1
-    for (uint32_t j = 0; j < GS_EXPORT_IPT; j++) {
+    for (uint32_t j = 0; j < GS_EDIT_IPT; j++) {
         if (!((take >> j) & 1u)) continue;
         const uint32_t i = i0 + j;
         const uint4 cs4 = splat[2 * (size_t)i], cc4 = splat[2 * (size_t)i + 1];
@@ -122,14 +52,13 @@ __global__ __launch_bounds__(GS_BLOCK) void k_export_scatter(const uint8_t *__re
     }
 }
 // the SH rows of the passing splats among the first n (= those that have a row): padded store rows -> padded rows, in stable order
-__global__ __launch_bounds__(GS_BLOCK) void k_export_sh(const uint8_t *__restrict__ state, uint32_t rows, uint32_t n, uint32_t mask, uint32_t value,
-                                                        const uint32_t *__restrict__ blk, const uint4 *__restrict__ sh, uint32_t row_q, uint4 *__restrict__ o_sh)
+__global__ __launch_bounds__(GS_BLOCK) void k_export_sh(StateFilter pass, uint32_t n, const uint32_t *__restrict__ blk, const uint4 *__restrict__ sh, uint32_t row_q,
+                                                        uint4 *__restrict__ o_sh)
 {
-    const uint32_t i0 = blockIdx.x * GS_EXPORT_CHUNK + threadIdx.x * GS_EXPORT_IPT;
-    uint32_t take;
-    uint32_t k = export_slot(state, rows, n, mask, value, blk, i0, take);
+    uint32_t i0, take;
+    uint32_t k = compact_slot(pass, n, blk, i0, take);
 #pragma unroll 1
-    for (uint32_t j = 0; j < GS_EXPORT_IPT; j++) {
+    for (uint32_t j = 0; j < GS_EDIT_IPT; j++) {
         if (!((take >> j) & 1u)) continue;
         for (uint32_t q = 0; q < row_q; q++) o_sh[(size_t)k * row_q + q] = sh[(size_t)(i0 + j) * row_q + q];
         k++;
@@ -144,34 +73,43 @@ struct ExportScratch {
     ~ExportScratch() { dev_free(blk); dev_free(index); dev_free(rows); dev_free(sh); dev_free(wide); }
 };
 
-// the reading passes' stream (gs_edit.hip: prop_begin makes the same one), and the filter's view of the state store
 int export_begin(gs_ctx *ctx, const char *name)
 {
     if (!ctx->renderable && ctx->n) FAIL(GS_E_STATE, "%s: context was fed worker matrices only (gs_push_matrices): it holds no packed records", name);
-    if (!ctx->n) return GS_OK;
-    GS_HIP(hipSetDevice(ctx->device));
-    if (!ctx->prop_stream) GS_HIP(hipStreamCreateWithFlags(&ctx->prop_stream, hipStreamNonBlocking));
-    return GS_OK;
+    return ctx->n ? reading_stream(ctx) : GS_OK;
 }
-uint32_t filter_rows(const gs_ctx *ctx, uint8_t mask) { return (mask && ctx->edit_state) ? (uint32_t)ctx->edit_n : 0u; }
 
-// count and offsets over the first n splats: S.blk[0, nblk) = where each workgroup's rows begin, *total = the passing splats
-int export_offsets(gs_ctx *ctx, ExportScratch &S, uint32_t n, uint8_t mask, uint8_t value, size_t *total)
+// One filter over the whole cloud, on the reading stream: count and offsets (S.blk, *total = the passing splats), then -- rows wanted and
+// some pass -- *rows, *wide and *index are allocated (wide, index: may be null, that part is not wanted) and the scatter is launched.
+// Not waited for: S.blk lives until the caller has
+int export_rows(gs_ctx *ctx, ExportScratch &S, uint8_t mask, uint8_t value, uint4 **rows /* null: the count alone */, float **wide, uint32_t **index, size_t *total)
 {
-    const uint32_t nblk = gs_div_up(n, GS_EXPORT_CHUNK);
-    TRY(dev_alloc(ctx, &S.blk, (size_t)nblk + 1));
-    hipStream_t st = ctx->prop_stream;
-    hipLaunchKernelGGL(k_export_count, dim3(nblk), dim3(GS_BLOCK), 0, st, (const uint8_t *)ctx->edit_state, filter_rows(ctx, mask), n, (uint32_t)mask, (uint32_t)value, S.blk);
-    hipLaunchKernelGGL(k_export_offsets, dim3(1), dim3(GS_BLOCK), 0, st, S.blk, nblk);
+    const uint32_t n = (uint32_t)ctx->n;
+    const StateFilter pass = { ctx->edit_state, filter_rows(ctx, mask), mask, value };
+    TRY(compact_offsets(ctx, ctx->prop_stream, pass, n, &S.blk, total));
+    if (!rows || !*total) return GS_OK;
+    TRY(dev_alloc(ctx, rows, *total * 2));
+    if (wide) TRY(dev_alloc(ctx, wide, *total * 7));
+    if (index) TRY(dev_alloc(ctx, index, *total));
+    hipLaunchKernelGGL(k_export_scatter, dim3(gs_div_up(n, GS_EDIT_CHUNK)), dim3(GS_BLOCK), 0, ctx->prop_stream, pass, n, (const uint32_t *)S.blk,
+                       (const uint4 *)ctx->splat, *rows, wide ? *wide : nullptr, index ? *index : nullptr);
     GS_HIP(hipGetLastError());
-    uint32_t t = 0;
-    GS_HIP(hipMemcpyAsync(&t, S.blk + nblk, sizeof t, hipMemcpyDeviceToHost, st));
-    GS_HIP(hipStreamSynchronize(st));
-    *total = t;
+    return GS_OK;
+}
+// ... and the same over the first ns splats, those that have an SH row: *sh = the passing ones' padded rows, row_q 16-byte words each
+int export_sh(gs_ctx *ctx, ExportScratch &S, uint32_t ns, uint8_t mask, uint8_t value, uint32_t row_q, uint4 **sh /* null: the count alone */, size_t *total)
+{
+    const StateFilter pass = { ctx->edit_state, filter_rows(ctx, mask), mask, value };
+    TRY(compact_offsets(ctx, ctx->prop_stream, pass, ns, &S.blk, total));
+    if (!sh || !*total) return GS_OK;
+    TRY(dev_alloc(ctx, sh, *total * row_q));
+    hipLaunchKernelGGL(k_export_sh, dim3(gs_div_up(ns, GS_EDIT_CHUNK)), dim3(GS_BLOCK), 0, ctx->prop_stream, pass, ns, (const uint32_t *)S.blk, (const uint4 *)ctx->sh,
+                       row_q, *sh);
+    GS_HIP(hipGetLastError());
     return GS_OK;
 }
 
-// gs_export_sh: the same count and offsets over the splats that have an SH row, then their rows (the store's degree)
+// gs_export_sh: the rows of the store's degree, tight
 int export_sh_rows(gs_ctx *ctx, uint8_t mask, uint8_t value, float *out_sh, size_t *out_nrows, int *out_degree)
 {
     *out_nrows = 0;
@@ -180,20 +118,12 @@ int export_sh_rows(gs_ctx *ctx, uint8_t mask, uint8_t value, float *out_sh, size
     const size_t n = ctx->sh_n < ctx->n ? ctx->sh_n : ctx->n;
     if (!n) return GS_OK;
     if (out_degree) *out_degree = ctx->sh_deg;
-    ExportScratch S;
-    size_t total = 0;
-    TRY(export_offsets(ctx, S, (uint32_t)n, mask, value, &total));
-    *out_nrows = total;
-    if (!out_sh || !total) return GS_OK;
     const size_t K = (size_t)gsm::sh_coefs(ctx->sh_deg), KS = (size_t)gsm::sh_channel_stride(ctx->sh_deg);
-    const uint32_t row_q = (uint32_t)(3 * KS / 4);
-    TRY(dev_alloc(ctx, &S.sh, total * row_q));
-    hipStream_t st = ctx->prop_stream;
-    hipLaunchKernelGGL(k_export_sh, dim3(gs_div_up(n, GS_EXPORT_CHUNK)), dim3(GS_BLOCK), 0, st, (const uint8_t *)ctx->edit_state, filter_rows(ctx, mask), (uint32_t)n,
-                       (uint32_t)mask, (uint32_t)value, (const uint32_t *)S.blk, (const uint4 *)ctx->sh, row_q, S.sh);
-    GS_HIP(hipGetLastError());
-    GS_HIP(hipMemcpy2DAsync(out_sh, K * 4, S.sh, KS * 4, K * 4, total * 3, hipMemcpyDeviceToHost, st));   // tight rows out of the padded ones
-    GS_HIP(hipStreamSynchronize(st));
+    ExportScratch S;
+    TRY(export_sh(ctx, S, (uint32_t)n, mask, value, (uint32_t)(3 * KS / 4), out_sh ? &S.sh : nullptr, out_nrows));
+    if (!out_sh || !*out_nrows) return GS_OK;
+    GS_HIP(hipMemcpy2DAsync(out_sh, K * 4, S.sh, KS * 4, K * 4, *out_nrows * 3, hipMemcpyDeviceToHost, ctx->prop_stream));   // tight rows out of the padded ones
+    GS_HIP(hipStreamSynchronize(ctx->prop_stream));
     return GS_OK;
 }
 
@@ -205,31 +135,18 @@ int gs_export_stage(gs_ctx *ctx, const char *name, uint8_t mask, uint8_t value, 
     *out = GsExportStage();
     TRY(export_begin(ctx, name));
     if (!ctx->n) return GS_OK;
-    const uint32_t n = (uint32_t)ctx->n;
-    hipStream_t st = ctx->prop_stream;
     {
         ExportScratch S;
-        TRY(export_offsets(ctx, S, n, mask, value, &out->total));
-        if (with_rows && out->total) {
-            TRY(dev_alloc(ctx, &out->rows, out->total * 2)); TRY(dev_alloc(ctx, &out->wide, out->total * 7)); TRY(dev_alloc(ctx, &out->index, out->total));
-            hipLaunchKernelGGL(k_export_scatter, dim3(gs_div_up(n, GS_EXPORT_CHUNK)), dim3(GS_BLOCK), 0, st, (const uint8_t *)ctx->edit_state, filter_rows(ctx, mask), n,
-                               (uint32_t)mask, (uint32_t)value, (const uint32_t *)S.blk, (const uint4 *)ctx->splat, out->rows, out->wide, out->index);
-            GS_HIP(hipGetLastError());
-            GS_HIP(hipStreamSynchronize(st));                    // (S.blk is released with this block)
-        }
+        TRY(export_rows(ctx, S, mask, value, with_rows ? &out->rows : nullptr, &out->wide, &out->index, &out->total));
+        if (with_rows && out->total) GS_HIP(hipStreamSynchronize(ctx->prop_stream));   // (S.blk is released with this block)
     }
     const size_t ns = ctx->sh_n < ctx->n ? ctx->sh_n : ctx->n;
     if (!ns) return GS_OK;
     out->sh_deg = ctx->sh_deg;
     out->sh_row_q = (uint32_t)(3 * (size_t)gsm::sh_channel_stride(ctx->sh_deg) / 4);
     ExportScratch S;
-    TRY(export_offsets(ctx, S, (uint32_t)ns, mask, value, &out->sh_total));
-    if (!with_rows || !out->sh_total) return GS_OK;
-    TRY(dev_alloc(ctx, &out->sh, out->sh_total * out->sh_row_q));
-    hipLaunchKernelGGL(k_export_sh, dim3(gs_div_up(ns, GS_EXPORT_CHUNK)), dim3(GS_BLOCK), 0, st, (const uint8_t *)ctx->edit_state, filter_rows(ctx, mask), (uint32_t)ns,
-                       (uint32_t)mask, (uint32_t)value, (const uint32_t *)S.blk, (const uint4 *)ctx->sh, out->sh_row_q, out->sh);
-    GS_HIP(hipGetLastError());
-    GS_HIP(hipStreamSynchronize(st));
+    TRY(export_sh(ctx, S, (uint32_t)ns, mask, value, out->sh_row_q, with_rows ? &out->sh : nullptr, &out->sh_total));
+    if (with_rows && out->sh_total) GS_HIP(hipStreamSynchronize(ctx->prop_stream));
     return GS_OK;
 }
 void gs_export_stage_free(GsExportStage *s) { dev_free(s->rows); dev_free(s->wide); dev_free(s->index); dev_free(s->sh); *s = GsExportStage(); }
@@ -243,19 +160,11 @@ GS_API int gs_export_splat(gs_ctx *ctx, uint8_t state_mask, uint8_t state_value,
     *out_nrows = 0;
     TRY(export_begin(ctx, "gs_export_splat"));
     if (!ctx->n) return GS_OK;
-    const uint32_t n = (uint32_t)ctx->n;
     ExportScratch S;
-    size_t total = 0;
-    TRY(export_offsets(ctx, S, n, state_mask, state_value, &total));
-    *out_nrows = total;
+    TRY(export_rows(ctx, S, state_mask, state_value, out_rows ? &S.rows : nullptr, out_wide ? &S.wide : nullptr, out_index ? &S.index : nullptr, out_nrows));
+    const size_t total = *out_nrows;
     if (!out_rows || !total) return GS_OK;                       // the size query, or nothing passes
-    TRY(dev_alloc(ctx, &S.rows, total * 2));
-    if (out_wide) TRY(dev_alloc(ctx, &S.wide, total * 7));
-    if (out_index) TRY(dev_alloc(ctx, &S.index, total));
     hipStream_t st = ctx->prop_stream;
-    hipLaunchKernelGGL(k_export_scatter, dim3(gs_div_up(n, GS_EXPORT_CHUNK)), dim3(GS_BLOCK), 0, st, (const uint8_t *)ctx->edit_state, filter_rows(ctx, state_mask), n,
-                       (uint32_t)state_mask, (uint32_t)state_value, (const uint32_t *)S.blk, (const uint4 *)ctx->splat, S.rows, S.wide, S.index);
-    GS_HIP(hipGetLastError());
     GS_HIP(hipMemcpyAsync(out_rows, S.rows, total * 32, hipMemcpyDeviceToHost, st));
     if (out_wide) GS_HIP(hipMemcpyAsync(out_wide, S.wide, total * 7 * sizeof(float), hipMemcpyDeviceToHost, st));
     if (out_index) GS_HIP(hipMemcpyAsync(out_index, S.index, total * sizeof(uint32_t), hipMemcpyDeviceToHost, st));

@@ -15,7 +15,7 @@ capi = pkg("capi")
 synth = pkg("synth")
 
 # the grid cap of the two kernels: the grid-strided loop of k_adjust_colour takes a second trip first at GRID * BLOCK + 1 splats
-GRID, BLOCK = _constant("GS_ADJUST_GRID", "gs_adjust.hip"), _constant("GS_BLOCK", "gs_internal.h")
+GRID, BLOCK = _constant("GS_EDIT_GRID", "gs_cloud_pass.h"), _constant("GS_BLOCK", "gs_internal.h")
 assert (GRID, BLOCK) == (2048, 256)
 SIZES = [1, 255, 256, 257, 2049, GRID * BLOCK + 1]
 HIDDEN, SELECTED, CALLER = capi.STATE_HIDDEN, capi.STATE_SELECTED, 0x40

@@ -28,8 +28,8 @@ pytestmark = pytest.mark.gpu
 capi = pkg("capi")
 synth = pkg("synth")
 
-IPT = _constant("GS_EDIT_IPT", "gs_edit.hip")
-GRID = _constant("GS_EDIT_GRID", "gs_edit.hip")
+IPT = _constant("GS_EDIT_IPT", "gs_cloud_pass.h")
+GRID = _constant("GS_EDIT_GRID", "gs_cloud_pass.h")
 BLOCK = _constant("GS_BLOCK", "gs_internal.h")
 CH, WAVE, STEP = IPT * BLOCK, 64 * IPT, BLOCK
 GB = GRID * BLOCK

@@ -2,7 +2,7 @@
 
 The rows, wide parts and indices are exact: capi.export_row -- the kernel's own function on the host, pinned to the header's rule by
 tests/test_export_cpu.py -- applied to the records the context holds (gs_download), for the splats the state filter passes, in order.
-Sizes sit below, at and across the compaction chunk (GS_EXPORT_CHUNK, read out of the source).  The picture of an exported cloud is held
+Sizes sit below, at and across the compaction chunk (GS_EDIT_CHUNK, read out of the source).  The picture of an exported cloud is held
 against what the format itself costs a picture, measured on the CPU oracle."""
 import numpy as np
 import pytest
@@ -16,8 +16,8 @@ pytestmark = pytest.mark.gpu
 capi = pkg("capi")
 synth = pkg("synth")
 
-CHUNK = _constant("GS_EXPORT_IPT", "gs_export.hip") * _constant("GS_BLOCK", "gs_internal.h")
-assert CHUNK == 2048 == _constant("GS_EDIT_IPT", "gs_edit.hip") * _constant("GS_BLOCK", "gs_internal.h")
+CHUNK = _constant("GS_EDIT_IPT", "gs_cloud_pass.h") * _constant("GS_BLOCK", "gs_internal.h")
+assert CHUNK == 2048
 HIDDEN, SELECTED, CALLER = capi.STATE_HIDDEN, capi.STATE_SELECTED, 0x40
 FILTERS = [(0, 0), (HIDDEN, 0), (3, SELECTED), (CALLER, CALLER)]
 SIZES = [1, CHUNK - 1, CHUNK, CHUNK + 1, 3 * CHUNK + 5]

@@ -19,8 +19,8 @@ capi = pkg("capi")
 synth = pkg("synth")
 
 BLOCK = _constant("GS_BLOCK", "gs_internal.h")
-CHUNK = _constant("GS_EDIT_IPT", "gs_edit.hip") * BLOCK
-GRID = _constant("GS_EDIT_GRID", "gs_edit.hip")
+CHUNK = _constant("GS_EDIT_IPT", "gs_cloud_pass.h") * BLOCK
+GRID = _constant("GS_EDIT_GRID", "gs_cloud_pass.h")
 HIDDEN, SELECTED, INVERT = capi.STATE_HIDDEN, capi.STATE_SELECTED, capi.SELECT_INVERT
 VIEW = np.array([0.0, 0.0, 1.0, 0.0], np.float32)
 FILTERS = [(0, 0), (1, 0), (3, 2), (0x40, 0x40)]
