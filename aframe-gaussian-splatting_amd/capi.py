@@ -68,6 +68,7 @@ EXPORTS = [
     "gs_export_row", "gs_export_splat", "gs_export_sh", "gs_splat_to_ply", "gs_export_ply", "gs_multi_export_splat", "gs_multi_export_ply",
     "gs_adjust_colour", "gs_adjust_word", "gs_adjust_sh_row", "gs_replace_splat", "gs_replace_sh",
     "gs_multi_adjust_colour", "gs_multi_replace_splat", "gs_multi_replace_sh",
+    "gs_transform", "gs_multi_transform", "gs_transform_record", "gs_transform_records", "gs_transform_sh_row", "gs_sh_rotation", "gs_similarity_about",
     "gs_project_record", "gs_ortho_matrix", "gs_projection_info",
     "gs_cply_info", "gs_cply_to_splat", "gs_cply_sh_host", "gs_splat_to_cply", "gs_log_fixed", "gs_load_cply", "gs_cply_to_splat_gpu", "gs_export_cply",
     "gs_multi_load_cply", "gs_multi_export_cply",
@@ -307,6 +308,15 @@ def load(build_if_missing=True):
             getattr(L, pre + "adjust_colour").argtypes = [vp, C.POINTER(ColourAdjust), u8, u8, szp]
             getattr(L, pre + "replace_splat").argtypes = [vp, sz, vp, sz]
             getattr(L, pre + "replace_sh").argtypes = [vp, sz, vp, sz, i32]
+    if hasattr(L, "gs_transform"):                             # (likewise)
+        u8, szp = C.c_uint8, C.POINTER(sz)
+        L.gs_transform_record.argtypes = [vp, vp, vp, C.POINTER(Similarity), vp, vp, vp, vp]
+        L.gs_transform_records.argtypes = [vp, vp, vp, sz, C.POINTER(Similarity), vp, vp, vp, vp]
+        L.gs_transform_sh_row.argtypes = [vp, i32, C.POINTER(Similarity), vp]
+        L.gs_sh_rotation.argtypes = [C.POINTER(Similarity), vp]
+        L.gs_similarity_about.argtypes = [vp, vp, f32, C.POINTER(Similarity)]
+        for pre in ("gs_", "gs_multi_"):
+            getattr(L, pre + "transform").argtypes = [vp, C.POINTER(Similarity), u8, u8, szp]
     L.gs_download.argtypes = [vp, i32, vp, sz]
     if hasattr(L, "gs_sort_inspect"):
         L.gs_sort_inspect.argtypes = [vp, C.POINTER(SortInfo), vp, sz]
@@ -338,6 +348,20 @@ def load(build_if_missing=True):
     L.gs_multi_sync.argtypes = [vp]
     _lib = L
     return L
+
+
+class Similarity(C.Structure):
+    """gs_similarity: p' = scale * R p + translation in the rows' object space; rotation = quaternion (w, x, y, z), need not be normalised"""
+    _fields_ = [("rotation", C.c_float * 4), ("scale", C.c_float), ("translation", C.c_float * 3)]
+
+
+def similarity(rotation=(1.0, 0.0, 0.0, 0.0), scale=1.0, translation=(0.0, 0.0, 0.0)):
+    """A Similarity; the defaults are the identity"""
+    t = Similarity()
+    t.rotation[:] = [float(v) for v in np.asarray(rotation, np.float32).reshape(4)]
+    t.scale = float(np.float32(scale))
+    t.translation[:] = [float(v) for v in np.asarray(translation, np.float32).reshape(3)]
+    return t
 
 
 def _p(a):
@@ -625,6 +649,71 @@ def adjust_sh_rows(sh_rows, degree, adjust, in_place=False):
         if rc != GS_OK:
             raise GsError(rc, "gs_adjust_sh_row: bad argument")
     return out
+
+
+def similarity_about(pivot, rotation=(1.0, 0.0, 0.0, 0.0), scale=1.0):
+    """gs_similarity_about: the Similarity that rotates and scales about `pivot` (rows' object space)"""
+    t = Similarity()
+    pv, q = np.ascontiguousarray(pivot, np.float32).reshape(3), np.ascontiguousarray(rotation, np.float32).reshape(4)
+    rc = load().gs_similarity_about(_p(pv), _p(q), float(np.float32(scale)), C.byref(t))
+    if rc != GS_OK:
+        raise GsError(rc, "gs_similarity_about: bad argument")
+    return t
+
+
+def transform_records(cs, cc, sort_rows, t, want_bound=False, one_by_one=False):
+    """gs_transform_records (one_by_one: gs_transform_record per record) over packed records (cs: [n, 4] f32 or its u32 bits, cc: [n, 4]
+    u32, sort_rows: [n, 4] f32 or bits, as gs_download returns them) -> (cs', cc', sort_rows') as uint32[n, 4] each [, bound:
+    float32[n]], by the kernel's own function"""
+    a = [np.ascontiguousarray(x).view(np.uint32).reshape(-1, 4) for x in (cs, cc, sort_rows)]
+    n = len(a[0])
+    out = [np.zeros((n, 4), np.uint32) for _ in range(3)]
+    bound = np.zeros(n, np.float32)
+    L, pt = load(), C.byref(t)
+    if not one_by_one:
+        rc = L.gs_transform_records(_p(a[0]), _p(a[1]), _p(a[2]), n, pt, _p(out[0]), _p(out[1]), _p(out[2]), _p(bound))
+        if rc != GS_OK:
+            raise GsError(rc, "gs_transform_records: bad argument")
+    else:
+        base = [x.ctypes.data for x in a] + [x.ctypes.data for x in out]
+        for i in range(n):
+            o = 16 * i
+            rc = L.gs_transform_record(base[0] + o, base[1] + o, base[2] + o, pt, base[3] + o, base[4] + o, base[5] + o, bound.ctypes.data + 4 * i)
+            if rc != GS_OK:
+                raise GsError(rc, "gs_transform_record: bad argument")
+    return (out[0], out[1], out[2], bound) if want_bound else tuple(out)
+
+
+def transform_sh_rows(sh_rows, degree, t, in_place=False):
+    """gs_transform_sh_row over rows of 3 (degree+1)^2 f32 each -> float32[n, 3 (degree+1)^2] (in_place: sh_rows itself, a C-contiguous
+    float32 array, is rewritten and returned)"""
+    k = 3 * (int(degree) + 1) ** 2
+    src = sh_rows if in_place else np.ascontiguousarray(sh_rows, np.float32).reshape(-1, k)
+    if in_place and (src.dtype != np.float32 or not src.flags.c_contiguous or src.size % k):
+        raise ValueError("in_place: a C-contiguous float32 array of whole rows expected")
+    out = src if in_place else np.zeros_like(src)
+    f, pt = load().gs_transform_sh_row, C.byref(t)
+    for i in range(src.size // k):
+        rc = f(src.ctypes.data + 4 * k * i, int(degree), pt, out.ctypes.data + 4 * k * i)
+        if rc != GS_OK:
+            raise GsError(rc, "gs_transform_sh_row: bad argument")
+    return out
+
+
+def sh_rotation(t):
+    """gs_sh_rotation: the band matrices the SH kernel is handed -> (D1 [3, 3], D2 [5, 5], D3 [7, 7]) float64"""
+    d = np.zeros(83, np.float64)
+    rc = load().gs_sh_rotation(C.byref(t), _p(d))
+    if rc != GS_OK:
+        raise GsError(rc, "gs_sh_rotation: bad argument")
+    return d[:9].reshape(3, 3).copy(), d[9:34].reshape(5, 5).copy(), d[34:].reshape(7, 7).copy()
+
+
+def _transform(fn, h, ck, t, of):
+    m, v = _of(of)
+    hit = C.c_size_t(0)
+    ck(fn(h, C.byref(t), m, v, C.byref(hit)))
+    return hit.value
 
 
 def _adjust_colour(fn, h, ck, adjust, of):
@@ -1029,6 +1118,11 @@ class Context:
     def adjust_colour(self, adjust, of="all"):
         """gs_adjust_colour: the ColourAdjust on the colour word and SH row of every passing splat -> how many pass"""
         return _adjust_colour(self._L.gs_adjust_colour, self._h, self._ck, adjust, of)
+
+    def transform(self, t, of="all"):
+        """gs_transform: the Similarity baked into every passing splat (records, sort rows, strip bounds, SH rows) -> how many pass;
+        every order is dropped, as by a push"""
+        return _transform(self._L.gs_transform, self._h, self._ck, t, of)
 
     def replace_splat(self, first, rows):
         """gs_replace_splat: .splat rows over splats [first, first + len(rows)); every order is dropped, as by a push"""
@@ -1445,6 +1539,10 @@ class Multi:
     def adjust_colour(self, adjust, of="all"):
         """gs_adjust_colour: the ColourAdjust on the colour word and SH row of every passing splat -> how many pass"""
         return _adjust_colour(self._L.gs_multi_adjust_colour, self._h, self._ck, adjust, of)
+
+    def transform(self, t, of="all"):
+        """gs_transform on every device -> how many pass on devices[0]"""
+        return _transform(self._L.gs_multi_transform, self._h, self._ck, t, of)
 
     def replace_splat(self, first, rows):
         """gs_replace_splat: .splat rows over splats [first, first + len(rows)); every order is dropped, as by a push"""

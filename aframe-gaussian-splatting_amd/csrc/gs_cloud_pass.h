@@ -1,5 +1,5 @@
-// gs_cloud_pass.h -- private to the editor passes over the resident cloud: gs_edit.hip, gs_export.hip, gs_adjust.hip and gs_cply.hip
-// include it, no other file does.  What those passes share, once: the wave and workgroup reductions, the state filter, the rule a
+// gs_cloud_pass.h -- private to the editor passes over the resident cloud: gs_edit.hip, gs_export.hip, gs_adjust.hip, gs_cply.hip and
+// gs_transform.hip include it, no other file does.  What those passes share, once: the wave and workgroup reductions, the state filter, the rule a
 // selection ends in, the stable compaction (count -> offsets -> scatter over a predicate) and the host sequences around them.
 // None of this is a per-frame path.  The frame kernels (gs_render.hip, gs_sort.hip, gs_prims.hip, gs_pack.hip, gs_frame.hip) keep
 // their own helpers on purpose: their DPP / NW-templated reductions are tuned for the frame and are not these.
@@ -96,7 +96,7 @@ __global__ __launch_bounds__(GS_BLOCK) void k_compact_count(P pred, uint32_t n, 
     __syncthreads();
     if (threadIdx.x == 0) blk[blockIdx.x] = s_c;
 }
-// one workgroup: blk[0, nblk) -> their exclusive sums in place, blk[nblk] = the total.  (Not a template: gs_adjust.hip and gs_cply.hip,
+// one workgroup: blk[0, nblk) -> their exclusive sums in place, blk[nblk] = the total.  (Not a template: gs_adjust.hip, gs_transform.hip and gs_cply.hip,
 // which launch no compaction, carry an unused copy of it in their code objects -- a few hundred bytes, accepted)
 __global__ __launch_bounds__(GS_BLOCK) void k_compact_offsets(uint32_t *__restrict__ blk, uint32_t nblk)
 {

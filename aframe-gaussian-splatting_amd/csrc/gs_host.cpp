@@ -20,6 +20,7 @@
 #include "gs_device_math.h"
 #include "gs_export.h"
 #include "gs_adjust.h"
+#include "gs_transform.h"
 #include "gs_cply.h"
 
 namespace {
@@ -463,6 +464,82 @@ GS_API int gs_adjust_sh_row(const float *sh_row, int degree, const gs_colour_adj
         gsm::adjust_sh_coef(in, k, p, o);
         out_row[k] = o[0]; out_row[K + k] = o[1]; out_row[2 * K + k] = o[2];
     }
+    return GS_OK;
+}
+
+// the similarity of gs_transform by the kernels' own functions (gs_transform.h)
+GS_API int gs_transform_record(const float cs[4], const uint32_t cc[4], const float sort_row[4], const gs_similarity *t,
+                               float cs_out[4], uint32_t cc_out[4], float sort_row_out[4], float *bound_out)
+{
+    gsm::TransformParams p;
+    if (!cs || !cc || !sort_row || !t || !cs_out || !cc_out || !sort_row_out) return GS_E_BADARG;
+    if (!gsm::transform_widen(t->rotation, t->scale, t->translation, p)) return GS_E_BADARG;
+    float bound;
+    gsm::transform_record(cs, cc, sort_row, p, cs_out, cc_out, sort_row_out, bound);
+    if (bound_out) *bound_out = bound;
+    return GS_OK;
+}
+
+GS_API int gs_transform_records(const float *cs, const uint32_t *cc, const float *sort_rows, size_t n, const gs_similarity *t,
+                                float *cs_out, uint32_t *cc_out, float *sort_rows_out, float *bounds_out)
+{
+    gsm::TransformParams p;
+    if (!t || !gsm::transform_widen(t->rotation, t->scale, t->translation, p)) return GS_E_BADARG;
+    if (n && (!cs || !cc || !sort_rows || !cs_out || !cc_out || !sort_rows_out)) return GS_E_BADARG;
+    for (size_t i = 0; i < n; i++) {
+        float bound;
+        gsm::transform_record(cs + 4 * i, cc + 4 * i, sort_rows + 4 * i, p, cs_out + 4 * i, cc_out + 4 * i, sort_rows_out + 4 * i, bound);
+        if (bounds_out) bounds_out[i] = bound;
+    }
+    return GS_OK;
+}
+
+GS_API int gs_transform_sh_row(const float *sh_row, int degree, const gs_similarity *t, float *out_row)
+{
+    gsm::TransformParams p;
+    if (!sh_row || !out_row || !t || degree < 0 || degree > GS_SH_MAX_DEGREE) return GS_E_BADARG;
+    if (!gsm::transform_widen(t->rotation, t->scale, t->translation, p)) return GS_E_BADARG;
+    gsm::ShRotation rot;
+    gsm::sh_rotation(p, rot);
+    const int K = gsm::sh_coefs(degree);
+    if (p.rot_identity) {                                        // scale and translation leave SH alone (gs_transform launches no SH kernel then)
+        memmove(out_row, sh_row, 3 * (size_t)K * sizeof(float));
+        return GS_OK;
+    }
+    for (int c = 0; c < 3; c++) {                                // (a channel's inputs are read before its outputs are written: out_row may be sh_row)
+        const float *in = sh_row + c * K;
+        float *out = out_row + c * K;
+        if (degree == 0) out[0] = in[0];
+        else if (degree == 1) gsm::transform_sh_channel<1>(in, rot, out);
+        else if (degree == 2) gsm::transform_sh_channel<2>(in, rot, out);
+        else gsm::transform_sh_channel<3>(in, rot, out);
+    }
+    return GS_OK;
+}
+
+GS_API int gs_sh_rotation(const gs_similarity *t, double out[83])
+{
+    gsm::TransformParams p;
+    if (!t || !out || !gsm::transform_widen(t->rotation, t->scale, t->translation, p)) return GS_E_BADARG;
+    gsm::ShRotation rot;
+    gsm::sh_rotation(p, rot);
+    memcpy(out, rot.d, sizeof rot.d);
+    return GS_OK;
+}
+
+GS_API int gs_similarity_about(const float pivot[3], const float rotation[4], float scale, gs_similarity *out)
+{
+    gsm::TransformParams p;
+    const float zero[3] = { 0.0f, 0.0f, 0.0f };
+    if (!pivot || !rotation || !out || !gsm::transform_widen(rotation, scale, zero, p)) return GS_E_BADARG;
+    float tr[3];
+    for (int i = 0; i < 3; i++) {
+        if (!gsm::transform_f32_finite(pivot[i])) return GS_E_BADARG;
+        tr[i] = (float)((double)pivot[i] - p.s * ((p.R[3 * i] * (double)pivot[0] + p.R[3 * i + 1] * (double)pivot[1]) + p.R[3 * i + 2] * (double)pivot[2]));
+    }
+    for (int i = 0; i < 4; i++) out->rotation[i] = rotation[i];
+    out->scale = scale;
+    for (int i = 0; i < 3; i++) out->translation[i] = tr[i];
     return GS_OK;
 }
 

@@ -326,6 +326,13 @@ GS_API int gs_multi_adjust_colour(gs_multi *m, const gs_colour_adjust *adjust, u
     return run_all(m, [=](gs_ctx *c, int i) { return gs_adjust_colour(c, adjust, state_mask, state_value, i == 0 ? out_hit : nullptr); });
 }
 
+GS_API int gs_multi_transform(gs_multi *m, const gs_similarity *t, uint8_t state_mask, uint8_t state_value, size_t *out_hit)
+{
+    if (!m) return GS_E_BADARG;
+    m->have_sort = false;                                        // positions change: as a push
+    return run_all(m, [=](gs_ctx *c, int i) { return gs_transform(c, t, state_mask, state_value, i == 0 ? out_hit : nullptr); });
+}
+
 GS_API int gs_multi_replace_splat(gs_multi *m, size_t first, const void *rows, size_t nrows)
 {
     if (!m) return GS_E_BADARG;

@@ -373,9 +373,16 @@ class GaussianSplatting {
     return native.adjustColour(this.handle, o.matrix || [1, 0, 0, 0, 1, 0, 0, 0, 1], o.offset || [0, 0, 0],
       o.alphaScale === undefined ? 1 : o.alphaScale, o.alphaOffset === undefined ? 0 : o.alphaOffset, f[0], f[1]);
   }
-  // replaceSplat / replaceSh: 32-byte .splat rows (spherical-harmonics rows of `degree`) over the resident ones from index `first` on --
-  // with exportSplat the way to move part of the cloud: export, transform on the host, write back.  Replaced rows drop the order like a
-  // push: the draws show the background until the next tick.
+  // transform: move, rotate and scale the splats of opts.of on the GPU, p' = scale x R p + translation in the rows' object space (rotation:
+  // quaternion [w, x, y, z], need not be normalised; scale > 0; defaults: the identity), records, sort rows and spherical-harmonics rows
+  // alike (gs_splat.h: gs_transform) -> how many were moved.  Drops the order like a push: the draws show the background until the next tick.
+  transform(opts) {
+    const o = opts || {}, f = PROP_FILTERS[o.of || 'all'];
+    if (!f) throw new RangeError("transform: of must be 'all', 'visible' or 'selected'");
+    return native.transform(this.handle, o.rotation || [1, 0, 0, 0], o.scale === undefined ? 1 : o.scale, o.translation || [0, 0, 0], f[0], f[1]);
+  }
+  // replaceSplat / replaceSh: 32-byte .splat rows (spherical-harmonics rows of `degree`) over the resident ones from index `first` on.
+  // Replaced rows drop the order like a push: the draws show the background until the next tick.
   replaceSplat(first, rows) { return native.replaceSplat(this.handle, first, rows); }
   replaceSh(first, rows, degree) { return native.replaceSh(this.handle, first, rows, degree); }
   // real deletion of the hidden splats (the GPU holds the cloud twice for the duration of the call) -> Uint32Array: the old index of

@@ -817,6 +817,27 @@ static napi_value fn_adjust_colour(napi_env env, napi_callback_info info)
     return make_count(env, hit);
 }
 
+/* transform(h, rotation4 (w, x, y, z), scale, translation3, stateMask, stateValue) -> splats moved (gs_splat.h: gs_transform) */
+static napi_value fn_transform(napi_env env, napi_callback_info info)
+{
+    napi_value argv[6];
+    if (!get_args(env, info, 6, argv, NULL)) return NULL;
+    gs_ctx *ctx = get_ctx(env, argv[0]); if (!ctx) return NULL;
+    gs_similarity t;
+    double scale = 1;
+    uint32_t mask = 0, value = 0;
+    if (!get_floats(env, argv[1], t.rotation, 4) || napi_get_value_double(env, argv[2], &scale) != napi_ok || !get_floats(env, argv[3], t.translation, 3) ||
+        !get_u32(env, argv[4], &mask) || !get_u32(env, argv[5], &value)) {
+        napi_throw_type_error(env, NULL, "transform: (handle, rotation4, scale, translation3, stateMask, stateValue)");
+        return NULL;
+    }
+    t.scale = (float)scale;
+    size_t hit = 0;
+    int rc = gs_transform(ctx, &t, (uint8_t)mask, (uint8_t)value, &hit);
+    if (rc != GS_OK) return throw_gs(env, ctx, rc);
+    return make_count(env, hit);
+}
+
 /* replaceSplat(h, first, rows) -> rows written: 32-byte .splat rows over splats [first, first + rows) */
 static napi_value fn_replace_splat(napi_env env, napi_callback_info info)
 {
@@ -1630,7 +1651,7 @@ static napi_value init(napi_env env, napi_value exports)
         { "renderContrib", fn_render_contrib }, { "contribClear", fn_contrib_clear }, { "contribInfo", fn_contrib_info },
         { "propRange", fn_prop_range }, { "histogram", fn_histogram }, { "selectRange", fn_select_range },
         { "exportSplat", fn_export_splat }, { "exportPly", fn_export_ply }, { "cplyInfo", fn_cply_info }, { "loadCply", fn_load_cply }, { "exportCply", fn_export_cply },
-        { "adjustColour", fn_adjust_colour }, { "replaceSplat", fn_replace_splat }, { "replaceSh", fn_replace_sh },
+        { "adjustColour", fn_adjust_colour }, { "transform", fn_transform },{ "replaceSplat", fn_replace_splat }, { "replaceSh", fn_replace_sh },
         { "selectMask", fn_select_mask }, { "maskPolygon", fn_mask_polygon }, { "highlightInfo", fn_highlight_info },
         { "createMulti", fn_create_multi }, { "multiDestroy", fn_multi_destroy }, { "multiPushSplat", fn_multi_push_splat },
         { "multiLoadPly", fn_multi_load_ply }, { "multiClear", fn_multi_clear }, { "multiCount", fn_multi_count },

@@ -291,8 +291,8 @@ GS_API int gs_pick(gs_ctx *ctx, const gs_render_params *p, const int32_t *xy, si
  *     render before the next sort draws the background only, as after a push), and gs_sync() does not draw frames of before the change again by itself.
  *     A state change takes effect at the NEXT sort: a draw uses the last completed order (index.js:201-207).
  *   - gs_stats.n_hidden: the hidden splats the last collected sort skipped.
- * Out of scope: in-place edits of a splat's position, rotation or scale ON THE DEVICE (rigid motion: gs_replace_splat takes rows that
- * were transformed on the host), undo. */
+ * Moving, rotating and scaling part of the cloud on the device is gs_transform (below, "Changing resident splats in place").
+ * Out of scope: undo of in-place edits, or of any other call. */
 #define GS_STATE_HIDDEN 1u
 #define GS_STATE_SELECTED 2u
 #define GS_SELECT_INVERT 1u      /* region calls: apply the rule to the splats NOT in the region */
@@ -388,12 +388,66 @@ GS_API int gs_adjust_sh_row(const float *sh_row, int degree, const gs_colour_adj
 /* ROWS: splats [first, first + nrows) are overwritten with .splat rows packed by the pack kernel of gs_push_splat: both records, the sort
  * row and the strip bound.  States, SH rows, contribution words and gs_count() stay.  Otherwise like a push: lanes drained, every
  * lane's order dropped, a sort posted with gs_sort_begin is run again when it is collected.  With gs_export_splat (and its wide parts)
- * this is how a host moves, rotates or scales part of the cloud: export, transform on the host, write back the rows it touched.
+ * a host can rewrite whatever it likes of the rows it touched; to move, rotate or scale part of the cloud use gs_transform (below), which
+ * keeps the record's precision (a row's quaternion is four bytes), turns the SH rows along and moves no row across the bus.
  * first + nrows > gs_count(): GS_E_BADARG, nothing changed.  Matrices-only context: GS_E_STATE.  nrows == 0: GS_OK. */
 GS_API int gs_replace_splat(gs_ctx *ctx, size_t first, const void *rows, size_t nrows);
 /* SH rows [first, first + nrows) of the store are overwritten (tight rows in, padded as by gs_push_sh).  Lanes drained, no order dropped.
  * A degree other than the store's, or a range beyond gs_sh_count(): GS_E_BADARG. */
 GS_API int gs_replace_sh(gs_ctx *ctx, size_t first, const float *sh_rows, size_t nrows, int degree);
+/* POSITION, ROTATION AND SIZE, on the GPU: the similarity p' = scale * R p + translation, baked once into the splats with (state &
+ * state_mask) == state_value (there is no per-frame pose).  THE RULE -- one function, csrc/gs_transform.h: transform_record, called by the
+ * kernel and by gs_transform_record below -- is, every operation IEEE f64, un-fused, on the parameters widened from f32, in this order:
+ *   1. q = rotation / n, n = sqrt(((w^2 + x^2) + y^2) + z^2).
+ *   2. R (rows' space) from q by the expressions of the pack loop (csrc/gs_device_math.h: pack_row, the r00 .. r22 lines).
+ *   3. Rm = R in the packed, z-mirrored space: Rm[i][j] = R[i][j], negated where exactly one of i, j is 2.
+ *   4. p = (cs[0], cs[1], -cs[2]);  p'_i = scale * ((R_i0 p_0 + R_i1 p_1) + R_i2 p_2) + translation_i;  cs'[0..2] = (f32 p'_0, f32 p'_1, f32 -p'_2).
+ *   5. A record whose cs[3] is not finite (decided on its bits) keeps cs[3] and cc[0..2].  Otherwise, if all nine entries of R compare equal
+ *      to the identity's, cc[0..2] are copied and cs'[3] = cs[3] if scale == 1, else f32(cs[3] * (scale * scale)): a pure translation never
+ *      touches the covariance, a pure scale never touches the int16 words.
+ *   6. Otherwise A = the symmetric matrix the export dequantises (int16 * cs[3], f64); B_ik = (Rm_i0 A_0k + Rm_i1 A_1k) + Rm_i2 A_2k;
+ *      E_ij = ((B_i0 Rm_j0 + B_i1 Rm_j1) + B_i2 Rm_j2) * (scale * scale) for (0,0), (1,0), (2,0), (1,1), (2,1), (2,2); max_value = the largest
+ *      |E|; cs'[3] = f32(max_value / 32767); each int16 = E * 32767 / max_value rounded to nearest, ties to even, clamped to [-32767, 32767],
+ *      NaN -> 0.  (NOT the truncation of the pack loop's parseInt: a truncating quantiser shrinks the splat with every edit.)
+ *   7. cc[3], the colour word, stays.
+ *   8. sort row = (cs'[0], cs'[1], cs'[2], f32(sort_row[3] * scale)): the size cull of the sort follows the scale.
+ *   9. The strip bound is the pack kernel's expression on cs'[3].
+ * The identity gives back every bit of a record with a finite position (a coordinate -0 may come back +0; a NaN is a NaN: its sign and
+ * payload are not part of the rule, and one NaN coordinate makes all three NaN).  Each general edit costs at
+ * most half a quantisation step of cs'[3] per covariance entry; translations and scales cost the covariance nothing.
+ *   SH rows: scale and translation leave them alone.  Under a rotation the coefficients of band l = 1..3 (k = 1..3, 4..8, 9..15) go through
+ * the band's matrix D_l: sh'[c][k0 + i] = f32(sum_j D_l[i][j] * sh[c][k0 + j]), summed in ascending j; k = 0 stays.  The matrices are built on
+ * the host, once per call, in f64 from + - * / sqrt, for the basis exactly as csrc/gs_sh.h orders and signs it, so that for every camera
+ * and position gs_sh_eval_unrounded(sh', D, scale R cam + t, scale R pos + t) = gs_sh_eval_unrounded(sh, D, cam, pos) up to the rounding of
+ * the coefficients.  An exact identity R gives exact identity matrices, and the SH kernel is not launched at all. */
+typedef struct gs_similarity {
+    float rotation[4];      /* quaternion (w, x, y, z) in the ROWS' object space (as a .ply / .splat row stores positions: the space of
+                               gs_select_sphere and GS_PROP_X..Z); need not be normalised */
+    float scale;            /* uniform, finite, > 0 */
+    float translation[3];   /* rows' object space */
+} gs_similarity;            /* p' = scale * R p + translation */
+/* Rewrites, for every passing splat (a splat beyond the state store has state 0): both halves of the 32-byte record except the colour
+ * word, the sort row, the strip bound and, where the splat has one, its SH row.  *out_hit (optional): the passing splats.  States (the
+ * store neither grows nor changes), the contribution store, gs_count(), the SH store's length and degree, every option and statistic
+ * stay.  Otherwise like gs_replace_splat: lanes drained, every lane's order dropped (a render before the next sort draws the background
+ * only), a sort posted with gs_sort_begin is run again when it is collected, gs_sync() does not draw frames of before the change again
+ * by itself.  Two streaming kernels of their own on the context's stream; the call waits for them.  Matrices-only context: GS_E_STATE.
+ * Nothing resident: hit 0, GS_OK.  NULL t, a parameter that is not finite, scale <= 0, a quaternion of norm 0: GS_E_BADARG.
+ * Out of scope: non-uniform scale, shear and mirroring; per-frame poses or groups; a transform applied at push time. */
+GS_API int gs_transform(gs_ctx *ctx, const gs_similarity *t, uint8_t state_mask, uint8_t state_value, size_t *out_hit);
+/* host, no context, no GPU: the kernels' own functions.  One record (the outputs may be the inputs; bound_out, optional: the strip bound),
+ * one SH row (tight, as gs_push_sh takes it; degree 0..3; out_row may be sh_row), the band matrices the kernel is handed (3x3, 5x5, 7x7,
+ * row-major, in that order: 83 doubles), and the similarity that rotates and scales about a pivot: rotation and scale copied, translation
+ * = f32(pivot - scale * R pivot), R as in steps 1-2, the sum as in step 4, f64, rounded once.  NULL pointers (but bound_out), a bad
+ * similarity as above, a degree out of range: GS_E_BADARG. */
+GS_API int gs_transform_record(const float cs[4], const uint32_t cc[4], const float sort_row[4], const gs_similarity *t,
+                               float cs_out[4], uint32_t cc_out[4], float sort_row_out[4], float *bound_out /* optional */);
+/* ... and n records in one call: arrays of n x 4 as gs_download returns them, each through gs_transform_record's function (bounds_out optional) */
+GS_API int gs_transform_records(const float *cs, const uint32_t *cc, const float *sort_rows, size_t n, const gs_similarity *t,
+                                float *cs_out, uint32_t *cc_out, float *sort_rows_out, float *bounds_out /* optional */);
+GS_API int gs_transform_sh_row(const float *sh_row, int degree, const gs_similarity *t, float *out_row);
+GS_API int gs_sh_rotation(const gs_similarity *t, double out[83]);
+GS_API int gs_similarity_about(const float pivot[3], const float rotation[4], float scale, gs_similarity *out);
 
 /* Scene compositing inputs (reference: the splat mesh is drawn in three.js' transparent pass with depthTest: true,
  * depthWrite: false over the opaque scene, index.js:177-181): an optional window-space depth buffer of that scene
@@ -533,6 +587,7 @@ GS_API int gs_multi_compact(gs_multi *m, uint32_t *out_old_index, size_t *out_n)
 GS_API int gs_multi_adjust_colour(gs_multi *m, const gs_colour_adjust *adjust, uint8_t state_mask, uint8_t state_value, size_t *out_hit);
 GS_API int gs_multi_replace_splat(gs_multi *m, size_t first, const void *rows, size_t nrows);
 GS_API int gs_multi_replace_sh(gs_multi *m, size_t first, const float *sh_rows, size_t nrows, int degree);
+GS_API int gs_multi_transform(gs_multi *m, const gs_similarity *t, uint8_t state_mask, uint8_t state_value, size_t *out_hit);
 GS_API size_t gs_multi_count(const gs_multi *m);
 GS_API int gs_multi_set_option(gs_multi *m, int option, int64_t value);              /* gs_set_option on every device     */
 /* tick + worker sort for the frame `views` describe (one view, or the two XR eyes with the head camera's view row, index.js:441):
